@@ -3,7 +3,7 @@
 on synthetic short reads, one process per GPU.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 30Mx150|1Mx100|<reads>x<len>]
-                  [--scaling weak|strong]
+                  [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 A step = one pass of the whole path over one block of reads resident in HBM
 (bfq_run_reads_device): `value`.  Blocks never interact (the BFQzip_parallel.py split), so there is
@@ -12,13 +12,25 @@ no data-path collective; only block sizes are exchanged.
   --scaling strong = BASELINE.json configs[3]: ONE collection of the named size cut by
                    split_blocks(reads, N) (BFQzip_parallel.py:288-323), rank r runs block r.
                    N = 1: the same run as weak.
-Rank 0 prints ONE JSON line.  Besides the contract's fields it carries (N = 1 only):
+Rank 0 prints ONE JSON line: the headline (value, ms_per_step, ...) with the kernel split and roofline
+figures of the timed steps themselves.  A plain run does nothing else; with --full the line also carries
+(N = 1 only; --no-cpu / --no-e2e / --no-dropin leave a leg out):
   e2e_host      SURVEY 8(d)'s metric: FASTQ text in pinned host memory -> bfq_fastq_run_job ->
                 the --m3 streams in pinned host memory, PCIe transfers included;
   dropin_wall_s the drop-in executables as BFQzip.py runs them (gsufsort, then bfq_int) on
                 /dev/shm files: wall seconds per tool;
   cpu_baseline  the reference CPU path on a bounded sample (1 core), and sample_parity;
-and for N > 1 in weak mode `strong`: the configs[3] measurement taken after the timed region.
+and for N > 1 in weak mode `strong`: the configs[3] measurement taken after the timed region; for every N
+`device_state` (clocks and power as rocm-smi reports them).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step returned (bases and qualities of the
+smoothed reads, device arrays of the workload's size, and the stats) as DIR/<name>.npy, 48 MB at most:
+  out_bases_sample / out_quals_sample   float32, the bytes at up to 4 Mi positions drawn by a fixed seed
+                                        (sorted, distinct), the same positions for the same workload;
+  out_bases_digest / out_quals_digest   float64, the whole arrays cut into up to 1 Mi equal blocks: per block
+                                        sum of byte * (1 + offset in the block), exact;
+  stats_<name>                          float64[1], one per counter bfq_run_reads_device returns.
+The inputs are seeded: the same arguments give the same inputs, so two builds can be compared file by file.
 """
 import argparse, json, os, shutil, subprocess, sys, tempfile, time
 import numpy as np
@@ -438,6 +450,32 @@ def device_state(local):
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+def dump_outputs(d, parts, st, seed=20240807, sample=1 << 22, blocks=1 << 20):
+    """What the timed path returned in its last step, in float npy files (module docstring: --dump-outputs)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    for name, ts in (("bases", [p[0] for p in parts]), ("quals", [p[1] for p in parts])):
+        x = ts[0] if len(ts) == 1 else torch.cat(ts)
+        T = x.numel()
+        idx = np.unique(np.random.default_rng(seed).integers(0, T, min(T, sample), dtype=np.int64))
+        v = x[torch.from_numpy(idx).to(x.device)].cpu().numpy().astype(np.float32)
+        np.save(os.path.join(d, f"out_{name}_sample.npy"), v)
+        bs = -(-T // min(T, blocks)); nb = -(-T // bs)
+        w = torch.arange(1, bs + 1, dtype=torch.int64, device=x.device)
+        dig = torch.empty(nb, dtype=torch.int64, device=x.device)
+        rows = max(1, (1 << 27) // bs)                           # 1 GiB of int64 per chunk
+        for r0 in range(0, nb, rows):
+            r1 = min(nb, r0 + rows)
+            seg = x[r0 * bs:min(T, r1 * bs)].to(torch.int64)
+            if seg.numel() < (r1 - r0) * bs:
+                seg = torch.nn.functional.pad(seg, (0, (r1 - r0) * bs - seg.numel()))
+            dig[r0:r1] = (seg.view(r1 - r0, bs) * w).sum(1)
+        np.save(os.path.join(d, f"out_{name}_digest.npy"), dig.cpu().numpy().astype(np.float64))
+        del x, w, dig
+    for k, val in st.items():
+        np.save(os.path.join(d, f"stats_{k}.npy"), np.array([val], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -452,6 +490,8 @@ def main():
     ap.add_argument("--piles", type=int, default=0, help="bfq_params.piles: 1 = step 1 pile by pile (13 n bytes of workspace instead of 28.6 n)")
     ap.add_argument("--M", type=int, default=2)
     ap.add_argument("--B", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also the legs beyond the headline (module docstring); off: headline only")
     args = ap.parse_args()
 
     import torch
@@ -484,7 +524,7 @@ def main():
 
     # the drop-in tools first, before this process holds any HBM (see dropin_wall)
     dropin_res, dropin_dir = {}, None
-    if world == 1 and not args.no_dropin:
+    if args.full and world == 1 and not args.no_dropin:
         dropin_res[f"{Nw}x{L}"], dropin_dir = dropin_wall(Nw, L, par, local, log, keep=not args.no_e2e)
         if (Nw, L) != (1_000_000, 100):
             dropin_res["1000000x100"], _ = dropin_wall(1_000_000, 100, dict(par, B=0), local, log)
@@ -495,8 +535,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(scaling, steps, warmup):
-        """K timed steps in the given mode; returns (seconds, bases this rank processed per step, prof, stats, reads)."""
+    def measure(scaling, steps, warmup, dump=None):
+        """K timed steps in the given mode; returns (seconds, bases this rank processed per step, prof, stats, reads).
+        dump: directory for the last step's outputs (rank 0; after the timed region)."""
         if scaling == "strong":
             blocks = parallel.split_blocks(Nw, world)
             mine = [blocks[k] for k in parallel.blocks_of_rank(len(blocks), rank, world)]
@@ -545,6 +586,9 @@ def main():
             dt, bases_all = float(tm[0].item()), float(ts[1].item())
         else:
             bases_all = float(bases)
+        if dump and rank == 0:
+            dump_outputs(dump, [(b[5], b[6]) for b in bufs], st)
+            torch.cuda.synchronize()
         prof = eng.prof()
         prof["_step_ms"] = step_ms
         prof["_scatter_ms"] = [float(x) for x in eng.prof_trace()]
@@ -554,11 +598,11 @@ def main():
         torch.cuda.empty_cache()
         return dt, bases_all, prof, st, reads
 
-    dt, bases_all, prof, st, reads_rank = measure(args.scaling, args.steps, args.warmup)
+    dt, bases_all, prof, st, reads_rank = measure(args.scaling, args.steps, args.warmup, args.dump_outputs)
     step_ms, scatter_ms = prof.pop("_step_ms"), prof.pop("_scatter_ms")
     log(f"{args.steps} timed steps ({args.scaling}): {dt:.3f}s")
     strong_extra = None
-    if world > 1 and args.scaling == "weak":                # configs[3] beside the weak figure
+    if args.full and world > 1 and args.scaling == "weak":  # configs[3] beside the weak figure
         sdt, sbases, _, _, sreads = measure("strong", args.steps, max(1, args.warmup))
         strong_extra = {"value": round(sbases / 1e6 / (sdt / args.steps), 2), "unit": "Mbases/s", "ms_per_step": round(sdt / args.steps * 1e3, 3),
                         "reads_total": Nw, "reads_rank0": sreads, "what": "BASELINE configs[3]: one collection cut by split_blocks(reads, N), one block per rank"}
@@ -625,11 +669,12 @@ def main():
                "roofline": roof, "kernel_ms_per_step": kern,
                "stats": {k: st[k] for k in ("num_clust", "bases_inside", "qs_smoothed", "modified", "n_segments", "n_big_segments")},
                "workspace_gib": round(eng.workspace_bytes() / 2**30, 2),
-               "step_ms": {"min": round(min(step_ms), 3), "median": round(float(np.median(step_ms)), 3), "max": round(max(step_ms), 3)},
-               "device_state": device_state(local)}
+               "step_ms": {"min": round(min(step_ms), 3), "median": round(float(np.median(step_ms)), 3), "max": round(max(step_ms), 3)}}
+        if args.full:
+            res["device_state"] = device_state(local)
         if strong_extra:
             res["strong"] = strong_extra
-        if world == 1:
+        if args.full and world == 1:
             text = None
             if not args.no_e2e:
                 try:

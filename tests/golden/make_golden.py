@@ -71,7 +71,45 @@ def main():
         index[name] = ent
         print(name, ent["n"], len(ent["out"]))
     json.dump(index, open(f"{HERE}/index.json", "w"), indent=1, sort_keys=True)
+    ref_cases()
+
+
+def ref_cases():
+    """ref_cases.npz / ref_cases.json: the random small inputs of tests/test_oracle_golden.py's two differential tests
+    (the same seeded draws those tests once made live) with the md5 of the reference bfq_int's output for each."""
+    from tests import util
+    arrays, meta = {}, {"fuzz": [], "tie": []}
+    rng = np.random.default_rng(7)
+    for it in range(60):
+        nreads = int(rng.integers(1, 120)); lmax = int(rng.integers(1, 50))
+        b, q, r = util.random_reads(rng, nreads, 1, lmax)
+        M, B = int(rng.integers(0, 4)), int(rng.integers(0, 2))
+        K = int(rng.choice([1, 2, 3, 5, 8, 16])); m = int(rng.choice([2, 3, 5, 9]))
+        v = int(rng.choice([62, 53, 73])); t = int(rng.choice([5, 20, 35])); f = int(rng.choice([40, 50, 70]))
+        bwt, qs, lcp = orc.build_ebwt(b, q, r)
+        out = run_ref(M, B, bwt, qs, ["-k", str(K), "-m", str(m), "-v", str(v), "-t", str(t), "-f", str(f)])
+        arrays[f"fuzz{it}_bases"], arrays[f"fuzz{it}_quals"], arrays[f"fuzz{it}_roff"] = b, q, np.asarray(r, np.uint64)
+        meta["fuzz"].append({"M": M, "B": B, "K": K, "m": m, "v": v, "t": t, "f": f,
+                             "bwt_md5": util.md5(bwt.tobytes()), "qs_md5": util.md5(qs.tobytes()), "out_md5": util.md5(out)})
+    rng = np.random.default_rng(99)
+    for it in range(12):
+        b, q, r = util.random_reads(rng, int(rng.integers(5, 60)), 1, int(rng.integers(4, 40)), dup=0.45, p_n=0.02)
+        bwt, qs, lcp = orc.build_ebwt(b, q, r)
+        sb, sq = util.shuffle_ties(bwt, qs, rng)
+        if np.array_equal(sb, bwt):
+            continue
+        K = int(rng.choice([2, 3, 5]))
+        out = run_ref(2, 0, sb, sq, ["-m", "2", "-k", str(K)])
+        i = len(meta["tie"])
+        arrays[f"tie{i}_bwt"], arrays[f"tie{i}_qs"] = sb, sq
+        meta["tie"].append({"K": K, "out_md5": util.md5(out)})
+    np.savez_compressed(f"{HERE}/ref_cases.npz", **arrays)
+    json.dump(meta, open(f"{HERE}/ref_cases.json", "w"), indent=1, sort_keys=True)
+    print("ref_cases", len(meta["fuzz"]), len(meta["tie"]))
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--ref-cases"]:
+        ref_cases()
+    else:
+        main()

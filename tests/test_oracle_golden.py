@@ -1,7 +1,8 @@
 """CPU tests: the oracle (oracle/bfq_oracle.c) against the golden vectors made by the
 compiled reference (tests/golden/make_golden.py), and against the reference
-binary itself (oracle/_ref, when present) on random small inputs."""
-import os, subprocess, tempfile
+binary's outputs on random small inputs (tests/golden/ref_cases.*; the binary itself is run
+again where oracle/_ref is built)."""
+import os, subprocess
 import numpy as np
 import pytest
 from bfqzip_amd import fastq
@@ -45,54 +46,50 @@ def test_example_known_answers(orc):
     assert np.array_equal(ob, b) and np.array_equal(oq, q) and st["num_clust"] == 0
 
 
-def test_oracle_vs_reference_binary_fuzz(orc):
-    """Differential fuzz against oracle/_ref/bfq_int_M?_B? (the reference compiled here)."""
-    if orc.ref_binary(2, 0) is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(7)
-    with tempfile.TemporaryDirectory() as d:
-        for it in range(60):
-            nreads = int(rng.integers(1, 120)); lmax = int(rng.integers(1, 50))
-            b, q, r = util.random_reads(rng, nreads, 1, lmax)
-            M, B = int(rng.integers(0, 4)), int(rng.integers(0, 2))
-            K = int(rng.choice([1, 2, 3, 5, 8, 16])); m = int(rng.choice([2, 3, 5, 9]))
-            v = int(rng.choice([62, 53, 73])); t = int(rng.choice([5, 20, 35])); f = int(rng.choice([40, 50, 70]))
-            bwt, qs, lcp = orc.build_ebwt(b, q, r)
+def test_oracle_vs_reference_binary_fuzz(orc, tmp_path):
+    """Differential fuzz against the reference bfq_int: 60 random small inputs with the md5 of the reference's output
+    for each (tests/golden/ref_cases.*, written by make_golden.py from oracle/_ref/bfq_int_M?_B?); the binaries
+    themselves are run again where they are built."""
+    cases, arr = util.ref_cases()
+    assert len(cases["fuzz"]) == 60
+    for it, c in enumerate(cases["fuzz"]):
+        b, q, r = arr[f"fuzz{it}_bases"], arr[f"fuzz{it}_quals"], arr[f"fuzz{it}_roff"]
+        bwt, qs, lcp = orc.build_ebwt(b, q, r)
+        assert util.md5(bwt.tobytes()) == c["bwt_md5"] and util.md5(qs.tobytes()) == c["qs_md5"], it
+        p = orc.params(K=c["K"], m=c["m"], v=c["v"], f=c["f"], t=c["t"], M=c["M"], B=c["B"])
+        ob, oq, oroff, st = orc.smooth_invert(bwt, qs, None, p)
+        assert util.md5(fastq.format_fastq(ob, oq, oroff)) == c["out_md5"], (it, c)
+        ref = orc.ref_binary(c["M"], c["B"])
+        if ref is not None:
+            d = str(tmp_path)
             bwt.tofile(d + "/x.bwt"); qs.tofile(d + "/x.bwt.qs")
-            cmd = [orc.ref_binary(M, B), "-e", d + "/x.bwt", "-q", d + "/x.bwt.qs", "-o", d + "/o.fq",
-                   "-k", str(K), "-m", str(m), "-v", str(v), "-t", str(t), "-f", str(f)]
+            cmd = [ref, "-e", d + "/x.bwt", "-q", d + "/x.bwt.qs", "-o", d + "/o.fq",
+                   "-k", str(c["K"]), "-m", str(c["m"]), "-v", str(c["v"]), "-t", str(c["t"]), "-f", str(c["f"])]
             subprocess.check_call(cmd, stdout=subprocess.DEVNULL, timeout=60)
-            ref = open(d + "/o.fq", "rb").read()
-            p = orc.params(K=K, m=m, v=v, f=f, t=t, M=M, B=B)
-            ob, oq, oroff, st = orc.smooth_invert(bwt, qs, None, p)
-            assert fastq.format_fastq(ob, oq, oroff) == ref, (it, M, B, K, m, v, t, f)
+            assert util.md5(open(d + "/o.fq", "rb").read()) == c["out_md5"], (it, c)
 
 
 def test_tie_order_of_identical_suffixes_is_free(orc, tmp_path):
     """The reference sees ONE terminator symbol: an eBWT whose identical suffixes (and terminator rows) are in any
-    order is processed all the same, LCP by the usual convention.  Pins, against the compiled reference, the contract the
+    order is processed all the same, LCP by the usual convention.  Pins, against the reference's output on eBWTs with
+    shuffled ties (tests/golden/ref_cases.*; the compiled reference is run again where it is built), the contract the
     GPU's BWT-only LCP deduction (k_bfs.hip) is tested with in tests/test_gpu_parity.py."""
-    import subprocess
+    cases, arr = util.ref_cases()
     ref = orc.ref_binary(2, 0)
-    if ref is None:
-        pytest.skip("reference bfq_int not built (oracle/_ref)")
-    rng = np.random.default_rng(99)
     done = 0
-    for it in range(12):
-        b, q, r = util.random_reads(rng, int(rng.integers(5, 60)), 1, int(rng.integers(4, 40)), dup=0.45, p_n=0.02)
-        bwt, qs, lcp = orc.build_ebwt(b, q, r)
-        sb, sq = util.shuffle_ties(bwt, qs, rng)
-        if np.array_equal(sb, bwt):
-            continue
+    for it, c in enumerate(cases["tie"]):
+        sb, sq = arr[f"tie{it}_bwt"], arr[f"tie{it}_qs"]
         suf, reads = util.decode_rows(sb)
         lc = util.lcp_of_rows(suf)
-        p = orc.params(m=2, K=int(rng.choice([2, 3, 5])))
+        p = orc.params(m=2, K=c["K"])
         ob, oq, oroff, st = orc.smooth_invert(sb, sq, lc, p)
         ob2, oq2, oroff2, st2 = orc.smooth_invert(sb, sq, None, p)            # the oracle's own BWT-only deduction
         assert np.array_equal(ob, ob2) and np.array_equal(oq, oq2) and st == st2
-        sb.tofile(str(tmp_path / "x.bwt")); sq.tofile(str(tmp_path / "x.bwt.qs"))
-        subprocess.check_call([ref, "-e", str(tmp_path / "x.bwt"), "-q", str(tmp_path / "x.bwt.qs"), "-o", str(tmp_path / "o.fq"),
-                               "-m", "2", "-k", str(p.K)], stdout=subprocess.DEVNULL)
-        assert open(str(tmp_path / "o.fq"), "rb").read() == fastq.format_fastq(ob, oq, oroff)
+        assert util.md5(fastq.format_fastq(ob, oq, oroff)) == c["out_md5"], (it, c)
+        if ref is not None:
+            sb.tofile(str(tmp_path / "x.bwt")); sq.tofile(str(tmp_path / "x.bwt.qs"))
+            subprocess.check_call([ref, "-e", str(tmp_path / "x.bwt"), "-q", str(tmp_path / "x.bwt.qs"), "-o", str(tmp_path / "o.fq"),
+                                   "-m", "2", "-k", str(p.K)], stdout=subprocess.DEVNULL)
+            assert util.md5(open(str(tmp_path / "o.fq"), "rb").read()) == c["out_md5"], (it, c)
         done += 1
     assert done >= 6

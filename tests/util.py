@@ -17,6 +17,13 @@ def golden_set(name):
     return b, q, r, h, bwt, qs, lcp
 
 
+def ref_cases():
+    """(parameters + md5 of the reference's output per case, the cases' input arrays) of tests/golden/ref_cases.*."""
+    meta = json.load(open(os.path.join(GOLDEN, "ref_cases.json")))
+    with np.load(os.path.join(GOLDEN, "ref_cases.npz")) as z:
+        return meta, {k: z[k] for k in z.files}
+
+
 def parse_case(key):
     """'M2B0 -m 5 -k 8 ...' -> dict of engine/oracle parameters (+ 'H' for headers)."""
     toks = key.split()
