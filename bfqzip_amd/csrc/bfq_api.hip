@@ -15,8 +15,6 @@
 #include <algorithm>
 #include <new>
 #include "bfq_internal.h"
-#include <atomic>
-extern std::atomic<bool> g_bfqHipStarted;                     // bfq_host.cpp
 #include "bfq_synth.h"
 #include "bfq_device.h"
 #include "bfq_rank.h"
@@ -29,13 +27,10 @@ const char *const BFQ_KERNEL_NAMES[K_NUM] = {
 static thread_local std::string g_createErr;
 
 // ---------------------------------------------------------------- context plumbing
-// The arena can also be built from physically contiguous chunks mapped into one address range (HIP's virtual memory
-// management: BFQ_WS_VMM=<chunk MiB>): what the 512 write streams of a radix pass cost depends on how the range is backed
-// (placement experiments).
 void bfq_ctx::reserveBegin(size_t bytes)
 {
     bytes = (bytes + 0xFFFFF) & ~(size_t)0xFFFFF;
-    if (wsThread || bytes <= wsCap || env.wsVmmMib || env.wsContig || (wsLimit() && bytes > wsLimit())) return;
+    if (wsThread || bytes <= wsCap || (wsLimit() && bytes > wsLimit())) return;
     wsPendBytes = bytes; wsPend = nullptr;
     const int dev = device;
     wsThread = new std::thread([this, dev, bytes] {
@@ -67,52 +62,8 @@ void bfq_ctx::wsFree()
 {
     if (!ws) return;
     (void)hipStreamSynchronize(stream);
-    if (wsVmmChunk) {
-        (void)hipMemUnmap(ws, wsCap);
-        for (auto h : wsHandles) (void)hipMemRelease((hipMemGenericAllocationHandle_t)h);
-        wsHandles.clear();
-        (void)hipMemAddressFree(ws, wsCap);
-        wsVmmChunk = 0;
-    } else (void)hipFree(ws);
+    (void)hipFree(ws);
     ws = nullptr; wsCap = 0; wsTop = 0;
-}
-static hipError_t ws_alloc_vmm(bfq_ctx *c, size_t bytes, size_t chunk, char **out, size_t *got)
-{
-    hipMemAllocationProp prop;
-    memset(&prop, 0, sizeof prop);
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = c->device;
-    size_t gran = 0;
-    hipError_t e = hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended);
-    if (e != hipSuccess) return e;
-    if (chunk < gran) chunk = gran;
-    chunk = (chunk + gran - 1) / gran * gran;
-    const size_t total = (bytes + chunk - 1) / chunk * chunk;
-    void *va = nullptr;
-    e = hipMemAddressReserve(&va, total, chunk, nullptr, 0);
-    if (e != hipSuccess) return e;
-    std::vector<void *> hs;
-    for (size_t o = 0; o < total && e == hipSuccess; o += chunk) {
-        hipMemGenericAllocationHandle_t h;
-        e = hipMemCreate(&h, chunk, &prop, 0);
-        if (e == hipSuccess) { hs.push_back((void *)h); e = hipMemMap((char *)va + o, chunk, 0, h, 0); }
-    }
-    if (e == hipSuccess) {
-        hipMemAccessDesc d;
-        memset(&d, 0, sizeof d);
-        d.location.type = hipMemLocationTypeDevice; d.location.id = c->device; d.flags = hipMemAccessFlagsProtReadWrite;
-        e = hipMemSetAccess(va, total, &d, 1);
-    }
-    if (e != hipSuccess) {
-        (void)hipMemUnmap(va, total);
-        for (auto h : hs) (void)hipMemRelease((hipMemGenericAllocationHandle_t)h);
-        (void)hipMemAddressFree(va, total);
-        return e;
-    }
-    c->wsHandles = hs; c->wsVmmChunk = chunk;
-    *out = (char *)va; *got = total;
-    return hipSuccess;
 }
 
 void bfq_ctx::reserve(size_t bytes)
@@ -128,18 +79,8 @@ void bfq_ctx::reserve(size_t bytes)
         wsFree();
         struct timespec t0, t1;
         clock_gettime(CLOCK_MONOTONIC, &t0);
-        hipError_t e = hipErrorOutOfMemory;
-        bool contig = false;
-        if (env.wsVmmMib) {
-            size_t got = 0;
-            e = ws_alloc_vmm(this, bytes, (size_t)env.wsVmmMib << 20, &ws, &got);
-            if (e == hipSuccess) bytes = got; else { (void)hipGetLastError(); ws = nullptr; }
-            if (bfq_env().trace) fprintf(stderr, "[bfq] workspace: VMM chunks of %d MiB %s\n", env.wsVmmMib, e == hipSuccess ? "mapped" : "refused");
-        }
-        if (e != hipSuccess && env.wsContig) { e = hipExtMallocWithFlags((void **)&ws, bytes, hipDeviceMallocContiguous); contig = e == hipSuccess; if (!contig) (void)hipGetLastError(); }
-        if (e != hipSuccess) e = hipMalloc((void **)&ws, bytes);
+        const hipError_t e = hipMalloc((void **)&ws, bytes);
         clock_gettime(CLOCK_MONOTONIC, &t1);
-        if (bfq_env().trace && env.wsContig) fprintf(stderr, "[bfq] workspace: contiguous allocation %s\n", contig ? "granted" : "refused");
         if (bfq_env().trace) fprintf(stderr, "[bfq] workspace %.1f GiB: hipMalloc %.3f s\n", bytes / 1073741824.0, (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec));
         if (e != hipSuccess) {
             ws = nullptr;
@@ -366,27 +307,6 @@ extern "C" int bfq_prof_get(bfq_ctx *c, int idx, char *name, int cap, double *ms
     return BFQ_OK;
 }
 
-// run `body` with the usual prologue/epilogue; maps exceptions to error codes
-template <class F> static int guarded(bfq_ctx *c, F body)
-{
-    if (!c) return BFQ_E_ARG;
-    try {
-        HIP_CHECK(hipSetDevice(c->device));
-        c->err.clear();
-        body();
-        return BFQ_OK;
-    } catch (const BfqError &e) {
-        c->err = e.msg;
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipGetLastError();
-        c->recs.clear(); c->evUsed = 0;
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        c->err = "host out of memory";
-        return BFQ_E_NOMEM;
-    }
-}
-
 static void check_counters(bfq_ctx *c)
 {
     const DevCounters &h = c->h_cnt;
@@ -459,7 +379,7 @@ static void reserve_step1(bfq_ctx *c, u64 n, u64 N, u64 extra, bool allowCapped 
     const u64 cap = n / 10 * 3 + (1u << 20);                     // a DNA pile holds about a quarter of the suffixes; larger ones are split again
     c->piles = false; c->capped = false;
     if (mode <= 0) {
-        try { c->reserve(ws_need(n, N, extra + c->env.abPad + ((c->env.abSwap || c->env.abOrder[0]) ? 12 * (n + 256) : 0))); return; }
+        try { c->reserve(ws_need(n, N, extra)); return; }
         catch (const BfqError &e) { if (mode < 0 || e.code != BFQ_E_NOMEM) throw; }
     }
     if (mode != 2) {
@@ -498,47 +418,23 @@ void bfq_step1_device(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u6
     size_t m0 = c->mark();
     u64 nwords = n / BFQ_SYMS_PER_WORD + 3;
     u64 *text3 = c->alloc<u64>(bfq_t3_alloc(nwords));
+    // the sort's two record buffers: A.w12, A.w0, B.w0, B.w12 in this order (where they lie moves a scatter pass between 26
+    // and 34 ms: profiles/r3/placement.md)
     SortRec A, B;
-    const bool abSwap = c->env.abSwap && !c->keepRecs;  // placement experiment: B below A
-    size_t mKeep = 0, mB = 0;
-    if (c->env.abOrder[0] && !c->keepRecs) {            // placement experiment: the four arrays in any order (0 A.w12, 1 A.w0, 2 B.w0, 3 B.w12)
-        for (int k = 0; k < 4; k++) {
-            switch (c->env.abOrder[k]) {
-            case '0': A.w12 = c->alloc<u64>(n + 16); break;
-            case '1': A.w0 = c->alloc<u32>(n + 16); break;
-            case '2': B.w0 = c->alloc<u32>(n + 16); break;
-            default: B.w12 = c->alloc<u64>(n + 16); break;
-            }
-        }
-        mKeep = mB = c->mark();
-    } else {
-    if (abSwap) { B.w0 = c->alloc<u32>(n + 16); B.w12 = c->alloc<u64>(n + 16); }
     A.w12 = c->alloc<u64>(n + 16);
-    mKeep = c->mark();                                  // position mode keeps the text and the records' (w1, w2) words
+    const size_t mKeep = c->mark();                     // position mode keeps the text and the records' (w1, w2) words
     A.w0 = c->alloc<u32>(n + 16);
-    mB = c->mark();
-    if (c->env.abPad) (void)c->allocBytes((size_t)c->env.abPad);
-    if (!abSwap) { B.w0 = c->alloc<u32>(n + 16); B.w12 = c->alloc<u64>(n + 16); }
-    }
+    const size_t mB = c->mark();
+    B.w0 = c->alloc<u32>(n + 16);
+    B.w12 = c->alloc<u64>(n + 16);
     if (bfq_env().trace) fprintf(stderr, "[bfq] sort buffers: A.w12 %p A.w0 %p B.w0 %p B.w12 %p (arena %p)\n", (void *)A.w12, (void *)A.w0, (void *)B.w0, (void *)B.w12, (void *)c->ws);
-    // k_build_keys writes the records to B, the byte text lying in A (dead before the sort's first scatter writes there).
-    // BFQ_KEY_FUSION=1 (tried in round 3, slower): the records never exist unsorted -- the first pass of the sort makes them
-    // from the text on its way (k_radix_scatter<2>; the byte text then lies in B, which that pass does not touch).  It saves
-    // 12 B/row written + 9.6 B/row read, but the key of a suffix (window, terminator mask, 40-bit packing) costs the scatter
-    // kernel more than the traffic it saves: k_build_keys 17.3 -> 6.4 ms (counts only), pass 0 36.4 -> 66.1 ms, step +17 ms.
-    const bool fused = c->env.keyFusion;
-    u8 *T8 = fused ? (u8 *)B.w0 : (u8 *)A.w0, *Q8 = fused ? (u8 *)B.w12 : (u8 *)A.w12;
+    // k_build_keys writes the records to B, the byte text lying in A (dead before the sort's first scatter writes there)
+    u8 *T8 = (u8 *)A.w0, *Q8 = (u8 *)A.w12;
     bfq_build_text(c, d_bases, d_quals, d_roff, N, n, T8, Q8, text3, nwords);
     u32 *hist0 = c->alloc<u32>(256 * ceil_div(n, bfq_radix_block_elems(n)));
     static_assert(BFQ_KEY_PASSES & 1, "an odd number of passes ends in the other buffer");
-    if (fused) {
-        bfq_key_hist(c, text3, n, hist0);               // the first pass's digit counts
-        const RadixText tx{T8, Q8, text3};
-        bfq_radix_sort(c, B, A, n, BFQ_KEY_PASSES, hist0, &tx);   // text -> A -> B -> A -> B -> A
-    } else {
-        bfq_build_keys(c, T8, Q8, text3, n, B, hist0);
-        bfq_radix_sort(c, B, A, n, BFQ_KEY_PASSES, hist0);
-    }
+    bfq_build_keys(c, T8, Q8, text3, n, B, hist0);
+    bfq_radix_sort(c, B, A, n, BFQ_KEY_PASSES, hist0);  // B -> A -> B -> A -> B -> A
     c->release(mB);                                     // the big-segment list reuses the B buffers
     bfq_refine(c, A, text3, n, c->d_lcp, st);
     bfq_emit_bwt(c, A, n, termOut, c->d_bwt, c->d_qual, c->d_gcnt);
@@ -1013,7 +909,6 @@ extern "C" int bfq_smooth_invert(bfq_ctx *c, const uint8_t *h_bwt, const uint8_t
 // ---------------------------------------------------------------- FASTQ text in / out
 // The FASTQ text lives outside the arena (its record count sizes the arena) in a buffer the context keeps
 // between calls: uploaded first, lines counted on the device, then the workspace is reserved for the real N.
-u64 bfq_fastq_count_lines(bfq_ctx *c, const u8 *d_buf, u64 len);   // k_fastq.hip
 u8 *bfq_ctx::textBuf(size_t bytes)
 {
     residentValid = false;                                      // whoever asks is about to overwrite the buffer
@@ -1314,9 +1209,6 @@ extern "C" int bfq_fastq_build_ebwt_fd(bfq_ctx *c, int fastq_fd, uint64_t len, i
     });
 }
 
-void bfq_fastq_part_index(bfq_ctx *c, const DevFastq *fq, const u64 *h_pstart, int nparts, u64 *d_idx);   // k_fastq.hip
-void bfq_pick_u64(bfq_ctx *c, const u64 *d_src, const u64 *d_idx, int count, u64 addIdx, u64 *d_out);      // k_fastq.hip
-
 extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
 {
     return guarded(c, [&] {
@@ -1582,7 +1474,6 @@ extern "C" int bfq_synth_device(bfq_ctx *c, const bfq_synth *s, uint8_t *d_bases
     });
 }
 
-u8 *bfq_synth_headers(bfq_ctx *c, const bfq_synth *s, u64 *len);   // k_synth.hip
 extern "C" int bfq_synth_fastq(bfq_ctx *c, const bfq_synth *s, uint8_t *h_out, uint64_t cap, uint64_t *out_len)
 {
     return guarded(c, [&] {

@@ -55,7 +55,6 @@ BfqEnv bfq_env_read()
         e.noOverlap = getenv("BFQ_NO_OVERLAP") != nullptr;
         e.noLengthGuess = getenv("BFQ_NO_LENGTH_GUESS") != nullptr;
         e.posMode = geti("BFQ_POSMODE", 0) != 0;
-        e.invertThreads = geti("BFQ_INVERT_THREADS", 0);
         e.ioThreads = geti("BFQ_IO_THREADS", 0);
         e.prefaultThreads = geti("BFQ_PREFAULT_THREADS", -1);
         e.hugeCap = getu("BFQ_HUGE_CAP", 0);
@@ -64,26 +63,13 @@ BfqEnv bfq_env_read()
         e.fakeDevices = geti("BFQ_FAKE_DEVICES", 0);
         e.lease = geti("BFQ_LEASE", 1) != 0;
         if (const char *d = getenv("BFQ_LEASE_DIR")) e.leaseDir = d;
-        e.invertNt = geti("BFQ_INVERT_NT", 1);
         e.noOutmap = getenv("BFQ_NO_OUTMAP") != nullptr;
-        e.wsContig = geti("BFQ_WS_CONTIG", 0) != 0;
         e.compact = geti("BFQ_COMPACT", 0) != 0;
         e.prefaultPause = geti("BFQ_PREFAULT_PAUSE", 0) != 0;
         e.compactWin = getu("BFQ_COMPACT_WIN", 0);
         e.compactRing = getu("BFQ_COMPACT_RING", 0);
         e.dnaStatic = geti("BFQ_DNA_STATIC", 0);
-        e.keyFusion = geti("BFQ_KEY_FUSION", 0) != 0;
         e.dnacK = geti("BFQ_DNAC_K", 0); e.dnacH = geti("BFQ_DNAC_H", 0); e.dnacW = geti("BFQ_DNAC_W", 0); e.dnacSkip = geti("BFQ_DNAC_TSKIP", -1);
-        e.wsVmmMib = geti("BFQ_WS_VMM", 0);
-        e.rsPerm = geti("BFQ_RS_PERM", 0) != 0;
-        e.abPad = getu("BFQ_AB_PAD", 0);
-        e.abSwap = geti("BFQ_AB_SWAP", 0) != 0;
-        if (const char *o = getenv("BFQ_AB_ORDER")) {
-            bool seen[4] = {false, false, false, false};
-            bool ok = strlen(o) == 4;
-            for (int k = 0; ok && k < 4; k++) { ok = o[k] >= '0' && o[k] <= '3' && !seen[o[k] - '0']; if (ok) seen[o[k] - '0'] = true; }
-            if (ok) memcpy(e.abOrder, o, 4);
-        }
         return e;
     }
 }
@@ -357,7 +343,6 @@ static void populate_slice(bfq_outmap *m, uint64_t idx)
     m->done += e - b;
 }
 // allocates (and zeroes) the file's pages from the front, 128 MiB per call
-extern std::atomic<bool> g_bfqHipStarted;
 static void hold_for_hip(bfq_outmap *m);
 static void falloc_worker(bfq_outmap *m)
 {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <functional>
+#include <new>
 #include <string>
 #include <vector>
 #include <thread>
@@ -83,8 +84,6 @@ struct bfq_ctx {
     char *wsPend = nullptr;
     size_t wsPendBytes = 0;
     double wsPendSecs = 0;
-    size_t wsVmmChunk = 0;              // != 0: the arena is VMM chunks of this size mapped into one range (experiment)
-    std::vector<void *> wsHandles;
     void dropWorkspace();           // frees the arena now (one-shot tools: lets the driver scrub it while outputs are written)
     void *allocBytes(size_t bytes);
     template <class T> T *alloc(size_t count) { return (T *)allocBytes(count * sizeof(T)); }
@@ -186,6 +185,27 @@ void bfq_upload_join(BfqAsyncUpload *u);
         HIP_CHECK(hipGetLastError());                                                          \
     } while (0)
 
+// run `body` of a C-ABI entry point with the usual prologue/epilogue; maps exceptions to error codes
+template <class F> static int guarded(bfq_ctx *c, F body)
+{
+    if (!c) return BFQ_E_ARG;
+    try {
+        HIP_CHECK(hipSetDevice(c->device));
+        c->err.clear();
+        body();
+        return BFQ_OK;
+    } catch (const BfqError &e) {
+        c->err = e.msg;
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipGetLastError();
+        c->recs.clear(); c->evUsed = 0;
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        c->err = "host out of memory";
+        return BFQ_E_NOMEM;
+    }
+}
+
 static inline u64 ceil_div(u64 a, u64 b) { return (a + b - 1) / b; }
 // HIP caps gridDim.x * blockDim.x below 2^32: every kernel is launched on at most
 // BFQ_MAX_GRID workgroups and strides over its work items.
@@ -214,6 +234,14 @@ u64 bfq_codec_raw_len(const u8 *h_in, u64 len);                    // all member
 u64 bfq_codec_member_len(const u8 *h_in, u64 len);                 // bytes of the first member
 u64 bfq_codec_compress_device(bfq_ctx *c, const u8 *d_in, u64 n, u8 *d_out, u64 cap);
 u64 bfq_codec_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
+u64 bfq_codec_checksum_device(bfq_ctx *c, const u8 *d_in, u64 n, u64 *d_tmp);
+u64 bfq_rans_compress_device(bfq_ctx *c, const u8 *d_in, u64 n, u8 *d_out, u64 cap, bool dry);
+u64 bfq_rans_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
+// DNA container (k_dnac.hip)
+u64 bfq_dnac_workspace(u64 n);
+u64 bfq_dnac_compress_device(bfq_ctx *c, const u8 *d_in, u64 n, u8 *d_out, u64 cap, u64 *nbases);
+u64 bfq_dnac_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
+u64 bfq_dnac_member_len(const u8 *h_in, u64 len);
 
 // step 1 pieces
 void bfq_build_text(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, u64 n,
@@ -232,14 +260,13 @@ static inline u64 bfq_radix_block_elems(u64 n)
 }
 void bfq_build_keys(bfq_ctx *c, const u8 *T8, const u8 *Q8, const u64 *text3, u64 n, SortRec out, u32 *hist0);   // hist0: [256][ceil(n / bfq_radix_block_elems(n))]
 // LSD radix sort of the records on their 48-bit key; result ends in A
-struct RadixText { const u8 *T8, *Q8; const u64 *text3; };   // the terminated text the first pass makes its records from
-void bfq_key_hist(bfq_ctx *c, const u64 *text3, u64 n, u32 *hist0);                                   // k_text.hip
-SortRec bfq_radix_sort(bfq_ctx *c, SortRec in, SortRec tmp, u64 n, int passes = BFQ_KEY_PASSES, const u32 *hist0 = nullptr, const RadixText *fromText = nullptr);   // returns the buffer holding the result (in: even passes, tmp: odd); fewer passes = low digits only; hist0: pass-0 counts already made
+SortRec bfq_radix_sort(bfq_ctx *c, SortRec in, SortRec tmp, u64 n, int passes = BFQ_KEY_PASSES, const u32 *hist0 = nullptr);   // returns the buffer holding the result (in: even passes, tmp: odd); fewer passes = low digits only; hist0: pass-0 counts already made
 // tie refinement: sorts vals inside equal-key segments by the remaining suffix, fills lcp
 void bfq_refine(bfq_ctx *c, SortRec rec, const u64 *text3, u64 n, u16 *lcp, bfq_stats *st);
 // segments above BFQ_HUGE_SEG rows (listed by k_refine_big): whole-device radix rounds on the following symbols
 #define BFQ_HUGE_SEG 2048
 void bfq_refine_huge(bfq_ctx *c, SortRec rec, const u64 *text3, u64 n, u16 *lcp, const u64 *hugeStart, const u64 *hugeLen);
+void bfq_refine_bitonic(bfq_ctx *c, SortRec rec, const u64 *text3, u64 n, u16 *lcp, const u64 *d_start, const u64 *d_len, u64 count);   // k_refine.hip
 void bfq_emit_bwt(bfq_ctx *c, SortRec rec, u64 n, int termOut, u8 *bwt, u8 *qs, u32 *gcnt);   // gcnt: [6][n/256+1] symbol counts
 // whole step 1 on device-resident reads; leaves c->d_bwt/d_qual/d_lcp
 void bfq_step1_device(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, u64 total,
@@ -257,6 +284,8 @@ void bfq_pack_text(bfq_ctx *c, const u8 *T8, u64 n, u64 *text3, u64 nwords);
 
 // steps 2-4 pieces
 RankIndex bfq_rank_build(bfq_ctx *c, const u8 *bwt, const u8 *qs, u64 n, int term, const u32 *gcnt = nullptr);
+u64 *bfq_symbol_scans(bfq_ctx *c, const u8 *bwt, u64 n, int term, const u32 *gcntIn, u32 *gcntOut);   // k_rank.hip
+void bfq_rank_blocks(bfq_ctx *c, const u8 *bwt, u64 n, int term, const u64 *scanned, u64 *rank);          // k_bfs.hip
 void bfq_lcp_flags(bfq_ctx *c, const u16 *lcp, u64 n, int K, u8 *in);
 // LCP array from the eBWT alone (k_bfs.hip): lcp has n + 1 entries
 void bfq_lcp_from_bwt(bfq_ctx *c, const u8 *bwt, u64 n, u64 N, int term, u16 *lcp, u32 *gcntOut = nullptr,   // gcntOut: [6][n/256+1] symbol counts, kept
@@ -283,6 +312,7 @@ void bfq_invert(bfq_ctx *c, const RankIndex &R, u64 N, const u64 *d_roff, int B,
 bool bfq_is_pinned(const void *p);
 
 void bfq_synth_launch(bfq_ctx *c, const bfq_synth *s, u8 *d_bases, u8 *d_quals, u64 *d_roff);
+u8 *bfq_synth_headers(bfq_ctx *c, const bfq_synth *s, u64 *len);   // k_synth.hip
 
 // FASTQ text on the device (k_fastq.hip)
 struct DevFastq { u64 N, total; void *rec; u64 *roff; u8 *bases, *quals; u64 *lineEnd; };
@@ -290,3 +320,5 @@ void bfq_fastq_parse(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq);
 u64 bfq_fastq_format(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, int mode, const u8 *d_hdr,
                      u64 hdrLen, const DevFastq *fq, u8 **d_out, u64 **recOffOut = nullptr, bool lines = false);
 void bfq_fastq_hdr_stream(bfq_ctx *c, u64 N, const u8 *d_fastq, const DevFastq *fq, u8 **d_hdr, u64 *hdrLen, u64 **hOffOut = nullptr);
+void bfq_fastq_part_index(bfq_ctx *c, const DevFastq *fq, const u64 *h_pstart, int nparts, u64 *d_idx);
+void bfq_pick_u64(bfq_ctx *c, const u64 *d_src, const u64 *d_idx, int count, u64 addIdx, u64 *d_out);

@@ -1,6 +1,7 @@
 // bfq_internal_host.h -- host-only helpers of libbfqhip.so (bfq_host.cpp): no HIP types here.
 #pragma once
 #include <stdint.h>
+#include <atomic>
 #include <string>
 #include "../../include/bfqzip_hip.h"
 
@@ -13,7 +14,6 @@ struct BfqEnv {
     bool noOverlap = false;         // BFQ_NO_OVERLAP: inversion and device -> host copies one after the other
     bool noLengthGuess = false;     // BFQ_NO_LENGTH_GUESS: always count read lengths by LF walks
     bool posMode = false;           // BFQ_POSMODE=1: steps 3-4 without LF table (position mode)
-    int invertThreads = 0;          // BFQ_INVERT_THREADS: workgroup size of k_invert (0: default)
     int ioThreads = 0;              // BFQ_IO_THREADS: staging workers (0: by core count)
     int prefaultThreads = -1;       // BFQ_PREFAULT_THREADS: helpers that fault in output mappings (-1: by core count)
     unsigned long long hugeCap = 0; // BFQ_HUGE_CAP: slot budget of the huge-segment rounds (test knob)
@@ -22,25 +22,19 @@ struct BfqEnv {
     int fakeDevices = 0;            // BFQ_FAKE_DEVICES=n: pretend n GPUs (slot k -> device k mod the real count): lease tests on one GPU
     bool lease = true;              // BFQ_LEASE=0: no lease files (the caller places the tools itself)
     std::string leaseDir;           // BFQ_LEASE_DIR: where the lock files live (default /dev/shm, else /tmp)
-    bool rsPerm = false;            // BFQ_RS_PERM=1: the radix passes take their blocks spread by a coprime stride instead of in order (placement experiments: no effect)
-    int wsVmmMib = 0;               // BFQ_WS_VMM=<MiB>: the workspace as physically contiguous chunks of that size mapped into one range (hipMemCreate / hipMemMap)
-    bool wsContig = false;          // BFQ_WS_CONTIG=1: ask for a physically contiguous workspace (hipDeviceMallocContiguous), plain hipMalloc if refused
-    unsigned long long abPad = 0;   // BFQ_AB_PAD: bytes left free between the two sort-record buffers (placement experiments)
-    char abOrder[8] = {0};          // BFQ_AB_ORDER=<permutation of 0123>: the order of A.w12, A.w0, B.w0, B.w12 in the arena (placement experiments)
-    bool abSwap = false;            // BFQ_AB_SWAP=1: the second record buffer below the first (placement experiments)
     bool compact = false;           // BFQ_COMPACT=1: steps 2-4 on a given eBWT + LCP without the LF table whatever the cap (k_compact.hip; test knob)
-    bool keyFusion = false;         // BFQ_KEY_FUSION=1: the sort's records are made by its first scatter pass from the text (slower: bfq_api.hip)
     int dnaStatic = 0;              // BFQ_DNA_STATIC=1: read-order DNA through the static BFQRANS2 container as well (4x faster, 3x larger)
     int dnacK = 0, dnacH = 0, dnacW = 0, dnacSkip = -1;   // BFQ_DNAC_K / _H / _W / _TSKIP: the BFQDNAC1 container's parameters (the header carries them; defaults in k_dnac.hip)
     unsigned long long compactRing = 0; // BFQ_COMPACT_RING: entries of the interval refinement's ring queue there (default: what the cap leaves; small values test the chunked levels / the move to host memory)
     unsigned long long compactWin = 0;  // BFQ_COMPACT_WIN: rows of the LCP file in flight there (default 64 Mi; small values test the windowing)
     bool prefaultPause = false;     // BFQ_PREFAULT_PAUSE=1: output files are not allocated while an input file is being read (default: both at once)
     bool noOutmap = false;          // BFQ_NO_OUTMAP: the tools write their outputs with pwrite instead of through a mapping (test knob)
-    int invertNt = 1;               // BFQ_INVERT_NT=0: plain instead of nontemporal LF-table loads in k_invert
 };
 BfqEnv bfq_env_read();
 const BfqEnv &bfq_env();
 int bfq_cpu_budget();            // CPUs this process may keep busy (cgroup quota, affinity, hardware)
+extern std::atomic<bool> g_bfqHipStarted;       // bfq_create() has initialised HIP: the output files' populate helpers may map pages now
+extern std::atomic<int> g_bfqUploadsRunning;    // staged uploads in progress (bfq_io.hip): the output helpers stand back meanwhile
 
 // output file mapped for writing, pre-faulted in the background
 struct bfq_outmap;

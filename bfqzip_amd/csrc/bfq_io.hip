@@ -122,7 +122,6 @@ static bool host_put(const HostRef &h, size_t off, const char *src, size_t sz)
 static bool io_trace() { return bfq_env().trace; }
 static double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
-extern std::atomic<int> g_bfqUploadsRunning;                   // bfq_host.cpp: the output helpers stand back meanwhile
 static void staged_copy(bfq_ctx *c, char *dev, HostRef host, size_t len, bool up)
 {
     struct Busy { bool on; Busy(bool o) : on(o) { if (on) g_bfqUploadsRunning++; } ~Busy() { if (on) g_bfqUploadsRunning--; } } busy(up && !host.ptr);

@@ -237,8 +237,6 @@ __global__ __launch_bounds__(256) void k_bfs_init(BfsArgs a, u64 N)
     }
 }
 
-u64 *bfq_symbol_scans(bfq_ctx *c, const u8 *bwt, u64 n, int term, const u32 *gcntIn, u32 *gcntOut);   // k_rank.hip
-
 // rank blocks of an eBWT (rank: (n / 256 + 1) * 4 + 2 blocks of 8 words); the symbol totals land in d_cnt->tot
 void bfq_rank_blocks(bfq_ctx *c, const u8 *bwt, u64 n, int term, const u64 *scanned, u64 *rank)
 {

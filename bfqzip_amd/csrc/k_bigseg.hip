@@ -163,8 +163,6 @@ static void huge_batch(bfq_ctx *c, SortRec rec, const u64 *text3, u16 *lcp, cons
     c->release(mk);
 }
 
-void bfq_refine_bitonic(bfq_ctx *c, SortRec rec, const u64 *text3, u64 n, u16 *lcp, const u64 *d_start, const u64 *d_len, u64 count);
-
 void bfq_refine_huge(bfq_ctx *c, SortRec rec, const u64 *text3, u64 n, u16 *lcp, const u64 *hugeStart, const u64 *hugeLen)
 {
     u64 hc[2] = {0, 0};

@@ -421,10 +421,6 @@ u64 bfq_codec_bound(u64 n)
     // (+ n / 2: a BFQDNAC1 container holds a second, small BFQRANS2 container -- the line lengths -- in front of its payload)
     return 32 + CQ_HDR + 256 + 512 + CQ_MAX_TABLE / 8 + 2ull * CQ_MAX_TABLE + 4 * nseg + n + n / 2 + 8 * nseg + 64 + n / 2 + (16u << 20);
 }
-u64 bfq_dnac_workspace(u64 n);                                                                   // k_dnac.hip
-u64 bfq_dnac_compress_device(bfq_ctx *c, const u8 *d_in, u64 n, u8 *d_out, u64 cap, u64 *nbases);
-u64 bfq_dnac_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
-u64 bfq_dnac_member_len(const u8 *h_in, u64 len);
 // device workspace of one compress / decompress call
 u64 bfq_codec_workspace(u64 n)
 {

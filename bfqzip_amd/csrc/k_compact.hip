@@ -87,9 +87,6 @@ __global__ __launch_bounds__(256) void k_lcp_widen_win(const u8 *__restrict__ ra
     }
 }
 
-u64 *bfq_symbol_scans(bfq_ctx *c, const u8 *bwt, u64 n, int term, const u32 *gcntIn, u32 *gcntOut);   // k_rank.hip
-void bfq_rank_blocks(bfq_ctx *c, const u8 *bwt, u64 n, int term, const u64 *scanned, u64 *rank);          // k_bfs.hip
-
 static u64 lcp_window(bfq_ctx *c, u64 n)
 {
     // (up to a third of the rows the window's 6 bytes per row lie where the reads go out later: it costs no workspace)

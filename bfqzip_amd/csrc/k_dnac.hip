@@ -32,10 +32,6 @@
 #define DQ_MAXLINE 65535u
 #define DQ_SLOT(cnt) (2ull * (cnt) + 16ull)          // scratch bytes of a segment of cnt symbols (a symbol costs at most 12 bits)
 
-u64 bfq_rans_compress_device(bfq_ctx *c, const u8 *d_in, u64 n, u8 *d_out, u64 cap, bool dry);              // k_codec.hip
-u64 bfq_rans_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
-u64 bfq_codec_checksum_device(bfq_ctx *c, const u8 *d_in, u64 n, u64 *d_tmp);
-
 static u32 dq_H(u64 nbases)
 {
     u32 H = 12;

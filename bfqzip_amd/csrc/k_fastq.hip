@@ -280,7 +280,7 @@ u64 bfq_fastq_format(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64
 
 // The header stream of BFQzip.py --m3 (OUT.h = `sed -n 1~4p in.fastq`): the header lines of the parsed FASTQ `fq`, one
 // per line; *hdrLen bytes in *d_hdr, line offsets in *hOffOut.  (The OUT.fq.dna / OUT.fq.qs streams are written by the
-// inversion itself, k_invert<.., 1>.)
+// inversion itself, k_invert<1>.)
 void bfq_fastq_hdr_stream(bfq_ctx *c, u64 N, const u8 *d_fastq, const DevFastq *fq, u8 **d_hdr, u64 *hdrLen, u64 **hOffOut)
 {
     u64 waves = N < (1u << 18) ? N : (1u << 18);

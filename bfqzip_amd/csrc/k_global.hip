@@ -20,28 +20,6 @@
 #include "bfq_internal.h"
 #include "bfq_device.h"
 
-u64 bfq_fastq_count_lines(bfq_ctx *c, const u8 *d_buf, u64 len);   // k_fastq.hip
-
-template <class F> static int guarded_g(bfq_ctx *c, F body)
-{
-    if (!c) return BFQ_E_ARG;
-    try {
-        HIP_CHECK(hipSetDevice(c->device));
-        c->err.clear();
-        body();
-        return BFQ_OK;
-    } catch (const BfqError &e) {
-        c->err = e.msg;
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipGetLastError();
-        c->recs.clear(); c->evUsed = 0;
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        c->err = "host out of memory";
-        return BFQ_E_NOMEM;
-    }
-}
-
 // the resident block text parsed again (cheap: a few streaming kernels); arena sized for the parse only
 static void reparse(bfq_ctx *c, DevFastq *fq, size_t extra)
 {
@@ -54,12 +32,9 @@ static void reparse(bfq_ctx *c, DevFastq *fq, size_t extra)
     bfq_fastq_parse(c, c->d_text, len, fq);
 }
 
-void bfq_fastq_part_index(bfq_ctx *c, const DevFastq *fq, const u64 *h_pstart, int nparts, u64 *d_idx);   // k_fastq.hip
-void bfq_pick_u64(bfq_ctx *c, const u64 *d_src, const u64 *d_idx, int count, u64 addIdx, u64 *d_out);      // k_fastq.hip
-
 extern "C" int bfq_glob_begin(bfq_ctx *c, const bfq_text_part *parts, int nparts, uint64_t *n_reads, uint64_t *total_bases)
 {
-    return guarded_g(c, [&] {
+    return guarded(c, [&] {
         if (nparts < 1 || nparts > BFQ_MAX_PARTS || !parts) throw BfqError{BFQ_E_ARG, "1..BFQ_MAX_PARTS parts"};
         u64 len = 0;
         std::vector<u8> addNl(nparts, 0);
@@ -97,7 +72,7 @@ extern "C" int bfq_glob_begin(bfq_ctx *c, const bfq_text_part *parts, int nparts
 
 extern "C" int bfq_glob_local_text(bfq_ctx *c, uint8_t *d_T8, uint8_t *d_Q8)
 {
-    return guarded_g(c, [&] {
+    return guarded(c, [&] {
         DevFastq fq;
         reparse(c, &fq, 0);
         const u64 n = fq.total + fq.N;
@@ -118,7 +93,7 @@ extern "C" int bfq_glob_local_text(bfq_ctx *c, uint8_t *d_T8, uint8_t *d_Q8)
 
 extern "C" int bfq_glob_pile_counts(bfq_ctx *c, const uint8_t *d_T8, uint64_t n, uint64_t *counts36)
 {
-    return guarded_g(c, [&] {
+    return guarded(c, [&] {
         if (!counts36) throw BfqError{BFQ_E_ARG, "null counts"};
         c->reserve(40 * (n / BFQ_RS_BLOCK_ELEMS + 64) * 8 + (64u << 20));
         memset(counts36, 0, 36 * sizeof(uint64_t));
@@ -139,7 +114,7 @@ __global__ __launch_bounds__(256) void k_glob_init_out(const u8 *__restrict__ T8
 }
 extern "C" int bfq_glob_init_out(bfq_ctx *c, const uint8_t *d_T8, const uint8_t *d_Q8, uint64_t n, uint8_t *d_sym, uint8_t *d_qual)
 {
-    return guarded_g(c, [&] {
+    return guarded(c, [&] {
         if (n) KLAUNCH(c, K_MISC, 4.0 * (double)n, k_glob_init_out, bfq_grid(n, 256), 256, d_T8, d_Q8, n, d_sym, d_qual);
         c->sync();
         c->profCollect();
@@ -149,7 +124,7 @@ extern "C" int bfq_glob_init_out(bfq_ctx *c, const uint8_t *d_T8, const uint8_t 
 extern "C" int bfq_glob_run_pile(bfq_ctx *c, const uint8_t *d_T8, const uint8_t *d_Q8, uint64_t n, int s, int s2, uint8_t *d_sym,
                                  uint8_t *d_qual, bfq_stats *st)
 {
-    return guarded_g(c, [&] {
+    return guarded(c, [&] {
         if (st) memset(st, 0, sizeof *st);
         if (s < 1 || s > 5 || s2 < 0 || s2 > 5) throw BfqError{BFQ_E_ARG, "pile symbols: first 1..5 (A C G N T), second 0..5"};
         if (c->P.K < 2) throw BfqError{BFQ_E_ARG, "global mode needs -k >= 2 (clusters must not cross the two-symbol piles)"};
@@ -199,7 +174,7 @@ __global__ __launch_bounds__(256) void k_bin_lines(u8 *__restrict__ qs, u64 n)
 // the parts whose shares of every output are reported).
 extern "C" int bfq_glob_finish(bfq_ctx *c, uint8_t *d_dna, uint8_t *d_qs, bfq_fastq_job *J)
 {
-    return guarded_g(c, [&] {
+    return guarded(c, [&] {
         if (!J) throw BfqError{BFQ_E_ARG, "null job"};
         DevFastq fq;
         reparse(c, &fq, 0);

@@ -41,7 +41,7 @@ __device__ __forceinline__ void store_tail(u8 *dst, u64 v, u32 cnt)
 // front of the read (len mod 16 bytes) needs narrower stores.
 // NL: the outputs are the line streams of BFQzip.py --m2/--m3 (OUT.fq.dna / OUT.fq.qs: read i at roff[i] + i, followed
 // by a newline) instead of the reads back to back.  Reads [first, first + count).
-template <int NT, int NL>
+template <int NL>
 __global__ __launch_bounds__(256) void k_invert(RankIndex R, u64 first, u64 count, const u64 *__restrict__ roff, int B,
                                                 u8 *__restrict__ out_bases, u8 *__restrict__ out_quals, DevCounters *cnt)
 {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_invert(RankIndex R, u64 first, u64 coun
         u32 have = 0;                                                  // bytes in the current chunk (filled from the top)
         bool bad = false;
         while (pos > lo) {
-            u64 x = NT ? __builtin_nontemporal_load(R.lfq + j) : R.lfq[j];
+            u64 x = __builtin_nontemporal_load(R.lfq + j);           // nontemporal loads: -15% (L1 bypass)
             u32 code = lfq_code(x);
             u64 nx = lfq_next(x);
             if (!code || nx >= R.n) { bad = true; break; }           // walk ended before the read did
@@ -110,10 +110,8 @@ void bfq_invert(bfq_ctx *c, const RankIndex &R, u64 N, const u64 *d_roff, int B,
 {
     if (count == ~0ull) count = N - first;
     if (!count) return;
-    const int nt = c->env.invertNt;                      // nontemporal loads: -15% (L1 bypass)
     const double bytes = 68.0 * (double)(R.n - N) * ((double)count / (double)N);
-#define INV_LAUNCH(NTV, NLV) KLAUNCH(c, K_INVERT, bytes, (k_invert<NTV, NLV>), bfq_grid(count, 256), 256, R, first, count, d_roff, B, out_bases, out_quals, c->d_cnt)
-    if (nt) { if (lines) INV_LAUNCH(1, 1); else INV_LAUNCH(1, 0); }
-    else { if (lines) INV_LAUNCH(0, 1); else INV_LAUNCH(0, 0); }
+#define INV_LAUNCH(NLV) KLAUNCH(c, K_INVERT, bytes, k_invert<NLV>, bfq_grid(count, 256), 256, R, first, count, d_roff, B, out_bases, out_quals, c->d_cnt)
+    if (lines) INV_LAUNCH(1); else INV_LAUNCH(0);
 #undef INV_LAUNCH
 }

@@ -1,6 +1,6 @@
 // placement.hip -- does WHERE two buffers lie inside one large allocation change the rate of moving data between them?
 // bench.py's per-pass times of k_radix_scatter alternate (B->A 32-36 ms, A->B 26-28 ms) and flip when the two record
-// buffers swap places in the arena (BFQ_AB_SWAP=1): this isolates the effect with plain kernels.
+// buffers swap places in the arena (round 3's BFQ_AB_SWAP=1 experiment, since removed): this isolates the effect with plain kernels.
 //   hipcc -O3 --offload-arch=gfx950 placement.hip -o placement && ./placement [GiB of the allocation, default 120]
 // 1. read and write rate of every 8 GiB slice of the allocation;
 // 2. copy 27 GiB low -> high and high -> low (streaming, 16 B per lane);
