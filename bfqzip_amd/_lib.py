@@ -24,6 +24,7 @@ SYMBOLS = [
     "bfq_prof_enable", "bfq_prof_reset", "bfq_prof_count", "bfq_prof_get", "bfq_prof_trace_select", "bfq_prof_trace",
     "bfq_stream_bound", "bfq_stream_raw_len", "bfq_stream_compress", "bfq_stream_decompress",
     "bfq_stream_reserve", "bfq_stream_compress_device", "bfq_stream_ebwt_decode",
+    "bfq_fastq_restore_bound", "bfq_fastq_restore", "bfq_fastq_restore_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -158,6 +159,10 @@ def lib():
         L.bfq_stream_decompress.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_stream_reserve.argtypes = [vp, u64]
         L.bfq_stream_ebwt_decode.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.bfq_fastq_restore_bound.restype = C.c_int64
+        L.bfq_fastq_restore_bound.argtypes = [vp, u64, vp, u64, vp, u64]
+        L.bfq_fastq_restore.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.bfq_fastq_restore_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.POINTER(u64), C.POINTER(u64)]
         L.bfq_stream_compress_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]
         L.bfq_prof_reset.argtypes = [vp]

@@ -424,6 +424,42 @@ class Engine:
                                                min(len(dna), len(qs)), C.byref(sl), C.byref(nr)))
         return dna[:int(sl.value)], qs[:int(sl.value)], int(nr.value)
 
+    # ---- the way back: containers -> FASTQ text (bfq_fastq_restore)
+    def fastq_restore(self, dna, qs, hdr=None, out=None):
+        """The FASTQ text of a collection from the containers of its streams (fastq_job(compress=1 / 2 / 3), stream_compress,
+        the .bsc files of parallel.py --compress): (text as a uint8 array, n_reads).  hdr=None: every header line is "@".
+        `out`: a uint8 array to fill (e.g. PinnedBuffer.array); the result is a view of it.  Streams that do not belong
+        together raise BfqError (BFQ_E_ARG, the message names the first offending read) and leave `out` untouched."""
+        dna, qs = _u8(dna), _u8(qs)
+        hdr = _u8(hdr) if hdr is not None else None
+        if out is None:
+            bound = int(self.L.bfq_fastq_restore_bound(_ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0))
+            if bound < 0:
+                raise BfqError(-1, "not a container (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQEBWT1)")
+            out = np.empty(max(bound, 1), np.uint8)
+        ol, nr = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.L.bfq_fastq_restore(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0,
+                                          _ptr(out), len(out), C.byref(ol), C.byref(nr)))
+        return out[:int(ol.value)], int(nr.value)
+
+    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path):
+        """bfq_fastq_restore_fd on named files (hdr_path may be None); returns (bytes written, n_reads)."""
+        import os
+        fds = []
+        try:
+            for p in (dna_path, qs_path, hdr_path):
+                fds.append(os.open(p, os.O_RDONLY) if p is not None else -1)
+            fds.append(os.open(out_path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            ol, nr = C.c_uint64(0), C.c_uint64(0)
+            size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
+            self._ck(self.L.bfq_fastq_restore_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]), fds[3],
+                                                 C.byref(ol), C.byref(nr)))
+            return int(ol.value), int(nr.value)
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
     def stream_compress_device(self, d_in, n, d_out, cap):
         """Device-resident form (after stream_reserve(n)); returns the container's length."""
         ol = C.c_uint64(0)

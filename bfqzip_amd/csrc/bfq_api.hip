@@ -22,7 +22,8 @@
 const char *const BFQ_KERNEL_NAMES[K_NUM] = {
     "k_text_from_reads", "k_pack3", "k_build_keys", "k_radix_hist", "k_scan", "k_radix_scatter", "k_huge_round",
     "k_cluster_big", "k_refine_chunk", "k_refine_big", "k_emit_bwt", "k_lf_count", "k_lf_build", "k_lcp_flags",
-    "k_cluster", "k_invert_count", "k_invert", "k_synth", "k_fastq", "k_bfs", "k_codec", "misc"};
+    "k_cluster", "k_invert_count", "k_invert", "k_synth", "k_fastq", "k_bfs", "k_codec", "misc",
+    "k_restore_index", "k_fq_format_lines"};
 
 static thread_local std::string g_createErr;
 
@@ -1011,34 +1012,7 @@ static void fastq_build_ebwt_core(bfq_ctx *c, TextSrc text, int term_out, HostRe
 }
 
 // ---- the one-shot tools (gsufsort / eGap / bfq_int / bfq_ext processes): files in, files out.
-// An output file: mapped and pre-faulted in the background when it is a regular file, written with pwrite otherwise.
-struct OutFile {
-    int fd = -1;
-    bfq_outmap *m = nullptr;
-    HostRef at(u64 off) const
-    {
-        if (!m) return HostRef::file(fd, off);
-        HostRef h = HostRef::mem(bfq_outmap_ptr(m) + off);
-        h.om = m; h.off = off;
-        return h;
-    }
-    void open(int f, u64 mapLen, u64 prefault)
-    {
-        fd = f;
-        if (f < 0) return;
-        m = bfq_outmap_take(f, mapLen);
-        if (m) bfq_outmap_extend(m, prefault);
-        else m = bfq_outmap_open(f, mapLen, prefault);
-    }
-    bool close(u64 finalLen)
-    {
-        bool ok = true;
-        if (m) ok = bfq_outmap_close(m, finalLen);
-        else if (fd >= 0) ok = ftruncate(fd, (off_t)finalLen) == 0 || errno == EINVAL;   // EINVAL: not a regular file
-        m = nullptr;
-        return ok;
-    }
-};
+// (an output file: OutFile, bfq_internal.h)
 static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int term_out, int bwt_fd, int qs_fd, int lcp_fd, int lcp_bytes,
                                      uint64_t *n_rows, uint64_t *n_reads)
 {
@@ -1567,72 +1541,84 @@ __global__ __launch_bounds__(256) void k_ebwt_mark(const u8 *__restrict__ sym, c
 }
 // eBWT-domain containers (bfq_fastq_job.compress_streams = 2) back to the line streams OUT.fq.dna / OUT.fq.qs: the two
 // containers are decoded on the device, the LF table is built from the rows and the reads are walked out (steps 4 of the
-// path; no clusters: the rows already hold the smoothed result).
+// path; no clusters: the rows already hold the smoothed result).  res != nullptr: the streams stay on the device for the
+// caller (bfq_fastq_restore); *stream_len / *n_reads are set as soon as the header has been checked.
+void bfq_ebwt_decode_lines(bfq_ctx *c, const u8 *h_bwtz, u64 len_b, const u8 *h_qsz, u64 len_q, u8 *h_dna, u8 *h_qs, u64 cap,
+                           uint64_t *stream_len, uint64_t *n_reads, size_t extraWs, EbwtLines *res)
+{
+    if (!h_bwtz || !h_qsz || len_b < 40 || memcmp(h_bwtz, "BFQEBWT1", 8)) throw BfqError{BFQ_E_ARG, "not a BFQEBWT1 stream"};
+    u64 n = 0, N = 0, symLen = 0;
+    u32 tb = 0, flags = 0;
+    memcpy(&n, h_bwtz + 8, 8); memcpy(&N, h_bwtz + 16, 8); memcpy(&tb, h_bwtz + 24, 4); memcpy(&flags, h_bwtz + 28, 4); memcpy(&symLen, h_bwtz + 32, 8);
+    const bool qsByRead = flags & 1u;
+    const BfqError bad{BFQ_E_ARG, "damaged BFQEBWT1 stream"};
+    if (symLen > len_b - 40 || N > n) throw bad;
+    const u8 *h_sym = h_bwtz + 40, *h_pat = h_bwtz + 40 + symLen;
+    const u64 patLen = len_b - 40 - symLen;
+    if (bfq_codec_raw_len(h_sym, symLen) != n || bfq_codec_raw_len(h_pat, patLen) != n || bfq_codec_raw_len(h_qsz, len_q) != n) throw bad;
+    if (n > cap) throw BfqError{BFQ_E_ARG, "output buffer too small for the streams"};
+    if (stream_len) *stream_len = n;
+    if (n_reads) *n_reads = N;
+    if (res) { res->n = n; res->N = N; }
+    if (!n) return;
+    const bool keepQs = res && qsByRead;                       // the decoded read-order qualities are a result of their own
+    c->reserve(ws_need_given(n, N, 5 * n + len_b + len_q + bfq_codec_workspace(n) / 2 + (64u << 20) + extraWs + (keepQs ? n + 4096 : 0)));
+    c->zeroCounters();
+    c->n = n; c->N = N;
+    c->d_bwt = c->alloc<u8>(n + 64); c->d_qual = c->alloc<u8>(n + 64);
+    u8 *d_sym = c->alloc<u8>(n + 64);                          // the symbols the reads get; d_bwt = the eBWT the walk navigates by
+    u8 *d_qsLine = keepQs ? c->alloc<u8>(n + 64) : nullptr;
+    {
+        const size_t mk = c->mark();
+        u8 *d_z = c->alloc<u8>((len_b > len_q ? len_b : len_q) + 64);
+        bfq_upload(c, d_z, h_sym, symLen);
+        bfq_codec_decompress_device(c, h_sym, d_z, symLen, d_sym, n);
+        bfq_upload(c, d_z, h_pat, patLen);
+        bfq_codec_decompress_device(c, h_pat, d_z, patLen, c->d_bwt, n);
+        KLAUNCH(c, K_MISC, 3.0 * (double)n, k_ebwt_unpatch, bfq_grid(n, 256 * 16), 256, (const u8 *)d_sym, c->d_bwt, n);
+        bfq_upload(c, d_z, h_qsz, len_q);
+        u8 *d_q0 = d_qsLine ? d_qsLine : c->d_qual;
+        bfq_codec_decompress_device(c, h_qsz, d_z, len_q, d_q0, n);
+        if (qsByRead) {                                        // already the line stream OUT.fq.qs: out as it is; the walk carries dummies
+            if (h_qs) bfq_download(c, h_qs, d_q0, n);
+            HIP_CHECK(hipMemsetAsync(c->d_qual, '!', n, c->stream));
+        }
+        c->release(mk);
+    }
+    u64 *d_roff = c->alloc<u64>(N + 2);
+    u32 *lens = c->alloc<u32>(N + 2);
+    u8 *d_dna = c->alloc<u8>(n + 64), *d_q = c->alloc<u8>(n + 64);
+    const size_t mWalk = c->mark();
+    const bfq_params keep = c->P;
+    c->P.term = (int)tb; c->P.B = 0;                           // the rows are binned already
+    try {
+        RankIndex R = bfq_rank_build(c, c->d_bwt, c->d_qual, n, c->P.term, nullptr);
+        KLAUNCH(c, K_MISC, 2.0 * (double)n, k_ebwt_mark, bfq_grid(n, 256 * 16), 256, (const u8 *)d_sym, (const u8 *)c->d_bwt, n, R.lfq);
+        c->fetchCounters();
+        if (c->h_cnt.tot[0] != N) throw BfqError{BFQ_E_NOT_EBWT, "terminator rows do not match the header"};
+        bool guessed = false;
+        if (N && (n - N) % N == 0) { bfq_fixed_offsets(c, N, (n - N) / N, d_roff); guessed = true; }
+        else count_lengths(c, R, d_roff, lens);
+        StreamOut so{h_dna, qsByRead ? nullptr : h_qs};
+        invert_lines(c, R, d_roff, d_dna, d_q, &so);
+        c->fetchCounters();
+        if (guessed && c->h_cnt.errInvert) {                   // not all of one length after all
+            HIP_CHECK(hipMemsetAsync(&c->d_cnt->errInvert, 0, sizeof(u64), c->stream));
+            count_lengths(c, R, d_roff, lens);
+            invert_lines(c, R, d_roff, d_dna, d_q, &so);
+            c->fetchCounters();
+        }
+        c->P = keep;
+    } catch (...) { c->P = keep; throw; }
+    c->profCollect();
+    check_counters(c);
+    c->d_bwt = c->d_qual = nullptr;
+    if (res) { res->dna = d_dna; res->qs = d_qsLine ? d_qsLine : d_q; c->release(mWalk); }   // the LF table is dead: its space is the caller's
+}
 extern "C" int bfq_stream_ebwt_decode(bfq_ctx *c, const uint8_t *h_bwtz, uint64_t len_b, const uint8_t *h_qsz, uint64_t len_q,
                                       uint8_t *h_dna, uint8_t *h_qs, uint64_t cap, uint64_t *stream_len, uint64_t *n_reads)
 {
     return guarded(c, [&] {
-        if (!h_bwtz || !h_qsz || len_b < 40 || memcmp(h_bwtz, "BFQEBWT1", 8)) throw BfqError{BFQ_E_ARG, "not a BFQEBWT1 stream"};
-        u64 n = 0, N = 0, symLen = 0;
-        u32 tb = 0, flags = 0;
-        memcpy(&n, h_bwtz + 8, 8); memcpy(&N, h_bwtz + 16, 8); memcpy(&tb, h_bwtz + 24, 4); memcpy(&flags, h_bwtz + 28, 4); memcpy(&symLen, h_bwtz + 32, 8);
-        const bool qsByRead = flags & 1u;
-        const BfqError bad{BFQ_E_ARG, "damaged BFQEBWT1 stream"};
-        if (symLen > len_b - 40 || N > n) throw bad;
-        const u8 *h_sym = h_bwtz + 40, *h_pat = h_bwtz + 40 + symLen;
-        const u64 patLen = len_b - 40 - symLen;
-        if (bfq_codec_raw_len(h_sym, symLen) != n || bfq_codec_raw_len(h_pat, patLen) != n || bfq_codec_raw_len(h_qsz, len_q) != n) throw bad;
-        if (n > cap) throw BfqError{BFQ_E_ARG, "output buffer too small for the streams"};
-        if (stream_len) *stream_len = n;
-        if (n_reads) *n_reads = N;
-        if (!n) return;
-        c->reserve(ws_need_given(n, N, 5 * n + len_b + len_q + bfq_codec_workspace(n) / 2 + (64u << 20)));
-        c->zeroCounters();
-        c->n = n; c->N = N;
-        c->d_bwt = c->alloc<u8>(n + 64); c->d_qual = c->alloc<u8>(n + 64);
-        u8 *d_sym = c->alloc<u8>(n + 64);                          // the symbols the reads get; d_bwt = the eBWT the walk navigates by
-        {
-            const size_t mk = c->mark();
-            u8 *d_z = c->alloc<u8>((len_b > len_q ? len_b : len_q) + 64);
-            bfq_upload(c, d_z, h_sym, symLen);
-            bfq_codec_decompress_device(c, h_sym, d_z, symLen, d_sym, n);
-            bfq_upload(c, d_z, h_pat, patLen);
-            bfq_codec_decompress_device(c, h_pat, d_z, patLen, c->d_bwt, n);
-            KLAUNCH(c, K_MISC, 3.0 * (double)n, k_ebwt_unpatch, bfq_grid(n, 256 * 16), 256, (const u8 *)d_sym, c->d_bwt, n);
-            bfq_upload(c, d_z, h_qsz, len_q);
-            bfq_codec_decompress_device(c, h_qsz, d_z, len_q, c->d_qual, n);
-            if (qsByRead) {                                        // already the line stream OUT.fq.qs: out as it is; the walk carries dummies
-                if (h_qs) bfq_download(c, h_qs, c->d_qual, n);
-                HIP_CHECK(hipMemsetAsync(c->d_qual, '!', n, c->stream));
-            }
-            c->release(mk);
-        }
-        u64 *d_roff = c->alloc<u64>(N + 2);
-        u32 *lens = c->alloc<u32>(N + 2);
-        u8 *d_dna = c->alloc<u8>(n + 64), *d_q = c->alloc<u8>(n + 64);
-        const bfq_params keep = c->P;
-        c->P.term = (int)tb; c->P.B = 0;                           // the rows are binned already
-        try {
-            RankIndex R = bfq_rank_build(c, c->d_bwt, c->d_qual, n, c->P.term, nullptr);
-            KLAUNCH(c, K_MISC, 2.0 * (double)n, k_ebwt_mark, bfq_grid(n, 256 * 16), 256, (const u8 *)d_sym, (const u8 *)c->d_bwt, n, R.lfq);
-            c->fetchCounters();
-            if (c->h_cnt.tot[0] != N) throw BfqError{BFQ_E_NOT_EBWT, "terminator rows do not match the header"};
-            bool guessed = false;
-            if (N && (n - N) % N == 0) { bfq_fixed_offsets(c, N, (n - N) / N, d_roff); guessed = true; }
-            else count_lengths(c, R, d_roff, lens);
-            StreamOut so{h_dna, qsByRead ? nullptr : h_qs};
-            invert_lines(c, R, d_roff, d_dna, d_q, &so);
-            c->fetchCounters();
-            if (guessed && c->h_cnt.errInvert) {                   // not all of one length after all
-                HIP_CHECK(hipMemsetAsync(&c->d_cnt->errInvert, 0, sizeof(u64), c->stream));
-                count_lengths(c, R, d_roff, lens);
-                invert_lines(c, R, d_roff, d_dna, d_q, &so);
-                c->fetchCounters();
-            }
-            c->P = keep;
-        } catch (...) { c->P = keep; throw; }
-        c->profCollect();
-        check_counters(c);
-        c->d_bwt = c->d_qual = nullptr;
+        bfq_ebwt_decode_lines(c, h_bwtz, len_b, h_qsz, len_q, h_dna, h_qs, cap, stream_len, n_reads, 0, nullptr);
     });
 }

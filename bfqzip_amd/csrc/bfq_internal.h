@@ -2,6 +2,8 @@
 // shared by the .hip translation units of libbfqhip.so.  Not part of the ABI.
 #pragma once
 #include <stdlib.h>
+#include <errno.h>
+#include <unistd.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <functional>
@@ -29,7 +31,7 @@ struct BfqError {
 enum BfqKernel {
     K_TEXT = 0, K_PACK, K_KEYS, K_RADIX_HIST, K_SCAN, K_RADIX_SCATTER, K_HUGE_ROUND, K_CLUSTER_BIG,
     K_REFINE_WAVE, K_REFINE_BIG, K_EMIT, K_RANK_BUILD, K_RANK_FINAL, K_LCP_FLAGS, K_CLUSTER,
-    K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_NUM
+    K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -177,6 +179,36 @@ struct BfqAsyncUpload;
 BfqAsyncUpload *bfq_upload_begin(bfq_ctx *c, void *d_dst, HostRef src, size_t len);
 void bfq_upload_join(BfqAsyncUpload *u);
 
+// An output file of the *_fd entry points: mapped and pre-faulted in the background when it is a regular file, written with
+// pwrite otherwise.
+struct OutFile {
+    int fd = -1;
+    bfq_outmap *m = nullptr;
+    HostRef at(u64 off) const
+    {
+        if (!m) return HostRef::file(fd, off);
+        HostRef h = HostRef::mem(bfq_outmap_ptr(m) + off);
+        h.om = m; h.off = off;
+        return h;
+    }
+    void open(int f, u64 mapLen, u64 prefault)
+    {
+        fd = f;
+        if (f < 0) return;
+        m = bfq_outmap_take(f, mapLen);
+        if (m) bfq_outmap_extend(m, prefault);
+        else m = bfq_outmap_open(f, mapLen, prefault);
+    }
+    bool close(u64 finalLen)
+    {
+        bool ok = true;
+        if (m) ok = bfq_outmap_close(m, finalLen);
+        else if (fd >= 0) ok = ftruncate(fd, (off_t)finalLen) == 0 || errno == EINVAL;   // EINVAL: not a regular file
+        m = nullptr;
+        return ok;
+    }
+};
+
 #define KLAUNCH(ctx, kid, bytes, kernel, grid, block, ...)                                     \
     do {                                                                                       \
         (ctx)->profBegin((kid), (double)(bytes));                                              \
@@ -320,5 +352,15 @@ void bfq_fastq_parse(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq);
 u64 bfq_fastq_format(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, int mode, const u8 *d_hdr,
                      u64 hdrLen, const DevFastq *fq, u8 **d_out, u64 **recOffOut = nullptr, bool lines = false);
 void bfq_fastq_hdr_stream(bfq_ctx *c, u64 N, const u8 *d_fastq, const DevFastq *fq, u8 **d_hdr, u64 *hdrLen, u64 **hOffOut = nullptr);
+// records from two line streams and an index made elsewhere (bfq_restore.hip): k_fq_format with lines = 1; d_hdr == nullptr: "@"
+void bfq_fastq_format_lines(bfq_ctx *c, const u8 *d_dna, const u8 *d_qs, const u64 *d_roff, const u8 *d_hdr, const u64 *hStart,
+                            const u32 *hLen, const u64 *recOff, u64 N, u64 outLen, u8 *d_out);
 void bfq_fastq_part_index(bfq_ctx *c, const DevFastq *fq, const u64 *h_pstart, int nparts, u64 *d_idx);
 void bfq_pick_u64(bfq_ctx *c, const u64 *d_src, const u64 *d_idx, int count, u64 addIdx, u64 *d_out);
+
+// eBWT-domain containers (bfq_api.hip): the body of bfq_stream_ebwt_decode.  Both line streams (n bytes each) stay in the
+// arena and are returned in *res when res != nullptr; the arena is reserved here, once, with extraWs bytes for the caller's
+// own use after the walk (the LF table's space is handed back to the caller as well).  h_dna / h_qs may be nullptr.
+struct EbwtLines { u8 *dna = nullptr, *qs = nullptr; u64 n = 0, N = 0; };
+void bfq_ebwt_decode_lines(bfq_ctx *c, const u8 *h_bwtz, u64 len_b, const u8 *h_qsz, u64 len_q, u8 *h_dna, u8 *h_qs, u64 cap,
+                           uint64_t *stream_len, uint64_t *n_reads, size_t extraWs, EbwtLines *res);

@@ -1,0 +1,344 @@
+// bfq_restore.hip -- the way back: compressed streams in, FASTQ text out, in one call (include/bfqzip_hip.h,
+// bfq_fastq_restore*).  The reference leaves this to `7z x` / `bsc d` and `paste` (BFQzip.py writes OUT.fq.dna / OUT.fq.qs /
+// OUT.h and compresses each, :192-275); the record layout is bfq_int's (bfq_int.cpp:797-810).
+//   host    the members of every input are walked and their raw lengths summed; the arena is reserved once from them
+//   device  every member is decoded into its slice of two (three) stream buffers (k_codec.hip / k_dnac.hip; eBWT-domain
+//           containers through the LF walk of bfq_ebwt_decode_lines), the line ends of each stream are compacted
+//           (k_nl_count / k_nl_write), k_restore_index checks that the streams describe the same reads and builds the
+//           record index, k_fq_format writes the text
+// The decoded streams never leave the device: the containers go up, the text comes down.
+#include <string.h>
+#include <stdio.h>
+#include <sys/mman.h>
+#include <algorithm>
+#include "bfq_internal.h"
+#include "bfq_device.h"
+
+// what k_restore_index found: (read index << 3) | reason, the smallest of all (so: the first offending read, and of two
+// reasons at one read the one with the smaller code); RS_NONE: the streams fit
+#define RS_NONE      (~0ull)
+#define RS_LEN       1u      // DNA line i and quality line i differ in length
+#define RS_LONG      2u      // line i is longer than BFQ_MAX_READ_LEN
+#define RS_COUNT     3u      // the streams have different numbers of lines (index: the first read without a partner)
+#define RS_HDR_COUNT 4u      // the header stream has another number of lines than there are reads
+
+// One pass over the line-end arrays of the DNA, quality and (optional) header stream.  DNA line i and quality line i
+// must be equally long, so the two arrays must be identical.  Per read: roff[i] = start of DNA line i minus i (= bases
+// before it: read i lies at roff[i] + i in both line streams), the header span, the size of the record for the scan.
+__global__ __launch_bounds__(256) void k_restore_index(const u64 *__restrict__ endD, u64 nD, const u64 *__restrict__ endQ, u64 nQ,
+                                                       const u64 *__restrict__ endH, u64 nH, int haveHdr, u64 *__restrict__ roff,
+                                                       u64 *__restrict__ hStart, u32 *__restrict__ hLen, u32 *__restrict__ sizes,
+                                                       unsigned long long *__restrict__ err)
+{
+    const u64 N = nD < nQ ? nD : nQ;
+    const u64 tid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u64 bad = RS_NONE;
+    if (tid == 0) {
+        if (nD != nQ) bad = (N << 3) | RS_COUNT;
+        if (haveHdr && nH != N) { const u64 b = ((nH < N ? nH : N) << 3) | RS_HDR_COUNT; if (b < bad) bad = b; }
+        if (N == 0) roff[0] = 0;
+    }
+    for (u64 i = tid; i < N; i += (u64)gridDim.x * blockDim.x) {
+        const u64 e = endD[i], s = i ? endD[i - 1] + 1 : 0;
+        u64 L = e - s;
+        if (endQ[i] != e) { const u64 b = (i << 3) | RS_LEN; if (b < bad) bad = b; }
+        if (L > BFQ_MAX_READ_LEN) { const u64 b = (i << 3) | RS_LONG; if (b < bad) bad = b; L = 0; }
+        roff[i] = s - i;
+        if (i == N - 1) roff[N] = e + 1 - N;
+        u32 hl = 1;                                              // "@"
+        if (haveHdr) {
+            u64 hs = 0;
+            hl = 0;
+            if (i < nH) { hs = i ? endH[i - 1] + 1 : 0; hl = (u32)(endH[i] - hs); }
+            hStart[i] = hs; hLen[i] = hl;
+        }
+        sizes[i] = hl + 2u * (u32)L + 5u;
+    }
+    if (bad != RS_NONE && bad < *(volatile unsigned long long *)err) atomicMin(err, (unsigned long long)bad);
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------
+struct RsSrc { const u8 *h = nullptr; u64 len = 0; };          // a compressed input as host memory (its headers are parsed there)
+struct RsPlan {
+    bool ebwt = false;
+    u64 rawD = 0, rawQ = 0, rawH = 0;       // decoded bytes of every stream (all members)
+    u64 maxMember = 0;                      // ... of the largest single member (sizes the codec's workspace)
+    u64 readsBound = 0;                     // upper bound of the number of reads
+    u64 textBound = 0;                      // ... and of the text
+};
+
+static u64 rs_get64(const u8 *p) { u64 v; memcpy(&v, p, 8); return v; }
+
+// members of one input, back to back: raw length of all of them; *reads: the read count when every member states one
+// (BFQDNAC1), else ~0
+static u64 rs_walk(const RsSrc &s, const char *what, u64 *maxMember, u64 *reads)
+{
+    if (!s.h || !s.len) throw BfqError{BFQ_E_ARG, std::string(what) + ": not a container (empty input)"};
+    u64 raw = 0, nr = 0;
+    for (u64 pos = 0; pos < s.len;) {
+        u64 ml = 0, n = 0;
+        try {
+            ml = bfq_codec_member_len(s.h + pos, s.len - pos);
+            n = bfq_codec_raw_len(s.h + pos, ml);
+        } catch (const BfqError &e) {
+            char b[96];
+            snprintf(b, sizeof b, ": not a container at byte %llu (", (unsigned long long)pos);
+            throw BfqError{BFQ_E_ARG, std::string(what) + b + e.msg + ")"};
+        }
+        if (nr != ~0ull && ml >= 72 && !memcmp(s.h + pos, "BFQDNAC1", 8) && rs_get64(s.h + pos + 16) <= n) nr += rs_get64(s.h + pos + 16);
+        else nr = ~0ull;
+        if (n > (1ull << 46) || raw + n < raw) throw BfqError{BFQ_E_ARG, std::string(what) + ": not a container (raw length)"};
+        raw += n;
+        if (n > *maxMember) *maxMember = n;
+        pos += ml;
+    }
+    if (reads) *reads = nr;
+    return raw;
+}
+
+static void rs_plan(const RsSrc &dna, const RsSrc &qs, const RsSrc &hdr, bool haveHdr, RsPlan &P)
+{
+    if (!dna.h || !qs.h) throw BfqError{BFQ_E_ARG, "null argument"};
+    u64 reads = ~0ull;
+    if (dna.len >= 8 && !memcmp(dna.h, "BFQEBWT1", 8)) {
+        // "BFQEBWT1" | rows | reads | terminator | flags | bytes of the symbols' container | that container | the patches' container
+        const BfqError bad{BFQ_E_ARG, "dna: damaged BFQEBWT1 stream"};
+        if (dna.len < 40) throw bad;
+        const u64 n = rs_get64(dna.h + 8), N = rs_get64(dna.h + 16), symLen = rs_get64(dna.h + 32);
+        if (symLen > dna.len - 40 || N > n) throw bad;
+        u64 mm = 0;
+        const RsSrc sym{dna.h + 40, symLen};
+        if (rs_walk(sym, "dna (eBWT symbols)", &mm, nullptr) != n) throw bad;
+        const u8 *pat = dna.h + 40 + symLen;
+        const u64 patLen = dna.len - 40 - symLen;
+        u64 pm = 0;
+        try { pm = bfq_codec_member_len(pat, patLen); } catch (const BfqError &) { throw bad; }
+        if (pm < patLen) {
+            if (patLen - pm >= 8 && !memcmp(pat + pm, "BFQEBWT1", 8))
+                throw BfqError{BFQ_E_ARG, "dna: more than one BFQEBWT1 member (eBWT-domain containers of several blocks are not supported)"};
+            throw bad;
+        }
+        if (bfq_codec_raw_len(pat, patLen) != n) throw bad;
+        P.ebwt = true;
+        P.rawD = n;
+        reads = N;
+        P.rawQ = rs_walk(qs, "qs", &mm, nullptr);
+        if (P.rawQ != n) {
+            char b[160];
+            snprintf(b, sizeof b, "qs: the quality container decodes to %llu bytes, the eBWT has %llu rows: not of the same collection",
+                     (unsigned long long)P.rawQ, (unsigned long long)n);
+            throw BfqError{BFQ_E_ARG, b};
+        }
+        if (bfq_codec_member_len(qs.h, qs.len) != qs.len) throw BfqError{BFQ_E_ARG, "qs: one member expected beside a BFQEBWT1 stream"};
+        P.maxMember = n;
+    } else {
+        P.rawD = rs_walk(dna, "dna", &P.maxMember, &reads);
+        P.rawQ = rs_walk(qs, "qs", &P.maxMember, nullptr);
+    }
+    if (haveHdr) P.rawH = rs_walk(hdr, "hdr", &P.maxMember, nullptr);
+    // every line costs its stream one byte at least (a last line without '\n' gets one)
+    const u64 byBytes = std::min(P.rawD, P.rawQ) + 1;
+    P.readsBound = reads != ~0ull && reads < byBytes ? reads + 1 : byBytes;
+    P.textBound = P.rawD + P.rawQ + 2 + 2 * P.readsBound + (haveHdr ? P.rawH + 1 : 2 * P.readsBound);   // "+\n", and "@\n" without headers
+}
+
+extern "C" int64_t bfq_fastq_restore_bound(const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                           const uint8_t *h_hdr, uint64_t hdr_len)
+{
+    try {
+        RsPlan P;
+        rs_plan(RsSrc{h_dna, dna_len}, RsSrc{h_qs, qs_len}, RsSrc{h_hdr, hdr_len}, h_hdr != nullptr, P);
+        return (int64_t)P.textBound;
+    } catch (const BfqError &) { return -1; }
+}
+
+// all members of `s` into d_out (raw bytes in all); d_z: room for the compressed bytes
+static void rs_decode(bfq_ctx *c, const RsSrc &s, u8 *d_z, u8 *d_out, u64 raw)
+{
+    bfq_upload(c, d_z, s.h, s.len);
+    u64 got = 0;
+    for (u64 pos = 0; pos < s.len;) {
+        const u64 ml = bfq_codec_member_len(s.h + pos, s.len - pos);
+        got += bfq_codec_decompress_device(c, s.h + pos, d_z + pos, ml, d_out + got, raw - got);
+        pos += ml;
+    }
+    if (got != raw) throw BfqError{BFQ_E_ARG, "damaged container (raw length)"};
+}
+
+static size_t rs_index_bytes(const RsPlan &P)
+{
+    // line ends of three streams, roff, hStart, hLen, sizes, recOff per read; chunk counts of the line index and of the scans
+    return 64 * (size_t)(P.readsBound + 64) + 3 * 32 * (size_t)((std::max(P.rawD, std::max(P.rawQ, P.rawH)) >> 12) + 64) + (1u << 20);
+}
+
+// sink: where the text goes once it is known to be good.  put(d_text, len) is called at most once.
+struct RsSink {
+    u64 cap = ~0ull;
+    std::function<void(u64)> sized;                 // the length of the text is known (before it is formatted)
+    std::function<void(const u8 *, u64)> put;
+};
+
+static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const RsSrc &hdr, bool haveHdr, const RsSink &sink,
+                         uint64_t *out_len, uint64_t *n_reads)
+{
+    if (out_len) *out_len = 0;
+    if (n_reads) *n_reads = 0;
+    RsPlan P;
+    rs_plan(dna, qs, hdr, haveHdr, P);
+    const size_t afterDecode = rs_index_bytes(P) + P.textBound + 4096;
+    u8 *dD = nullptr, *dQ = nullptr, *dH = nullptr;
+    u64 lenD = P.rawD, lenQ = P.rawQ;
+    if (P.ebwt) {
+        const size_t hdrPart = haveHdr ? P.rawH + hdr.len + bfq_codec_workspace(P.rawH) : 0;
+        EbwtLines r;
+        bfq_phase("alloc");
+        bfq_ebwt_decode_lines(c, dna.h, dna.len, qs.h, qs.len, nullptr, nullptr, ~0ull, nullptr, nullptr, afterDecode + hdrPart + 4096, &r);
+        if (!r.n) { c->reserve(afterDecode + hdrPart + (64u << 20)); r.dna = c->alloc<u8>(64); r.qs = c->alloc<u8>(64); }
+        dD = r.dna; dQ = r.qs;
+        if (haveHdr) {
+            dH = c->alloc<u8>(P.rawH + 64);
+            const size_t mk = c->mark();
+            rs_decode(c, hdr, c->alloc<u8>(hdr.len + 64), dH, P.rawH);
+            c->release(mk);
+        }
+    } else {
+        const size_t streams = (size_t)P.rawD + P.rawQ + P.rawH + 3 * 320;
+        const size_t decode = (size_t)dna.len + qs.len + (haveHdr ? hdr.len : 0) + 3 * 320 + bfq_codec_workspace(P.maxMember);
+        bfq_phase("alloc");
+        c->reserve(streams + std::max(decode, afterDecode) + (64u << 20));
+        c->zeroCounters();
+        dD = c->alloc<u8>(P.rawD + 64); dQ = c->alloc<u8>(P.rawQ + 64);
+        if (haveHdr) dH = c->alloc<u8>(P.rawH + 64);
+        const size_t mk = c->mark();
+        u8 *zD = c->alloc<u8>(dna.len + 64), *zQ = c->alloc<u8>(qs.len + 64), *zH = haveHdr ? c->alloc<u8>(hdr.len + 64) : nullptr;
+        bfq_phase("read_h2d");
+        rs_decode(c, dna, zD, dD, P.rawD);
+        bfq_phase("gpu");
+        rs_decode(c, qs, zQ, dQ, P.rawQ);
+        if (haveHdr) rs_decode(c, hdr, zH, dH, P.rawH);
+        c->release(mk);
+    }
+    bfq_phase("gpu");
+    // line ends (a last line without '\n' gets one) and the record index
+    u64 nD = 0, nQ = 0, nH = 0;
+    const u64 *endD = bfq_line_index(c, dD, lenD, &nD);
+    const u64 *endQ = bfq_line_index(c, dQ, lenQ, &nQ);
+    const u64 *endH = haveHdr ? bfq_line_index(c, dH, P.rawH, &nH) : nullptr;
+    const u64 N = std::min(nD, nQ);
+    u64 *roff = c->alloc<u64>(N + 2), *recOff = c->alloc<u64>(N + 2);
+    u64 *hStart = haveHdr ? c->alloc<u64>(N + 1) : nullptr;
+    u32 *hLen = haveHdr ? c->alloc<u32>(N + 1) : nullptr, *sizes = c->alloc<u32>(N + 1);
+    unsigned long long *d_err = (unsigned long long *)c->alloc<u64>(1);
+    HIP_CHECK(hipMemsetAsync(d_err, 0xFF, 8, c->stream));
+    KLAUNCH(c, K_RESTORE, (haveHdr ? 48.0 : 28.0) * (double)N, k_restore_index, bfq_grid(N ? N : 1, 256), 256, endD, nD, endQ, nQ, endH, nH,
+            haveHdr ? 1 : 0, roff, hStart, hLen, sizes, d_err);
+    bfq_exscan_u32(c, sizes, recOff, N, recOff + N);
+    u64 err = RS_NONE, ol = 0;
+    HIP_CHECK(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(&ol, recOff + N, 8, hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    if (err != RS_NONE) {
+        const unsigned long long i = err >> 3;
+        char b[256];
+        switch ((u32)(err & 7)) {
+        case RS_LEN:
+            snprintf(b, sizeof b, "read %llu: its DNA line and its quality line differ in length (streams of different collections?)", i);
+            break;
+        case RS_LONG:
+            snprintf(b, sizeof b, "read %llu: line longer than BFQ_MAX_READ_LEN (%d)", i, BFQ_MAX_READ_LEN);
+            break;
+        case RS_COUNT:
+            snprintf(b, sizeof b, "read %llu has no partner: the DNA stream has %llu lines, the quality stream %llu", i, (unsigned long long)nD,
+                     (unsigned long long)nQ);
+            break;
+        default:
+            snprintf(b, sizeof b, "read %llu: the header stream has %llu lines for %llu reads", i, (unsigned long long)nH, (unsigned long long)N);
+            break;
+        }
+        throw BfqError{BFQ_E_ARG, b};
+    }
+    if (ol > sink.cap) throw BfqError{BFQ_E_ARG, "output buffer smaller than the FASTQ text (see bfq_fastq_restore_bound)"};
+    if (sink.sized) sink.sized(ol);
+    u8 *d_out = c->alloc<u8>(ol + 64);
+    bfq_fastq_format_lines(c, dD, dQ, roff, dH, hStart, hLen, recOff, N, ol, d_out);
+    sink.put(d_out, ol);
+    c->profCollect();
+    if (out_len) *out_len = ol;
+    if (n_reads) *n_reads = N;
+}
+
+extern "C" int bfq_fastq_restore(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                 const uint8_t *h_hdr, uint64_t hdr_len, uint8_t *h_out, uint64_t cap, uint64_t *out_len,
+                                 uint64_t *n_reads)
+{
+    return guarded(c, [&] {
+        if (!h_dna || !h_qs || (!h_out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
+        RsSink sink;
+        sink.cap = cap;
+        sink.put = [&](const u8 *d_text, u64 len) {
+            bfq_phase("d2h_write");
+            bfq_download(c, h_out, d_text, len);
+            c->sync();                                            // pinned destinations are written by asynchronous DMA
+        };
+        restore_core(c, RsSrc{h_dna, dna_len}, RsSrc{h_qs, qs_len}, RsSrc{h_hdr, hdr_len}, h_hdr != nullptr, sink, out_len, n_reads);
+    });
+}
+
+// a compressed input file as read-only memory (its pages are the page cache's; the staging workers copy from them)
+struct RsMap {
+    void *p = nullptr; size_t len = 0;
+    const u8 *open(int fd, u64 n)
+    {
+        if (!n) return nullptr;
+        void *m = mmap(nullptr, (size_t)n, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m == MAP_FAILED) throw BfqError{BFQ_E_IO, "cannot map an input file"};
+        p = m; len = (size_t)n;
+        (void)madvise(m, len, MADV_SEQUENTIAL);
+        return (const u8 *)m;
+    }
+    ~RsMap() { if (p) munmap(p, len); }
+};
+
+extern "C" int bfq_fastq_restore_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                    int out_fd, uint64_t *out_len, uint64_t *n_reads)
+{
+    return guarded(c, [&] {
+        if (dna_fd < 0 || qs_fd < 0 || out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
+        const bool haveHdr = hdr_fd >= 0;
+        RsMap mD, mQ, mH;
+        const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
+        const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
+        OutFile of;
+        bool opened = false;
+        try {
+            RsPlan P;
+            rs_plan(dna, qs, hdr, haveHdr, P);
+            // mapped to the bound; what is certain of it (the bases, the qualities and their newlines) is pre-faulted beside
+            // the upload and the decoding
+            of.open(out_fd, P.textBound + 4096, P.rawD + P.rawQ);
+            opened = true;
+            RsSink sink;
+            sink.sized = [&](u64 len) {
+                if (of.m && len > bfq_outmap_len(of.m)) throw BfqError{BFQ_E_IO, "output mapping smaller than the FASTQ text"};
+                if (of.m) bfq_outmap_extend(of.m, len);
+            };
+            sink.put = [&](const u8 *d_text, u64 len) {
+                bfq_write_async(c, of.at(0), d_text, len);
+                c->sync();
+                bfq_phase("d2h_write");
+                bfq_write_wait(c);
+            };
+            uint64_t ol = 0;
+            restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads);
+            if (out_len) *out_len = ol;
+            opened = false;
+            if (!of.close(ol)) throw BfqError{BFQ_E_IO, "cannot size the output file"};
+        } catch (...) {
+            if (opened) { try { bfq_write_wait(c); } catch (...) {} }
+            else { of.fd = out_fd; of.m = bfq_outmap_take(out_fd, 0); }   // (a mapping the caller registered goes with the file's contents)
+            of.close(0);
+            if (out_len) *out_len = 0;
+            throw;
+        }
+    });
+}

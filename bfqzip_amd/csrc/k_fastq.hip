@@ -278,6 +278,12 @@ u64 bfq_fastq_format(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64
     return outLen;
 }
 
+void bfq_fastq_format_lines(bfq_ctx *c, const u8 *d_dna, const u8 *d_qs, const u64 *d_roff, const u8 *d_hdr, const u64 *hStart,
+                            const u32 *hLen, const u64 *recOff, u64 N, u64 outLen, u8 *d_out)
+{
+    if (N) KLAUNCH(c, K_FQ_FORMAT, 2.0 * (double)outLen, k_fq_format, bfq_grid(N, 16), 256, d_dna, d_qs, d_roff, d_hdr, hStart, hLen, recOff, N, d_out, 1);
+}
+
 // The header stream of BFQzip.py --m3 (OUT.h = `sed -n 1~4p in.fastq`): the header lines of the parsed FASTQ `fq`, one
 // per line; *hdrLen bytes in *d_hdr, line offsets in *hOffOut.  (The OUT.fq.dna / OUT.fq.qs streams are written by the
 // inversion itself, k_invert<1>.)

@@ -146,3 +146,46 @@ def format_headers(headers):
     if n:
         out[_seg_index(off, hl)] = headers.concat()
     return out.tobytes()
+
+
+def _line_ends(a):
+    """Positions of the line ends of a line stream; a last line without newline gets one (as the device line index does)."""
+    nl = np.flatnonzero(a == 10).astype(np.int64)
+    if a.size and a[-1] != 10:
+        nl = np.append(nl, np.int64(a.size))
+    return nl
+
+
+def restore_text(dna, qs, hdr=None):
+    """The way back from the line streams OUT.fq.dna / OUT.fq.qs (and OUT.h) to the FASTQ text: for read i the header line
+    (or '@'), the DNA line, '+', the quality line -- bfq_int.cpp:797-810.  The host mirror of bfq_fastq_restore (which takes
+    the streams' containers); raises ValueError naming the first offending read (0-based) when the streams do not describe
+    the same reads."""
+    d = np.frombuffer(dna, np.uint8) if not isinstance(dna, np.ndarray) else np.asarray(dna, np.uint8)
+    q = np.frombuffer(qs, np.uint8) if not isinstance(qs, np.ndarray) else np.asarray(qs, np.uint8)
+    ed, eq = _line_ends(d), _line_ends(q)
+    n = min(len(ed), len(eq))
+    bad = []                                        # (read, reason): the smallest read wins, as on the device
+    diff = np.flatnonzero(ed[:n] != eq[:n])
+    if len(diff):
+        bad.append((int(diff[0]), "its DNA line and its quality line differ in length"))
+    if len(ed) != len(eq):
+        bad.append((n, f"no partner: the DNA stream has {len(ed)} lines, the quality stream {len(eq)}"))
+    headers = None
+    if hdr is not None:
+        h = np.frombuffer(hdr, np.uint8) if not isinstance(hdr, np.ndarray) else np.asarray(hdr, np.uint8)
+        eh = _line_ends(h)
+        if len(eh) != n:
+            bad.append((min(len(eh), n), f"the header stream has {len(eh)} lines for {n} reads"))
+        else:
+            hs = np.concatenate([[0], eh[:-1] + 1]) if n else np.zeros(0, np.int64)
+            headers = HeaderSpans(h, hs, eh)
+    if bad:
+        i, why = min(bad, key=lambda t: t[0])
+        raise ValueError(f"read {i}: {why}")
+    starts = np.concatenate([[0], ed[:-1] + 1]) if n else np.zeros(0, np.int64)
+    lens = ed - starts
+    roff = np.zeros(n + 1, np.uint64)
+    roff[1:] = np.cumsum(lens)
+    idx = _seg_index(starts, lens)
+    return format_fastq(d[idx], q[idx], roff, headers)

@@ -310,6 +310,34 @@ int bfq_stream_decompress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t
  * bfq_stream_ebwt_decode inverts them back to the line streams OUT.fq.dna / OUT.fq.qs (cap >= rows bytes each). */
 int bfq_stream_ebwt_decode(bfq_ctx *c, const uint8_t *h_bwtz, uint64_t len_b, const uint8_t *h_qsz, uint64_t len_q,
                            uint8_t *h_dna, uint8_t *h_qs, uint64_t cap, uint64_t *stream_len, uint64_t *n_reads);
+/* ---- the way back: the compressed streams of one collection -> its FASTQ text, in one call.  The reference leaves this to
+ * `7z x` / `bsc d` on every stream and `paste`; here the containers are decoded on the device, the decoded streams stay
+ * there, and only the finished text comes down.  For read i: header line i of the header stream verbatim (h_hdr NULL /
+ * hdr_fd < 0: "@"), '\n', DNA line i, "\n+\n", quality line i, '\n' -- byte for byte what bfq_fastq_run_job writes to
+ * out_fastq with the same keep_headers (bfq_int.cpp:797-810).  Accepted inputs are what the project's own writers produce:
+ *   read-order containers (compress_streams = 1, `bsc e`, parallel.py --compress): dna and qs one or more BFQDNAC1 / BFQRANS2
+ *     members back to back each, hdr one or more BFQLINE1 / BFQRANS2 members; the member boundaries of the three inputs
+ *     need not coincide;
+ *   eBWT-domain containers (compress_streams = 2 / 3): dna ONE BFQEBWT1 member, qs the one-member container of the rows'
+ *     (mode 2) or the reads' (mode 3) qualities.  More than one BFQEBWT1 member is refused with BFQ_E_ARG: no writer of the
+ *     project produces that (a sharded run writes read-order containers).
+ * An input that is not a container is BFQ_E_ARG; raw streams are not guessed at.  Streams that do not describe the same
+ * reads (line counts differ, DNA and quality line of a read differ in length, header count != read count, a line beyond
+ * BFQ_MAX_READ_LEN) are BFQ_E_ARG with a message that names the first offending read (0-based); nothing is written to
+ * h_out / out_fd then (the file is left empty).  Device memory: the decoded streams + the text + the larger of the codec's
+ * workspace for the largest member and 64 bytes per read of index, reserved once from the container headers; above
+ * ws_cap_mib: BFQ_E_NOMEM with the size in the message.  A static (BFQRANS2) DNA container states no read count: the index
+ * is then sized for one read per byte.
+ *   bfq_fastq_restore_bound: upper bound of the text; host only, reads the container headers; -1: not containers
+ *   bfq_fastq_restore      : host buffers (pinned: direct DMA); cap >= the text, else BFQ_E_ARG and *out_len = 0
+ *   bfq_fastq_restore_fd   : open files; the text goes out through the background writers into out_fd (a mapping
+ *                            registered by bfq_output_prefault is picked up), which is cut to its real length */
+int64_t bfq_fastq_restore_bound(const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                const uint8_t *h_hdr, uint64_t hdr_len);
+int bfq_fastq_restore(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                      const uint8_t *h_hdr, uint64_t hdr_len, uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads);
+int bfq_fastq_restore_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len,
+                         int hdr_fd, uint64_t hdr_len, int out_fd, uint64_t *out_len, uint64_t *n_reads);
 /* device-resident form (input and output in device memory): bfq_stream_reserve(len) sizes the workspace once */
 int bfq_stream_reserve(bfq_ctx *c, uint64_t len);
 int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
