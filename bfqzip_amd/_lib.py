@@ -25,6 +25,7 @@ SYMBOLS = [
     "bfq_stream_bound", "bfq_stream_raw_len", "bfq_stream_compress", "bfq_stream_decompress",
     "bfq_stream_reserve", "bfq_stream_compress_device", "bfq_stream_ebwt_decode",
     "bfq_fastq_restore_bound", "bfq_fastq_restore", "bfq_fastq_restore_fd",
+    "bfq_reorder_key", "bfq_fastq_reorder", "bfq_fastq_reorder_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -56,6 +57,10 @@ MAX_PARTS = 4
 
 class TextPart(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_uint64)]
+
+
+class ReorderOpts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("k", C.c_int32), ("seed", C.c_uint64), ("reserved", C.c_uint64 * 2)]
 
 
 class FastqJob(C.Structure):
@@ -163,6 +168,12 @@ def lib():
         L.bfq_fastq_restore_bound.argtypes = [vp, u64, vp, u64, vp, u64]
         L.bfq_fastq_restore.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
         L.bfq_fastq_restore_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.POINTER(u64), C.POINTER(u64)]
+        L.bfq_reorder_key.restype = u64
+        L.bfq_reorder_key.argtypes = [vp, u64, C.c_int]
+        L.bfq_fastq_reorder.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(ReorderOpts), C.POINTER(vp), C.POINTER(u64),
+                                        C.POINTER(u64), vp, C.POINTER(u64)]
+        L.bfq_fastq_reorder_fd.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(u64), C.c_int, C.POINTER(ReorderOpts), C.POINTER(C.c_int),
+                                           C.POINTER(u64), C.POINTER(u64)]
         L.bfq_stream_compress_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]
         L.bfq_prof_reset.argtypes = [vp]

@@ -460,6 +460,50 @@ class Engine:
                 if fd >= 0:
                     os.close(fd)
 
+    # ---- the reads in another order before the input is cut into blocks (bfq_fastq_reorder; parallel.py --reorder)
+    def fastq_reorder(self, parts, mode=2, k=21, seed=0, out=None):
+        """The records of a FASTQ text (parts = [text], or [mates 1, mates 2]: record i of both move together) in the order of
+        include/bfqzip_hip.h: mode 2 by the smallest hashed k-mer of every read, mode 1 by a seeded hash of its index, ties
+        in input order.  Returns ([text per part as uint8 arrays], perm) with perm[j] = input index of output record j.
+        `out`: one uint8 array per part to fill (too small: BFQ_E_ARG, nothing written); the results are views of them."""
+        arrs = [_u8(p) for p in parts]
+        np_ = len(arrs)
+        tp = (_lib.TextPart * max(np_, 1))()
+        for i, a in enumerate(arrs):
+            tp[i].data = a.ctypes.data if len(a) else None
+            tp[i].len = len(a)
+        outs = list(out) if out is not None else [np.empty(len(a) + 1, np.uint8) for a in arrs]
+        ho = (C.c_void_p * max(np_, 1))(*[o.ctypes.data for o in outs])
+        cap = (C.c_uint64 * max(np_, 1))(*[len(o) for o in outs])
+        ol = (C.c_uint64 * max(np_, 1))()
+        nr = C.c_uint64(0)
+        perm = np.empty(max((min(len(a) for a in arrs) if arrs else 0) // 4 + 1, 1), np.uint64)   # a record has 4 bytes at least
+        O = _lib.ReorderOpts(mode=mode, k=k, seed=seed)
+        self._ck(self.L.bfq_fastq_reorder(self.h, tp, np_, C.byref(O), ho, cap, ol, _ptr(perm), C.byref(nr)))
+        return [o[:int(ol[i])] for i, o in enumerate(outs)], perm[:int(nr.value)]
+
+    def fastq_reorder_files(self, inputs, outputs, mode=2, k=21, seed=0):
+        """bfq_fastq_reorder_fd on named files (one, or the two files of mates); returns (bytes written per file, n_reads).
+        On failure the output files are left empty."""
+        import os
+        assert len(inputs) == len(outputs)
+        fin, fout = [], []
+        try:
+            for p in inputs:
+                fin.append(os.open(p, os.O_RDONLY))
+            for p in outputs:
+                fout.append(os.open(p, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            n = len(fin)
+            ol = (C.c_uint64 * max(n, 1))()
+            nr = C.c_uint64(0)
+            O = _lib.ReorderOpts(mode=mode, k=k, seed=seed)
+            self._ck(self.L.bfq_fastq_reorder_fd(self.h, (C.c_int * max(n, 1))(*fin), (C.c_uint64 * max(n, 1))(*[os.fstat(fd).st_size for fd in fin]), n,
+                                                 C.byref(O), (C.c_int * max(n, 1))(*fout), ol, C.byref(nr)))
+            return [int(ol[i]) for i in range(n)], int(nr.value)
+        finally:
+            for fd in fin + fout:
+                os.close(fd)
+
     def stream_compress_device(self, d_in, n, d_out, cap):
         """Device-resident form (after stream_reserve(n)); returns the container's length."""
         ol = C.c_uint64(0)
@@ -508,6 +552,12 @@ class Engine:
 
     def workspace_bytes(self):
         return int(self.L.bfq_workspace_bytes(self.h))
+
+
+def reorder_key(seq, k=21):
+    """The mode-2 sort key of one sequence line (bfq_reorder_key: host only, no GPU)."""
+    a = _u8(seq)
+    return int(_lib.lib().bfq_reorder_key(_ptr(a) if len(a) else None, len(a), k))
 
 
 def synth_spec(N, L, Lmax=None, seed=20240807, **kw):

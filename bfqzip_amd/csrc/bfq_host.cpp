@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 #include "bfq_internal_host.h"
+#include "bfq_reorder.h"
 
 static double now_s()
 {
@@ -625,4 +626,17 @@ extern "C" int bfq_file_unmap(void *p, uint64_t off, uint64_t len)
     const long pg = sysconf(_SC_PAGESIZE);
     const uint64_t a0 = off / (uint64_t)pg * (uint64_t)pg;
     return munmap((char *)p - (off - a0), (size_t)(off + len - a0)) == 0 ? BFQ_OK : BFQ_E_IO;
+}
+
+// ---------------------------------------------------------------- the reordering key, stated on the host
+// key of one sequence line (include/bfqzip_hip.h): every window of k bytes in ACGT is packed two bits per base and hashed;
+// the smallest hash, cut to its 40 high bits.  What k_reorder.hip computes with a lane per read.
+extern "C" uint64_t bfq_reorder_key(const uint8_t *seq, uint64_t len, int k)
+{
+    if (k < BFQ_RO_KMIN || k > BFQ_RO_KMAX || (!seq && len)) return ~0ull;
+    const u64 mask = bfq_ro_mask(k);
+    BfqRoRoll r;
+    bfq_ro_init(r);
+    for (uint64_t i = 0; i < len; i++) bfq_ro_push(r, bfq_ro_code(seq[i]), k, mask, true);
+    return r.found ? r.best >> 24 : BFQ_RO_NOKEY;
 }

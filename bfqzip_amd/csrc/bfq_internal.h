@@ -31,7 +31,7 @@ struct BfqError {
 enum BfqKernel {
     K_TEXT = 0, K_PACK, K_KEYS, K_RADIX_HIST, K_SCAN, K_RADIX_SCATTER, K_HUGE_ROUND, K_CLUSTER_BIG,
     K_REFINE_WAVE, K_REFINE_BIG, K_EMIT, K_RANK_BUILD, K_RANK_FINAL, K_LCP_FLAGS, K_CLUSTER,
-    K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_NUM
+    K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -347,8 +347,10 @@ void bfq_synth_launch(bfq_ctx *c, const bfq_synth *s, u8 *d_bases, u8 *d_quals, 
 u8 *bfq_synth_headers(bfq_ctx *c, const bfq_synth *s, u64 *len);   // k_synth.hip
 
 // FASTQ text on the device (k_fastq.hip)
+struct FqRec { u64 hdrStart, seqStart, qualStart; u32 hdrLen, len; };   // one record: where its lines start (len: CR dropped)
 struct DevFastq { u64 N, total; void *rec; u64 *roff; u8 *bases, *quals; u64 *lineEnd; };
-void bfq_fastq_parse(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq);
+void bfq_fastq_index(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq);   // lines, records, read offsets, the checks: no gather (bases / quals nullptr)
+void bfq_fastq_parse(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq);   // ... and lines 2 and 4 gathered back to back
 u64 bfq_fastq_format(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, int mode, const u8 *d_hdr,
                      u64 hdrLen, const DevFastq *fq, u8 **d_out, u64 **recOffOut = nullptr, bool lines = false);
 void bfq_fastq_hdr_stream(bfq_ctx *c, u64 N, const u8 *d_fastq, const DevFastq *fq, u8 **d_hdr, u64 *hdrLen, u64 **hOffOut = nullptr);
@@ -364,3 +366,11 @@ void bfq_pick_u64(bfq_ctx *c, const u64 *d_src, const u64 *d_idx, int count, u64
 struct EbwtLines { u8 *dna = nullptr, *qs = nullptr; u64 n = 0, N = 0; };
 void bfq_ebwt_decode_lines(bfq_ctx *c, const u8 *h_bwtz, u64 len_b, const u8 *h_qsz, u64 len_q, u8 *h_dna, u8 *h_qs, u64 cap,
                            uint64_t *stream_len, uint64_t *n_reads, size_t extraWs, EbwtLines *res);
+
+// records in another order (k_reorder.hip; bfq_reorder.hip drives them).  A text of the call: its bytes, its record index,
+// its length.  The sort records carry the 40-bit key where bfq_radix_sort() reads its digits (w0 = key >> 8, bits 24..31 of
+// w1 = key & 255) and the read index in the 56 bits that are left.
+struct RoText { const u8 *buf; const FqRec *rec; u64 len; };
+void bfq_reorder_keys(bfq_ctx *c, const RoText *mates, int nmates, u64 N, int mode, int k, u64 seed, SortRec out);
+void bfq_reorder_perm(bfq_ctx *c, SortRec sorted, const RoText *mates, int nmates, u64 N, u64 *perm, u64 *const *sizes);
+void bfq_reorder_gather(bfq_ctx *c, const RoText &t, const u64 *perm, const u64 *newOff, u64 N, u8 *d_out);

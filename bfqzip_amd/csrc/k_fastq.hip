@@ -57,8 +57,6 @@ __global__ __launch_bounds__(256) void k_nl_write(const u8 *__restrict__ buf, u6
     }
 }
 
-struct FqRec { u64 hdrStart, seqStart, qualStart; u32 hdrLen, len; };
-
 __global__ __launch_bounds__(256) void k_fq_records(const u8 *__restrict__ buf, const u64 *__restrict__ lineEnd, u64 N, FqRec *__restrict__ rec, u32 *__restrict__ lens,
                                                     DevCounters *cnt)
 {
@@ -215,7 +213,7 @@ u64 bfq_fastq_count_lines(bfq_ctx *c, const u8 *d_buf, u64 len)
     return nl + 1;
 }
 
-void bfq_fastq_parse(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq)
+void bfq_fastq_index(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq)
 {
     u64 nlines = 0;
     u64 *lineEnd = bfq_line_index(c, d_fastq, len, &nlines);
@@ -233,13 +231,20 @@ void bfq_fastq_parse(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq)
     c->fetchCounters();
     if (c->h_cnt.errFastq) throw BfqError{BFQ_E_ARG, "FASTQ: len(DNA) != len(QS) in a record"};
     if (c->h_cnt.errTooLong) throw BfqError{BFQ_E_TOO_LONG, "read longer than BFQ_MAX_READ_LEN"};
+    fq->bases = fq->quals = nullptr;
+    fq->lineEnd = lineEnd;
+}
+
+void bfq_fastq_parse(bfq_ctx *c, const u8 *d_fastq, u64 len, DevFastq *fq)
+{
+    bfq_fastq_index(c, d_fastq, len, fq);
+    const u64 N = fq->N;
     fq->bases = c->alloc<u8>(fq->total + 64);
     fq->quals = c->alloc<u8>(fq->total + 64);
     if (N) {
         KLAUNCH(c, K_FASTQ, 4.0 * (double)fq->total, k_fq_gather, bfq_grid(N, 16), 256, d_fastq, (const FqRec *)fq->rec,
                 (const u64 *)fq->roff, N, fq->bases, fq->quals);
     }
-    fq->lineEnd = lineEnd;
 }
 
 // Headers: mode 0 = "@"; 1 = d_hdr is a text of header lines (bfq_int -H); 2 = d_hdr is the FASTQ

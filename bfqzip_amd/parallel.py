@@ -178,6 +178,32 @@ def output_names(inputs, out, paired):
     return [{"fastq": f, "dna": f + ".dna", "qs": f + ".qs", "hdr": b + ".h"} for f, b in zip(fq, base)]
 
 
+def reordered_names(inputs, mode):
+    """Where --reorder puts its intermediate files: <root>.reordered<ext> (mode 2, BFQzip_parallel.py:398) or
+    <root>.random<ext> (mode 1, :421) beside every input."""
+    tag = ".reordered" if mode == 2 else ".random"
+    return [root + tag + ext for root, ext in (os.path.splitext(p) for p in inputs)]
+
+
+def reorder_inputs(eng, comm, inputs, mode, k=21, seed=0, paired=False, log=None):
+    """--reorder {1,2} of BFQzip_parallel.py (:59-75): the reads of the input(s) are written in another order (mode 2: by
+    locus, mode 1: seeded random; eng.fastq_reorder_files -- mates move together) by rank 0, and the run goes on with those
+    files: returns the new input list (the reference replaces args.input and re-derives the output names from it, :403-404,
+    :432-435).  mode 0: the inputs as they are."""
+    if not mode:
+        return list(inputs)
+    if mode not in (1, 2):
+        raise ValueError("--reorder: 0 (no reorder), 1 (random) or 2 (locus)")
+    src = list(inputs[:2 if paired else 1])
+    dst = reordered_names(src, mode)
+    if comm.rank == 0:
+        sizes, n = eng.fastq_reorder_files(src, dst, mode=mode, k=k, seed=seed)
+        if log:
+            log(f"reorder {mode}: {n} reads, {sum(sizes)} bytes -> {' '.join(dst)}")
+    comm.barrier()
+    return dst + list(inputs[len(src):])
+
+
 KINDS = ("fastq", "dna", "qs", "hdr")
 
 
@@ -484,6 +510,11 @@ def main(argv=None):
     ap.add_argument("--pinned", action="store_true", help="page-locked output buffers (direct DMA)")
     ap.add_argument("--global", dest="glob", action="store_true",
                     help="ONE eBWT over the whole input, its piles dealt to the GPUs: the result of the unsharded run (-t is ignored)")
+    ap.add_argument("--reorder", type=int, default=0, choices=(0, 1, 2),
+                    help="reorder the reads before the input is cut into blocks (0: no reorder, 1: random, 2: by locus): "
+                         "writes <input>.random<ext> / <input>.reordered<ext> and runs on those")
+    ap.add_argument("--reorder-k", type=int, default=21, help="k-mer length of --reorder 2 (8..32)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of --reorder 1")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
     if a.paired and len(a.input) != 2:
@@ -512,9 +543,10 @@ def main(argv=None):
     if a.rv:
         par["v"] = ord(a.rv)
     eng = api.Engine(local, **par)
-    names = output_names(a.input, a.out, a.paired)
-    streams = a.m2 or a.m3
     log = (lambda m: print(f"[rank {comm.rank}] {m}", flush=True)) if a.v else None
+    a.input = reorder_inputs(eng, comm, a.input, a.reorder, k=a.reorder_k, seed=a.seed, paired=a.paired, log=log)
+    names = output_names(a.input, a.out, a.paired)                   # after the replacement, as define_basename() in the reference
+    streams = a.m2 or a.m3
     if a.glob:
         tot = run_global(eng, comm, a.input[:2 if a.paired else 1], names, headers=a.headers, want_fastq=not (streams and a.streams_only),
                          want_streams=streams, want_hdr=a.m3, log=log, pinned=a.pinned)

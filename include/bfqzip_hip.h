@@ -338,6 +338,38 @@ int bfq_fastq_restore(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const 
                       const uint8_t *h_hdr, uint64_t hdr_len, uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads);
 int bfq_fastq_restore_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len,
                          int hdr_fd, uint64_t hdr_len, int out_fd, uint64_t *out_len, uint64_t *n_reads);
+/* ---- reads of a FASTQ in another order (the pre-pass of `BFQzip_parallel.py --reorder {1,2}`, :35,59-75,389-437, which shells
+ * out to randomFASTQ.py / SPRING's reorder-only tool): FASTQ text in -> the same records, verbatim, in a new order out.  A
+ * sharded run cuts the input into blocks of consecutive reads; reads of one locus brought together end up in one block and
+ * keep their clusters.  The order is ascending key, ties in input order:
+ *   mode 2 "locus" : over every window of k consecutive bytes of the sequence line (CR before LF dropped) that are all in
+ *                    ACGT: x = the window packed two bits per base (A 0, C 1, G 2, T 3, first base most significant), h =
+ *                    MurmurHash3's 64-bit finaliser of x; key = (min h) >> 24, 40 bits.  No valid window: 2^40 - 1.
+ *                    k: 8..32, 0 = 21.
+ *   mode 1 "random": key = fmix64(seed + read index) >> 24.
+ * Two parts are mates: record i of part 2 moves with record i of part 1; the pair's key is mate 1's, or mate 2's when mate 1
+ * has no valid window; different record counts are BFQ_E_ARG.  A record is its four lines byte for byte (header, '+' line
+ * and CRs as they are); a part that lacks its final newline gets one, so out_len[p] = parts[p].len (+ 1 then).
+ * h_perm (uint64[number of reads] or NULL): perm[j] = input index of output record j.  Malformed text: the code and message
+ * of bfq_fastq_run.  cap[p] < out_len[p]: BFQ_E_ARG, out_len zeroed, nothing written.  Device memory: the input, the
+ * output and ~160 bytes of index per read; above ws_cap_mib: BFQ_E_NOMEM with the size in the message (an input larger than
+ * device memory is not split).
+ *   bfq_reorder_key     : the mode-2 key of one sequence line, host only (the statement the kernel is tested against);
+ *                         UINT64_MAX when k is outside 8..32
+ *   bfq_fastq_reorder   : host buffers (pinned: direct DMA)
+ *   bfq_fastq_reorder_fd: open files (nparts inputs, nparts outputs); the text goes out through the background writers into
+ *                         out_fd[p] (a mapping registered by bfq_output_prefault is picked up); on failure they are left empty */
+typedef struct bfq_reorder_opts {
+    int32_t  mode;       /* 1 random, 2 locus                           */
+    int32_t  k;          /* window of mode 2: 8..32, 0 = 21             */
+    uint64_t seed;       /* mode 1                                      */
+    uint64_t reserved[2];
+} bfq_reorder_opts;
+uint64_t bfq_reorder_key(const uint8_t *seq, uint64_t len, int k);
+int bfq_fastq_reorder(bfq_ctx *c, const bfq_text_part *parts, int nparts, const bfq_reorder_opts *opts, uint8_t *const *h_out,
+                      const uint64_t *cap, uint64_t *out_len, uint64_t *h_perm, uint64_t *n_reads);
+int bfq_fastq_reorder_fd(bfq_ctx *c, const int *in_fd, const uint64_t *in_len, int nparts, const bfq_reorder_opts *opts,
+                         const int *out_fd, uint64_t *out_len, uint64_t *n_reads);
 /* device-resident form (input and output in device memory): bfq_stream_reserve(len) sizes the workspace once */
 int bfq_stream_reserve(bfq_ctx *c, uint64_t len);
 int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
