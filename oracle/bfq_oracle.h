@@ -14,6 +14,20 @@
  * consumers (bfq_int.cpp:775-791 starts read i at BWT row i; dna_bwt_n.hpp:46-61
  * lays F out as # A C G N T) and is pinned only through the round trip
  * "oracle eBWT -> reference bfq_int -k 10000 -> original reads".
+ * tests/golden/ref_wide* (make_golden.py --ref-wide) carries that pinning over
+ * the input space of tests/soak_gpu.py: output md5 and all eight counters of
+ * the reference for ~220 collections (plateaus of equal LCP, empty / one-base /
+ * N-only reads, clusters beyond 2048 rows, qualities up to 126 and as raw
+ * bytes 1..255 -- signed char there and here) x the whole range of -k -m -v -f
+ * -t x every (M,B), plus 24 tie-shuffled eBWTs.
+ *
+ * OWN DEFINITION, not the reference's: a collection made ONLY of empty reads
+ * (an eBWT of terminators alone).  The reference cannot process it -- its
+ * suffix-tree root has a single child and bfq_int aborts in
+ * update_lcp_threshold (include.hpp:897, assert number_of_children(x) >= 2).
+ * Here, and in the HIP library, such a collection has no cluster: N empty
+ * reads come back, every counter is 0.  Empty reads among others ARE the
+ * reference's behaviour (recorded in ref_wide_empty.npz and elsewhere).
  */
 #ifndef BFQ_ORACLE_H
 #define BFQ_ORACLE_H

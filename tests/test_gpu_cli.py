@@ -50,6 +50,18 @@ def test_int_mem_pipeline(tools, tmp_path, name):
         assert util.md5(open(out + ".x.fq", "rb").read()) == want, key
 
 
+def test_int_mem_statistics_block(tools, tmp_path):
+    """The statistics block bfq_int prints (bfq_int.cpp:1004-1018): for the example's eBWT with -m 5, all eight counters are
+    the numbers the reference printed for that run (its block is recorded in tests/golden/ref_wide.json)."""
+    _, _, ref = util.ref_wide()
+    assert util.parse_stats(ref["block"].encode()) == ref["stats"]
+    g = os.path.join(util.GOLDEN, "example")
+    r = _run([tools["bfq_int"], "-e", g + ".bwt", "-q", g + ".bwt.qs", "-o", str(tmp_path / "o.fq"), "-m", "5"])
+    assert r.returncode == 0, r.stdout
+    assert open(str(tmp_path / "o.fq"), "rb").read() == open(g + ".M2B0.fq", "rb").read()
+    assert util.parse_stats(r.stdout) == ref["stats"], r.stdout
+
+
 def test_headers_option(tools, tmp_path):
     name = "example"
     fq = os.path.join(util.GOLDEN, name + ".fastq")

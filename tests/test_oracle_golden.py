@@ -93,3 +93,64 @@ def test_tie_order_of_identical_suffixes_is_free(orc, tmp_path):
             assert util.md5(open(str(tmp_path / "o.fq"), "rb").read()) == c["out_md5"], (it, c)
         done += 1
     assert done >= 6
+
+
+def _ref_rerun(orc, tmp_path, c, bwt, qs):
+    """The compiled reference again, where it is built: (md5 of its output, its eight counters); None where it is not."""
+    ref = orc.ref_binary(c["M"], c["B"])
+    if ref is None:
+        return None
+    d = str(tmp_path)
+    bwt.tofile(d + "/x.bwt"); qs.tofile(d + "/x.bwt.qs")
+    cmd = [ref, "-e", d + "/x.bwt", "-q", d + "/x.bwt.qs", "-o", d + "/o.fq",
+           "-k", str(c["k"]), "-m", str(c["m"]), "-v", str(c["v"]), "-t", str(c["t"]), "-f", str(c["f"])]
+    out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=120, check=True).stdout
+    return util.md5(open(d + "/o.fq", "rb").read()), util.parse_stats(out)
+
+
+def _stats8(st):
+    return {k: st[k] for k in util.STAT_KEYS}
+
+
+def test_oracle_vs_reference_wide(orc, tmp_path):
+    """The oracle over the input space tests/soak_gpu.py draws from, against what the reference bfq_int itself wrote and
+    printed there (tests/golden/ref_wide*, made by make_golden.py --ref-wide): collection shapes with plateaus of equal LCP,
+    empty / one-base / N-only reads, clusters beyond 2048 rows with two frequent symbols, qualities up to 126 and as raw bytes
+    (signed char in the reference), -k 1..39 -m 1..8 -v 33..99 -f 34..100 -t 0..44 in every (M,B) build.  The output's md5
+    and all eight counters, in bfq_int mode (LCP deduced from the BWT), with the explicit LCP, and through orc.run_reads."""
+    cases, _, _ = util.ref_wide()
+    assert len(cases) >= 200 and sum(c["family"] == "raw" for c in cases) == 12
+    for c in cases:
+        b, q, r = c["bases"], c["quals"], c["roff"]
+        bwt, qs, lcp = orc.build_ebwt(b, q, r)
+        assert util.md5(bwt.tobytes()) == c["bwt_md5"] and util.md5(qs.tobytes()) == c["qs_md5"], c["id"]
+        p = orc.params(K=c["k"], m=c["m"], v=c["v"], f=c["f"], t=c["t"], M=c["M"], B=c["B"])
+        for given in (None, lcp):
+            ob, oq, oroff, st = orc.smooth_invert(bwt, qs, given, p)
+            assert util.md5(fastq.format_fastq(ob, oq, oroff)) == c["out_md5"], (c["id"], given is None)
+            assert _stats8(st) == c["stats"], (c["id"], given is None)
+        ob, oq, st = orc.run_reads(b, q, r, p)
+        assert util.md5(fastq.format_fastq(ob, oq, r)) == c["out_md5"] and _stats8(st) == c["stats"], c["id"]
+        again = _ref_rerun(orc, tmp_path, c, bwt, qs)
+        if again is not None:
+            assert again == (c["out_md5"], c["stats"]), c["id"]
+
+
+def test_oracle_vs_reference_wide_ties(orc, tmp_path):
+    """Tie-shuffled eBWTs (identical suffixes and terminator rows in any order) in every (M,B) build and K in {1,2,3,5,8}:
+    the oracle's output and counters against the reference's (tests/golden/ref_wide_tie.npz), with its own BWT-only LCP
+    deduction and with the LCP of the decoded rows."""
+    _, ties, _ = util.ref_wide()
+    assert len(ties) == 24 and {(c["M"], c["B"]) for c in ties} == {(M, B) for M in range(4) for B in range(2)}
+    assert {c["k"] for c in ties} == {1, 2, 3, 5, 8}
+    for c in ties:
+        sb, sq = c["bwt"], c["qs"]
+        suf, _ = util.decode_rows(sb)
+        p = orc.params(K=c["k"], m=c["m"], v=c["v"], f=c["f"], t=c["t"], M=c["M"], B=c["B"])
+        for given in (None, util.lcp_of_rows(suf)):
+            ob, oq, oroff, st = orc.smooth_invert(sb, sq, given, p)
+            assert util.md5(fastq.format_fastq(ob, oq, oroff)) == c["out_md5"], (c["id"], given is None)
+            assert _stats8(st) == c["stats"], (c["id"], given is None)
+        again = _ref_rerun(orc, tmp_path, c, sb, sq)
+        if again is not None:
+            assert again == (c["out_md5"], c["stats"]), c["id"]

@@ -24,6 +24,54 @@ def ref_cases():
         return meta, {k: z[k] for k in z.files}
 
 
+STAT_KEYS = ("num_clust", "num_clust_discarded", "num_clust_amb_discarded", "num_clust_mod", "num_clust_alleq",
+             "bases_inside", "qs_smoothed", "modified")
+_STAT_RE = (("num_clust", rb"^Tot: (\d+)$"), ("bases_inside", rb"^(\d+) \(\S+%\) bases fall inside clusters$"),
+            ("num_clust_discarded", rb"^Discarded: (\d+)\("), ("num_clust_amb_discarded", rb"^Ambiguous discarded: (\d+)\("),
+            ("num_clust_mod", rb"^Processed: (\d+)\("), ("num_clust_alleq", rb"^Clusters with only one symbol: (\d+)\("),
+            ("qs_smoothed", rb"^(\d+)/\d+ qualities have been modified"), ("modified", rb"^(\d+)/\d+ bases have been modified"))
+_WIDE = None
+
+
+def parse_stats(stdout):
+    """The eight counters of the statistics block bfq_int prints (bfq_int.cpp:1004-1018), each found exactly once."""
+    import re
+    st = {}
+    for key, pat in _STAT_RE:
+        got = re.findall(pat, stdout, re.M)
+        assert len(got) == 1, (key, got)
+        st[key] = int(got[0])
+    return st
+
+
+def ref_wide():
+    """tests/golden/ref_wide*: (cases, tie cases, the record of the example run) as make_golden.py's ref_wide() wrote them.
+    Every case is a dict of its parameters, the md5 of the reference bfq_int's output FASTQ and the eight counters the
+    reference printed ('stats'), plus its arrays: 'bases', 'quals', 'roff' (cases) or 'bwt', 'qs' (tie cases).  Loaded once;
+    the arrays are read-only."""
+    global _WIDE
+    if _WIDE is None:
+        meta = json.load(open(os.path.join(GOLDEN, "ref_wide.json")))
+        z = {}
+        for c in meta["cases"]:
+            if c["family"] not in z:
+                with np.load(os.path.join(GOLDEN, "ref_wide_%s.npz" % c["family"])) as f:
+                    z[c["family"]] = {k: f[k] for k in f.files}
+            a = z[c["family"]]
+            c["bases"], c["quals"] = a["%d_bases" % c["i"]], a["%d_quals" % c["i"]]
+            c["roff"] = np.concatenate([[0], np.cumsum(a["%d_len" % c["i"]].astype(np.uint64))]).astype(np.uint64)
+            c["id"] = "%s%d" % (c["family"], c["i"])
+        with np.load(os.path.join(GOLDEN, "ref_wide_tie.npz")) as f:
+            for j, c in enumerate(meta["tie"]):
+                c["bwt"], c["qs"], c["id"] = f["%d_bwt" % j], f["%d_qs" % j], "tie%d" % j
+        for c in meta["cases"] + meta["tie"]:
+            for k in ("bases", "quals", "roff", "bwt", "qs"):
+                if k in c:
+                    c[k].setflags(write=False)
+        _WIDE = (meta["cases"], meta["tie"], meta["example_m5"])
+    return _WIDE
+
+
 def parse_case(key):
     """'M2B0 -m 5 -k 8 ...' -> dict of engine/oracle parameters (+ 'H' for headers)."""
     toks = key.split()
