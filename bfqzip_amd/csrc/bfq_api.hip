@@ -31,7 +31,7 @@ static thread_local std::string g_createErr;
 void bfq_ctx::reserveBegin(size_t bytes)
 {
     bytes = (bytes + 0xFFFFF) & ~(size_t)0xFFFFF;
-    if (wsThread || bytes <= wsCap || (wsLimit() && bytes > wsLimit())) return;
+    if (wsThread || bytes <= ws.cap || (wsLimit() && bytes > wsLimit())) return;
     wsPendBytes = bytes; wsPend = nullptr;
     const int dev = device;
     wsThread = new std::thread([this, dev, bytes] {
@@ -52,19 +52,17 @@ void bfq_ctx::reserveJoin(bool adopt, size_t need)
     delete wsThread;
     wsThread = nullptr;
     if (!wsPend) return;
-    if (adopt && need <= wsPendBytes && need > wsCap && !(wsLimit() && wsPendBytes > wsLimit())) {
-        wsFree();
-        ws = wsPend; wsCap = wsPendBytes; wsTop = 0;
-        if (bfq_env().trace) fprintf(stderr, "[bfq] workspace %.1f GiB: hipMalloc %.3f s, beside the upload\n", wsCap / 1073741824.0, wsPendSecs);
+    if (adopt && need <= wsPendBytes && need > ws.cap && !(wsLimit() && wsPendBytes > wsLimit())) {
+        adoptWorkspace(wsPend, wsPendBytes);
+        if (bfq_env().trace) fprintf(stderr, "[bfq] workspace %.1f GiB: hipMalloc %.3f s, beside the upload\n", ws.cap / 1073741824.0, wsPendSecs);
     } else (void)hipFree(wsPend);
     wsPend = nullptr; wsPendBytes = 0;
 }
-void bfq_ctx::wsFree()
+void bfq_ctx::wsFree() { adoptWorkspace(nullptr, 0); }
+void bfq_ctx::adoptWorkspace(char *p, size_t bytes)
 {
-    if (!ws) return;
-    (void)hipStreamSynchronize(stream);
-    (void)hipFree(ws);
-    ws = nullptr; wsCap = 0; wsTop = 0;
+    if (ws.base) { quiesce(); (void)hipFree(ws.base); }
+    ws = Arena{p, bytes, 0, ws.peak};
 }
 
 void bfq_ctx::reserve(size_t bytes)
@@ -76,41 +74,29 @@ void bfq_ctx::reserve(size_t bytes)
         snprintf(b, sizeof b, "device workspace of %.1f GiB is above the cap of %.1f GiB (bfq_params.ws_cap_mib / BFQ_WS_CAP)", bytes / 1073741824.0, wsLimit() / 1073741824.0);
         throw BfqError{BFQ_E_NOMEM, b};
     }
-    if (bytes > wsCap || (wsLimit() && wsCap > wsLimit())) {    // (an arena from before the cap was set goes back)
+    if (bytes > ws.cap || (wsLimit() && ws.cap > wsLimit())) {    // (an arena from before the cap was set goes back)
         wsFree();
         struct timespec t0, t1;
         clock_gettime(CLOCK_MONOTONIC, &t0);
-        const hipError_t e = hipMalloc((void **)&ws, bytes);
+        char *p = nullptr;
+        const hipError_t e = hipMalloc((void **)&p, bytes);
         clock_gettime(CLOCK_MONOTONIC, &t1);
         if (bfq_env().trace) fprintf(stderr, "[bfq] workspace %.1f GiB: hipMalloc %.3f s\n", bytes / 1073741824.0, (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec));
         if (e != hipSuccess) {
-            ws = nullptr;
             char b[160];
             snprintf(b, sizeof b, "device workspace of %zu bytes: %s", bytes, hipGetErrorString(e));
             (void)hipGetLastError();
             throw BfqError{BFQ_E_NOMEM, b};
         }
-        wsCap = bytes;
+        adoptWorkspace(p, bytes);
     }
-    wsTop = 0;
+    ws.release(0);
     d_bwt = d_qual = nullptr; d_lcp = nullptr; d_gcnt = nullptr; n = N = 0;
 }
 void bfq_ctx::dropWorkspace()
 {
     wsFree();
     d_bwt = d_qual = nullptr; d_lcp = nullptr; d_gcnt = nullptr;
-}
-void *bfq_ctx::allocBytes(size_t bytes)
-{
-    size_t a = (wsTop + 255) & ~(size_t)255;
-    if (a + bytes > wsCap) {
-        char b[160];
-        snprintf(b, sizeof b, "workspace exhausted: need %zu more bytes at %zu of %zu", bytes, a, wsCap);
-        throw BfqError{BFQ_E_NOMEM, b};
-    }
-    wsTop = a + bytes;
-    if (wsTop > wsPeak) wsPeak = wsTop;
-    return ws + a;
 }
 void bfq_ctx::profBegin(int id, double bytes)
 {
@@ -255,7 +241,7 @@ extern "C" void bfq_destroy(bfq_ctx *c)
     for (auto e : c->evPool) (void)hipEventDestroy(e);
     c->ioFree();
     if (c->d_text) (void)hipFree(c->d_text);
-    if (bfq_env().trace && c->wsCap) fprintf(stderr, "[bfq] workspace: %.1f GiB reserved, %.1f GiB used at the peak\n", c->wsCap / 1073741824.0, c->wsPeak / 1073741824.0);
+    if (bfq_env().trace && c->ws.cap) fprintf(stderr, "[bfq] workspace: %.1f GiB reserved, %.1f GiB used at the peak\n", c->ws.cap / 1073741824.0, c->ws.peak / 1073741824.0);
     c->wsFree();
     if (c->d_cnt) (void)hipFree(c->d_cnt);
     if (c->d_powtab) (void)hipFree(c->d_powtab);
@@ -273,7 +259,7 @@ extern "C" int bfq_set_params(bfq_ctx *c, const bfq_params *p)
 }
 extern "C" const char *bfq_last_error(bfq_ctx *c) { return c ? c->err.c_str() : "null context"; }
 extern "C" void *bfq_stream(bfq_ctx *c) { return c ? (void *)c->stream : nullptr; }
-extern "C" uint64_t bfq_workspace_bytes(bfq_ctx *c) { return c ? c->wsCap : 0; }
+extern "C" uint64_t bfq_workspace_bytes(bfq_ctx *c) { return c ? c->ws.cap : 0; }
 extern "C" int bfq_prof_enable(bfq_ctx *c, int on) { if (!c) return BFQ_E_ARG; c->profOn = on != 0; return BFQ_OK; }
 extern "C" void bfq_prof_reset(bfq_ctx *c)
 {
@@ -317,8 +303,12 @@ static void check_counters(bfq_ctx *c)
     if (h.mismatch) throw BfqError{BFQ_E_NOT_EBWT, "eBWT is not in #_i<#_j<A<C<G<N<T suffix order"};
     if (h.errFreq3) throw BfqError{BFQ_E_FREQ3, "three frequent symbols in a cluster (bfq_int.cpp:505 assert); raise -f"};
 }
-static void fill_stats(bfq_ctx *c, bfq_stats *st)
+// the end of a call: waits for the stream, reports what the kernels flagged, fills the caller's statistics
+static void finish_call(bfq_ctx *c, bfq_stats *st = nullptr)
 {
+    c->fetchCounters();
+    c->profCollect();
+    check_counters(c);
     if (!st) return;
     const u64 *s = c->h_cnt.stats;
     st->num_clust = s[0]; st->num_clust_discarded = s[1]; st->num_clust_amb_discarded = s[2];
@@ -378,13 +368,12 @@ static void reserve_step1(bfq_ctx *c, u64 n, u64 N, u64 extra, bool allowCapped 
     if (c->env.piles) mode = c->env.piles;
     if (mode == 2 && !allowCapped) mode = 1;                     // the caller wants the eBWT arrays: the capped mode has none
     const u64 cap = n / 10 * 3 + (1u << 20);                     // a DNA pile holds about a quarter of the suffixes; larger ones are split again
-    c->piles = false; c->capped = false;
     if (mode <= 0) {
         try { c->reserve(ws_need(n, N, extra)); return; }
         catch (const BfqError &e) { if (mode < 0 || e.code != BFQ_E_NOMEM) throw; }
     }
     if (mode != 2) {
-        try { c->reserve(bfq_ws_need_piles(n, N, cap, extra)); c->piles = true; return; }
+        try { c->reserve(bfq_ws_need_piles(n, N, cap, extra)); c->call.piles = true; return; }
         catch (const BfqError &e) { if (e.code != BFQ_E_NOMEM || !c->wsLimit() || !allowCapped) throw; }
     }
     // Below 13 n bytes (a workspace cap): the capped mode.  Its arena holds the terminated text (T8, Q8, packed text), the
@@ -399,19 +388,19 @@ static void reserve_step1(bfq_ctx *c, u64 n, u64 N, u64 extra, bool allowCapped 
         throw BfqError{BFQ_E_NOMEM, b};
     }
     c->reserve(ws_need_capped(n, N, rows, extra));
-    c->capped = true; c->cappedPileRows = rows;
+    c->call.capped = true; c->call.cappedPileRows = rows;
 }
 
 // ---------------------------------------------------------------- step 1
 void bfq_step1_device(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, u64 total,
                       int termOut, bfq_stats *st)
 {
-    if (c->piles) { bfq_step1_piles(c, d_bases, d_quals, d_roff, N, total, termOut, st); return; }
+    if (c->call.piles) { bfq_step1_piles(c, d_bases, d_quals, d_roff, N, total, termOut, st); return; }
     u64 n = total + N;
     if (n >= (1ull << BFQ_POS_BITS)) throw BfqError{BFQ_E_ARG, "collection too large (2^37 rows)"};
     c->n = n; c->N = N;
-    c->d_bwt = c->extBwt ? c->extBwt : c->alloc<u8>(n + 64);
-    c->d_qual = c->extQual ? c->extQual : c->alloc<u8>(n + 64);
+    c->d_bwt = c->call.extBwt ? c->call.extBwt : c->alloc<u8>(n + 64);
+    c->d_qual = c->call.extQual ? c->call.extQual : c->alloc<u8>(n + 64);
     c->d_lcp = c->alloc<u16>(n + 64);
     c->d_gcnt = c->alloc<u32>(6 * (n / 256 + 1));
     c->gcntTerm = termOut & 0xFF;
@@ -428,7 +417,7 @@ void bfq_step1_device(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u6
     const size_t mB = c->mark();
     B.w0 = c->alloc<u32>(n + 16);
     B.w12 = c->alloc<u64>(n + 16);
-    if (bfq_env().trace) fprintf(stderr, "[bfq] sort buffers: A.w12 %p A.w0 %p B.w0 %p B.w12 %p (arena %p)\n", (void *)A.w12, (void *)A.w0, (void *)B.w0, (void *)B.w12, (void *)c->ws);
+    if (bfq_env().trace) fprintf(stderr, "[bfq] sort buffers: A.w12 %p A.w0 %p B.w0 %p B.w12 %p (arena %p)\n", (void *)A.w12, (void *)A.w0, (void *)B.w0, (void *)B.w12, (void *)c->ws.base);
     // k_build_keys writes the records to B, the byte text lying in A (dead before the sort's first scatter writes there)
     u8 *T8 = (u8 *)A.w0, *Q8 = (u8 *)A.w12;
     bfq_build_text(c, d_bases, d_quals, d_roff, N, n, T8, Q8, text3, nwords);
@@ -439,9 +428,9 @@ void bfq_step1_device(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u6
     c->release(mB);                                     // the big-segment list reuses the B buffers
     bfq_refine(c, A, text3, n, c->d_lcp, st);
     bfq_emit_bwt(c, A, n, termOut, c->d_bwt, c->d_qual, c->d_gcnt);
-    if (c->keepRecs) { c->release(mKeep); c->d_w12 = A.w12; c->d_text3 = text3; c->keepMark = m0; }
+    if (c->call.keepRecs) { c->release(mKeep); c->call.d_w12 = A.w12; c->call.d_text3 = text3; c->call.keepMark = m0; }
     else c->release(m0);
-    if (c->onRows) c->onRows(0, n);
+    if (c->call.onRows) c->call.onRows(0, n);
 }
 
 // ---------------------------------------------------------------- steps 2-4
@@ -477,23 +466,21 @@ static void invert_lines(bfq_ctx *c, const RankIndex &R, const u64 *d_roff, u8 *
         if (so->h_qs) bfq_download(c, so->h_qs, d_qs, sl);
         return;
     }
-    if (!c->copyStream) HIP_CHECK(hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
+    const hipStream_t cs = c->copy();
     u64 first[9], off[9];
     for (int j = 0; j <= C; j++) first[j] = N * (u64)j / C;
     for (int j = 0; j <= C; j++) HIP_CHECK(hipMemcpyAsync(&off[j], d_roff + first[j], 8, hipMemcpyDeviceToHost, c->stream));
     c->sync();
-    hipEvent_t ev[8];
+    ScopedEvent ev[8];
     for (int j = 0; j < C; j++) {
-        HIP_CHECK(hipEventCreateWithFlags(&ev[j], hipEventDisableTiming));
         bfq_invert(c, R, N, d_roff, c->P.B, d_dna, d_qs, first[j], first[j + 1] - first[j], lines);
         HIP_CHECK(hipEventRecord(ev[j], c->stream));
-        HIP_CHECK(hipStreamWaitEvent(c->copyStream, ev[j], 0));
+        HIP_CHECK(hipStreamWaitEvent(cs, ev[j], 0));
         const u64 b0 = off[j] + (lines ? first[j] : 0), b1 = off[j + 1] + (lines ? first[j + 1] : 0);
-        if (so->h_dna) HIP_CHECK(hipMemcpyAsync(so->h_dna + b0, d_dna + b0, b1 - b0, hipMemcpyDeviceToHost, c->copyStream));
-        if (so->h_qs) HIP_CHECK(hipMemcpyAsync(so->h_qs + b0, d_qs + b0, b1 - b0, hipMemcpyDeviceToHost, c->copyStream));
+        if (so->h_dna) HIP_CHECK(hipMemcpyAsync(so->h_dna + b0, d_dna + b0, b1 - b0, hipMemcpyDeviceToHost, cs));
+        if (so->h_qs) HIP_CHECK(hipMemcpyAsync(so->h_qs + b0, d_qs + b0, b1 - b0, hipMemcpyDeviceToHost, cs));
     }
-    HIP_CHECK(hipStreamSynchronize(c->copyStream));
-    for (int j = 0; j < C; j++) (void)hipEventDestroy(ev[j]);
+    HIP_CHECK(hipStreamSynchronize(cs));
 }
 // eBWT-domain output (bfq_fastq_job.compress_streams == 2): the rows of the eBWT as the cluster step left them -- symbol after
 // noise reduction, quality after smoothing (binned when B = 1; a constant at the terminator rows, whose quality byte never
@@ -535,25 +522,14 @@ static void steps234_device(bfq_ctx *c, u64 *d_roff, u8 *d_out_bases, u8 *d_out_
         if (eo->lineQs) { StreamOut none{nullptr, nullptr}; invert_lines(c, R, d_roff, eo->lineDna, eo->lineQs, &none); }
         return;
     }
-    if (so) {
-        invert_lines(c, R, d_roff, d_out_bases, d_out_quals, so);
-        if (guessed) {
-            c->fetchCounters();
-            if (c->h_cnt.errInvert) {                              // not all of one length after all: count, then walk again
-                HIP_CHECK(hipMemsetAsync(&c->d_cnt->errInvert, 0, sizeof(u64), c->stream));
-                count_lengths(c, R, d_roff, lens);
-                invert_lines(c, R, d_roff, d_out_bases, d_out_quals, so);
-            }
-        }
-        return;
-    }
-    bfq_invert(c, R, N, d_roff, c->P.B, d_out_bases, d_out_quals);
+    auto walk = [&] { if (so) invert_lines(c, R, d_roff, d_out_bases, d_out_quals, so); else bfq_invert(c, R, N, d_roff, c->P.B, d_out_bases, d_out_quals); };
+    walk();
     if (guessed) {
         c->fetchCounters();
         if (c->h_cnt.errInvert) {                              // not all of one length after all: count, then walk again
             HIP_CHECK(hipMemsetAsync(&c->d_cnt->errInvert, 0, sizeof(u64), c->stream));
             count_lengths(c, R, d_roff, lens);
-            bfq_invert(c, R, N, d_roff, c->P.B, d_out_bases, d_out_quals);
+            walk();
         }
     }
 }
@@ -593,7 +569,7 @@ static void steps34_positions(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, 
     if (N) KLAUNCH(c, K_MISC, 4.0 * (double)(n - N), k_lines_init, bfq_grid(N, 16), 256, d_bases, d_quals, d_roff, N, c->P.B, dna, qs);
     u8 *in = c->alloc<u8>(n + 64);
     bfq_lcp_flags(c, c->d_lcp, n, c->P.K, in);
-    ClusterPos pm{c->d_w12, c->d_text3, dna, qs, c->P.B};
+    ClusterPos pm{c->call.d_w12, c->call.d_text3, dna, qs, c->P.B};
     RankIndex none{nullptr, n};
     bfq_clusters(c, none, c->d_bwt, c->d_qual, in, n, &pm);
     if (N) KLAUNCH(c, K_MISC, 4.0 * (double)(n - N), k_lines_strip, bfq_grid(N, 16), 256, (const u8 *)dna, (const u8 *)qs, d_roff, N, d_out_bases, d_out_quals);
@@ -631,15 +607,15 @@ static void steps_capped(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const
             u64 rows = 0;
             if (two) rows = cnt[6 * s + s2]; else for (int q = 0; q < 6; q++) rows += cnt[6 * s + q];
             if (!rows) continue;
-            if (rows > c->cappedPileRows) {
+            if (rows > c->call.cappedPileRows) {
                 char b[220];
                 snprintf(b, sizeof b, "pile '%c%c' holds %llu rows, the workspace cap leaves room for %llu: raise bfq_params.ws_cap_mib / BFQ_WS_CAP",
-                         "#ACGNT"[s], two ? "#ACGNT"[s2] : '*', (unsigned long long)rows, (unsigned long long)c->cappedPileRows);
+                         "#ACGNT"[s], two ? "#ACGNT"[s2] : '*', (unsigned long long)rows, (unsigned long long)c->call.cappedPileRows);
                 throw BfqError{BFQ_E_NOMEM, b};
             }
             const size_t mp = c->mark();
             PileRows pr;
-            if (bfq_env().trace) fprintf(stderr, "[bfq capped] pile %c%c: %llu rows, arena %zu of %zu used\n", "#ACGNT"[s], two ? "#ACGNT"[s2] : '*', (unsigned long long)rows, c->wsTop, c->wsCap);
+            if (bfq_env().trace) fprintf(stderr, "[bfq capped] pile %c%c: %llu rows, arena %zu of %zu used\n", "#ACGNT"[s], two ? "#ACGNT"[s2] : '*', (unsigned long long)rows, c->ws.top, c->ws.cap);
             const u64 m = bfq_run_one_pile(c, T8, Q8, text3, n, s, s2, c->P.term & 0xFF, &pr);
             if (bfq_env().trace) { c->sync(); fprintf(stderr, "[bfq capped]   sorted + refined\n"); }
             if (m) {
@@ -656,7 +632,13 @@ static void steps_capped(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const
     }
     c->release(m0);
 }
-
+// ... from packed reads to packed reads: the line streams (total + N bytes each) are the caller's scratch
+static void run_capped_reads(bfq_ctx *c, const u8 *bases, const u8 *quals, const u64 *roff, u64 N, u64 total, u8 *ob, u8 *oq)
+{
+    u8 *dna = c->alloc<u8>(total + N + 64), *qs = c->alloc<u8>(total + N + 64);
+    steps_capped(c, bases, quals, roff, N, total, dna, qs);
+    if (N) KLAUNCH(c, K_MISC, 4.0 * (double)total, k_lines_strip, bfq_grid(N, 16), 256, (const u8 *)dna, (const u8 *)qs, roff, N, ob, oq);
+}
 
 extern "C" int bfq_run_reads_device(bfq_ctx *c, const uint8_t *d_bases, const uint8_t *d_quals,
                                     const uint64_t *d_read_off, uint64_t N, uint64_t total, uint8_t *d_out_bases,
@@ -666,27 +648,15 @@ extern "C" int bfq_run_reads_device(bfq_ctx *c, const uint8_t *d_bases, const ui
         if (st) memset(st, 0, sizeof *st);
         reserve_step1(c, total + N, N, 0);
         c->zeroCounters();
-        if (c->capped) {
-            const u64 n = total + N;
-            u8 *dna = c->alloc<u8>(n + 64), *qs = c->alloc<u8>(n + 64);
-            steps_capped(c, d_bases, d_quals, (const u64 *)d_read_off, N, total, dna, qs);
-            if (N) KLAUNCH(c, K_MISC, 4.0 * (double)total, k_lines_strip, bfq_grid(N, 16), 256, (const u8 *)dna, (const u8 *)qs, (const u64 *)d_read_off, N, d_out_bases, d_out_quals);
-            c->fetchCounters();
-            c->profCollect();
-            check_counters(c);
-            fill_stats(c, st);
-            return;
+        const u64 *roff = (const u64 *)d_read_off;
+        c->call.keepRecs = !c->call.capped && !c->call.piles && c->env.posMode;   // position mode
+        if (c->call.capped) run_capped_reads(c, d_bases, d_quals, roff, N, total, d_out_bases, d_out_quals);
+        else {
+            bfq_step1_device(c, d_bases, d_quals, roff, N, total, c->P.term, st);
+            if (c->call.keepRecs) steps34_positions(c, d_bases, d_quals, roff, d_out_bases, d_out_quals);
+            else steps234_device(c, (u64 *)d_read_off, d_out_bases, d_out_quals);
         }
-        const bool posMode = !c->piles && c->env.posMode;
-        c->keepRecs = posMode;
-        bfq_step1_device(c, d_bases, d_quals, (const u64 *)d_read_off, N, total, c->P.term, st);
-        c->keepRecs = false;
-        if (posMode) steps34_positions(c, d_bases, d_quals, (const u64 *)d_read_off, d_out_bases, d_out_quals);
-        else steps234_device(c, (u64 *)d_read_off, d_out_bases, d_out_quals);
-        c->fetchCounters();
-        c->profCollect();
-        check_counters(c);
-        fill_stats(c, st);
+        finish_call(c, st);
     });
 }
 
@@ -705,20 +675,14 @@ extern "C" int bfq_run_reads(bfq_ctx *c, const uint8_t *h_bases, const uint8_t *
         bfq_upload(c, db, h_bases, total);
         bfq_upload(c, dq, h_quals, total);
         bfq_upload(c, dr, h_read_off, 8 * (N + 1));
-        if (c->capped) {
-            u8 *dna = c->alloc<u8>(total + N + 64), *qs = c->alloc<u8>(total + N + 64);
-            steps_capped(c, db, dq, dr, N, total, dna, qs);
-            if (N) KLAUNCH(c, K_MISC, 4.0 * (double)total, k_lines_strip, bfq_grid(N, 16), 256, (const u8 *)dna, (const u8 *)qs, (const u64 *)dr, N, ob, oq);
-        } else {
+        if (c->call.capped) run_capped_reads(c, db, dq, dr, N, total, ob, oq);
+        else {
             bfq_step1_device(c, db, dq, dr, N, total, c->P.term, st);
             steps234_device(c, dr, ob, oq);
         }
         bfq_download(c, h_out_bases, ob, total);
         bfq_download(c, h_out_quals, oq, total);
-        c->fetchCounters();
-        c->profCollect();
-        check_counters(c);
-        fill_stats(c, st);
+        finish_call(c, st);
     });
 }
 
@@ -739,9 +703,7 @@ extern "C" int bfq_build_ebwt(bfq_ctx *c, const uint8_t *h_bases, const uint8_t 
         if (h_bwt) bfq_download(c, h_bwt, c->d_bwt, n);
         if (h_bwtqs) bfq_download(c, h_bwtqs, c->d_qual, n);
         if (h_lcp16) bfq_download(c, h_lcp16, c->d_lcp, 2 * n);
-        c->fetchCounters();
-        c->profCollect();
-        check_counters(c);
+        finish_call(c);
     });
 }
 
@@ -851,15 +813,13 @@ static void smooth_invert_core(bfq_ctx *c, HostRef h_bwt, HostRef h_bwtqs, HostR
         BfqAsyncUpload *qsUp = nullptr;
         const bool qsPinned = h_bwtqs.ptr && bfq_is_pinned(h_bwtqs.ptr);
         const bool qsAsync = !haveLcp && n >= (64u << 20) && !c->env.noOverlap;
-        hipEvent_t qsEv = nullptr;
-        if (qsAsync && qsPinned) {                                 // one DMA on the copy stream, beside the kernels of the LCP deduction
-            if (!c->copyStream) HIP_CHECK(hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
-            HIP_CHECK(hipEventCreateWithFlags(&qsEv, hipEventDisableTiming));
-            HIP_CHECK(hipMemcpyAsync(in_qs, h_bwtqs.ptr, n, hipMemcpyHostToDevice, c->copyStream));
-            HIP_CHECK(hipEventRecord(qsEv, c->copyStream));
+        std::optional<ScopedEvent> qsEv;
+        if (qsAsync && qsPinned) {                                 // one DMA on the copy stream, beside the kernels of the LCP deduction (a throw: guarded() waits for it)
+            qsEv.emplace();
+            HIP_CHECK(hipMemcpyAsync(in_qs, h_bwtqs.ptr, n, hipMemcpyHostToDevice, c->copy()));
+            HIP_CHECK(hipEventRecord(*qsEv, c->copyStream));
         } else if (qsAsync) qsUp = bfq_upload_begin(c, in_qs, h_bwtqs, n);
         else bfq_upload(c, in_qs, h_bwtqs, n);
-        struct EvGuard { hipEvent_t &e; bfq_ctx *c; ~EvGuard() { if (e) { (void)hipStreamSynchronize(c->copyStream); (void)hipEventDestroy(e); e = nullptr; } } } evGuard{qsEv, c};
         struct Join { BfqAsyncUpload *u; ~Join() { if (u) { try { bfq_upload_join(u); } catch (...) {} } } } joinGuard{qsUp};
         u8 *ob = c->alloc<u8>(total + 64), *oq = c->alloc<u8>(total + 64);
         u64 *d_roff = c->alloc<u64>(N + 1);
@@ -884,7 +844,7 @@ static void smooth_invert_core(bfq_ctx *c, HostRef h_bwt, HostRef h_bwtqs, HostR
             c->gcntTerm = c->P.term & 0xFF;
         }
         if (qsUp) { bfq_phase("read_h2d"); joinGuard.u = nullptr; bfq_upload_join(qsUp); }
-        if (qsEv) HIP_CHECK(hipStreamWaitEvent(c->stream, qsEv, 0));
+        if (qsEv) HIP_CHECK(hipStreamWaitEvent(c->stream, *qsEv, 0));
         bfq_phase("gpu");
         steps234_device(c, d_roff, ob, oq, lens, hostOut);
         res->ob = ob; res->oq = oq; res->roff = d_roff; res->N = N; res->total = total;
@@ -900,10 +860,7 @@ extern "C" int bfq_smooth_invert(bfq_ctx *c, const uint8_t *h_bwt, const uint8_t
         const StreamOut ho{h_out_bases, h_out_quals, true};
         smooth_invert_core(c, HostRef::mem(h_bwt), HostRef::mem(h_bwtqs), HostRef::mem(h_lcp), lcp_bytes, n, 0, st, &r, &ho);
         bfq_download(c, h_out_read_off, r.roff, 8 * (r.N + 1));
-        c->fetchCounters();
-        c->profCollect();
-        check_counters(c);
-        fill_stats(c, st);
+        finish_call(c, st);
     });
 }
 
@@ -1006,9 +963,7 @@ static void fastq_build_ebwt_core(bfq_ctx *c, TextSrc text, int term_out, HostRe
             bfq_download(c, lcp, raw, (size_t)lcp_bytes * n);
         }
     }
-    c->fetchCounters();
-    c->profCollect();
-    check_counters(c);
+    finish_call(c);
 }
 
 // ---- the one-shot tools (gsufsort / eGap / bfq_int / bfq_ext processes): files in, files out.
@@ -1028,7 +983,6 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
     oq.open(qs_fd, capRows, est);
     if (wantLcp) ol.open(lcp_fd, capRows * (u64)lcp_bytes, est * (u64)lcp_bytes);
     u64 n = 0;
-    bool done = false;
     // HBM of this process, and why it is cut into pieces: the driver scrubs freed HBM at ~30 GB/s and the NEXT process's
     // allocations wait for it (profiles/microbench/alloc_after_exit.hip; profiles/r3/dropin_phases.md: bfq_int waited 1.3-4.3 s
     // behind a gsufsort that had held 102 GiB).  So every piece is as small as its contents and goes back the moment it is dead:
@@ -1037,17 +991,9 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
     //   arena         sort records + histograms of ONE pile, sized from the actual pile sizes, in the parse arena's memory
     //                 (what the next process waits for is everything this one ever gave back, not what it held last)
     //   text arrays   T8 / Q8 / packed text: until the last pile is sorted
-    char *pws = nullptr, *tws = nullptr;
-    char *ws0 = c->ws; size_t cap0 = c->wsCap;
-    bool swapped = false;
-    auto restoreArena = [&] { if (swapped) { c->ws = ws0; c->wsCap = cap0; c->wsTop = 0; swapped = false; } };
+    DevBuf pws, tws;                                             // parse arena, text arrays: freed after the writers have been waited for
     auto finish = [&](bool ok) {
-        c->onRows = nullptr; c->extBwt = c->extQual = nullptr; c->lcpScratch = false;
         if (!ok) { try { bfq_write_wait(c); } catch (...) {} }
-        (void)hipStreamSynchronize(c->stream);
-        restoreArena();
-        if (pws) { (void)hipFree(pws); pws = nullptr; }
-        if (tws) { (void)hipFree(tws); tws = nullptr; }
         const bool a = ob.close(ok ? n : 0), b = oq.close(ok ? n : 0), l = ol.close(ok ? n * (u64)lcp_bytes : 0);
         if (ok && !(a && b && l)) throw BfqError{BFQ_E_IO, "cannot size the output files"};
     };
@@ -1066,9 +1012,8 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
         const u64 Nb = nlines / 4 + 1;
         bfq_phase("alloc");
         const size_t parseBytes = (tl + 8192) + 128 * (Nb + 64) + 8 * (nlines + 64) + 16 * (tl / 4096 + 16) + (64u << 20);
-        if (hipMalloc((void **)&pws, parseBytes) != hipSuccess) { (void)hipGetLastError(); pws = nullptr; throw BfqError{BFQ_E_NOMEM, "device buffer for the parsed records"}; }
-        ws0 = c->ws; cap0 = c->wsCap;                                          // (the small arena of the line count)
-        c->ws = pws; c->wsCap = parseBytes; c->wsTop = 0; swapped = true;      // ws0 comes back below
+        pws.alloc(parseBytes, "the parsed records");
+        ScopedArena parse(c, pws.p, parseBytes);                // the small arena of the line count comes back below
         bfq_phase("gpu");
         c->zeroCounters();
         DevFastq fq;
@@ -1077,7 +1022,7 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
         const u64 N = fq.N;
         if (n_rows) *n_rows = n;
         if (n_reads) *n_reads = N;
-        c->writeHint = (size_t)n * (2 + (wantLcp ? (size_t)lcp_bytes : 0));
+        c->call.writeHint = (size_t)n * (2 + (wantLcp ? (size_t)lcp_bytes : 0));
         const u64 npad = (n + 64 + 255) & ~255ull;
         const bool ext = 2 * npad <= c->textCap;                // always (rows <= bytes / 2); the FASTQ text is dead from here on
         u8 *raw = nullptr;
@@ -1097,30 +1042,29 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
         const size_t lcpExtra = wantLcp ? (size_t)(lcp_bytes == 2 ? 0 : lcp_bytes) * (n + 256) + 4096 : 0;
         if (n < (32u << 20)) {
             // a small collection: one piece in one arena (0.9 GB at most); the parsed reads stay where they are meanwhile
-            restoreArena();
+            parse.restore();
             bfq_phase("alloc");
             c->reserve(ws_need(n, N, lcpExtra));
             bfq_phase("gpu");
-            c->piles = false;
-            if (ext) { c->extBwt = c->d_text; c->extQual = c->d_text + npad; }
+            if (ext) { c->call.extBwt = c->d_text; c->call.extQual = c->d_text + npad; }
             if (wantLcp && lcp_bytes != 2) raw = c->alloc<u8>((size_t)lcp_bytes * n + 64);
-            c->onRows = hook;
+            c->call.onRows = hook;
             bfq_step1_device(c, fq.bases, fq.quals, fq.roff, N, fq.total, term_out, nullptr);
         } else {
             const u64 nwords = n / BFQ_SYMS_PER_WORD + 3;
             const size_t w3 = (8 * bfq_t3_alloc(nwords) + 255) & ~(size_t)255;
             bfq_phase("alloc");
-            if (hipMalloc((void **)&tws, 2 * npad + w3 + 8 * (N + 2) + 4096) != hipSuccess) { (void)hipGetLastError(); tws = nullptr; throw BfqError{BFQ_E_NOMEM, "device buffer for the text arrays"}; }
+            tws.alloc(2 * npad + w3 + 8 * (N + 2) + 4096, "the text arrays");
             bfq_phase("gpu");
-            PileText pt{(u8 *)tws, (u8 *)tws + npad, (u64 *)(tws + 2 * npad)};
-            u64 *roff2 = (u64 *)(tws + 2 * npad + w3);
+            PileText pt{(u8 *)tws.p, (u8 *)tws.p + npad, (u64 *)(tws.p + 2 * npad)};
+            u64 *roff2 = (u64 *)(tws.p + 2 * npad + w3);
             bfq_build_text(c, fq.bases, fq.quals, fq.roff, N, n, pt.T8, pt.Q8, pt.text3, nwords);
             HIP_CHECK(hipMemcpyAsync(roff2, fq.roff, 8 * (N + 1), hipMemcpyDeviceToDevice, c->stream));
             u64 cnt[36];
             bfq_pile_pair_counts(c, pt.T8, n, cnt);             // synchronises
             c->fetchCounters();
             check_counters(c);                                  // forbidden symbols, reads beyond BFQ_MAX_READ_LEN
-            restoreArena();                                     // the parsed reads are dead
+            parse.restore();                                    // the parsed reads are dead
             // piles above an eighth of the rows are split by their second symbol; the arena holds the largest piece
             const u64 capTarget = n / 8 + (1u << 20);
             u64 cap = 1u << 20;
@@ -1131,37 +1075,30 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
             }
             bfq_phase("alloc");
             const size_t needPiles = bfq_ws_need_piles(n, N, cap, lcpExtra + (wantLcp ? 2 * (n + 256) : 0), true);
-            if (parseBytes >= needPiles + (1u << 20) && !(c->wsLimit() && parseBytes > c->wsLimit())) {
-                c->wsFree();                                    // the pile arena lives where the parsed reads were
-                c->ws = pws; c->wsCap = parseBytes; c->wsTop = 0; pws = nullptr;
-            } else { (void)hipFree(pws); pws = nullptr; }
+            if (parseBytes >= needPiles + (1u << 20) && !(c->wsLimit() && parseBytes > c->wsLimit()))
+                c->adoptWorkspace(pws.release(), parseBytes);   // the pile arena lives where the parsed reads were
+            else pws.free();
             c->reserve(needPiles);
             bfq_phase("gpu");
-            c->piles = true;
-            c->lcpScratch = !wantLcp;
-            if (ext) { c->extBwt = c->d_text; c->extQual = c->d_text + npad; }
-            else { c->extBwt = nullptr; c->extQual = nullptr; }
+            c->call.piles = true;
+            c->call.lcpScratch = !wantLcp;
+            if (ext) { c->call.extBwt = c->d_text; c->call.extQual = c->d_text + npad; }
             if (wantLcp && lcp_bytes != 2) raw = c->alloc<u8>((size_t)lcp_bytes * n + 64);
-            c->onRows = hook;
+            c->call.onRows = hook;
             bfq_step1_piles(c, nullptr, nullptr, roff2, N, fq.total, term_out, nullptr, &pt, capTarget);
         }
-        c->onRows = nullptr;
-        c->fetchCounters();                                     // waits for the stream
-        c->profCollect();
-        check_counters(c);
+        finish_call(c);                                         // waits for the stream
         bfq_phase("d2h_write");
         if (ext && !wantLcp) {                                  // what is still being written lives in the text buffer: the rest goes back now
             c->dropWorkspace();
-            if (tws) { (void)hipFree(tws); tws = nullptr; }
-            if (pws) { (void)hipFree(pws); pws = nullptr; }
+            tws.free(); pws.free();
         }
         bfq_write_wait(c);
-        done = true;
     } catch (...) {
         finish(false);
         throw;
     }
-    if (done) finish(true);
+    finish(true);
 }
 
 extern "C" int bfq_fastq_build_ebwt(bfq_ctx *c, const uint8_t *h_fastq, uint64_t len, int term_out, uint8_t *h_bwt,
@@ -1205,8 +1142,8 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
         const bool ebwtDomain = J->compress_streams == 2 || J->compress_streams == 3;   // rows of the edited eBWT instead of reads
         const bool qsByRead = J->compress_streams == 3;            // ... but the qualities in read order (they keep their along-the-read correlation)
         if (ebwtDomain && (!J->out_dna || !J->out_qs || J->out_fastq)) throw BfqError{BFQ_E_ARG, "compress_streams = 2 gives out_dna and out_qs (no FASTQ text)"};
-        if (c->capped && ebwtDomain) throw BfqError{BFQ_E_NOMEM, "eBWT-domain containers need the LF table: above the workspace cap"};
-        const bool lines = J->out_dna || J->out_qs || c->capped;  // the inversion writes the line streams itself (the capped mode knows nothing else)
+        if (c->call.capped && ebwtDomain) throw BfqError{BFQ_E_NOMEM, "eBWT-domain containers need the LF table: above the workspace cap"};
+        const bool lines = J->out_dna || J->out_qs || c->call.capped;  // the inversion writes the line streams itself (the capped mode knows nothing else)
         const u64 sl = fq.total + fq.N;
         const bool wantLines = J->out_dna || J->out_qs;
         if (wantLines && sl > J->cap_stream) throw BfqError{BFQ_E_ARG, "stream buffer too small (the input length is always enough)"};
@@ -1236,13 +1173,10 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
                 if (hl > J->cap_hdr) throw BfqError{BFQ_E_ARG, "stream buffer too small (the input length is always enough)"};
                 if (hl >= (1u << 20) && bfq_is_pinned(J->out_hdr) && !c->env.noOverlap) {
                     // a pinned destination: the copy rides the copy stream beside the sort instead of in front of it
-                    if (!c->copyStream) HIP_CHECK(hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
-                    hipEvent_t ev;
-                    HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+                    ScopedEvent ev;
                     HIP_CHECK(hipEventRecord(ev, c->stream));
-                    HIP_CHECK(hipStreamWaitEvent(c->copyStream, ev, 0));
+                    HIP_CHECK(hipStreamWaitEvent(c->copy(), ev, 0));
                     HIP_CHECK(hipMemcpyAsync(J->out_hdr, d_hdr, hl, hipMemcpyDeviceToHost, c->copyStream));
-                    (void)hipEventDestroy(ev);
                     hdrOnCopyStream = true;
                 } else bfq_download(c, J->out_hdr, d_hdr, hl);
                 J->hdr_bytes = hl;
@@ -1253,7 +1187,7 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
         if (wantStreams) { bfq_pick_u64(c, fq.roff, d_pidx, np + 1, 1, d_pick + 2 * (np + 1)); pickS = true; }   // roff[i] + i
         size_t m = c->mark();
         StreamOut so{cz ? nullptr : J->out_dna, cz ? nullptr : J->out_qs};
-        if (c->capped) {
+        if (c->call.capped) {
             steps_capped(c, fq.bases, fq.quals, fq.roff, fq.N, fq.total, ob, oq);
             if (so.h_dna) bfq_download(c, so.h_dna, ob, sl);
             if (so.h_qs) bfq_download(c, so.h_qs, oq, sl);
@@ -1300,10 +1234,7 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
         }
         HIP_CHECK(hipMemcpyAsync(hp.data() + (np + 1), d_pick + (np + 1), 8 * 3 * (np + 1), hipMemcpyDeviceToHost, c->stream));
         if (hdrOnCopyStream) HIP_CHECK(hipStreamSynchronize(c->copyStream));
-        c->fetchCounters();
-        c->profCollect();
-        check_counters(c);
-        fill_stats(c, st);
+        finish_call(c, st);
         for (int p = 0; p <= np; p++) {
             J->part_reads[p] = hp[p];
             J->part_fastq_off[p] = pickF ? hp[(np + 1) + p] : 0;
@@ -1363,17 +1294,9 @@ static void smooth_invert_fastq_core(bfq_ctx *c, HostRef bwt, HostRef qs, HostRe
     if (outFile) {
         if (outFile->m && ol > bfq_outmap_len(outFile->m)) throw BfqError{BFQ_E_IO, "output mapping smaller than the FASTQ text"};
         bfq_write_async(c, outFile->at(0), d_out, ol);
-        c->fetchCounters();
-        c->profCollect();
-        bfq_phase("d2h_write");
-        bfq_write_wait(c);
-    } else {
-        bfq_download(c, out, d_out, ol);
-        c->fetchCounters();
-        c->profCollect();
-    }
-    check_counters(c);
-    fill_stats(c, st);
+    } else bfq_download(c, out, d_out, ol);
+    finish_call(c, st);
+    if (outFile) { bfq_phase("d2h_write"); bfq_write_wait(c); }
 }
 
 extern "C" int bfq_smooth_invert_fastq(bfq_ctx *c, const uint8_t *h_bwt, const uint8_t *h_bwtqs, const void *h_lcp,
@@ -1520,7 +1443,7 @@ extern "C" int bfq_stream_reserve(bfq_ctx *c, uint64_t len)
 extern "C" int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len)
 {
     return guarded(c, [&] {
-        c->wsTop = 0;
+        c->release(0);
         *out_len = bfq_codec_compress_device(c, d_in, len, d_out, cap);
         c->sync();
         c->profCollect();

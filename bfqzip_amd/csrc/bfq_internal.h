@@ -8,17 +8,14 @@
 #include <stdint.h>
 #include <functional>
 #include <new>
+#include <optional>
 #include <string>
 #include <vector>
 #include <thread>
 #include "../../include/bfqzip_hip.h"
 #include "bfq_common.h"
 #include "bfq_internal_host.h"
-
-struct BfqError {
-    int code;
-    std::string msg;
-};
+#include "bfq_arena.h"
 
 #define HIP_CHECK(expr)                                                                        \
     do {                                                                                       \
@@ -65,19 +62,39 @@ struct RankIndex {
     u64 n;
 };
 
+// What one top-level call decides for the stages below it.  guarded() starts every call from CallState{} and puts that back
+// when the call throws: nothing here survives a call.
+struct CallState {
+    bool piles = false;             // step 1 runs pile by pile (k_piles.hip): set by the reservation of the current call
+    bool capped = false;            // the whole path in position mode, one two-symbol pile at a time (workspace cap): set likewise
+    u64 cappedPileRows = 0;         // ... and the rows of the largest pile its arena has room for
+    bool keepRecs = false;          // step 1 leaves the packed text and the sorted records' (w1, w2) words in the arena (position mode)
+    const u64 *d_w12 = nullptr, *d_text3 = nullptr;
+    size_t keepMark = 0;
+    size_t writeHint = 0;           // bytes the caller is going to queue in all: sizes the writer pool when it is created
+    // one-shot tools (the *_fd entry points): the eBWT and its qualities live outside the arena (in the text buffer, whose
+    // FASTQ text is dead once the reads are gathered), so that the arena can be freed while they are still being written;
+    // onRows(start, rows) is called whenever rows [start, start + rows) of the eBWT / QS / LCP are final (pile by pile)
+    u8 *extBwt = nullptr, *extQual = nullptr;
+    bool lcpScratch = false;        // pile mode: nobody reads the LCP (gsufsort): one pile's worth of scratch instead of 2 n bytes
+    std::function<void(u64, u64)> onRows;
+};
+
 struct bfq_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t copyStream = nullptr;   // device -> host copies that overlap the tail of the inversion
+    hipStream_t copy() { if (!copyStream) HIP_CHECK(hipStreamCreateWithFlags(&copyStream, hipStreamNonBlocking)); return copyStream; }   // ... created on first use
     bfq_params P;
     BfqEnv env;                         // the BFQ_* environment as bfq_create() / bfq_set_params() found it
     std::string err;
 
     // workspace arena (bump allocator, reset per top-level call)
-    char *ws = nullptr;
-    size_t wsCap = 0, wsTop = 0, wsPeak = 0;
+    Arena ws;
     void reserve(size_t bytes);
     void wsFree();
+    void adoptWorkspace(char *p, size_t bytes);   // frees the arena: this buffer is the arena now, and the context's to free
+    void quiesce() { (void)hipStreamSynchronize(stream); }
     // an arena being allocated on a helper thread while the caller uploads its input (a one-shot tool's 86 GB can land on
     // memory the driver has not cleared yet: 2 s instead of 0); reserve() joins it and takes it over when it is large enough
     void reserveBegin(size_t bytes);
@@ -87,10 +104,10 @@ struct bfq_ctx {
     size_t wsPendBytes = 0;
     double wsPendSecs = 0;
     void dropWorkspace();           // frees the arena now (one-shot tools: lets the driver scrub it while outputs are written)
-    void *allocBytes(size_t bytes);
+    void *allocBytes(size_t bytes) { return ws.alloc(bytes); }
     template <class T> T *alloc(size_t count) { return (T *)allocBytes(count * sizeof(T)); }
-    size_t mark() const { return wsTop; }
-    void release(size_t m) { wsTop = m; }
+    size_t mark() const { return ws.mark(); }
+    void release(size_t m) { ws.release(m); }
 
     DevCounters *d_cnt = nullptr;   // device
     DevCounters h_cnt;              // host copy
@@ -103,13 +120,8 @@ struct bfq_ctx {
     u32 *d_gcnt = nullptr;          // symbol counts per 256-row group, written by k_emit_bwt
     int gcntTerm = -1;              // terminator byte those counts were taken with
     u64 n = 0, N = 0;
-    bool piles = false;             // step 1 runs pile by pile (k_piles.hip): set by the reservation of the current call
-    bool capped = false;            // the whole path in position mode, one two-symbol pile at a time (workspace cap): set likewise
-    u64 cappedPileRows = 0;         // ... and the rows of the largest pile its arena has room for
+    CallState call;
     size_t wsLimit() const { return env.wsCap ? (size_t)env.wsCap : (size_t)(P.ws_cap_mib > 0 ? P.ws_cap_mib : 0) << 20; }
-    bool keepRecs = false;          // step 1 leaves the packed text and the sorted records' (w1, w2) words in the arena (position mode)
-    const u64 *d_w12 = nullptr, *d_text3 = nullptr;
-    size_t keepMark = 0;
 
     // profiling
     bool profOn = true;
@@ -136,14 +148,6 @@ struct bfq_ctx {
     void ioInit(int want);          // at least min(want, the thread budget) staging workers exist afterwards
     void ioFree();
     struct BfqWriter *writer = nullptr;  // background device -> host / file writes (bfq_write_async, bfq_io.hip)
-    size_t writeHint = 0;               // bytes the caller is going to queue in all: sizes the writer pool when it is created
-
-    // one-shot tools (the *_fd entry points): the eBWT and its qualities live outside the arena (in the text buffer, whose
-    // FASTQ text is dead once the reads are gathered), so that the arena can be freed while they are still being written;
-    // onRows(start, rows) is called whenever rows [start, start + rows) of the eBWT / QS / LCP are final (pile by pile)
-    u8 *extBwt = nullptr, *extQual = nullptr;
-    bool lcpScratch = false;            // pile mode: nobody reads the LCP (gsufsort): one pile's worth of scratch instead of 2 n bytes
-    std::function<void(u64, u64)> onRows;
 
     // device copy of the FASTQ text of the current call (outside the arena: its record count sizes the arena);
     // kept between calls, grown when a larger text arrives
@@ -157,6 +161,35 @@ struct bfq_ctx {
     u64 globN = 0;                  // global mode: the two-symbol pile sizes bfq_glob_pile_counts found for a text of globN rows
     u64 globCounts[36] = {0};
 };
+using ScopedArena = ScopedArenaT<bfq_ctx>;
+
+// one hipMalloc and its hipFree
+struct DevBuf {
+    char *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { free(); }
+    bool tryAlloc(size_t bytes)
+    {
+        free();
+        if (hipMalloc((void **)&p, bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        p = nullptr;
+        return false;
+    }
+    void alloc(size_t bytes, const char *what) { if (!tryAlloc(bytes)) throw BfqError{BFQ_E_NOMEM, std::string("device buffer for ") + what}; }
+    void free() { if (p) (void)hipFree(p); p = nullptr; }
+    char *release() { char *q = p; p = nullptr; return q; }   // to another owner
+};
+// an event without timing, to order one stream behind another
+struct ScopedEvent {
+    hipEvent_t e = nullptr;
+    ScopedEvent() { HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+    ScopedEvent(const ScopedEvent &) = delete; ScopedEvent &operator=(const ScopedEvent &) = delete;
+    ~ScopedEvent() { (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
 // a host-side operand of a transfer: memory, or an open file at an offset (the front-ends' files)
 struct HostRef {
     void *ptr = nullptr; int fd = -1; u64 off = 0;
@@ -224,16 +257,20 @@ template <class F> static int guarded(bfq_ctx *c, F body)
     try {
         HIP_CHECK(hipSetDevice(c->device));
         c->err.clear();
+        c->call = CallState{};
         body();
         return BFQ_OK;
     } catch (const BfqError &e) {
         c->err = e.msg;
+        c->call = CallState{};
         (void)hipStreamSynchronize(c->stream);
+        if (c->copyStream) (void)hipStreamSynchronize(c->copyStream);   // copies into the caller's buffers have landed or failed
         (void)hipGetLastError();
         c->recs.clear(); c->evUsed = 0;
         return e.code;
     } catch (const std::bad_alloc &) {
         c->err = "host out of memory";
+        c->call = CallState{};
         return BFQ_E_NOMEM;
     }
 }

@@ -5,6 +5,12 @@
 #include <string>
 #include "../../include/bfqzip_hip.h"
 
+// what a failing stage throws: a BFQ_E_* code and the text bfq_last_error() returns
+struct BfqError {
+    int code;
+    std::string msg;
+};
+
 // The BFQ_* environment variables.  bfq_env(): read once per process (first use) -- tracing, lease, thread counts.
 // A context keeps its own copy, refreshed by bfq_create() and bfq_set_params() only (test knobs change between calls).
 struct BfqEnv {

@@ -302,7 +302,7 @@ static BfqWriter *writer_get(bfq_ctx *c, size_t firstBytes)
     if (c->writer) return c->writer;
     BfqWriter *W = new BfqWriter();
     W->c = c;
-    // sized by what the caller expects to write in all (bfq_ctx::writeHint) or by the first job: one thread per 128 MiB
+    // sized by what the caller expects to write in all (CallState::writeHint) or by the first job: one thread per 128 MiB
     const int T = (int)std::min<size_t>((size_t)io_threads(), std::max<size_t>(1, (firstBytes + (128u << 20) - 1) / (128u << 20)));
     for (int t = 0; t < T; t++) {
         HIP_CHECK(hipStreamCreateWithFlags(&W->w[t].stream, hipStreamNonBlocking));
@@ -318,7 +318,7 @@ static BfqWriter *writer_get(bfq_ctx *c, size_t firstBytes)
 void bfq_write_async(bfq_ctx *c, HostRef dst, const void *d_src, size_t len)
 {
     if (!len) return;
-    BfqWriter *W = writer_get(c, std::max<size_t>(len, c->writeHint));
+    BfqWriter *W = writer_get(c, std::max<size_t>(len, c->call.writeHint));
     hipEvent_t ev;
     HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     HIP_CHECK(hipEventRecord(ev, c->stream));

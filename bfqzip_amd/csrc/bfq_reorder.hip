@@ -173,7 +173,7 @@ extern "C" int bfq_fastq_reorder_fd(bfq_ctx *c, const int *in_fd, const uint64_t
             ro_check_opts(opts, nparts, &k);
             // mapped to their final length and pre-faulted beside the upload
             for (int p = 0; p < nparts; p++) { of[p].open(out_fd[p], tl[p] + 4096, tl[p]); opened = p + 1; }
-            c->writeHint = (size_t)(tl[0] + tl[1]);
+            c->call.writeHint = (size_t)(tl[0] + tl[1]);
             RoSink sink;
             sink.put = [&](int p, const u8 *d_text, u64 len) { bfq_write_async(c, of[p].at(0), d_text, len); };
             reorder_core(c, src, nparts, opts, sink, tl, nullptr, n_reads);

@@ -180,30 +180,22 @@ void bfq_refine_huge(bfq_ctx *c, SortRec rec, const u64 *text3, u64 n, u16 *lcp,
     for (u64 i = 0; i < nh; i++) maxLen = std::max(maxLen, hl[i]);
     const size_t fixed = (48u << 20) + 16 * nh;
     auto slots = [&](size_t bytes) { return bytes > fixed ? (u64)((bytes - fixed) / HUGE_BYTES_PER_SLOT) : 0ull; };
-    u64 cap = slots(c->wsCap - c->wsTop);
-    char *side = nullptr;
-    char *const ws0 = c->ws;
-    const size_t cap0 = c->wsCap, top0 = c->wsTop;
+    u64 cap = slots(c->ws.room());
+    DevBuf side;                                       // freed after the guard has waited for the rounds and put the arena back
+    std::optional<ScopedArena> inSide;
     if (cap < maxLen && !c->env.hugeCap) {
         size_t freeB = 0, totalB = 0;
         HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
         size_t want = fixed + (size_t)std::min<u64>(hc[1], 1ull << 31) * HUGE_BYTES_PER_SLOT;
         size_t most = freeB - freeB / 8;
         if (want > most) want = most;
-        if (slots(want) > cap && hipMalloc((void **)&side, want) == hipSuccess) {
-            c->ws = side; c->wsCap = want; c->wsTop = 0;
+        if (slots(want) > cap && side.tryAlloc(want)) {
+            inSide.emplace(c, side.p, want);
             cap = slots(want);
-        } else {
-            (void)hipGetLastError();
-            side = nullptr;
         }
     }
-    struct Restore {                                   // the arena goes back however the rounds end
-        bfq_ctx *c; char *ws; size_t cap, top; char *side;
-        ~Restore() { if (side) { (void)hipStreamSynchronize(c->stream); (void)hipFree(side); c->ws = ws; c->wsCap = cap; c->wsTop = top; } }
-    } restore{c, ws0, cap0, top0, side};
-    if (bfq_env().trace) fprintf(stderr, "[bfq huge] %llu segments, %llu rows, longest %llu; slots %llu%s\n", (unsigned long long)nh, (unsigned long long)hc[1],
-                                 (unsigned long long)maxLen, (unsigned long long)cap, side ? " (side buffer)" : "");
+    if (c->env.trace) fprintf(stderr, "[bfq huge] %llu segments, %llu rows, longest %llu; slots %llu%s\n", (unsigned long long)nh, (unsigned long long)hc[1],
+                                 (unsigned long long)maxLen, (unsigned long long)cap, side.p ? " (side buffer)" : "");
     if (cap > (1ull << 31)) cap = 1ull << 31;          // slot numbers and sub-segment ids are 32-bit sort keys
     if (c->env.hugeCap && c->env.hugeCap < cap) cap = c->env.hugeCap;   // BFQ_HUGE_CAP, test hook: exercise batching and the oversize route on small inputs
     std::vector<u64> overS, overL;

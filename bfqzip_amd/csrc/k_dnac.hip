@@ -328,7 +328,7 @@ struct DqMem {
     template <typename Tp> Tp *get(u64 count)
     {
         const u64 bytes = count * sizeof(Tp) + 256;
-        if (c->wsCap - c->wsTop >= bytes + 512) return c->alloc<Tp>(count);
+        if (c->ws.room() >= bytes + 512) return c->alloc<Tp>(count);
         void *p = nullptr;
         if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); throw BfqError{BFQ_E_NOMEM, "stream codec: no device memory for the context table"}; }
         own.push_back(p);
@@ -343,7 +343,7 @@ static bool dq_prepare(bfq_ctx *c, DqMem &M, const u8 *d_in, u64 n, DqInput &I)
 {
     if (n < 65536 || c->env.dnaStatic) return false;
     // under a workspace cap the context table (8 bytes per base, up to 34 GB) must fit what the arena has left: else the static container
-    if (c->wsLimit() && c->wsCap - c->wsTop < (8ull << dq_H(n)) + 4 * n + (256u << 20)) return false;
+    if (c->wsLimit() && c->ws.room() < (8ull << dq_H(n)) + 4 * n + (256u << 20)) return false;
     u8 last = 0;
     HIP_CHECK(hipMemcpyAsync(&last, d_in + n - 1, 1, hipMemcpyDeviceToHost, c->stream));
     const u64 nl = bfq_fastq_count_lines(c, d_in, n) - 1;        // (synchronises)

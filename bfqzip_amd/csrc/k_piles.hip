@@ -175,16 +175,16 @@ size_t bfq_ws_need_piles(u64 n, u64 N, u64 cap, u64 extra, bool lean)
 
 // pre != nullptr: the text arrays exist already (one-shot tools: they live in an allocation of their own, so that the
 // arena can be sized from the actual pile sizes).  capTarget != 0: piles above it are split by their second symbol even
-// when they would fit.  c->lcpScratch: nobody wants the LCP -- every pile writes its entries to the same scratch.
+// when they would fit.  c->call.lcpScratch: nobody wants the LCP -- every pile writes its entries to the same scratch.
 void bfq_step1_piles(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, u64 total, int termOut, bfq_stats *st,
                      const PileText *pre, u64 capTarget)
 {
     const u64 n = total + N;
     if (n >= (1ull << BFQ_POS_BITS)) throw BfqError{BFQ_E_ARG, "collection too large (2^37 rows)"};
     c->n = n; c->N = N;
-    c->d_bwt = c->extBwt ? c->extBwt : c->alloc<u8>(n + 64);
-    c->d_qual = c->extQual ? c->extQual : c->alloc<u8>(n + 64);
-    const bool scratch = c->lcpScratch;
+    c->d_bwt = c->call.extBwt ? c->call.extBwt : c->alloc<u8>(n + 64);
+    c->d_qual = c->call.extQual ? c->call.extQual : c->alloc<u8>(n + 64);
+    const bool scratch = c->call.lcpScratch;
     c->d_lcp = scratch ? nullptr : c->alloc<u16>(n + 64);
     c->d_gcnt = nullptr; c->gcntTerm = -1;                       // symbol counts per group are not produced pile by pile
     if (!n) return;
@@ -211,9 +211,9 @@ void bfq_step1_piles(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64
     if (tot[0] != N) throw BfqError{BFQ_E_ARG, "pile counts do not match the collection"};
     if (N) KLAUNCH(c, K_EMIT, 12.0 * (double)N, k_term_pile, bfq_grid(N, 256), 256, (const u8 *)T8, (const u8 *)Q8, d_roff, N,
                    (u32)(termOut & 0xFF), c->d_bwt, c->d_qual, c->d_lcp);
-    if (c->onRows) c->onRows(0, N);
+    if (c->call.onRows) c->call.onRows(0, N);
 
-    const size_t avail = c->wsCap - c->wsTop;
+    const size_t avail = c->ws.room();
     auto fits = [&](u64 m) { return (size_t)(24 * (m + 256) + 12 * 256 * (ceil_div(m + 1, bfq_radix_block_elems(m)) + 8) + (m / 32768 + 4096) * 64 + (scratch ? 2 * (m + 256) : 0) + (48u << 20)) <= avail; };
     // one pile (first symbol s, second symbol s2 or 7 = any) of m suffixes -> rows [start, start + m)
     auto run_pile = [&](u32 s, u32 s2, u64 m, u64 start, const u64 *off) {
@@ -236,7 +236,7 @@ void bfq_step1_piles(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64
     for (u32 s = 1; s <= 5; s++) {
         const u64 m = tot[s];
         if (!m) continue;
-        if (fits(m) && !c->env.pilesSplit && !(capTarget && m > capTarget)) { run_pile(s, 7u, m, start, blkOff + (u64)s * nb); if (c->onRows) c->onRows(start, m); start += m; continue; }
+        if (fits(m) && !c->env.pilesSplit && !(capTarget && m > capTarget)) { run_pile(s, 7u, m, start, blkOff + (u64)s * nb); if (c->call.onRows) c->call.onRows(start, m); start += m; continue; }
         // a pile beyond the workspace (skewed base composition, low-complexity reads): once more by its second symbol
         const size_t ms = c->mark();
         u32 *cnt2 = c->alloc<u32>(6 * nb);
@@ -264,7 +264,7 @@ void bfq_step1_piles(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64
                 c->sync();
             }
             firstSub = false;
-            if (c->onRows) c->onRows(start, m2);
+            if (c->call.onRows) c->call.onRows(start, m2);
             start += m2;
         }
         c->release(ms);

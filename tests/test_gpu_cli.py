@@ -161,6 +161,14 @@ def test_tools_on_files_beyond_one_staging_chunk(tools, tmp_path, engine):
         r = _run([tools["gsufsort"], fq, "--bwt", "--qs", "-o", out + "n"], env=dict(os.environ, **env))
         assert r.returncode == 0 and np.array_equal(np.fromfile(out + "n.bwt", np.uint8), bwt)
         assert np.array_equal(np.fromfile(out + "n.bwt.qs", np.uint8), qs)
+    # 70.7 M rows are above the builder's one-piece limit (2^25): the parse arena became the pile arena above.  The same
+    # input with one record whose quality line is a byte short: the builder gives up while the parse arena stands in for the
+    # context's own, exits non-zero and leaves empty outputs
+    ends = np.flatnonzero(text == 10)
+    np.delete(text, int(ends[4 * 350_000 + 3]) - 1).tofile(fq + ".bad")
+    r = _run([tools["gsufsort"], fq + ".bad", "--bwt", "--qs", "-o", out + "b"])
+    assert r.returncode != 0, r.stdout
+    assert os.path.getsize(out + "b.bwt") == 0 and os.path.getsize(out + "b.bwt.qs") == 0
 
 
 def _lease_lines(blob):

@@ -123,6 +123,98 @@ def test_errors_are_loud(engine):
         engine.smooth_invert(A(b"AC#G"), A(b"IIII"))          # not an eBWT in suffix order
 
 
+@pytest.fixture(scope="module")
+def small_set(orc):
+    """2 000 x 60 bp synthetic reads with what the oracle makes of them (shared, read-only)."""
+    b, q, r = api.synth_host(api.synth_spec(2000, 60, seed=31, coverage=25))
+    par = dict(k=16, m=5, v=ord(">"), f=40, t=20, M=2, B=0)
+    p = orc.params(K=par["k"], m=par["m"], v=par["v"], f=par["f"], t=par["t"], M=par["M"], B=par["B"])
+    return dict(b=b, q=q, r=r, par=par, ebwt=orc.build_ebwt(b, q, r), reads=orc.run_reads(b, q, r, p))
+
+
+def _check_small_set(e, s, device=False):
+    """Good calls on the 2 000 x 60 set: reads, statistics, eBWT / QS / LCP and bfq_fetch_ebwt against the oracle."""
+    ob, oq, ost = s["reads"]
+    hb, hq, hst = e.run_reads(s["b"], s["q"], s["r"])
+    assert np.array_equal(hb, ob) and np.array_equal(hq, oq) and all(ost[k] == hst[k] for k in ost)
+    if device:
+        import torch
+        dev = torch.device("cuda:0")
+        db, dq = torch.from_numpy(s["b"]).to(dev), torch.from_numpy(s["q"]).to(dev)
+        dr = torch.from_numpy(s["r"].astype(np.int64)).to(dev)
+        xb, xq = torch.empty_like(db), torch.empty_like(db)
+        dst = e.run_reads_device(db.data_ptr(), dq.data_ptr(), dr.data_ptr(), len(s["r"]) - 1, len(s["b"]), xb.data_ptr(), xq.data_ptr())
+        torch.cuda.synchronize()
+        assert np.array_equal(xb.cpu().numpy(), ob) and np.array_equal(xq.cpu().numpy(), oq) and all(ost[k] == dst[k] for k in ost)
+    bwt, qs, lcp = s["ebwt"]
+    for gb, gq, gl in (e.build_ebwt(s["b"], s["q"], s["r"]), e.fetch_ebwt(len(bwt))):
+        assert np.array_equal(gb, bwt) and np.array_equal(gq, qs) and np.array_equal(gl.astype(np.uint32), lcp)
+
+
+@pytest.mark.parametrize("mode", ["default", "posmode", "piles", "capped"])
+def test_failed_call_leaves_nothing_behind(engine, small_set, monkeypatch, mode):
+    """A call that ends in BFQ_E_SYMBOL (one 'X' among 2 000 x 60 bp reads; through the host arrays and through device
+    pointers, where the position mode lives) leaves no per-call state in the context: the good calls that follow on the same
+    engine are bit-exact against the oracle, and bfq_fetch_ebwt returns the eBWT just built.  The capped mode is asked for
+    with piles = 2 beside ws_cap_mib: at this size no cap selects it by itself (the one-piece arena is smaller than the capped
+    mode's own), and bfq_build_ebwt, which needs the eBWT arrays, then runs pile by pile under that cap."""
+    torch = pytest.importorskip("torch")
+    s = small_set
+    env = dict(posmode=("BFQ_POSMODE", "1"), piles=("BFQ_PILES", "1")).get(mode)
+    if env:
+        monkeypatch.setenv(*env)
+    par = dict(s["par"], **(dict(piles=2, ws_cap_mib=400) if mode == "capped" else {}))
+    bad = s["b"].copy()
+    bad[len(bad) // 2] = ord("X")
+    dev = torch.device("cuda:0")
+    db, dq = torch.from_numpy(bad).to(dev), torch.from_numpy(s["q"]).to(dev)
+    dr = torch.from_numpy(s["r"].astype(np.int64)).to(dev)
+    xb, xq = torch.empty_like(db), torch.empty_like(db)
+    try:
+        engine.set_params(**par)                                         # (reads the environment again)
+        with pytest.raises(api.BfqError) as e:
+            engine.run_reads_device(db.data_ptr(), dq.data_ptr(), dr.data_ptr(), len(s["r"]) - 1, len(bad), xb.data_ptr(), xq.data_ptr())
+        assert e.value.code == -3
+        with pytest.raises(api.BfqError) as e:
+            engine.run_reads(bad, s["q"], s["r"])
+        assert e.value.code == -3
+        torch.cuda.synchronize()
+        _check_small_set(engine, s, device=True)
+        if mode == "capped":
+            assert engine.workspace_bytes() <= 400 << 20
+    finally:
+        if env:
+            monkeypatch.delenv(env[0])
+        engine.set_params()
+
+
+def test_huge_segment_side_buffer(orc, small_set, monkeypatch, capfd):
+    """A segment the arena has no room for: 20 000 reads of 100 A (beside 200 random reads) put ~1.7 M rows into one segment of
+    equal sort keys; at 112 bytes per slot its radix rounds need ~190 MB where the arena of a 2.04 M-row call (ws_need) has
+    ~90 MB left, so bfq_refine_huge runs them in a side buffer that stands in for the arena meanwhile.  The engine is this
+    test's own: the shared one may hold a larger arena from earlier tests.  eBWT / QS / LCP against the oracle (2.7 s on
+    the CPU for this input), and the small set on the same engine afterwards: the arena is back."""
+    monkeypatch.setenv("BFQ_TRACE", "1")
+    rng = np.random.default_rng(11)
+    nA = 20_000
+    b = np.concatenate([np.full(nA * 100, ord("A"), np.uint8), rng.choice(np.frombuffer(b"ACGT", np.uint8), 200 * 100)])
+    q = (np.arange(len(b)) % 40 + 35).astype(np.uint8)
+    r = np.arange(nA + 200 + 1, dtype=np.uint64) * 100
+    e = api.Engine(0)
+    try:
+        capfd.readouterr()
+        gb, gq, gl = e.build_ebwt(b, q, r)
+        huge = [l for l in capfd.readouterr().err.splitlines() if l.startswith("[bfq huge]")]
+        print("\n".join(huge))
+        assert huge and all("(side buffer)" in l for l in huge), huge
+        bwt, qs, lcp = orc.build_ebwt(b, q, r)
+        assert np.array_equal(gb, bwt) and np.array_equal(gq, qs) and np.array_equal(gl.astype(np.uint32), lcp)
+        e.set_params(**small_set["par"])
+        _check_small_set(e, small_set)
+    finally:
+        e.close()
+
+
 def test_device_resident_and_synth_device(engine, orc):
     torch = pytest.importorskip("torch")
     sp = api.synth_spec(20000, 100, seed=77)

@@ -87,6 +87,15 @@ def test_shared_host_device_helpers(tmp_path):
     assert r.returncode == 0, r.stdout.decode()[-2000:]
 
 
+def test_arena_host(tmp_path):
+    """bfq_arena.h (the workspace bump allocator and the guard that lends a context another buffer) compiled for the host."""
+    import subprocess
+    exe = str(tmp_path / "test_arena")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cxx", "test_arena.cpp")])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, timeout=120)
+    assert r.returncode == 0, r.stdout.decode()[-2000:]
+
+
 # ---- per-GPU lease of the one-shot tools (bfq_device_lease: host only, no GPU needed).  BFQzip_parallel.py:277-285
 # starts n concurrent children; each must end up on a GPU of its own, and never two on one.
 _LEASE_CHILD = r"""
