@@ -26,6 +26,9 @@ SYMBOLS = [
     "bfq_stream_reserve", "bfq_stream_compress_device", "bfq_stream_ebwt_decode",
     "bfq_fastq_restore_bound", "bfq_fastq_restore", "bfq_fastq_restore_fd",
     "bfq_reorder_key", "bfq_fastq_reorder", "bfq_fastq_reorder_fd",
+    "bfq_perm_bound", "bfq_perm_reads", "bfq_perm_encode", "bfq_perm_decode",
+    "bfq_fastq_reorder_keep", "bfq_fastq_reorder_keep_fd", "bfq_fastq_unreorder", "bfq_fastq_unreorder_fd",
+    "bfq_fastq_restore_ordered", "bfq_fastq_restore_ordered_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -174,6 +177,19 @@ def lib():
                                         C.POINTER(u64), vp, C.POINTER(u64)]
         L.bfq_fastq_reorder_fd.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(u64), C.c_int, C.POINTER(ReorderOpts), C.POINTER(C.c_int),
                                            C.POINTER(u64), C.POINTER(u64)]
+        pu64, pint = C.POINTER(u64), C.POINTER(C.c_int)
+        L.bfq_perm_bound.restype = u64
+        L.bfq_perm_bound.argtypes = [u64]
+        L.bfq_perm_reads.restype = C.c_int64
+        L.bfq_perm_reads.argtypes = [vp, u64]
+        L.bfq_perm_encode.argtypes = [vp, u64, C.POINTER(ReorderOpts), vp, u64, pu64]
+        L.bfq_perm_decode.argtypes = [vp, u64, vp, u64, pu64, C.POINTER(ReorderOpts), pu64]
+        L.bfq_fastq_reorder_keep.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(ReorderOpts), C.POINTER(vp), pu64, pu64, vp, u64, pu64, pu64]
+        L.bfq_fastq_reorder_keep_fd.argtypes = [vp, pint, pu64, C.c_int, C.POINTER(ReorderOpts), pint, C.c_int, pu64, pu64, pu64]
+        L.bfq_fastq_unreorder.argtypes = [vp, C.POINTER(TextPart), C.c_int, vp, u64, C.POINTER(vp), pu64, pu64, pu64]
+        L.bfq_fastq_unreorder_fd.argtypes = [vp, pint, pu64, C.c_int, C.c_int, u64, pint, pu64, pu64]
+        L.bfq_fastq_restore_ordered.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, pu64, pu64]
+        L.bfq_fastq_restore_ordered_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, pu64, pu64]
         L.bfq_stream_compress_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]
         L.bfq_prof_reset.argtypes = [vp]

@@ -425,35 +425,47 @@ class Engine:
         return dna[:int(sl.value)], qs[:int(sl.value)], int(nr.value)
 
     # ---- the way back: containers -> FASTQ text (bfq_fastq_restore)
-    def fastq_restore(self, dna, qs, hdr=None, out=None):
+    def fastq_restore(self, dna, qs, hdr=None, out=None, perm=None):
         """The FASTQ text of a collection from the containers of its streams (fastq_job(compress=1 / 2 / 3), stream_compress,
         the .bsc files of parallel.py --compress): (text as a uint8 array, n_reads).  hdr=None: every header line is "@".
         `out`: a uint8 array to fill (e.g. PinnedBuffer.array); the result is a view of it.  Streams that do not belong
-        together raise BfqError (BFQ_E_ARG, the message names the first offending read) and leave `out` untouched."""
+        together raise BfqError (BFQ_E_ARG, the message names the first offending read) and leave `out` untouched.
+        `perm`: the BFQPERM1 container of the reordering the collection went through (fastq_reorder(keep=True)): the records
+        come back in the order before it (bfq_fastq_restore_ordered)."""
         dna, qs = _u8(dna), _u8(qs)
         hdr = _u8(hdr) if hdr is not None else None
+        perm = _u8(perm) if perm is not None else None
         if out is None:
             bound = int(self.L.bfq_fastq_restore_bound(_ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0))
             if bound < 0:
                 raise BfqError(-1, "not a container (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQEBWT1)")
             out = np.empty(max(bound, 1), np.uint8)
         ol, nr = C.c_uint64(0), C.c_uint64(0)
-        self._ck(self.L.bfq_fastq_restore(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0,
-                                          _ptr(out), len(out), C.byref(ol), C.byref(nr)))
+        if perm is not None:
+            self._ck(self.L.bfq_fastq_restore_ordered(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0,
+                                                      _ptr(perm) if len(perm) else None, len(perm), _ptr(out), len(out), C.byref(ol), C.byref(nr)))
+        else:
+            self._ck(self.L.bfq_fastq_restore(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0,
+                                              _ptr(out), len(out), C.byref(ol), C.byref(nr)))
         return out[:int(ol.value)], int(nr.value)
 
-    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path):
-        """bfq_fastq_restore_fd on named files (hdr_path may be None); returns (bytes written, n_reads)."""
+    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None):
+        """bfq_fastq_restore_fd on named files (hdr_path may be None); returns (bytes written, n_reads).  perm_path: the
+        BFQPERM1 file of the reordering (bfq_fastq_restore_ordered_fd): the text in the order before it."""
         import os
         fds = []
         try:
-            for p in (dna_path, qs_path, hdr_path):
+            for p in (dna_path, qs_path, hdr_path, perm_path):
                 fds.append(os.open(p, os.O_RDONLY) if p is not None else -1)
             fds.append(os.open(out_path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
             ol, nr = C.c_uint64(0), C.c_uint64(0)
             size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
-            self._ck(self.L.bfq_fastq_restore_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]), fds[3],
-                                                 C.byref(ol), C.byref(nr)))
+            if perm_path is not None:
+                self._ck(self.L.bfq_fastq_restore_ordered_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
+                                                             fds[3], size(fds[3]), fds[4], C.byref(ol), C.byref(nr)))
+            else:
+                self._ck(self.L.bfq_fastq_restore_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]), fds[4],
+                                                     C.byref(ol), C.byref(nr)))
             return int(ol.value), int(nr.value)
         finally:
             for fd in fds:
@@ -461,11 +473,28 @@ class Engine:
                     os.close(fd)
 
     # ---- the reads in another order before the input is cut into blocks (bfq_fastq_reorder; parallel.py --reorder)
-    def fastq_reorder(self, parts, mode=2, k=21, seed=0, out=None):
+    def fastq_reorder(self, parts, mode=2, k=21, seed=0, out=None, keep=False):
         """The records of a FASTQ text (parts = [text], or [mates 1, mates 2]: record i of both move together) in the order of
         include/bfqzip_hip.h: mode 2 by the smallest hashed k-mer of every read, mode 1 by a seeded hash of its index, ties
         in input order.  Returns ([text per part as uint8 arrays], perm) with perm[j] = input index of output record j.
-        `out`: one uint8 array per part to fill (too small: BFQ_E_ARG, nothing written); the results are views of them."""
+        `out`: one uint8 array per part to fill (too small: BFQ_E_ARG, nothing written); the results are views of them.
+        keep=True (bfq_fastq_reorder_keep): returns ([texts], container) instead, the permutation as the BFQPERM1 container
+        that fastq_unreorder / fastq_restore(perm=) undo (perm_decode gives its entries)."""
+        arrs, np_, tp, outs, ho, cap, ol = self._text_parts(parts, out)
+        nr = C.c_uint64(0)
+        O = _lib.ReorderOpts(mode=mode, k=k, seed=seed)
+        nmax = (min(len(a) for a in arrs) if arrs else 0) // 4 + 1                                # a record has 4 bytes at least
+        if keep:
+            z = np.empty(int(self.L.bfq_perm_bound(nmax)), np.uint8)
+            zl = C.c_uint64(0)
+            self._ck(self.L.bfq_fastq_reorder_keep(self.h, tp, np_, C.byref(O), ho, cap, ol, _ptr(z), len(z), C.byref(zl), C.byref(nr)))
+            return [o[:int(ol[i])] for i, o in enumerate(outs)], z[:int(zl.value)]
+        perm = np.empty(max(nmax, 1), np.uint64)
+        self._ck(self.L.bfq_fastq_reorder(self.h, tp, np_, C.byref(O), ho, cap, ol, _ptr(perm), C.byref(nr)))
+        return [o[:int(ol[i])] for i, o in enumerate(outs)], perm[:int(nr.value)]
+
+    @staticmethod
+    def _text_parts(parts, out):
         arrs = [_u8(p) for p in parts]
         np_ = len(arrs)
         tp = (_lib.TextPart * max(np_, 1))()
@@ -476,33 +505,71 @@ class Engine:
         ho = (C.c_void_p * max(np_, 1))(*[o.ctypes.data for o in outs])
         cap = (C.c_uint64 * max(np_, 1))(*[len(o) for o in outs])
         ol = (C.c_uint64 * max(np_, 1))()
-        nr = C.c_uint64(0)
-        perm = np.empty(max((min(len(a) for a in arrs) if arrs else 0) // 4 + 1, 1), np.uint64)   # a record has 4 bytes at least
-        O = _lib.ReorderOpts(mode=mode, k=k, seed=seed)
-        self._ck(self.L.bfq_fastq_reorder(self.h, tp, np_, C.byref(O), ho, cap, ol, _ptr(perm), C.byref(nr)))
-        return [o[:int(ol[i])] for i, o in enumerate(outs)], perm[:int(nr.value)]
+        return arrs, np_, tp, outs, ho, cap, ol
 
-    def fastq_reorder_files(self, inputs, outputs, mode=2, k=21, seed=0):
-        """bfq_fastq_reorder_fd on named files (one, or the two files of mates); returns (bytes written per file, n_reads).
-        On failure the output files are left empty."""
+    def fastq_unreorder(self, parts, perm, out=None):
+        """The records of a reordered FASTQ text (parts as in fastq_reorder) back in their input order: output record perm[j]
+        is input record j.  perm: the BFQPERM1 container fastq_reorder(keep=True) returned.  Returns [text per part].  A
+        container that is not one, is of another read count or is not a permutation raises BfqError (BFQ_E_ARG; the message
+        names the counts / the first offending position) and leaves `out` untouched."""
+        z = _u8(perm)
+        arrs, np_, tp, outs, ho, cap, ol = self._text_parts(parts, out)
+        nr = C.c_uint64(0)
+        self._ck(self.L.bfq_fastq_unreorder(self.h, tp, np_, _ptr(z) if len(z) else None, len(z), ho, cap, ol, C.byref(nr)))
+        return [o[:int(ol[i])] for i, o in enumerate(outs)]
+
+    def _reorder_files(self, inputs, outputs, perm_path, perm_write, call):
         import os
         assert len(inputs) == len(outputs)
-        fin, fout = [], []
+        fin, fout, fperm = [], [], []
         try:
             for p in inputs:
                 fin.append(os.open(p, os.O_RDONLY))
             for p in outputs:
                 fout.append(os.open(p, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            if perm_path is not None:
+                fperm.append(os.open(perm_path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) if perm_write else os.open(perm_path, os.O_RDONLY))
             n = len(fin)
             ol = (C.c_uint64 * max(n, 1))()
             nr = C.c_uint64(0)
-            O = _lib.ReorderOpts(mode=mode, k=k, seed=seed)
-            self._ck(self.L.bfq_fastq_reorder_fd(self.h, (C.c_int * max(n, 1))(*fin), (C.c_uint64 * max(n, 1))(*[os.fstat(fd).st_size for fd in fin]), n,
-                                                 C.byref(O), (C.c_int * max(n, 1))(*fout), ol, C.byref(nr)))
+            call((C.c_int * max(n, 1))(*fin), (C.c_uint64 * max(n, 1))(*[os.fstat(fd).st_size for fd in fin]), n, (C.c_int * max(n, 1))(*fout),
+                 fperm[0] if fperm else -1, ol, nr)
             return [int(ol[i]) for i in range(n)], int(nr.value)
         finally:
-            for fd in fin + fout:
+            for fd in fin + fout + fperm:
                 os.close(fd)
+
+    def fastq_reorder_files(self, inputs, outputs, mode=2, k=21, seed=0, perm_path=None):
+        """bfq_fastq_reorder_fd on named files (one, or the two files of mates); returns (bytes written per file, n_reads).
+        On failure the output files are left empty.  perm_path: also write the permutation there as a BFQPERM1 container
+        (bfq_fastq_reorder_keep_fd)."""
+        O = _lib.ReorderOpts(mode=mode, k=k, seed=seed)
+
+        def call(fin, sizes, n, fout, fperm, ol, nr):
+            if perm_path is None:
+                self._ck(self.L.bfq_fastq_reorder_fd(self.h, fin, sizes, n, C.byref(O), fout, ol, C.byref(nr)))
+            else:
+                zl = C.c_uint64(0)
+                self._ck(self.L.bfq_fastq_reorder_keep_fd(self.h, fin, sizes, n, C.byref(O), fout, fperm, ol, C.byref(zl), C.byref(nr)))
+        return self._reorder_files(inputs, outputs, perm_path, True, call)
+
+    def fastq_unreorder_files(self, inputs, outputs, perm_path):
+        """bfq_fastq_unreorder_fd on named files: the reordered file(s) and the BFQPERM1 file -> the records in their input
+        order; returns (bytes written per file, n_reads).  On failure the output files are left empty."""
+        import os
+
+        def call(fin, sizes, n, fout, fperm, ol, nr):
+            self._ck(self.L.bfq_fastq_unreorder_fd(self.h, fin, sizes, n, fperm, os.fstat(fperm).st_size, fout, ol, C.byref(nr)))
+        return self._reorder_files(inputs, outputs, perm_path, False, call)
+
+    # ---- the permutation as a container (host only)
+    @staticmethod
+    def perm_encode(perm, mode=0, k=0, seed=0):
+        return perm_encode(perm, mode=mode, k=k, seed=seed)
+
+    @staticmethod
+    def perm_decode(permz):
+        return perm_decode(permz)
 
     def stream_compress_device(self, d_in, n, d_out, cap):
         """Device-resident form (after stream_reserve(n)); returns the container's length."""
@@ -558,6 +625,55 @@ def reorder_key(seq, k=21):
     """The mode-2 sort key of one sequence line (bfq_reorder_key: host only, no GPU)."""
     a = _u8(seq)
     return int(_lib.lib().bfq_reorder_key(_ptr(a) if len(a) else None, len(a), k))
+
+
+class PermError(BfqError):
+    """perm_encode / perm_decode refused their input; first_bad: the first offending position, None for a fault in the header
+    (or, from perm_encode, which reports no position)."""
+
+    def __init__(self, code, msg, first_bad=None):
+        super().__init__(code, msg)
+        self.first_bad = first_bad
+
+
+def perm_bound(n_reads):
+    """The exact length of the BFQPERM1 container of n_reads entries."""
+    return int(_lib.lib().bfq_perm_bound(n_reads))
+
+
+def perm_reads(permz):
+    """N of a BFQPERM1 container, or -1 when its magic, entry width, length or padding are wrong (host only)."""
+    z = _u8(permz)
+    return int(_lib.lib().bfq_perm_reads(_ptr(z) if len(z) else None, len(z)))
+
+
+def perm_encode(perm, mode=0, k=0, seed=0):
+    """perm (uint64 array: perm[j] = input index of output record j) -> its BFQPERM1 container as a uint8 array
+    (bfq_perm_encode: host only, no GPU).  Not a permutation: PermError."""
+    p = np.ascontiguousarray(perm, np.uint64)
+    out = np.empty(perm_bound(len(p)), np.uint8)
+    O = _lib.ReorderOpts(mode=mode, k=k, seed=seed)
+    ol = C.c_uint64(0)
+    rc = _lib.lib().bfq_perm_encode(_ptr(p) if len(p) else None, len(p), C.byref(O), _ptr(out), len(out), C.byref(ol))
+    if rc:
+        raise PermError(rc, "bfq_perm_encode: not a permutation")
+    return out[:int(ol.value)]
+
+
+def perm_decode(permz):
+    """BFQPERM1 container -> (perm as a uint64 array, dict(mode, k, seed)) (bfq_perm_decode: host only, no GPU).  A container
+    that is not well formed: PermError with first_bad."""
+    z = _u8(permz)
+    L = _lib.lib()
+    n = max(int(L.bfq_perm_reads(_ptr(z) if len(z) else None, len(z))), 0)
+    p = np.empty(max(n, 1), np.uint64)
+    N, bad = C.c_uint64(0), C.c_uint64(0)
+    O = _lib.ReorderOpts()
+    rc = L.bfq_perm_decode(_ptr(z) if len(z) else None, len(z), _ptr(p), n, C.byref(N), C.byref(O), C.byref(bad))
+    if rc:
+        fb = None if bad.value == (1 << 64) - 1 else int(bad.value)
+        raise PermError(rc, "bfq_perm_decode: not a well-formed BFQPERM1 container" + ("" if fb is None else f": entry {fb}"), fb)
+    return p[:int(N.value)], dict(mode=int(O.mode), k=int(O.k), seed=int(O.seed))
 
 
 def synth_spec(N, L, Lmax=None, seed=20240807, **kw):

@@ -26,6 +26,7 @@
 #include <vector>
 #include "bfq_internal_host.h"
 #include "bfq_reorder.h"
+#include "bfq_perm.h"
 
 static double now_s()
 {
@@ -639,4 +640,23 @@ extern "C" uint64_t bfq_reorder_key(const uint8_t *seq, uint64_t len, int k)
     bfq_ro_init(r);
     for (uint64_t i = 0; i < len; i++) bfq_ro_push(r, bfq_ro_code(seq[i]), k, mask, true);
     return r.found ? r.best >> 24 : BFQ_RO_NOKEY;
+}
+
+// ---------------------------------------------------------------- the permutation of a reordering as a container, stated on the host
+// BFQPERM1 (include/bfqzip_hip.h; the layout and the arithmetic are bfq_perm.h's): what k_perm_pack / k_perm_unpack /
+// k_perm_invert / k_perm_check of k_reorder.hip are tested against.
+extern "C" uint64_t bfq_perm_bound(uint64_t n_reads) { return n_reads >> 56 ? 0 : bfq_perm_bound_of(n_reads); }
+extern "C" int64_t bfq_perm_reads(const uint8_t *h_permz, uint64_t len)
+{
+    u64 N = 0;
+    return bfq_perm_header(h_permz, len, &N, nullptr, nullptr) ? (int64_t)N : -1;
+}
+extern "C" int bfq_perm_encode(const uint64_t *h_perm, uint64_t N, const bfq_reorder_opts *opts, uint8_t *h_out, uint64_t cap, uint64_t *out_len)
+{
+    return bfq_perm_encode_host((const u64 *)h_perm, N, opts, h_out, cap, (u64 *)out_len, nullptr);
+}
+extern "C" int bfq_perm_decode(const uint8_t *h_permz, uint64_t len, uint64_t *h_perm, uint64_t cap_entries, uint64_t *N,
+                               bfq_reorder_opts *opts_out, uint64_t *first_bad)
+{
+    return bfq_perm_decode_host(h_permz, len, (u64 *)h_perm, cap_entries, (u64 *)N, opts_out, (u64 *)first_bad);
 }

@@ -28,7 +28,8 @@
 enum BfqKernel {
     K_TEXT = 0, K_PACK, K_KEYS, K_RADIX_HIST, K_SCAN, K_RADIX_SCATTER, K_HUGE_ROUND, K_CLUSTER_BIG,
     K_REFINE_WAVE, K_REFINE_BIG, K_EMIT, K_RANK_BUILD, K_RANK_FINAL, K_LCP_FLAGS, K_CLUSTER,
-    K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER, K_NUM
+    K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER,
+    K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -394,6 +395,10 @@ void bfq_fastq_hdr_stream(bfq_ctx *c, u64 N, const u8 *d_fastq, const DevFastq *
 // records from two line streams and an index made elsewhere (bfq_restore.hip): k_fq_format with lines = 1; d_hdr == nullptr: "@"
 void bfq_fastq_format_lines(bfq_ctx *c, const u8 *d_dna, const u8 *d_qs, const u64 *d_roff, const u8 *d_hdr, const u64 *hStart,
                             const u32 *hLen, const u64 *recOff, u64 N, u64 outLen, u8 *d_out);
+// ... record i of the text being read inv[i] of the streams (bfq_fastq_restore_ordered): k_fq_format_ordered
+void bfq_fastq_format_ordered(bfq_ctx *c, const u8 *d_dna, const u8 *d_qs, const u64 *d_roff, const u8 *d_hdr, const u64 *hStart,
+                              const u32 *hLen, const u64 *recOff, const u64 *inv, u64 N, u64 outLen, u8 *d_out);
+void bfq_restore_sizes_ordered(bfq_ctx *c, const u32 *sizes, const u64 *inv, u64 N, u32 *sizesOut);   // sizesOut[i] = sizes[inv[i]]
 void bfq_fastq_part_index(bfq_ctx *c, const DevFastq *fq, const u64 *h_pstart, int nparts, u64 *d_idx);
 void bfq_pick_u64(bfq_ctx *c, const u64 *d_src, const u64 *d_idx, int count, u64 addIdx, u64 *d_out);
 
@@ -411,3 +416,7 @@ struct RoText { const u8 *buf; const FqRec *rec; u64 len; };
 void bfq_reorder_keys(bfq_ctx *c, const RoText *mates, int nmates, u64 N, int mode, int k, u64 seed, SortRec out);
 void bfq_reorder_perm(bfq_ctx *c, SortRec sorted, const RoText *mates, int nmates, u64 N, u64 *perm, u64 *const *sizes);
 void bfq_reorder_gather(bfq_ctx *c, const RoText &t, const u64 *perm, const u64 *newOff, u64 N, u8 *d_out);
+// the way back: the permutation as a BFQPERM1 payload (bfq_perm.h) and its inverse (k_reorder.hip)
+void bfq_perm_pack(bfq_ctx *c, const u64 *perm, u64 N, u64 *d_words);                            // d_words: bfq_perm_words() of them
+u64 bfq_perm_unpack_invert(bfq_ctx *c, const u64 *d_words, u64 N, u64 *perm, u64 *inv);         // the first offending position, ~0: none; synchronises
+void bfq_reorder_sizes(bfq_ctx *c, const u64 *order, const RoText *mates, int nmates, u64 N, u64 *const *sizes);   // sizes[p][j] = size of record order[j]

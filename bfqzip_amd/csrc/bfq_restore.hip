@@ -7,12 +7,18 @@
 //           (k_nl_count / k_nl_write), k_restore_index checks that the streams describe the same reads and builds the
 //           record index, k_fq_format writes the text
 // The decoded streams never leave the device: the containers go up, the text comes down.
+// bfq_fastq_restore_ordered* also take the BFQPERM1 container of a reordering (bfq_perm.h) and write the records in the order
+// the reads had before it: after k_restore_index the container is unpacked, validated and inverted (k_reorder.hip), the
+// record sizes are scanned through the inverse and k_fq_format_ordered reads line inv[i] for record i -- no second pass over
+// the text.
 #include <string.h>
 #include <stdio.h>
 #include <sys/mman.h>
+#include <sys/stat.h>
 #include <algorithm>
 #include "bfq_internal.h"
 #include "bfq_device.h"
+#include "bfq_perm.h"
 
 // what k_restore_index found: (read index << 3) | reason, the smallest of all (so: the first offending read, and of two
 // reasons at one read the one with the smaller code); RS_NONE: the streams fit
@@ -165,10 +171,11 @@ static void rs_decode(bfq_ctx *c, const RsSrc &s, u8 *d_z, u8 *d_out, u64 raw)
     if (got != raw) throw BfqError{BFQ_E_ARG, "damaged container (raw length)"};
 }
 
-static size_t rs_index_bytes(const RsPlan &P)
+static size_t rs_index_bytes(const RsPlan &P, bool ordered)
 {
-    // line ends of three streams, roff, hStart, hLen, sizes, recOff per read; chunk counts of the line index and of the scans
-    return 64 * (size_t)(P.readsBound + 64) + 3 * 32 * (size_t)((std::max(P.rawD, std::max(P.rawQ, P.rawH)) >> 12) + 64) + (1u << 20);
+    // line ends of three streams, roff, hStart, hLen, sizes, recOff per read; chunk counts of the line index and of the scans;
+    // ordered: the container's payload, the unpacked permutation, its inverse (8 bytes each) and the sizes in output order
+    return (ordered ? 64 + 32 : 64) * (size_t)(P.readsBound + 64) + 3 * 32 * (size_t)((std::max(P.rawD, std::max(P.rawQ, P.rawH)) >> 12) + 64) + (1u << 20);
 }
 
 // sink: where the text goes once it is known to be good.  put(d_text, len) is called at most once.
@@ -178,14 +185,15 @@ struct RsSink {
     std::function<void(const u8 *, u64)> put;
 };
 
+// permz != nullptr: the records leave in the order before the reordering whose BFQPERM1 container this is
 static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const RsSrc &hdr, bool haveHdr, const RsSink &sink,
-                         uint64_t *out_len, uint64_t *n_reads)
+                         uint64_t *out_len, uint64_t *n_reads, const RsSrc *permz = nullptr)
 {
     if (out_len) *out_len = 0;
     if (n_reads) *n_reads = 0;
     RsPlan P;
     rs_plan(dna, qs, hdr, haveHdr, P);
-    const size_t afterDecode = rs_index_bytes(P) + P.textBound + 4096;
+    const size_t afterDecode = rs_index_bytes(P, permz != nullptr) + P.textBound + 4096;
     u8 *dD = nullptr, *dQ = nullptr, *dH = nullptr;
     u64 lenD = P.rawD, lenQ = P.rawQ;
     if (P.ebwt) {
@@ -257,19 +265,45 @@ static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const Rs
         }
         throw BfqError{BFQ_E_ARG, b};
     }
+    const u64 *inv = nullptr;
+    if (permz) {
+        u64 PN = 0;
+        if (!bfq_perm_header(permz->h, permz->len, &PN, nullptr, nullptr))
+            throw BfqError{BFQ_E_ARG, "perm: not a BFQPERM1 container (magic, entry width, length or padding)"};
+        if (PN != N) {
+            char b[200];
+            snprintf(b, sizeof b, "perm: a permutation of %llu reads for streams of %llu reads", (unsigned long long)PN, (unsigned long long)N);
+            throw BfqError{BFQ_E_ARG, b};
+        }
+        const u64 nw = bfq_perm_words(N, bfq_perm_width(N));
+        u64 *words = c->alloc<u64>(nw + 1), *perm = c->alloc<u64>(N + 1), *iv = c->alloc<u64>(N + 1);
+        if (nw) bfq_upload(c, words, permz->h + BFQ_PERM_HDR, 8 * nw);
+        const u64 bad = bfq_perm_unpack_invert(c, words, N, perm, iv);
+        if (bad != BFQ_PERM_NOPOS) {
+            char b[200];
+            snprintf(b, sizeof b, "perm: not a permutation: entry %llu is out of range or repeats an earlier one", (unsigned long long)bad);
+            throw BfqError{BFQ_E_ARG, b};
+        }
+        inv = iv;
+    }
     if (ol > sink.cap) throw BfqError{BFQ_E_ARG, "output buffer smaller than the FASTQ text (see bfq_fastq_restore_bound)"};
     if (sink.sized) sink.sized(ol);
+    if (inv) {                                                    // the same sizes in output order: the same total
+        u32 *sizesOut = c->alloc<u32>(N + 1);
+        bfq_restore_sizes_ordered(c, sizes, inv, N, sizesOut);
+        bfq_exscan_u32(c, sizesOut, recOff, N, recOff + N);
+    }
     u8 *d_out = c->alloc<u8>(ol + 64);
-    bfq_fastq_format_lines(c, dD, dQ, roff, dH, hStart, hLen, recOff, N, ol, d_out);
+    if (inv) bfq_fastq_format_ordered(c, dD, dQ, roff, dH, hStart, hLen, recOff, inv, N, ol, d_out);
+    else bfq_fastq_format_lines(c, dD, dQ, roff, dH, hStart, hLen, recOff, N, ol, d_out);
     sink.put(d_out, ol);
     c->profCollect();
     if (out_len) *out_len = ol;
     if (n_reads) *n_reads = N;
 }
 
-extern "C" int bfq_fastq_restore(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
-                                 const uint8_t *h_hdr, uint64_t hdr_len, uint8_t *h_out, uint64_t cap, uint64_t *out_len,
-                                 uint64_t *n_reads)
+static int rs_run_mem(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len, const uint8_t *h_hdr,
+                      uint64_t hdr_len, const RsSrc *permz, uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads)
 {
     return guarded(c, [&] {
         if (!h_dna || !h_qs || (!h_out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
@@ -280,8 +314,23 @@ extern "C" int bfq_fastq_restore(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_
             bfq_download(c, h_out, d_text, len);
             c->sync();                                            // pinned destinations are written by asynchronous DMA
         };
-        restore_core(c, RsSrc{h_dna, dna_len}, RsSrc{h_qs, qs_len}, RsSrc{h_hdr, hdr_len}, h_hdr != nullptr, sink, out_len, n_reads);
+        restore_core(c, RsSrc{h_dna, dna_len}, RsSrc{h_qs, qs_len}, RsSrc{h_hdr, hdr_len}, h_hdr != nullptr, sink, out_len, n_reads, permz);
     });
+}
+
+extern "C" int bfq_fastq_restore(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                 const uint8_t *h_hdr, uint64_t hdr_len, uint8_t *h_out, uint64_t cap, uint64_t *out_len,
+                                 uint64_t *n_reads)
+{
+    return rs_run_mem(c, h_dna, dna_len, h_qs, qs_len, h_hdr, hdr_len, nullptr, h_out, cap, out_len, n_reads);
+}
+
+extern "C" int bfq_fastq_restore_ordered(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                         const uint8_t *h_hdr, uint64_t hdr_len, const uint8_t *h_permz, uint64_t permz_len,
+                                         uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads)
+{
+    const RsSrc permz{h_permz, permz_len};
+    return rs_run_mem(c, h_dna, dna_len, h_qs, qs_len, h_hdr, hdr_len, &permz, h_out, cap, out_len, n_reads);
 }
 
 // a compressed input file as read-only memory (its pages are the page cache's; the staging workers copy from them)
@@ -299,13 +348,18 @@ struct RsMap {
     ~RsMap() { if (p) munmap(p, len); }
 };
 
-extern "C" int bfq_fastq_restore_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
-                                    int out_fd, uint64_t *out_len, uint64_t *n_reads)
+static int rs_run_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len, bool ordered,
+                     int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads)
 {
+    if (out_len) *out_len = 0;
+    if (n_reads) *n_reads = 0;
     return guarded(c, [&] {
-        if (dna_fd < 0 || qs_fd < 0 || out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
+        if (dna_fd < 0 || qs_fd < 0 || out_fd < 0 || (ordered && perm_fd < 0)) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
         const bool haveHdr = hdr_fd >= 0;
-        RsMap mD, mQ, mH;
+        RsMap mD, mQ, mH, mP;
+        struct stat st;
+        if (ordered && fstat(perm_fd, &st) == 0 && S_ISREG(st.st_mode) && (u64)st.st_size < permz_len) permz_len = (u64)st.st_size;   // (refused as a container below)
+        const RsSrc permz{ordered ? mP.open(perm_fd, permz_len) : nullptr, ordered ? permz_len : 0};
         const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
         const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
         OutFile of;
@@ -329,7 +383,7 @@ extern "C" int bfq_fastq_restore_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, in
                 bfq_write_wait(c);
             };
             uint64_t ol = 0;
-            restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads);
+            restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads, ordered ? &permz : nullptr);
             if (out_len) *out_len = ol;
             opened = false;
             if (!of.close(ol)) throw BfqError{BFQ_E_IO, "cannot size the output file"};
@@ -341,4 +395,16 @@ extern "C" int bfq_fastq_restore_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, in
             throw;
         }
     });
+}
+
+extern "C" int bfq_fastq_restore_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                    int out_fd, uint64_t *out_len, uint64_t *n_reads)
+{
+    return rs_run_fd(c, dna_fd, dna_len, qs_fd, qs_len, hdr_fd, hdr_len, false, -1, 0, out_fd, out_len, n_reads);
+}
+
+extern "C" int bfq_fastq_restore_ordered_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                            int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads)
+{
+    return rs_run_fd(c, dna_fd, dna_len, qs_fd, qs_len, hdr_fd, hdr_len, true, perm_fd, permz_len, out_fd, out_len, n_reads);
 }

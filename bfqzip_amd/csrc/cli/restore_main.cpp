@@ -1,8 +1,9 @@
 // restore_main.cpp -- the way back from the compressed streams to a FASTQ file (not a tool of the reference, which leaves
 // this to `7z x` / `bsc d` + `paste`):
-//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] -o OUT.fq [-V]
+//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM] -o OUT.fq [-V]
 // The inputs are what `bsc e`, bfq_fastq_job.compress_streams = 1 / 2 / 3 and parallel.py --compress write
-// (include/bfqzip_hip.h, bfq_fastq_restore_fd).  Exit status 0 on success; 1 with the library's message otherwise, and then
+// (include/bfqzip_hip.h, bfq_fastq_restore_fd).  -P PERM: the BFQPERM1 file `bfq_reorder -P` / `parallel.py --keep-order`
+// wrote for the run: the records come back in the order of the original file (bfq_fastq_restore_ordered_fd).  Exit status 0 on success; 1 with the library's message otherwise, and then
 // OUT.fq is left empty.
 #include <unistd.h>
 #include <sys/mman.h>
@@ -10,10 +11,11 @@
 
 static int usage(const char *argv0)
 {
-    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] -o OUT.fq [-V]\n"
+    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM] -o OUT.fq [-V]\n"
                     "  -d <arg>  container(s) of the DNA stream (OUT.fq.dna; BFQDNAC1 / BFQRANS2 members, or one BFQEBWT1) (REQUIRED)\n"
                     "  -q <arg>  container(s) of the quality stream (OUT.fq.qs) (REQUIRED)\n"
                     "  -H <arg>  container(s) of the header stream (OUT.h); without it every header line is \"@\"\n"
+                    "  -P <arg>  BFQPERM1 file of the reordering the collection went through: the text in the order before it\n"
                     "  -o <arg>  output FASTQ (REQUIRED)\n"
                     "  -V        phase timeline on stderr\n", argv0);
     return 1;
@@ -22,21 +24,22 @@ static int usage(const char *argv0)
 int main(int argc, char **argv)
 {
     bfq_phase("start");
-    std::string dna, qs, hdr, output;
+    std::string dna, qs, hdr, perm, output;
     int opt;
-    while ((opt = getopt(argc, argv, "d:q:H:o:Vh")) != -1) {
+    while ((opt = getopt(argc, argv, "d:q:H:P:o:Vh")) != -1) {
         switch (opt) {
         case 'd': dna = optarg; break;
         case 'q': qs = optarg; break;
         case 'H': hdr = optarg; break;
+        case 'P': perm = optarg; break;
         case 'o': output = optarg; break;
         case 'V': bfq_phase_enable(1); break;
         default: return usage(argv[0]);
         }
     }
     if (dna.empty() || qs.empty() || output.empty()) return usage(argv[0]);
-    InFile fd, fq, fh;
-    if (!fd.open(dna) || !fq.open(qs) || (!hdr.empty() && !fh.open(hdr))) { fprintf(stderr, "bfq_restore: cannot read the inputs\n"); return 1; }
+    InFile fd, fq, fh, fp;
+    if (!fd.open(dna) || !fq.open(qs) || (!hdr.empty() && !fh.open(hdr)) || (!perm.empty() && !fp.open(perm))) { fprintf(stderr, "bfq_restore: cannot read the inputs\n"); return 1; }
     OutFile outText;
     if (!outText.open(output)) { perror("bfq_restore"); return 1; }
     {   // the bound of the text from the container headers: the output's pages are prepared while the GPU starts up
@@ -56,7 +59,9 @@ int main(int argc, char **argv)
     bfq_ctx *c = create_on_free_gpu("bfq_restore", &P);
     if (!c) return 1;
     uint64_t outLen = 0, reads = 0;
-    const int rc = bfq_fastq_restore_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, outText.fd, &outLen, &reads);
+    const int rc = perm.empty() ? bfq_fastq_restore_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, outText.fd, &outLen, &reads)
+                                : bfq_fastq_restore_ordered_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, fp.fd, fp.size,
+                                                               outText.fd, &outLen, &reads);
     if (rc) {
         fprintf(stderr, "bfq_restore: %s\n", bfq_last_error(c));
         bfq_destroy(c);

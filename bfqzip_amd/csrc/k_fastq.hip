@@ -154,6 +154,35 @@ __global__ __launch_bounds__(256) void k_fq_format(const u8 *__restrict__ bases,
     }
 }
 
+// The same records in another order (bfq_fastq_restore_ordered): record i of the text is read s = inv[i] of the line streams
+// -- bases and qualities at roff[s] + s, header span hStart[s] / hLen[s] -- written at recOff[i].  The destinations run in
+// sequence as in k_fq_format; the source lines are read at random.
+__global__ __launch_bounds__(256) void k_fq_format_ordered(const u8 *__restrict__ bases, const u8 *__restrict__ quals,
+                                                           const u64 *__restrict__ roff, const u8 *__restrict__ hdr,
+                                                           const u64 *__restrict__ hStart, const u32 *__restrict__ hLen,
+                                                           const u64 *__restrict__ recOff, const u64 *__restrict__ inv, u64 N,
+                                                           u8 *__restrict__ out)
+{
+    const u32 sub = threadIdx.x & 15u;                           // 16 lanes per record, 8 bytes per lane and step
+    const u64 ngrp = ((u64)gridDim.x * blockDim.x) >> 4;
+    for (u64 i = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 4; i < N; i += ngrp) {
+        const u64 s = inv[i], r0 = roff[s], L = roff[s + 1] - r0, b = r0 + s;
+        u64 o = recOff[i];
+        const u64 hl = hdr ? hLen[s] : 1;
+        if (hdr) copy_bytes(out + o, hdr + hStart[s], hl, sub, 16);
+        else if (sub == 0) out[o] = (u8)'@';
+        o += hl;
+        if (sub == 0) { out[o] = 10; out[o + 1 + L] = 10; out[o + 2 + L] = (u8)'+'; out[o + 3 + L] = 10; out[o + 4 + 2 * L] = 10; }
+        copy_bytes(out + o + 1, bases + b, L, sub, 16);
+        copy_bytes(out + o + 4 + L, quals + b, L, sub, 16);
+    }
+}
+__global__ __launch_bounds__(256) void k_fq_sizes_ordered(const u32 *__restrict__ sizes, const u64 *__restrict__ inv, u64 N,
+                                                          u32 *__restrict__ sizesOut)
+{
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (u64)gridDim.x * blockDim.x) sizesOut[i] = sizes[inv[i]];
+}
+
 __global__ __launch_bounds__(256) void k_fq_hdrsize(const FqRec *__restrict__ rec, u64 N, u32 *__restrict__ sizes)
 {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (u64)gridDim.x * blockDim.x) sizes[i] = rec[i].hdrLen + 1;
@@ -336,4 +365,15 @@ void bfq_fastq_part_index(bfq_ctx *c, const DevFastq *fq, const u64 *h_pstart, i
 void bfq_pick_u64(bfq_ctx *c, const u64 *d_src, const u64 *d_idx, int count, u64 addIdx, u64 *d_out)
 {
     KLAUNCH(c, K_FASTQ, 0.0, k_pick_u64, 1, 64, d_src, d_idx, count, addIdx, d_out);
+}
+
+void bfq_fastq_format_ordered(bfq_ctx *c, const u8 *d_dna, const u8 *d_qs, const u64 *d_roff, const u8 *d_hdr, const u64 *hStart,
+                              const u32 *hLen, const u64 *recOff, const u64 *inv, u64 N, u64 outLen, u8 *d_out)
+{
+    if (N) KLAUNCH(c, K_FQ_FORMAT_ORD, 2.0 * (double)outLen + 8.0 * (double)N, k_fq_format_ordered, bfq_grid(N, 16), 256, d_dna, d_qs, d_roff, d_hdr,
+                   hStart, hLen, recOff, inv, N, d_out);
+}
+void bfq_restore_sizes_ordered(bfq_ctx *c, const u32 *sizes, const u64 *inv, u64 N, u32 *sizesOut)
+{
+    if (N) KLAUNCH(c, K_MISC, 16.0 * (double)N, k_fq_sizes_ordered, bfq_grid(N, 256), 256, sizes, inv, N, sizesOut);
 }

@@ -13,9 +13,18 @@
 //                    scan of the sizes (k_scan.hip) gives the new offsets
 //   k_ro_gather    : every record copied verbatim to its new offset
 // Memory-bound integer work: the key pass reads the sequence lines once, the gather reads and writes the text once.
+//
+// The way back (bfq_fastq_reorder_keep, bfq_fastq_unreorder, bfq_fastq_restore_ordered) keeps the permutation as a BFQPERM1
+// container (bfq_perm.h) and undoes it:
+//   k_perm_pack    : the container's payload from perm[], one lane per 64-bit word, assembled from the entries that overlap it
+//   k_perm_unpack  : perm[] from a payload, one lane per entry
+//   k_perm_invert  : inv[v] = the smallest j with perm[j] = v (64-bit atomicMin into an array preset to all-ones)
+//   k_perm_check   : the smallest j with perm[j] >= N or inv[perm[j]] != j -- an entry out of range, or a value met before
+//   k_ro_sizes     : the record sizes in the order of an index array; k_ro_gather with inv as its permutation does the rest
 #include "bfq_internal.h"
 #include "bfq_device.h"
 #include "bfq_reorder.h"
+#include "bfq_perm.h"
 
 // One lane, one sequence line, 16 bytes per load (the text buffer is padded: the last load may run past the line)
 __device__ __forceinline__ u64 ro_key_lane(const u8 *__restrict__ s, u32 L, int k, u64 mask)
@@ -90,6 +99,45 @@ __global__ __launch_bounds__(256) void k_ro_gather(RoText t, const u64 *__restri
     }
 }
 
+// ---- the permutation as a container, and its inverse ------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_perm_pack(const u64 *__restrict__ perm, u64 N, u32 w, u64 nwords, u64 *__restrict__ out)
+{
+    for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < nwords; q += (u64)gridDim.x * blockDim.x)
+        out[q] = bfq_perm_word(perm, N, w, q);
+}
+__global__ __launch_bounds__(256) void k_perm_unpack(const u64 *__restrict__ words, u64 N, u32 w, u64 *__restrict__ perm)
+{
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += (u64)gridDim.x * blockDim.x)
+        perm[j] = bfq_perm_get(words, j, w);
+}
+__global__ __launch_bounds__(256) void k_perm_invert(const u64 *__restrict__ perm, u64 N, unsigned long long *__restrict__ inv)
+{
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += (u64)gridDim.x * blockDim.x) {
+        const u64 v = perm[j];
+        if (v < N) atomicMin(inv + v, (unsigned long long)j);
+    }
+}
+__global__ __launch_bounds__(256) void k_perm_check(const u64 *__restrict__ perm, u64 N, const u64 *__restrict__ inv,
+                                                    unsigned long long *__restrict__ firstBad)
+{
+    u64 bad = ~0ull;
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += (u64)gridDim.x * blockDim.x) {
+        const u64 v = perm[j];
+        if ((v >= N || inv[v] != j) && j < bad) bad = j;
+    }
+    if (bad != ~0ull) atomicMin(firstBad, (unsigned long long)bad);
+}
+// sizes of the records order[0], order[1], ... of every mate
+__global__ __launch_bounds__(256) void k_ro_sizes(const u64 *__restrict__ order, RoText m0, RoText m1, int nmates, u64 N,
+                                                  u64 *__restrict__ sizes0, u64 *__restrict__ sizes1)
+{
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += (u64)gridDim.x * blockDim.x) {
+        const u64 i = order[j];
+        sizes0[j] = ro_rec_end(m0, i, N) - m0.rec[i].hdrStart;
+        if (nmates > 1) sizes1[j] = ro_rec_end(m1, i, N) - m1.rec[i].hdrStart;
+    }
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------------------
 void bfq_reorder_keys(bfq_ctx *c, const RoText *mates, int nmates, u64 N, int mode, int k, u64 seed, SortRec out)
 {
@@ -112,4 +160,36 @@ void bfq_reorder_gather(bfq_ctx *c, const RoText &t, const u64 *perm, const u64 
 {
     if (!N) return;
     KLAUNCH(c, K_RO_GATHER, 2.0 * (double)t.len + 48.0 * (double)N, k_ro_gather, bfq_grid(N, 16), 256, t, perm, newOff, N, d_out);
+}
+
+void bfq_perm_pack(bfq_ctx *c, const u64 *perm, u64 N, u64 *d_words)
+{
+    const u32 w = bfq_perm_width(N);
+    const u64 nw = bfq_perm_words(N, w);
+    if (nw) KLAUNCH(c, K_PERM_PACK, 8.0 * (double)N + 8.0 * (double)nw, k_perm_pack, bfq_grid(nw, 256), 256, perm, N, w, nw, d_words);
+}
+
+// perm[] and inv[] (N entries each) from the payload of a container of N entries; returns the first offending position
+// (BFQ_PERM_NOPOS: a permutation).  Synchronises the stream.
+u64 bfq_perm_unpack_invert(bfq_ctx *c, const u64 *d_words, u64 N, u64 *perm, u64 *inv)
+{
+    if (!N) return BFQ_PERM_NOPOS;
+    const u32 w = bfq_perm_width(N);
+    unsigned long long *d_bad = (unsigned long long *)c->alloc<u64>(1);
+    HIP_CHECK(hipMemsetAsync(inv, 0xFF, 8 * N, c->stream));
+    HIP_CHECK(hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    KLAUNCH(c, K_PERM_INVERT, 8.0 * (double)N + 8.0 * (double)bfq_perm_words(N, w), k_perm_unpack, bfq_grid(N, 256), 256, d_words, N, w, perm);
+    KLAUNCH(c, K_PERM_INVERT, 16.0 * (double)N, k_perm_invert, bfq_grid(N, 256), 256, (const u64 *)perm, N, (unsigned long long *)inv);
+    KLAUNCH(c, K_PERM_INVERT, 16.0 * (double)N, k_perm_check, bfq_grid(N, 256), 256, (const u64 *)perm, N, (const u64 *)inv, d_bad);
+    u64 bad = BFQ_PERM_NOPOS;
+    HIP_CHECK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    return bad;
+}
+
+void bfq_reorder_sizes(bfq_ctx *c, const u64 *order, const RoText *mates, int nmates, u64 N, u64 *const *sizes)
+{
+    if (!N) return;
+    KLAUNCH(c, K_MISC, (8.0 + 72.0 * nmates) * (double)N, k_ro_sizes, bfq_grid(N, 256), 256, order, mates[0], nmates > 1 ? mates[1] : mates[0],
+            nmates, N, sizes[0], nmates > 1 ? sizes[1] : sizes[0]);
 }

@@ -185,11 +185,12 @@ def reordered_names(inputs, mode):
     return [root + tag + ext for root, ext in (os.path.splitext(p) for p in inputs)]
 
 
-def reorder_inputs(eng, comm, inputs, mode, k=21, seed=0, paired=False, log=None):
+def reorder_inputs(eng, comm, inputs, mode, k=21, seed=0, paired=False, log=None, perm_path=None):
     """--reorder {1,2} of BFQzip_parallel.py (:59-75): the reads of the input(s) are written in another order (mode 2: by
     locus, mode 1: seeded random; eng.fastq_reorder_files -- mates move together) by rank 0, and the run goes on with those
     files: returns the new input list (the reference replaces args.input and re-derives the output names from it, :403-404,
-    :432-435).  mode 0: the inputs as they are."""
+    :432-435).  mode 0: the inputs as they are.  perm_path (--keep-order): rank 0 also writes the permutation there, as a
+    BFQPERM1 file (restore_order() and `bfq_restore -P` undo it)."""
     if not mode:
         return list(inputs)
     if mode not in (1, 2):
@@ -197,11 +198,38 @@ def reorder_inputs(eng, comm, inputs, mode, k=21, seed=0, paired=False, log=None
     src = list(inputs[:2 if paired else 1])
     dst = reordered_names(src, mode)
     if comm.rank == 0:
-        sizes, n = eng.fastq_reorder_files(src, dst, mode=mode, k=k, seed=seed)
+        keep = dict(perm_path=perm_path) if perm_path else {}
+        sizes, n = eng.fastq_reorder_files(src, dst, mode=mode, k=k, seed=seed, **keep)
         if log:
-            log(f"reorder {mode}: {n} reads, {sum(sizes)} bytes -> {' '.join(dst)}")
+            log(f"reorder {mode}: {n} reads, {sum(sizes)} bytes -> {' '.join(dst)}" + (f", permutation -> {perm_path}" if perm_path else ""))
     comm.barrier()
     return dst + list(inputs[len(src):])
+
+
+def restore_order(eng, comm, outputs, perm_path, log=None):
+    """--keep-order after the run: rank 0 replaces the merged FASTQ output (or the two mates' outputs, in one call) by its
+    un-reordered form (eng.fastq_unreorder_files with the permutation reorder_inputs kept), through temporary files in the
+    same directories and os.replace, after the barrier that ends the writes."""
+    import tempfile
+    comm.barrier()
+    if comm.rank == 0:
+        tmps = []
+        try:
+            for o in outputs:
+                fd, t = tempfile.mkstemp(prefix=os.path.basename(o) + ".", suffix=".tmp", dir=os.path.dirname(o) or ".")
+                os.close(fd)
+                tmps.append(t)
+            sizes, n = eng.fastq_unreorder_files(list(outputs), tmps, perm_path)
+            for t, o in zip(tmps, outputs):
+                os.replace(t, o)
+            tmps = []
+            if log:
+                log(f"keep-order: {n} reads, {sum(sizes)} bytes back in input order -> {' '.join(outputs)}")
+        finally:
+            for t in tmps:
+                if os.path.exists(t):
+                    os.remove(t)
+    comm.barrier()
 
 
 KINDS = ("fastq", "dna", "qs", "hdr")
@@ -513,6 +541,9 @@ def main(argv=None):
     ap.add_argument("--reorder", type=int, default=0, choices=(0, 1, 2),
                     help="reorder the reads before the input is cut into blocks (0: no reorder, 1: random, 2: by locus): "
                          "writes <input>.random<ext> / <input>.reordered<ext> and runs on those")
+    ap.add_argument("--keep-order", action="store_true",
+                    help="with --reorder 1|2: keep the permutation as <first reordered intermediate>.perm and give the merged "
+                         "FASTQ text back in input order (streams and --compress containers stay in run order: bfq_restore -P)")
     ap.add_argument("--reorder-k", type=int, default=21, help="k-mer length of --reorder 2 (8..32)")
     ap.add_argument("--seed", type=int, default=0, help="seed of --reorder 1")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
@@ -544,7 +575,9 @@ def main(argv=None):
         par["v"] = ord(a.rv)
     eng = api.Engine(local, **par)
     log = (lambda m: print(f"[rank {comm.rank}] {m}", flush=True)) if a.v else None
-    a.input = reorder_inputs(eng, comm, a.input, a.reorder, k=a.reorder_k, seed=a.seed, paired=a.paired, log=log)
+    perm_path = reordered_names(a.input[:1], a.reorder)[0] + ".perm" if (a.keep_order and a.reorder) else None
+    keep = dict(perm_path=perm_path) if perm_path else {}
+    a.input = reorder_inputs(eng, comm, a.input, a.reorder, k=a.reorder_k, seed=a.seed, paired=a.paired, log=log, **keep)
     names = output_names(a.input, a.out, a.paired)                   # after the replacement, as define_basename() in the reference
     streams = a.m2 or a.m3
     if a.glob:
@@ -554,6 +587,13 @@ def main(argv=None):
         tot = run_files(eng, comm, a.input, a.threads, names, paired=a.paired, headers=a.headers,
                         want_fastq=not (streams and a.streams_only), want_streams=streams, want_hdr=a.m3, log=log,
                         compress=a.compress and not a.m0, pinned=a.pinned)
+    if perm_path:
+        want_fastq = not (streams and a.streams_only)
+        compress = a.compress and not a.m0 and not a.glob
+        if want_fastq and not compress:
+            restore_order(eng, comm, [n["fastq"] for n in names], perm_path, log=log)
+        if log and comm.rank == 0 and (streams or compress):
+            log(f"keep-order: the {'containers' if compress else 'raw streams'} stay in run order; pass {perm_path} to bfq_restore -P")
     if a.v:
         print(f"[rank {comm.rank}] {tot}", flush=True)
     eng.close()

@@ -370,6 +370,65 @@ int bfq_fastq_reorder(bfq_ctx *c, const bfq_text_part *parts, int nparts, const 
                       const uint64_t *cap, uint64_t *out_len, uint64_t *h_perm, uint64_t *n_reads);
 int bfq_fastq_reorder_fd(bfq_ctx *c, const int *in_fd, const uint64_t *in_len, int nparts, const bfq_reorder_opts *opts,
                          const int *out_fd, uint64_t *out_len, uint64_t *n_reads);
+/* ---- the way back to the input order.  A reordered run loses the order of the original file unless the permutation is
+ * kept; these calls keep it, as a file, and undo it on the device.
+ * Container BFQPERM1, all fields little endian:
+ *   header, 40 bytes: "BFQPERM1" | u64 N (reads) | u32 w (bits per entry) | u32 mode | u32 k | u32 reserved = 0 | u64 seed
+ *                     (mode / k / seed: the bfq_reorder_opts it came from, k = 0 written as 21; informational).  w = bit length of N - 1, and 1
+ *                     when N <= 2; N < 2^56.
+ *   payload         : ceil(N w / 64) u64 words.  Entry j is perm[j], the input index of output record j (h_perm of
+ *                     bfq_fastq_reorder); it occupies bits [j w, (j + 1) w) of the bit stream, bit b of the stream being bit
+ *                     b % 64 of word b / 64.  The padding bits of the last word are 0.
+ *   total length    : exactly 40 + 8 ceil(N w / 64) bytes (~94 MB at 30 M reads, against 240 MB as raw u64).
+ * A container is well formed only if the magic, w, the total length and the zero padding are as above, every entry is < N and
+ * no value occurs twice.  Its first offending position is the smallest j with perm[j] >= N or perm[j] met at an earlier
+ * position.
+ * Host only (no GPU; the statement the kernels are tested against):
+ *   bfq_perm_bound : the exact container length for n_reads (0 when n_reads >= 2^56)
+ *   bfq_perm_reads : N, or -1 when magic / w / length / padding are wrong (the entries are not looked at)
+ *   bfq_perm_encode: h_perm[N] -> container; BFQ_E_ARG and nothing written when cap < bfq_perm_bound(N) or h_perm is not a
+ *                    permutation of 0..N-1
+ *   bfq_perm_decode: container -> h_perm[N], *N, *opts_out (may be NULL); BFQ_E_ARG and nothing written when the container is
+ *                    not well formed or cap_entries < N; *first_bad (may be NULL) is then the first offending position, or
+ *                    UINT64_MAX when the fault is in the header or the arguments
+ * On the device:
+ *   bfq_fastq_reorder_keep / _keep_fd: bfq_fastq_reorder / _fd, and the container of what they did: the permutation is packed
+ *     on the device and leaves as the packed bytes.  cap_permz < bfq_perm_bound(N): BFQ_E_ARG, nothing written (the texts
+ *     neither).  On any failure *permz_len = 0 and h_permz is untouched / perm_fd is left empty, like the text outputs.
+ *   bfq_fastq_unreorder / _fd: FASTQ text in the order of a reordered run + its container -> output record perm[j] is input
+ *     record j, byte for byte; two parts are mates and the one permutation applies to both; a missing final newline is added.
+ *     The container is uploaded, unpacked, validated and inverted on the device (inv[v] = the smallest j with perm[j] = v),
+ *     and the reorder's gather reads through the inverse.  Refusals, all BFQ_E_ARG with nothing written (files left empty):
+ *     not a BFQPERM1 container; a permutation of X reads for a text of Y records (the message names both); an entry out of
+ *     range or a value twice (the message names the first offending position).  Malformed text, cap[p] too small and memory
+ *     above ws_cap_mib: as bfq_fastq_reorder.  Device memory: as bfq_fastq_reorder.
+ *   bfq_fastq_restore_ordered / _fd: bfq_fastq_restore / _fd with the records un-reordered in the same call: the output is
+ *     that of bfq_fastq_restore with output record perm[j] = its record j.  After the streams have been checked (their
+ *     messages are those of bfq_fastq_restore and come first) the container is validated and inverted as above, the record
+ *     sizes are scanned through the inverse, and the text is written once, record i from read inv[i] of the line streams: no
+ *     second pass over the text.  A permutation whose N differs from the streams' read count is BFQ_E_ARG with both numbers
+ *     in the message.  Device memory: bfq_fastq_restore's, with 96 instead of 64 bytes of index per read (the container's
+ *     payload, the unpacked permutation and its inverse: ~24 bytes per read, and 4 of sizes), reserved in the same single
+ *     reservation. */
+uint64_t bfq_perm_bound(uint64_t n_reads);
+int64_t  bfq_perm_reads(const uint8_t *h_permz, uint64_t len);
+int bfq_perm_encode(const uint64_t *h_perm, uint64_t N, const bfq_reorder_opts *opts, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+int bfq_perm_decode(const uint8_t *h_permz, uint64_t len, uint64_t *h_perm, uint64_t cap_entries, uint64_t *N,
+                    bfq_reorder_opts *opts_out, uint64_t *first_bad);
+int bfq_fastq_reorder_keep(bfq_ctx *c, const bfq_text_part *parts, int nparts, const bfq_reorder_opts *opts, uint8_t *const *h_out,
+                           const uint64_t *cap, uint64_t *out_len, uint8_t *h_permz, uint64_t cap_permz, uint64_t *permz_len,
+                           uint64_t *n_reads);
+int bfq_fastq_reorder_keep_fd(bfq_ctx *c, const int *in_fd, const uint64_t *in_len, int nparts, const bfq_reorder_opts *opts,
+                              const int *out_fd, int perm_fd, uint64_t *out_len, uint64_t *permz_len, uint64_t *n_reads);
+int bfq_fastq_unreorder(bfq_ctx *c, const bfq_text_part *parts, int nparts, const uint8_t *h_permz, uint64_t permz_len,
+                        uint8_t *const *h_out, const uint64_t *cap, uint64_t *out_len, uint64_t *n_reads);
+int bfq_fastq_unreorder_fd(bfq_ctx *c, const int *in_fd, const uint64_t *in_len, int nparts, int perm_fd, uint64_t permz_len,
+                           const int *out_fd, uint64_t *out_len, uint64_t *n_reads);
+int bfq_fastq_restore_ordered(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                              const uint8_t *h_hdr, uint64_t hdr_len, const uint8_t *h_permz, uint64_t permz_len,
+                              uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads);
+int bfq_fastq_restore_ordered_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                 int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads);
 /* device-resident form (input and output in device memory): bfq_stream_reserve(len) sizes the workspace once */
 int bfq_stream_reserve(bfq_ctx *c, uint64_t len);
 int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
