@@ -24,6 +24,7 @@ SYMBOLS = [
     "bfq_prof_enable", "bfq_prof_reset", "bfq_prof_count", "bfq_prof_get", "bfq_prof_trace_select", "bfq_prof_trace",
     "bfq_stream_bound", "bfq_stream_raw_len", "bfq_stream_compress", "bfq_stream_decompress",
     "bfq_stream_reserve", "bfq_stream_compress_device", "bfq_stream_ebwt_decode",
+    "bfq_names_compress", "bfq_names_compress_device",
     "bfq_fastq_restore_bound", "bfq_fastq_restore", "bfq_fastq_restore_fd",
     "bfq_reorder_key", "bfq_fastq_reorder", "bfq_fastq_reorder_fd",
     "bfq_perm_bound", "bfq_perm_reads", "bfq_perm_encode", "bfq_perm_decode",
@@ -75,7 +76,7 @@ class FastqJob(C.Structure):
                 ("n_reads", C.c_uint64), ("total_bases", C.c_uint64),
                 ("part_reads", C.c_uint64 * (MAX_PARTS + 1)), ("part_fastq_off", C.c_uint64 * (MAX_PARTS + 1)),
                 ("part_stream_off", C.c_uint64 * (MAX_PARTS + 1)), ("part_hdr_off", C.c_uint64 * (MAX_PARTS + 1)),
-                ("compress_streams", C.c_int32), ("reserved0", C.c_int32),
+                ("compress_streams", C.c_int32), ("name_codec", C.c_int32),
                 ("dna_bytes", C.c_uint64), ("qs_bytes", C.c_uint64), ("hdr_bytes", C.c_uint64)]
 
 
@@ -166,6 +167,8 @@ def lib():
         L.bfq_stream_compress.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_stream_decompress.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_stream_reserve.argtypes = [vp, u64]
+        L.bfq_names_compress.argtypes = [vp, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.bfq_names_compress_device.argtypes = [vp, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
         L.bfq_stream_ebwt_decode.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
         L.bfq_fastq_restore_bound.restype = C.c_int64
         L.bfq_fastq_restore_bound.argtypes = [vp, u64, vp, u64, vp, u64]

@@ -1130,6 +1130,7 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
         J->fastq_len = J->stream_len = J->hdr_len = J->n_reads = J->total_bases = 0;
         J->dna_bytes = J->qs_bytes = J->hdr_bytes = 0;
         const bool cz = J->compress_streams != 0;
+        if (J->name_codec != 0 && J->name_codec != 1) throw BfqError{BFQ_E_ARG, "bfq_fastq_job: name_codec is 0 or 1"};
         std::vector<u64> ps;
         TextSrc src[BFQ_MAX_PARTS];
         for (int p = 0; p < np; p++) src[p] = TextSrc{HostRef::mem(J->parts[p].data), J->parts[p].len};
@@ -1167,7 +1168,11 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
                 const size_t mz = c->mark();
                 const u64 bound = bfq_codec_bound(hl) < J->cap_hdr ? bfq_codec_bound(hl) : J->cap_hdr;
                 u8 *d_z = c->alloc<u8>(bound + 16);
-                J->hdr_bytes = bfq_codec_compress_device(c, d_hdr, hl, d_z, bound);
+                if (J->name_codec == 1) {                      // tokenised names where they are shorter (bfq_names_compress, flags 0)
+                    NamesSized S;
+                    bfq_names_size(c, d_hdr, hl, &S);
+                    J->hdr_bytes = bfq_names_finish(c, d_hdr, hl, S, 0, d_z, bound);
+                } else J->hdr_bytes = bfq_codec_compress_device(c, d_hdr, hl, d_z, bound);
                 bfq_download(c, J->out_hdr, d_z, J->hdr_bytes);
                 c->release(mz);
             } else {
@@ -1419,9 +1424,10 @@ extern "C" int bfq_stream_decompress(bfq_ctx *c, const uint8_t *h_in, uint64_t l
 {
     return guarded(c, [&] {
         if (!h_in || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
-        const u64 raw = bfq_codec_raw_len(h_in, len);
+        u64 nameWs = 0;                                            // (a BFQNAME1 member decodes four members inside it)
+        const u64 raw = bfq_codec_raw_len(h_in, len, &nameWs);
         if (raw > cap || (raw && !h_out)) throw BfqError{BFQ_E_ARG, "output buffer too small for the raw stream"};
-        c->reserve(bfq_codec_workspace(raw) + len);
+        c->reserve(bfq_codec_workspace(raw) + nameWs + len);
         u8 *d_in = c->alloc<u8>(len + 16), *d_out = c->alloc<u8>(raw + 16);
         bfq_upload(c, d_in, h_in, len);
         u64 got = 0;
@@ -1446,6 +1452,58 @@ extern "C" int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint6
     return guarded(c, [&] {
         c->release(0);
         *out_len = bfq_codec_compress_device(c, d_in, len, d_out, cap);
+        c->sync();
+        c->profCollect();
+    });
+}
+
+// read names (k_names.hip): the BFQNAME1 container where it applies and (flags 0) pays, else what bfq_stream_compress writes.
+// The arena is sized for the general container and a stream of typical lines.  What a stream needs beyond that is known only
+// on the way -- its line count, then the sizes of its three token streams -- so at either point the arena may grow once, and
+// the call starts over in the larger one (an arena's contents do not survive growing).  begin(): the input and output buffers
+// of a fresh arena (the input is uploaded again), or the caller's own device buffers.
+struct NamesBufs { const u8 *in; u8 *out; };
+static u64 names_compress_core(bfq_ctx *c, const std::function<NamesBufs(u64)> &begin, u64 len, u32 flags, u64 cap)
+{
+    if (flags & ~1u) throw BfqError{BFQ_E_ARG, "bfq_names_compress: unknown flags"};
+    const u64 bound = bfq_codec_bound(len) < cap ? bfq_codec_bound(len) : cap;
+    size_t need = len + bound + 4096 + bfq_names_sized_bytes(len, len / 16) + bfq_codec_workspace(len);
+    for (;;) {
+        c->reserve(need);
+        const NamesBufs b = begin(bound);
+        const u64 nl = len ? bfq_fastq_count_lines(c, b.in, len) : 0;
+        need = c->mark() + bfq_names_sized_bytes(len, nl) + bfq_codec_workspace(len);
+        if (need > c->ws.cap) continue;                            // more lines than guessed: their index needs the room
+        NamesSized S;
+        bfq_names_size(c, b.in, len, &S);
+        need = c->mark() + bfq_names_rest_bytes(len, S) + 4096;
+        if (need > c->ws.cap) { need += bfq_names_sized_bytes(len, nl); continue; }   // (the sizing comes before it again)
+        return bfq_names_finish(c, b.in, len, S, flags, b.out, bound);
+    }
+}
+extern "C" int bfq_names_compress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint32_t flags, uint8_t *h_out, uint64_t cap, uint64_t *out_len)
+{
+    return guarded(c, [&] {
+        if ((len && !h_in) || !h_out || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
+        u8 *d_out = nullptr;
+        const u64 got = names_compress_core(c, [&](u64 bound) {
+            u8 *d_in = c->alloc<u8>(len + 16);
+            d_out = c->alloc<u8>(bound + 16);
+            if (len) bfq_upload(c, d_in, h_in, len);
+            return NamesBufs{d_in, d_out};
+        }, len, flags, cap);
+        bfq_download(c, h_out, d_out, got);
+        c->sync();                                             // pinned destinations are written by asynchronous DMA
+        c->profCollect();
+        *out_len = got;
+    });
+}
+// both buffers on the device, outside the context's workspace (which this call sizes itself)
+extern "C" int bfq_names_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint32_t flags, uint8_t *d_out, uint64_t cap, uint64_t *out_len)
+{
+    return guarded(c, [&] {
+        if ((len && !d_in) || !d_out || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
+        *out_len = names_compress_core(c, [&](u64) { return NamesBufs{d_in, d_out}; }, len, flags, cap);
         c->sync();
         c->profCollect();
     });

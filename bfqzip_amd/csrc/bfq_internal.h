@@ -300,7 +300,7 @@ u64 bfq_fastq_count_lines(bfq_ctx *c, const u8 *d_buf, u64 len);          // k_f
 // stream codec (k_codec.hip)
 u64 bfq_codec_bound(u64 n);
 u64 bfq_codec_workspace(u64 n);
-u64 bfq_codec_raw_len(const u8 *h_in, u64 len);                    // all members of a file
+u64 bfq_codec_raw_len(const u8 *h_in, u64 len, u64 *nameWs = nullptr);   // all members of a file
 u64 bfq_codec_member_len(const u8 *h_in, u64 len);                 // bytes of the first member
 u64 bfq_codec_compress_device(bfq_ctx *c, const u8 *d_in, u64 n, u8 *d_out, u64 cap);
 u64 bfq_codec_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
@@ -312,6 +312,17 @@ u64 bfq_dnac_workspace(u64 n);
 u64 bfq_dnac_compress_device(bfq_ctx *c, const u8 *d_in, u64 n, u8 *d_out, u64 cap, u64 *nbases);
 u64 bfq_dnac_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
 u64 bfq_dnac_member_len(const u8 *h_in, u64 len);
+// tokenised read names (k_names.hip): the BFQNAME1 container.  The encoder is sized first (bfq_names_size: line index, the
+// lines' shares of the three streams, eligibility), so that a caller that owns the reservation can grow the arena by
+// bfq_names_rest_bytes() before bfq_names_finish() writes, codes and chooses (flags as bfq_names_compress).
+struct NamesSized { bool eligible = false; u64 nl = 0; const u64 *lineEnd = nullptr; u64 *offO = nullptr, *offN = nullptr, *offT = nullptr; u64 total[3] = {0, 0, 0}; };
+bool bfq_names_size(bfq_ctx *c, const u8 *d_in, u64 n, NamesSized *S);
+u64 bfq_names_sized_bytes(u64 n, u64 nl);
+u64 bfq_names_rest_bytes(u64 n, const NamesSized &S);
+u64 bfq_names_finish(bfq_ctx *c, const u8 *d_in, u64 n, const NamesSized &S, u32 flags, u8 *d_out, u64 cap);
+u64 bfq_names_member_len(const u8 *h_in, u64 len);
+u64 bfq_names_decode_extra(const u8 *h_in, u64 len, u64 *maxInner);   // arena bytes beside the codec's workspace for the largest inner member
+u64 bfq_names_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
 
 // step 1 pieces
 void bfq_build_text(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, u64 n,

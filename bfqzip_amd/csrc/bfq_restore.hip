@@ -68,7 +68,9 @@ struct RsSrc { const u8 *h = nullptr; u64 len = 0; };          // a compressed i
 struct RsPlan {
     bool ebwt = false;
     u64 rawD = 0, rawQ = 0, rawH = 0;       // decoded bytes of every stream (all members)
-    u64 maxMember = 0;                      // ... of the largest single member (sizes the codec's workspace)
+    u64 maxMember = 0;                      // ... of the largest single member (sizes the codec's workspace); a BFQNAME1 member's inner members count
+    u64 hdrMember = 0;                      // ... of the header stream alone
+    u64 nameExtra = 0;                      // the four decoded members of the largest BFQNAME1 member
     u64 readsBound = 0;                     // upper bound of the number of reads
     u64 textBound = 0;                      // ... and of the text
 };
@@ -77,7 +79,7 @@ static u64 rs_get64(const u8 *p) { u64 v; memcpy(&v, p, 8); return v; }
 
 // members of one input, back to back: raw length of all of them; *reads: the read count when every member states one
 // (BFQDNAC1), else ~0
-static u64 rs_walk(const RsSrc &s, const char *what, u64 *maxMember, u64 *reads)
+static u64 rs_walk(const RsSrc &s, const char *what, u64 *maxMember, u64 *reads, u64 *nameExtra = nullptr)
 {
     if (!s.h || !s.len) throw BfqError{BFQ_E_ARG, std::string(what) + ": not a container (empty input)"};
     u64 raw = 0, nr = 0;
@@ -86,6 +88,10 @@ static u64 rs_walk(const RsSrc &s, const char *what, u64 *maxMember, u64 *reads)
         try {
             ml = bfq_codec_member_len(s.h + pos, s.len - pos);
             n = bfq_codec_raw_len(s.h + pos, ml);
+            if (!memcmp(s.h + pos, "BFQNAME1", 8)) {
+                const u64 x = bfq_names_decode_extra(s.h + pos, ml, maxMember);
+                if (nameExtra && x > *nameExtra) *nameExtra = x;
+            }
         } catch (const BfqError &e) {
             char b[96];
             snprintf(b, sizeof b, ": not a container at byte %llu (", (unsigned long long)pos);
@@ -138,10 +144,13 @@ static void rs_plan(const RsSrc &dna, const RsSrc &qs, const RsSrc &hdr, bool ha
         if (bfq_codec_member_len(qs.h, qs.len) != qs.len) throw BfqError{BFQ_E_ARG, "qs: one member expected beside a BFQEBWT1 stream"};
         P.maxMember = n;
     } else {
-        P.rawD = rs_walk(dna, "dna", &P.maxMember, &reads);
-        P.rawQ = rs_walk(qs, "qs", &P.maxMember, nullptr);
+        P.rawD = rs_walk(dna, "dna", &P.maxMember, &reads, &P.nameExtra);
+        P.rawQ = rs_walk(qs, "qs", &P.maxMember, nullptr, &P.nameExtra);
     }
-    if (haveHdr) P.rawH = rs_walk(hdr, "hdr", &P.maxMember, nullptr);
+    if (haveHdr) {
+        P.rawH = rs_walk(hdr, "hdr", &P.hdrMember, nullptr, &P.nameExtra);
+        if (!P.ebwt) P.maxMember = std::max(P.maxMember, P.hdrMember);
+    }
     // every line costs its stream one byte at least (a last line without '\n' gets one)
     const u64 byBytes = std::min(P.rawD, P.rawQ) + 1;
     P.readsBound = reads != ~0ull && reads < byBytes ? reads + 1 : byBytes;
@@ -197,7 +206,7 @@ static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const Rs
     u8 *dD = nullptr, *dQ = nullptr, *dH = nullptr;
     u64 lenD = P.rawD, lenQ = P.rawQ;
     if (P.ebwt) {
-        const size_t hdrPart = haveHdr ? P.rawH + hdr.len + bfq_codec_workspace(P.rawH) : 0;
+        const size_t hdrPart = haveHdr ? P.rawH + hdr.len + bfq_codec_workspace(std::max(P.rawH, P.hdrMember)) + P.nameExtra : 0;
         EbwtLines r;
         bfq_phase("alloc");
         bfq_ebwt_decode_lines(c, dna.h, dna.len, qs.h, qs.len, nullptr, nullptr, ~0ull, nullptr, nullptr, afterDecode + hdrPart + 4096, &r);
@@ -211,7 +220,7 @@ static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const Rs
         }
     } else {
         const size_t streams = (size_t)P.rawD + P.rawQ + P.rawH + 3 * 320;
-        const size_t decode = (size_t)dna.len + qs.len + (haveHdr ? hdr.len : 0) + 3 * 320 + bfq_codec_workspace(P.maxMember);
+        const size_t decode = (size_t)dna.len + qs.len + (haveHdr ? hdr.len : 0) + 3 * 320 + bfq_codec_workspace(P.maxMember) + P.nameExtra;
         bfq_phase("alloc");
         c->reserve(streams + std::max(decode, afterDecode) + (64u << 20));
         c->zeroCounters();

@@ -575,6 +575,7 @@ static void cdc_parse(const u8 *in, u64 len, CdcHeader &H)
 u64 bfq_codec_member_len(const u8 *h_in, u64 len)
 {
     if (len >= 8 && !memcmp(h_in, "BFQDNAC1", 8)) return bfq_dnac_member_len(h_in, len);
+    if (len >= 8 && !memcmp(h_in, "BFQNAME1", 8)) return bfq_names_member_len(h_in, len);
     if (len >= 32 && !memcmp(h_in, "BFQLINE1", 8)) return 32 + bfq_codec_member_len(h_in + 32, len - 32);
     CdcHeader H;
     cdc_parse(h_in, len, H);
@@ -582,14 +583,24 @@ u64 bfq_codec_member_len(const u8 *h_in, u64 len)
     for (u32 g = 0; g < H.m.nseg; g++) total += H.segBytes[g];
     return total;
 }
-u64 bfq_codec_raw_len(const u8 *h_in, u64 len)
+// *nameWs (optional): the device workspace the largest BFQNAME1 member takes to decode -- its four decoded members and the
+// codec's workspace for the largest of them -- or 0 when there is none
+u64 bfq_codec_raw_len(const u8 *h_in, u64 len, u64 *nameWs)
 {
     u64 pos = 0, raw = 0;
+    if (nameWs) *nameWs = 0;
     do {
-        const bool lx = (len - pos >= 32 && !memcmp(h_in + pos, "BFQLINE1", 8)) || (len - pos >= 72 && !memcmp(h_in + pos, "BFQDNAC1", 8));
+        const bool lx = (len - pos >= 32 && !memcmp(h_in + pos, "BFQLINE1", 8)) || (len - pos >= 72 && !memcmp(h_in + pos, "BFQDNAC1", 8)) ||
+                        (len - pos >= 64 && !memcmp(h_in + pos, "BFQNAME1", 8));
         if (!lx && (len - pos < CQ_HDR + 256 || memcmp(h_in + pos, "BFQRANS2", 8))) throw BfqError{BFQ_E_ARG, "not a BFQRANS2 stream"};
         raw += get64(h_in + pos + 8);
-        pos += bfq_codec_member_len(h_in + pos, len - pos);
+        const u64 ml = bfq_codec_member_len(h_in + pos, len - pos);
+        if (nameWs && !memcmp(h_in + pos, "BFQNAME1", 8)) {
+            u64 inner = 0;
+            const u64 ws = bfq_names_decode_extra(h_in + pos, ml, &inner) + bfq_codec_workspace(inner);
+            if (ws > *nameWs) *nameWs = ws;
+        }
+        pos += ml;
     } while (pos < len);
     return raw;
 }
@@ -767,6 +778,7 @@ u64 bfq_codec_compress_device(bfq_ctx *c, const u8 *d_in, u64 n, u8 *d_out, u64 
 u64 bfq_codec_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap)
 {
     if (len >= 8 && !memcmp(h_in, "BFQDNAC1", 8)) return bfq_dnac_decompress_device(c, h_in, d_in, len, d_out, cap);
+    if (len >= 8 && !memcmp(h_in, "BFQNAME1", 8)) return bfq_names_decompress_device(c, h_in, d_in, len, d_out, cap);
     if (len < 32 || memcmp(h_in, "BFQLINE1", 8)) return bfq_rans_decompress_device(c, h_in, d_in, len, d_out, cap);
     const BfqError bad{BFQ_E_ARG, "damaged BFQLINE1 stream"};
     const u64 n = get64(h_in + 8), nl = get64(h_in + 24);

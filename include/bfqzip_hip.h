@@ -210,7 +210,8 @@ typedef struct bfq_fastq_job {
      * length is enough from a few MB on); out_dna of modes 2 / 3 holds two containers: twice that + 40. */
     int32_t  compress_streams;                /* 1: as described; 2: eBWT-domain containers (bfq_stream_ebwt_decode, below);
                                                  3: the same with the qualities in read order (smallest output) */
-    int32_t  reserved0;
+    int32_t  name_codec;                      /* 0: out_hdr as described; 1 (with compress_streams 1, 2 or 3): out_hdr is what
+                                                 bfq_names_compress(flags 0) gives for the header stream (BFQNAME1 where shorter) */
     uint64_t dna_bytes, qs_bytes, hdr_bytes;
 } bfq_fastq_job;
 int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *job, bfq_stats *st);
@@ -292,7 +293,7 @@ int bfq_synth_fastq(bfq_ctx *c, const bfq_synth *s, uint8_t *h_out, uint64_t cap
  * dropin/external/libbsc/bsc takes that command line (`bsc e IN OUT [options]`, `bsc d IN OUT`).
  * The containers are this project's own -- neither 7z nor libbsc are part of the reference tree -- and are stated in
  * oracle/bfq_codec_ref.c: "BFQRANS2" (any bytes: static order-k model + range-ANS, segments of 8192 symbols), "BFQLINE1"
- * (read names: a line-delta transform in front of it) and "BFQDNAC1" (read-order DNA, lines of A C G T N: a hashed
+ * (read names: a line-delta transform in front of it; "BFQNAME1", below, is the opt-in tokenised form) and "BFQDNAC1" (read-order DNA, lines of A C G T N: a hashed
  * order-K context model that adapts block by block, rebuilt by the decoder from what it has decoded; a third of the static
  * container's size at 30x coverage, a quarter of its speed; $BFQ_DNA_STATIC=1 keeps the static one).
  * Any bytes compress; host buffers in and out.  bfq_stream_decompress takes containers of any kind back to back. */
@@ -300,6 +301,45 @@ uint64_t bfq_stream_bound(uint64_t len);                          /* capacity th
 int64_t  bfq_stream_raw_len(const uint8_t *h_in, uint64_t len);   /* raw length of a container, -1 if it is not one  */
 int bfq_stream_compress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
 int bfq_stream_decompress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+/* ---- read names as tokens: the opt-in container "BFQNAME1" (k_names.hip; tests/names_model.py states it in Python).  On real
+ * names the counters change in every line, so the shared-prefix transform of BFQLINE1 leaves most of a line as literals; here
+ * a line is cut into tokens and every token is coded against the token at the same place of the line before.
+ * All fields little endian.  The stream is lines, each ended by '\n'; a line is its bytes without the '\n'.
+ *   tokens   : maximal runs of ASCII digits / of other bytes.  A digit token is NUMERIC when it has at most 18 digits and
+ *              either one digit or a first digit other than '0'; its value is its decimal value (< 10^18).  Every other token
+ *              (non-digits, a leading zero, 19 digits or more) is text.
+ *   groups   : R = 256 consecutive lines (the last may be shorter).  A line is coded against the line before it in the
+ *              input, the first line of a group against the empty line (no tokens).  Groups decode independently.
+ *   streams  : `ops` (operations), `num` (DELTA payloads), `text` (TEXT payloads).  For token t of a line, P = token t of the
+ *              line before (or absent), v = the token's value, u = P's value when P exists and is numeric, else 0, d = v - u:
+ *                SAME   P exists with the same bytes.  Consecutive SAME tokens form a run, written when another operation
+ *                       or the end of the line follows, in pieces of at most 240, the 240s first: a piece of k is byte 15 + k
+ *                INC    numeric, d = 1: byte 2
+ *                DELTA  numeric otherwise: byte 3; `num` gets the LEB128 of z = 2 d (d >= 0) or -2 d - 1 (d < 0)
+ *                TEXT   anything else: byte 4; `text` gets the LEB128 of the token's length, then its bytes
+ *              in this order of precedence; after a line's last token (and its pending run) byte 0 (END).  Bytes 1 and 5..15
+ *              are no operations.  LEB128: seven bits per byte, low groups first, bit 7 set on all but the last byte.
+ *   index    : per group four u32: its bytes of ops, of num, of text, and its raw bytes (newlines included)
+ *   container: "BFQNAME1" | u64 raw_len | u32 R = 256 | u32 0 | u64 lines | u64 bytes of member 0..3 | the members back to
+ *              back: index, ops, num, text, each exactly what bfq_stream_compress writes for those bytes (an empty member
+ *              included); the members carry the codec's checksums.
+ * Eligible: a stream of at least one byte that ends with '\n' and has no line longer than 65 535 bytes.
+ * The decoder re-tokenises the line it has just written to find P and writes numbers as shortest decimals.  It refuses with
+ * BFQ_E_ARG "damaged BFQNAME1 stream": R != 256 or the reserved field set; no lines or more lines than raw bytes; member lengths
+ * that do not add up to the container; an index of other than 16 ceil(lines / 256) bytes; members whose raw lengths are not
+ * the sums of the index columns; raw shares that do not add up to raw_len (or members larger than any encoder output: ops and
+ * text above 2 raw_len, num above 5 raw_len); and in a group: a byte that is no operation, a SAME run past the tokens of the
+ * line before, a DELTA result outside 0 .. 10^18 - 1, a LEB128 of more than nine bytes, a TEXT length of 0 or past the group's
+ * text share, a line beyond 65 535 bytes, a share of ops / num / text not consumed exactly, a raw share not filled exactly, a
+ * line count other than min(256, lines left).  Every read and write stays inside the group's stated shares.
+ * bfq_stream_decompress, bfq_stream_raw_len and bfq_fastq_restore* take BFQNAME1 members wherever they take BFQLINE1 ones.
+ *   bfq_names_compress       : flags 0: the BFQNAME1 container when the stream is eligible and the container is strictly
+ *                              shorter than what bfq_stream_compress writes for the same bytes, else exactly those bytes;
+ *                              bfq_stream_bound(len) therefore suffices.  flags bit 0 ("always"): BFQNAME1 whenever the stream
+ *                              is eligible (tests, diagnostics).  Other bits: BFQ_E_ARG.
+ *   bfq_names_compress_device: both buffers in device memory outside the context's workspace, which the call sizes itself */
+int bfq_names_compress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint32_t flags, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+int bfq_names_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint32_t flags, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
 /* eBWT-domain containers (bfq_fastq_job.compress_streams = 2; out_fastq must be NULL): out_dna receives "BFQEBWT1" |
  * u64 rows | u64 reads | u32 terminator byte | u32 flags | u64 bytes of the next container | the container of the eBWT's
  * symbols AFTER noise reduction | the container of the replaced rows' original symbols (0 elsewhere), out_qs the
@@ -316,7 +356,7 @@ int bfq_stream_ebwt_decode(bfq_ctx *c, const uint8_t *h_bwtz, uint64_t len_b, co
  * hdr_fd < 0: "@"), '\n', DNA line i, "\n+\n", quality line i, '\n' -- byte for byte what bfq_fastq_run_job writes to
  * out_fastq with the same keep_headers (bfq_int.cpp:797-810).  Accepted inputs are what the project's own writers produce:
  *   read-order containers (compress_streams = 1, `bsc e`, parallel.py --compress): dna and qs one or more BFQDNAC1 / BFQRANS2
- *     members back to back each, hdr one or more BFQLINE1 / BFQRANS2 members; the member boundaries of the three inputs
+ *     members back to back each, hdr one or more BFQLINE1 / BFQRANS2 / BFQNAME1 members; the member boundaries of the three inputs
  *     need not coincide;
  *   eBWT-domain containers (compress_streams = 2 / 3): dna ONE BFQEBWT1 member, qs the one-member container of the rows'
  *     (mode 2) or the reads' (mode 3) qualities.  More than one BFQEBWT1 member is refused with BFQ_E_ARG: no writer of the
