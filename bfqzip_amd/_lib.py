@@ -25,6 +25,7 @@ SYMBOLS = [
     "bfq_stream_bound", "bfq_stream_raw_len", "bfq_stream_compress", "bfq_stream_decompress",
     "bfq_stream_reserve", "bfq_stream_compress_device", "bfq_stream_ebwt_decode",
     "bfq_names_compress", "bfq_names_compress_device",
+    "bfq_quals_compress", "bfq_quals_compress_device",
     "bfq_fastq_restore_bound", "bfq_fastq_restore", "bfq_fastq_restore_fd",
     "bfq_reorder_key", "bfq_fastq_reorder", "bfq_fastq_reorder_fd",
     "bfq_perm_bound", "bfq_perm_reads", "bfq_perm_encode", "bfq_perm_decode",
@@ -77,7 +78,8 @@ class FastqJob(C.Structure):
                 ("part_reads", C.c_uint64 * (MAX_PARTS + 1)), ("part_fastq_off", C.c_uint64 * (MAX_PARTS + 1)),
                 ("part_stream_off", C.c_uint64 * (MAX_PARTS + 1)), ("part_hdr_off", C.c_uint64 * (MAX_PARTS + 1)),
                 ("compress_streams", C.c_int32), ("name_codec", C.c_int32),
-                ("dna_bytes", C.c_uint64), ("qs_bytes", C.c_uint64), ("hdr_bytes", C.c_uint64)]
+                ("dna_bytes", C.c_uint64), ("qs_bytes", C.c_uint64), ("hdr_bytes", C.c_uint64),
+                ("qual_codec", C.c_int32), ("reserved1", C.c_int32)]
 
 
 def build(clean=False):
@@ -169,6 +171,8 @@ def lib():
         L.bfq_stream_reserve.argtypes = [vp, u64]
         L.bfq_names_compress.argtypes = [vp, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
         L.bfq_names_compress_device.argtypes = [vp, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.bfq_quals_compress.argtypes = [vp, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.bfq_quals_compress_device.argtypes = [vp, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
         L.bfq_stream_ebwt_decode.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
         L.bfq_fastq_restore_bound.restype = C.c_int64
         L.bfq_fastq_restore_bound.argtypes = [vp, u64, vp, u64, vp, u64]

@@ -240,13 +240,14 @@ class Engine:
         return (dna[:sl.value].tobytes(), qs[:sl.value].tobytes(),
                 hdr[:hl.value].tobytes() if want_headers else None, st.as_dict())
 
-    def fastq_job(self, parts, keep_headers=False, fastq=True, streams=False, hdr=False, out=None, compress=False, names=False):
+    def fastq_job(self, parts, keep_headers=False, fastq=True, streams=False, hdr=False, out=None, compress=False, names=False, quals=False):
         """One block of BFQzip_parallel.py in one call (bfq_fastq_run_job): `parts` = 1..4 byte ranges (bytes,
         uint8 arrays, memmap slices) processed as one collection; outputs as asked: the FASTQ text, the --m2
         streams (dna, qs), the --m3 header stream.  `out` may give reusable output arrays (e.g. PinnedBuffer.array)
         under the keys 'fastq', 'dna', 'qs', 'hdr'.  compress=True: the streams come back as BFQRANS2 containers
         (steps 1-5 of the reference in one call; stream_decompress gives the raw stream).  names=True (with compress): the
-        header stream leaves as names_compress writes it (the tokenised BFQNAME1 container where that is shorter)."""
+        header stream leaves as names_compress writes it (the tokenised BFQNAME1 container where that is shorter).  quals=True
+        (with compress 1 or 3): the quality stream leaves as quals_compress writes it (BFQQUAL1 where that is shorter)."""
         arrs = [_u8(p) for p in parts]
         np_ = len(arrs)
         tp = (_lib.TextPart * np_)()
@@ -265,6 +266,7 @@ class Engine:
         J.parts = tp; J.nparts = np_; J.keep_headers = 1 if keep_headers else 0
         J.compress_streams = int(compress)                     # 0 raw, 1 containers of the streams, 2 eBWT-domain containers
         J.name_codec = 1 if names else 0
+        J.qual_codec = 1 if quals else 0
         bf = buf("fastq", fastq, inlen + 5 * np_ + 16)
         zcap = (2 * int(self.L.bfq_stream_bound(inlen)) + 64) if compress else 0      # a tiny stream's container is larger than the stream
         bd, bq = buf("dna", streams, max(inlen + 16, zcap)), buf("qs", streams, max(inlen + 16, zcap))
@@ -413,12 +415,31 @@ class Engine:
         self._ck(self.L.bfq_names_compress(self.h, _ptr(data), len(data), 1 if always else 0, _ptr(out), len(out), C.byref(ol)))
         return out[:int(ol.value)]
 
+    @staticmethod
+    def _quals_flags(always, rung):
+        if rung is not None and rung not in (0, 1, 2, 3):
+            raise ValueError("rung is None or 0..3")
+        return (1 if always else 0) | (0 if rung is None else 2 | (int(rung) << 8))
+
+    def quals_compress(self, data, always=False, rung=None, out=None):
+        """Quality lines in read order as the BFQQUAL1 container (values coded by their place in the read) when the stream is
+        eligible (a final newline, at least one value, no line above 65 535 bytes, at most 64 distinct values) and the
+        container is shorter than stream_compress's; else exactly what stream_compress gives.  always=True: BFQQUAL1 whenever
+        the stream is eligible.  rung=0..3 forces the model's rung (tests, diagnostics).  stream_decompress and fastq_restore
+        take either."""
+        data = _u8(data)
+        if out is None:
+            out = np.empty(int(self.L.bfq_stream_bound(len(data))), np.uint8)
+        ol = C.c_uint64(0)
+        self._ck(self.L.bfq_quals_compress(self.h, _ptr(data), len(data), self._quals_flags(always, rung), _ptr(out), len(out), C.byref(ol)))
+        return out[:int(ol.value)]
+
     def stream_decompress(self, blob, out=None):
-        """The raw bytes of a container of the stream codec (BFQRANS2 / BFQDNAC1 / BFQLINE1 / BFQNAME1; several back to back)."""
+        """The raw bytes of a container of the stream codec (BFQRANS2 / BFQDNAC1 / BFQLINE1 / BFQNAME1 / BFQQUAL1; several back to back)."""
         blob = _u8(blob)
         n = int(self.L.bfq_stream_raw_len(_ptr(blob), len(blob)))
         if n < 0:
-            raise BfqError(-1, "not a BFQRANS2 / BFQDNAC1 / BFQLINE1 / BFQNAME1 stream (or a damaged one)")
+            raise BfqError(-1, "not a BFQRANS2 / BFQDNAC1 / BFQLINE1 / BFQNAME1 / BFQQUAL1 stream (or a damaged one)")
         if out is None:
             out = np.empty(max(n, 1), np.uint8)
         ol = C.c_uint64(0)
@@ -451,7 +472,7 @@ class Engine:
         if out is None:
             bound = int(self.L.bfq_fastq_restore_bound(_ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0))
             if bound < 0:
-                raise BfqError(-1, "not a container (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQNAME1 / BFQEBWT1)")
+                raise BfqError(-1, "not a container (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQNAME1 / BFQQUAL1 / BFQEBWT1)")
             out = np.empty(max(bound, 1), np.uint8)
         ol, nr = C.c_uint64(0), C.c_uint64(0)
         if perm is not None:
@@ -595,6 +616,13 @@ class Engine:
         workspace itself.  Returns the container's length."""
         ol = C.c_uint64(0)
         self._ck(self.L.bfq_names_compress_device(self.h, d_in, n, 1 if always else 0, d_out, cap, C.byref(ol)))
+        return int(ol.value)
+
+    def quals_compress_device(self, d_in, n, d_out, cap, always=False, rung=None):
+        """quals_compress with both buffers in device memory (pointers, e.g. torch data_ptr()); the call sizes the engine's
+        workspace itself.  Returns the container's length."""
+        ol = C.c_uint64(0)
+        self._ck(self.L.bfq_quals_compress_device(self.h, d_in, n, self._quals_flags(always, rung), d_out, cap, C.byref(ol)))
         return int(ol.value)
 
     def stream_reserve(self, n):

@@ -1131,6 +1131,8 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
         J->dna_bytes = J->qs_bytes = J->hdr_bytes = 0;
         const bool cz = J->compress_streams != 0;
         if (J->name_codec != 0 && J->name_codec != 1) throw BfqError{BFQ_E_ARG, "bfq_fastq_job: name_codec is 0 or 1"};
+        if (J->qual_codec != 0 && J->qual_codec != 1) throw BfqError{BFQ_E_ARG, "bfq_fastq_job: qual_codec is 0 or 1"};
+        if (J->qual_codec == 1 && J->compress_streams == 2) throw BfqError{BFQ_E_ARG, "bfq_fastq_job: qual_codec needs qualities in read order (compress_streams 1 or 3)"};
         std::vector<u64> ps;
         TextSrc src[BFQ_MAX_PARTS];
         for (int p = 0; p < np; p++) src[p] = TextSrc{HostRef::mem(J->parts[p].data), J->parts[p].len};
@@ -1225,7 +1227,11 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
                 bfq_download(c, J->out_dna, d_z, J->dna_bytes);
             } else
             if (J->out_dna) { J->dna_bytes = bfq_codec_compress_device(c, ob, sl, d_z, bound); bfq_download(c, J->out_dna, d_z, J->dna_bytes); }
-            if (J->out_qs) { J->qs_bytes = bfq_codec_compress_device(c, qsByRead ? lineQs : oq, sl, d_z, bound); bfq_download(c, J->out_qs, d_z, J->qs_bytes); }
+            if (J->out_qs) {                                   // (qual_codec: by their place in the read where that is shorter)
+                const u8 *qsrc = qsByRead ? lineQs : oq;
+                J->qs_bytes = J->qual_codec == 1 ? bfq_quals_finish(c, qsrc, sl, 0, d_z, bound) : bfq_codec_compress_device(c, qsrc, sl, d_z, bound);
+                bfq_download(c, J->out_qs, d_z, J->qs_bytes);
+            }
             c->release(mz);
         }
         if (J->out_fastq) {
@@ -1504,6 +1510,50 @@ extern "C" int bfq_names_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64
     return guarded(c, [&] {
         if ((len && !d_in) || !d_out || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
         *out_len = names_compress_core(c, [&](u64) { return NamesBufs{d_in, d_out}; }, len, flags, cap);
+        c->sync();
+        c->profCollect();
+    });
+}
+
+// quality lines (k_quals.hip): the BFQQUAL1 container where it applies and (flags 0) pays, else what bfq_stream_compress
+// writes.  The arena is sized from len for reads of 64 values and more; a stream of shorter lines needs more for its line
+// index and lengths, which is known once the lines are counted: the arena then grows once and the call starts over.
+static u64 quals_compress_core(bfq_ctx *c, const std::function<NamesBufs(u64)> &begin, u64 len, u32 flags, u64 cap)
+{
+    if ((flags & ~0x303u) || (!(flags & 2u) && (flags & 0x300u))) throw BfqError{BFQ_E_ARG, "bfq_quals_compress: unknown flags"};
+    const u64 bound = bfq_codec_bound(len) < cap ? bfq_codec_bound(len) : cap;
+    size_t need = len + bound + 4096 + bfq_quals_workspace(len, len / 64) + bfq_codec_workspace(len);
+    for (;;) {
+        c->reserve(need);
+        const NamesBufs b = begin(bound);
+        const u64 nl = len ? bfq_fastq_count_lines(c, b.in, len) : 0;
+        need = c->mark() + bfq_quals_workspace(len, nl) + bfq_codec_workspace(len);
+        if (need > c->ws.cap) continue;                            // more lines than guessed
+        return bfq_quals_finish(c, b.in, len, flags, b.out, bound);
+    }
+}
+extern "C" int bfq_quals_compress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint32_t flags, uint8_t *h_out, uint64_t cap, uint64_t *out_len)
+{
+    return guarded(c, [&] {
+        if ((len && !h_in) || !h_out || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
+        u8 *d_out = nullptr;
+        const u64 got = quals_compress_core(c, [&](u64 bound) {
+            u8 *d_in = c->alloc<u8>(len + 16);
+            d_out = c->alloc<u8>(bound + 16);
+            if (len) bfq_upload(c, d_in, h_in, len);
+            return NamesBufs{d_in, d_out};
+        }, len, flags, cap);
+        bfq_download(c, h_out, d_out, got);
+        c->sync();                                             // pinned destinations are written by asynchronous DMA
+        c->profCollect();
+        *out_len = got;
+    });
+}
+extern "C" int bfq_quals_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint32_t flags, uint8_t *d_out, uint64_t cap, uint64_t *out_len)
+{
+    return guarded(c, [&] {
+        if ((len && !d_in) || !d_out || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
+        *out_len = quals_compress_core(c, [&](u64) { return NamesBufs{d_in, d_out}; }, len, flags, cap);
         c->sync();
         c->profCollect();
     });

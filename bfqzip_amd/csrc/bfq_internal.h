@@ -323,6 +323,14 @@ u64 bfq_names_finish(bfq_ctx *c, const u8 *d_in, u64 n, const NamesSized &S, u32
 u64 bfq_names_member_len(const u8 *h_in, u64 len);
 u64 bfq_names_decode_extra(const u8 *h_in, u64 len, u64 *maxInner);   // arena bytes beside the codec's workspace for the largest inner member
 u64 bfq_names_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
+// quality lines by their place in the read (k_quals.hip): the BFQQUAL1 container.  bfq_quals_finish: what bfq_quals_compress
+// gives for a stream on the device (flags as there); bfq_quals_workspace: arena bytes beside the general codec's.
+u64 bfq_quals_workspace(u64 n, u64 nl);
+u64 bfq_quals_finish(bfq_ctx *c, const u8 *d_in, u64 n, u32 flags, u8 *d_out, u64 cap);
+u64 bfq_quals_member_len(const u8 *h_in, u64 len);
+u64 bfq_quals_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 len, u8 *d_out, u64 cap);
+void bfq_codec_normalise(const u32 *cnt, u32 A, u16 *f);           // k_codec.hip: a row of counts -> frequencies that sum to 2^12
+u32 bfq_codec_bit_cost(u32 f);                                     // (12 - log2 f) * 256
 
 // step 1 pieces
 void bfq_build_text(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u64 N, u64 n,

@@ -51,7 +51,7 @@ int main(int argc, char **argv)
         if (md != MAP_FAILED) munmap(md, fd.size);
         if (mq != MAP_FAILED) munmap(mq, fq.size);
         if (mh != MAP_FAILED) munmap(mh, fh.size);
-        if (bound < 0) { fprintf(stderr, "bfq_restore: the inputs are not containers (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQNAME1 / BFQEBWT1)\n"); outText.close(); return 1; }
+        if (bound < 0) { fprintf(stderr, "bfq_restore: the inputs are not containers (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQNAME1 / BFQQUAL1 / BFQEBWT1)\n"); outText.close(); return 1; }
         if (bound >= (64 << 20)) (void)bfq_output_prefault(outText.fd, (uint64_t)bound + 4096, (uint64_t)bound / 2);
     }
     bfq_params P;

@@ -398,6 +398,9 @@ static u32 cdc_choose_order(std::vector<u32> &cnt, u32 A, u32 kmax, u32 S)
     std::copy(keep.begin(), keep.end(), cnt.begin());
     return best;
 }
+// (the same normalisation and cost for the other containers' models: k_quals.hip)
+void bfq_codec_normalise(const u32 *cnt, u32 A, u16 *f) { cdc_normalise(cnt, A, f); }
+u32 bfq_codec_bit_cost(u32 f) { return cdc_bit_cost(f); }
 static u32 cdc_choose_seg(u64 n)
 {
     u32 seg = CQ_SEG_MAX;
@@ -576,6 +579,7 @@ u64 bfq_codec_member_len(const u8 *h_in, u64 len)
 {
     if (len >= 8 && !memcmp(h_in, "BFQDNAC1", 8)) return bfq_dnac_member_len(h_in, len);
     if (len >= 8 && !memcmp(h_in, "BFQNAME1", 8)) return bfq_names_member_len(h_in, len);
+    if (len >= 8 && !memcmp(h_in, "BFQQUAL1", 8)) return bfq_quals_member_len(h_in, len);
     if (len >= 32 && !memcmp(h_in, "BFQLINE1", 8)) return 32 + bfq_codec_member_len(h_in + 32, len - 32);
     CdcHeader H;
     cdc_parse(h_in, len, H);
@@ -591,7 +595,7 @@ u64 bfq_codec_raw_len(const u8 *h_in, u64 len, u64 *nameWs)
     if (nameWs) *nameWs = 0;
     do {
         const bool lx = (len - pos >= 32 && !memcmp(h_in + pos, "BFQLINE1", 8)) || (len - pos >= 72 && !memcmp(h_in + pos, "BFQDNAC1", 8)) ||
-                        (len - pos >= 64 && !memcmp(h_in + pos, "BFQNAME1", 8));
+                        (len - pos >= 64 && !memcmp(h_in + pos, "BFQNAME1", 8)) || (len - pos >= 72 && !memcmp(h_in + pos, "BFQQUAL1", 8));
         if (!lx && (len - pos < CQ_HDR + 256 || memcmp(h_in + pos, "BFQRANS2", 8))) throw BfqError{BFQ_E_ARG, "not a BFQRANS2 stream"};
         raw += get64(h_in + pos + 8);
         const u64 ml = bfq_codec_member_len(h_in + pos, len - pos);
@@ -779,6 +783,7 @@ u64 bfq_codec_decompress_device(bfq_ctx *c, const u8 *h_in, const u8 *d_in, u64 
 {
     if (len >= 8 && !memcmp(h_in, "BFQDNAC1", 8)) return bfq_dnac_decompress_device(c, h_in, d_in, len, d_out, cap);
     if (len >= 8 && !memcmp(h_in, "BFQNAME1", 8)) return bfq_names_decompress_device(c, h_in, d_in, len, d_out, cap);
+    if (len >= 8 && !memcmp(h_in, "BFQQUAL1", 8)) return bfq_quals_decompress_device(c, h_in, d_in, len, d_out, cap);
     if (len < 32 || memcmp(h_in, "BFQLINE1", 8)) return bfq_rans_decompress_device(c, h_in, d_in, len, d_out, cap);
     const BfqError bad{BFQ_E_ARG, "damaged BFQLINE1 stream"};
     const u64 n = get64(h_in + 8), nl = get64(h_in + 24);

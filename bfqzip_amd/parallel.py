@@ -243,13 +243,14 @@ def _pinned_outputs(kinds, cap):
 
 
 def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fastq=True, want_streams=False,
-              want_hdr=False, out_bufs=None, log=None, compress=False, pinned=False, name_codec=False):
+              want_hdr=False, out_bufs=None, log=None, compress=False, pinned=False, name_codec=False, qual_codec=False):
     """The whole multi-GPU job.  eng: Engine-like (fastq_job, text_line_counts/text_nth_newline via `eng.host`).
     Returns per-rank totals {"blocks", "reads", "bases", "stats"} (stats summed over this rank's blocks).
     compress: step 5 too (BFQzip.py:253-275) -- every block's share of every output goes through the stream codec
     (eng.stream_compress) and the files `<name>.bsc` hold one BFQRANS2 container per block, in block order
     (`bsc d` / stream_decompress read them back as one stream).  name_codec: the header shares go through
-    eng.names_compress instead (the tokenised BFQNAME1 container where it is shorter; restore takes either)."""
+    eng.names_compress instead (the tokenised BFQNAME1 container where it is shorter; restore takes either), qual_codec:
+    the quality shares through eng.quals_compress (BFQQUAL1 where it is shorter)."""
     host = eng.host
     bufs = [map_file(p) for p in inputs]
     idx = [TextIndex(b, comm, host.text_line_counts, host.text_nth_newline) for b in bufs]
@@ -298,7 +299,8 @@ def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fas
                         hi = cut[kind][o + 1] if o < len(parts) else cut[kind][-1]
                         sizes[o, ki] = hi - lo
                         if compress:                                 # this mate's share of the block as one container
-                            code = eng.names_compress if (name_codec and kind == "hdr") else eng.stream_compress
+                            code = (eng.names_compress if (name_codec and kind == "hdr") else
+                                    eng.quals_compress if (qual_codec and kind == "qs") else eng.stream_compress)
                             blobs[(o, kind)] = code(raw[kind][lo:hi])
                             sizes[o, ki] = len(blobs[(o, kind)])
             tot["blocks"] += 1; tot["reads"] += res.n_reads; tot["bases"] += res.total_bases
@@ -532,6 +534,8 @@ def main(argv=None):
                     help="step 5 on the GPU: every output goes through the stream codec, files get the suffix .bsc (one container per block)")
     ap.add_argument("--names", action="store_true",
                     help="with --compress: read names (OUT.h) as tokens, the BFQNAME1 container where it is shorter than the general one")
+    ap.add_argument("--quals", action="store_true",
+                    help="with --compress: quality lines coded by their place in the read, the BFQQUAL1 container where it is shorter than the general one")
     ap.add_argument("-p", "--paired", action="store_true")
     ap.add_argument("-t", "--threads", type=int, default=0, help="number of blocks")
     ap.add_argument("-c", "--check", action="store_true", help="accepted: records are always checked on the GPU")
@@ -590,7 +594,7 @@ def main(argv=None):
     else:
         tot = run_files(eng, comm, a.input, a.threads, names, paired=a.paired, headers=a.headers,
                         want_fastq=not (streams and a.streams_only), want_streams=streams, want_hdr=a.m3, log=log,
-                        compress=a.compress and not a.m0, pinned=a.pinned, name_codec=a.names)
+                        compress=a.compress and not a.m0, pinned=a.pinned, name_codec=a.names, qual_codec=a.quals)
     if perm_path:
         want_fastq = not (streams and a.streams_only)
         compress = a.compress and not a.m0 and not a.glob

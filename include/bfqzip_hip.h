@@ -213,6 +213,11 @@ typedef struct bfq_fastq_job {
     int32_t  name_codec;                      /* 0: out_hdr as described; 1 (with compress_streams 1, 2 or 3): out_hdr is what
                                                  bfq_names_compress(flags 0) gives for the header stream (BFQNAME1 where shorter) */
     uint64_t dna_bytes, qs_bytes, hdr_bytes;
+    int32_t  qual_codec;                      /* 0: out_qs as described; 1 (with compress_streams 1 or 3, whose qualities are lines in
+                                                 read order): out_qs is what bfq_quals_compress(flags 0) gives for the quality stream
+                                                 (BFQQUAL1 where shorter); with compress_streams 2 (qualities in row order): BFQ_E_ARG.
+                                                 The two fields stand behind the older ones, whose offsets do not change. */
+    int32_t  reserved1;
 } bfq_fastq_job;
 int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *job, bfq_stats *st);
 
@@ -340,6 +345,49 @@ int bfq_stream_decompress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t
  *   bfq_names_compress_device: both buffers in device memory outside the context's workspace, which the call sizes itself */
 int bfq_names_compress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint32_t flags, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
 int bfq_names_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint32_t flags, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
+/* ---- quality lines by their place in the read: the opt-in container "BFQQUAL1" (k_quals.hip; tests/quals_model.py states it
+ * in Python).  BFQRANS2 sees the k bytes in front of a value inside an arbitrary segment; here a value is coded against the
+ * value before it, a coarse view of the two before that, its place in the read and how noisy the read has been so far.
+ * All fields little endian.  The stream is lines, each ended by '\n'; lens[i] = length of line i, vals = the lines without
+ * their newlines, nvals = len(vals), maxlen = max(lens).
+ *   eligible : the stream ends with '\n', nvals >= 1, no line longer than 65 535, vals has at most 64 distinct byte values
+ *              (and nvals < 2^38: the model's counters are 32 bits wide).  Otherwise the general container is written.
+ *   alphabet : the distinct values of vals, ascending, A of them; a value's rank is its index there.
+ *   segments : S = 1024; segment g = the reads whose first value has an index in [g S, (g + 1) S) of vals (the rule of
+ *              BFQDNAC1; a segment may be empty, a read longer than S lies in one segment); nseg = ceil(nvals / S).
+ *   context  : for value j of a read with ranks s[0..l), a missing predecessor counting as 0: q1 = s[j-1], q2 = s[j-2],
+ *              q3 = s[j-3]; m8 = max(q2, q3) 8 / A; e = (q2 == q3); p16 = min(15, j / W), W = max(1, ceil(maxlen / 16));
+ *              delta = sum over t = 1..j-1 of |s[t] - s[t-1]|; d4 = (delta >= 8) + (delta >= 32) + (delta >= 128).
+ *   rungs    : rung r = 0..3 has (M, P, D, E) = (1,1,1,1), (4,4,2,1), (8,8,4,1), (8,16,4,2); m = m8 >> (3 - log2 M),
+ *              p = p16 >> (4 - log2 P), d = d4 >> (2 - log2 D), e counts only when E = 2;
+ *              ctx = (((p D + d) E + e) M + m) A + q1, rows = P D E M A.  The rungs are nested.
+ *   model    : static, counted on a sample: the segments with g % St == 0, St = clamp(nvals / 2^24, 1, 64).  Counts are taken
+ *              at rmax, the largest rung with rows A <= min(2^22, max(4096, (nvals / St) / 16)) (rung 0 always qualifies);
+ *              the container is made with the rung <= rmax whose estimated size is smallest (choose_order()'s estimator in
+ *              oracle/bfq_codec_ref.c: payload from the normalised rows times St, + 16 A bits per used row + 1 bit per row;
+ *              the lowest rung among equals).  Rows are normalised to 2^12 as normalise() there: every symbol has a
+ *              non-zero share in every row.  The order-0 row `dflt` (all counts of the chosen rung) serves rows without counts.
+ *   rANS     : BFQRANS2's (state in [2^23, 2^31), byte-wise renormalisation), one stream per non-empty segment: the values
+ *              of the segment's reads in order, coded last to first.
+ *   container: "BFQQUAL1" | u64 raw_len | u64 nreads | u64 nvals | u32 S, nseg, A, rung, scale_bits (12), maxlen
+ *              | u64 checksum of the raw bytes (the codec's) | u64 Lb | a BFQRANS2 container (Lb bytes) of lens[] as u32
+ *              | u8 alphabet[64] | u16 dflt[A] | u8 used[ceil(rows / 8)] | u16 freq[used rows][A] | u32 seg_bytes[nseg] | payload
+ * The decoder refuses with BFQ_E_ARG "damaged BFQQUAL1 stream": S != 1024, scale != 12, A outside 1..64, rung > 3, an
+ * alphabet that is not ascending or holds '\n', nseg != ceil(nvals / S), a lens member whose raw length is not 4 nreads,
+ * sum(lens) != nvals or max(lens) != maxlen, nvals + nreads != raw_len, a row (dflt included) that does not sum to 2^12,
+ * seg_bytes that do not add up to the payload, bytes for an empty segment, an initial state below 2^23, a refill past the
+ * segment's share or a share not consumed exactly, a checksum mismatch.  Every read and write stays inside the stated shares.
+ * bfq_stream_decompress, bfq_stream_raw_len and bfq_fastq_restore* take BFQQUAL1 members wherever they take BFQRANS2 members
+ * of a quality input; members of both kinds may be mixed in one file.
+ *   bfq_quals_compress       : flags 0: the BFQQUAL1 container when the stream is eligible and the container is strictly
+ *                              shorter than what bfq_stream_compress writes for the same bytes, else exactly those bytes;
+ *                              bfq_stream_bound(len) therefore suffices.  Bit 0 ("always"): BFQQUAL1 whenever the stream is
+ *                              eligible.  Bit 1 ("rung forced"): the rung is bits 8-9 and the counts are taken there (the
+ *                              sample budget is ignored, the 2^22 cap always holds for A <= 64); tests and diagnostics.
+ *                              Any other bit (bits 8-9 without bit 1 included): BFQ_E_ARG.
+ *   bfq_quals_compress_device: both buffers in device memory outside the context's workspace, which the call sizes itself */
+int bfq_quals_compress(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint32_t flags, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+int bfq_quals_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint32_t flags, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
 /* eBWT-domain containers (bfq_fastq_job.compress_streams = 2; out_fastq must be NULL): out_dna receives "BFQEBWT1" |
  * u64 rows | u64 reads | u32 terminator byte | u32 flags | u64 bytes of the next container | the container of the eBWT's
  * symbols AFTER noise reduction | the container of the replaced rows' original symbols (0 elsewhere), out_qs the
@@ -356,7 +404,7 @@ int bfq_stream_ebwt_decode(bfq_ctx *c, const uint8_t *h_bwtz, uint64_t len_b, co
  * hdr_fd < 0: "@"), '\n', DNA line i, "\n+\n", quality line i, '\n' -- byte for byte what bfq_fastq_run_job writes to
  * out_fastq with the same keep_headers (bfq_int.cpp:797-810).  Accepted inputs are what the project's own writers produce:
  *   read-order containers (compress_streams = 1, `bsc e`, parallel.py --compress): dna and qs one or more BFQDNAC1 / BFQRANS2
- *     members back to back each, hdr one or more BFQLINE1 / BFQRANS2 / BFQNAME1 members; the member boundaries of the three inputs
+ *     (qs also BFQQUAL1) members back to back each, hdr one or more BFQLINE1 / BFQRANS2 / BFQNAME1 members; the member boundaries of the three inputs
  *     need not coincide;
  *   eBWT-domain containers (compress_streams = 2 / 3): dna ONE BFQEBWT1 member, qs the one-member container of the rows'
  *     (mode 2) or the reads' (mode 3) qualities.  More than one BFQEBWT1 member is refused with BFQ_E_ARG: no writer of the
