@@ -31,6 +31,7 @@ SYMBOLS = [
     "bfq_perm_bound", "bfq_perm_reads", "bfq_perm_encode", "bfq_perm_decode",
     "bfq_fastq_reorder_keep", "bfq_fastq_reorder_keep_fd", "bfq_fastq_unreorder", "bfq_fastq_unreorder_fd",
     "bfq_fastq_restore_ordered", "bfq_fastq_restore_ordered_fd",
+    "bfq_fastq_restore_groups", "bfq_stream_members", "bfq_fastq_restore_grouped", "bfq_fastq_restore_grouped_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -66,6 +67,11 @@ class TextPart(C.Structure):
 
 class ReorderOpts(C.Structure):
     _fields_ = [("mode", C.c_int32), ("k", C.c_int32), ("seed", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+class RestoreGroup(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("dna_off", "dna_len", "qs_off", "qs_len", "hdr_off", "hdr_len", "raw_stream", "raw_hdr",
+                                          "reads", "text_bound")]
 
 
 class FastqJob(C.Structure):
@@ -197,6 +203,12 @@ def lib():
         L.bfq_fastq_unreorder_fd.argtypes = [vp, pint, pu64, C.c_int, C.c_int, u64, pint, pu64, pu64]
         L.bfq_fastq_restore_ordered.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, pu64, pu64]
         L.bfq_fastq_restore_ordered_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, pu64, pu64]
+        L.bfq_fastq_restore_groups.restype = C.c_int64
+        L.bfq_fastq_restore_groups.argtypes = [vp, u64, vp, u64, vp, u64, C.POINTER(RestoreGroup), u64, C.c_char_p, C.c_int]
+        L.bfq_stream_members.restype = C.c_int64
+        L.bfq_stream_members.argtypes = [vp, u64]
+        L.bfq_fastq_restore_grouped.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, u64, vp, u64, pu64, pu64]
+        L.bfq_fastq_restore_grouped_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, u64, u64, C.c_int, pu64, pu64]
         L.bfq_stream_compress_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]
         L.bfq_prof_reset.argtypes = [vp]

@@ -113,12 +113,45 @@ class FileRange:
     __del__ = close
 
 
+ALL_GROUPS = (1 << 64) - 1
+
+
+def restore_groups(dna, qs, hdr=None):
+    """The group plan of an archive (bfq_fastq_restore_groups: container headers only, no GPU): a list of dicts, one per
+    group that decodes on its own -- a block of a sharded run -- with the keys of bfq_restore_group (dna_off, dna_len, qs_off,
+    qs_len, hdr_off, hdr_len, raw_stream, raw_hdr, reads (None where a DNA member states none), text_bound) plus the member
+    counts members = (dna, qs, hdr).  Inputs that do not group raise BfqError with the library's reason."""
+    L = _lib.lib()
+    dna, qs = _u8(dna), _u8(qs)
+    hdr = _u8(hdr) if hdr is not None else None
+    pad = np.zeros(1, np.uint8)                                      # (an empty input: a pointer the library can name as such)
+    pd, pq, ph = (_ptr(a if len(a) else pad) if a is not None else None for a in (dna, qs, hdr))
+    args = (pd, len(dna), pq, len(qs), ph, len(hdr) if hdr is not None else 0)
+    why = C.create_string_buffer(512)
+    G = int(L.bfq_fastq_restore_groups(*args, None, 0, why, len(why)))
+    arr = (_lib.RestoreGroup * max(G, 1))()
+    if G > 0:
+        G = int(L.bfq_fastq_restore_groups(*args, arr, G, why, len(why)))
+    if G < 0:
+        raise BfqError(G, why.value.decode())
+    out = []
+    for k in range(G):
+        g = {name: int(getattr(arr[k], name)) for name, _ in _lib.RestoreGroup._fields_}
+        if g["reads"] == ALL_GROUPS:
+            g["reads"] = None
+        cnt = lambda a, off, n: int(L.bfq_stream_members(C.c_void_p(a.ctypes.data + off), n)) if a is not None and n else 0
+        g["members"] = (cnt(dna, g["dna_off"], g["dna_len"]), cnt(qs, g["qs_off"], g["qs_len"]), cnt(hdr, g["hdr_off"], g["hdr_len"]))
+        out.append(g)
+    return out
+
+
 class HostText:
     """Host-side text helpers of libbfqhip.so (no GPU involved)."""
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
     file_put = staticmethod(file_put)
+    restore_groups = staticmethod(restore_groups)
 
 
 class Engine:
@@ -459,34 +492,54 @@ class Engine:
         return dna[:int(sl.value)], qs[:int(sl.value)], int(nr.value)
 
     # ---- the way back: containers -> FASTQ text (bfq_fastq_restore)
-    def fastq_restore(self, dna, qs, hdr=None, out=None, perm=None):
+    def fastq_restore(self, dna, qs, hdr=None, out=None, perm=None, groups=None):
         """The FASTQ text of a collection from the containers of its streams (fastq_job(compress=1 / 2 / 3), stream_compress,
         the .bsc files of parallel.py --compress): (text as a uint8 array, n_reads).  hdr=None: every header line is "@".
         `out`: a uint8 array to fill (e.g. PinnedBuffer.array); the result is a view of it.  Streams that do not belong
         together raise BfqError (BFQ_E_ARG, the message names the first offending read) and leave `out` untouched.
         `perm`: the BFQPERM1 container of the reordering the collection went through (fastq_reorder(keep=True)): the records
-        come back in the order before it (bfq_fastq_restore_ordered)."""
+        come back in the order before it (bfq_fastq_restore_ordered).
+        `groups`: True, or (first, count) with count None = to the end: block by block (bfq_fastq_restore_grouped) -- the
+        groups of HostText.restore_groups one after another in a device workspace sized by the largest of them, the same
+        bytes as without; several BFQEBWT1 members are taken.  A failure after the first group may leave the texts of the
+        groups before it in `out`.  Not with `perm`."""
+        if groups is not None and groups is not False and perm is not None:
+            raise ValueError("fastq_restore: groups and perm do not go together (records in the original order draw on all groups at once)")
         dna, qs = _u8(dna), _u8(qs)
         hdr = _u8(hdr) if hdr is not None else None
         perm = _u8(perm) if perm is not None else None
+        hl = len(hdr) if hdr is not None else 0
+        ol, nr = C.c_uint64(0), C.c_uint64(0)
+        if groups is not None and groups is not False:
+            first, count = (0, None) if groups is True else groups
+            count = ALL_GROUPS if count is None else int(count)
+            if out is None:
+                plan = restore_groups(dna, qs, hdr)
+                last = len(plan) if count == ALL_GROUPS else min(len(plan), first + count)
+                out = np.empty(max(sum(g["text_bound"] for g in plan[first:last]), 1), np.uint8)
+            self._ck(self.L.bfq_fastq_restore_grouped(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), hl, int(first), count,
+                                                      _ptr(out), len(out), C.byref(ol), C.byref(nr)))
+            return out[:int(ol.value)], int(nr.value)
         if out is None:
-            bound = int(self.L.bfq_fastq_restore_bound(_ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0))
+            bound = int(self.L.bfq_fastq_restore_bound(_ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), hl))
             if bound < 0:
                 raise BfqError(-1, "not a container (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQNAME1 / BFQQUAL1 / BFQEBWT1)")
             out = np.empty(max(bound, 1), np.uint8)
-        ol, nr = C.c_uint64(0), C.c_uint64(0)
         if perm is not None:
-            self._ck(self.L.bfq_fastq_restore_ordered(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0,
+            self._ck(self.L.bfq_fastq_restore_ordered(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), hl,
                                                       _ptr(perm) if len(perm) else None, len(perm), _ptr(out), len(out), C.byref(ol), C.byref(nr)))
         else:
-            self._ck(self.L.bfq_fastq_restore(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), len(hdr) if hdr is not None else 0,
+            self._ck(self.L.bfq_fastq_restore(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), hl,
                                               _ptr(out), len(out), C.byref(ol), C.byref(nr)))
         return out[:int(ol.value)], int(nr.value)
 
-    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None):
+    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None, grouped=False):
         """bfq_fastq_restore_fd on named files (hdr_path may be None); returns (bytes written, n_reads).  perm_path: the
-        BFQPERM1 file of the reordering (bfq_fastq_restore_ordered_fd): the text in the order before it."""
+        BFQPERM1 file of the reordering (bfq_fastq_restore_ordered_fd): the text in the order before it.  grouped: True or
+        (first, count) as fastq_restore's `groups` (bfq_fastq_restore_grouped_fd); not with perm_path."""
         import os
+        if grouped and perm_path is not None:
+            raise ValueError("fastq_restore_files: grouped and perm_path do not go together")
         fds = []
         try:
             for p in (dna_path, qs_path, hdr_path, perm_path):
@@ -494,7 +547,12 @@ class Engine:
             fds.append(os.open(out_path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
             ol, nr = C.c_uint64(0), C.c_uint64(0)
             size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
-            if perm_path is not None:
+            if grouped:
+                first, count = (0, None) if grouped is True else grouped
+                self._ck(self.L.bfq_fastq_restore_grouped_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
+                                                             int(first), ALL_GROUPS if count is None else int(count), fds[4],
+                                                             C.byref(ol), C.byref(nr)))
+            elif perm_path is not None:
                 self._ck(self.L.bfq_fastq_restore_ordered_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
                                                              fds[3], size(fds[3]), fds[4], C.byref(ol), C.byref(nr)))
             else:

@@ -1571,6 +1571,17 @@ __global__ __launch_bounds__(256) void k_ebwt_mark(const u8 *__restrict__ sym, c
     for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (u64)gridDim.x * blockDim.x)
         if (sym[r] != orig[r]) lfq_set_repl(lfq, r, bfq_base_code(orig[r]), bfq_base_code(sym[r]));
 }
+static size_t ebwt_decode_need(u64 n, u64 N, u64 len_b, u64 len_q, size_t extraWs, bool keepQs)
+{
+    return ws_need_given(n, N, 5 * n + len_b + len_q + bfq_codec_workspace(n) / 2 + (64u << 20) + extraWs + (keepQs ? n + 4096 : 0));
+}
+size_t bfq_ebwt_decode_need(const u8 *h_bwtz, u64 len_b, u64 len_q, size_t extraWs, bool keepLines)
+{
+    u64 n = 0, N = 0;
+    u32 flags = 0;
+    memcpy(&n, h_bwtz + 8, 8); memcpy(&N, h_bwtz + 16, 8); memcpy(&flags, h_bwtz + 28, 4);
+    return ebwt_decode_need(n, N, len_b, len_q, extraWs, keepLines && (flags & 1u));
+}
 // eBWT-domain containers (bfq_fastq_job.compress_streams = 2) back to the line streams OUT.fq.dna / OUT.fq.qs: the two
 // containers are decoded on the device, the LF table is built from the rows and the reads are walked out (steps 4 of the
 // path; no clusters: the rows already hold the smoothed result).  res != nullptr: the streams stay on the device for the
@@ -1594,7 +1605,9 @@ void bfq_ebwt_decode_lines(bfq_ctx *c, const u8 *h_bwtz, u64 len_b, const u8 *h_
     if (res) { res->n = n; res->N = N; }
     if (!n) return;
     const bool keepQs = res && qsByRead;                       // the decoded read-order qualities are a result of their own
-    c->reserve(ws_need_given(n, N, 5 * n + len_b + len_q + bfq_codec_workspace(n) / 2 + (64u << 20) + extraWs + (keepQs ? n + 4096 : 0)));
+    const size_t need = ebwt_decode_need(n, N, len_b, len_q, extraWs, keepQs);
+    if (!c->call.arenaHeld) c->reserve(need);
+    else if (need > c->ws.room()) throw BfqError{BFQ_E_NOMEM, "workspace exhausted: the held arena has no room for the eBWT walk"};
     c->zeroCounters();
     c->n = n; c->N = N;
     c->d_bwt = c->alloc<u8>(n + 64); c->d_qual = c->alloc<u8>(n + 64);

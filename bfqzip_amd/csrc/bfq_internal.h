@@ -73,6 +73,8 @@ struct CallState {
     const u64 *d_w12 = nullptr, *d_text3 = nullptr;
     size_t keepMark = 0;
     size_t writeHint = 0;           // bytes the caller is going to queue in all: sizes the writer pool when it is created
+    bool arenaHeld = false;         // the caller reserved the arena for several pieces of work and holds buffers in it (grouped
+                                    // restore): bfq_ebwt_decode_lines allocates above the current top and reserves nothing
     // one-shot tools (the *_fd entry points): the eBWT and its qualities live outside the arena (in the text buffer, whose
     // FASTQ text is dead once the reads are gathered), so that the arena can be freed while they are still being written;
     // onRows(start, rows) is called whenever rows [start, start + rows) of the eBWT / QS / LCP are final (pile by pile)
@@ -424,7 +426,10 @@ void bfq_pick_u64(bfq_ctx *c, const u64 *d_src, const u64 *d_idx, int count, u64
 // eBWT-domain containers (bfq_api.hip): the body of bfq_stream_ebwt_decode.  Both line streams (n bytes each) stay in the
 // arena and are returned in *res when res != nullptr; the arena is reserved here, once, with extraWs bytes for the caller's
 // own use after the walk (the LF table's space is handed back to the caller as well).  h_dna / h_qs may be nullptr.
+// CallState::arenaHeld: no reservation -- the arena is the caller's, who sized it with bfq_ebwt_decode_need() for the same
+// extraWs; the walk's buffers go above the current top.
 struct EbwtLines { u8 *dna = nullptr, *qs = nullptr; u64 n = 0, N = 0; };
+size_t bfq_ebwt_decode_need(const u8 *h_bwtz, u64 len_b, u64 len_q, size_t extraWs, bool keepLines);   // what bfq_ebwt_decode_lines reserves (header fields as they stand)
 void bfq_ebwt_decode_lines(bfq_ctx *c, const u8 *h_bwtz, u64 len_b, const u8 *h_qsz, u64 len_q, u8 *h_dna, u8 *h_qs, u64 cap,
                            uint64_t *stream_len, uint64_t *n_reads, size_t extraWs, EbwtLines *res);
 

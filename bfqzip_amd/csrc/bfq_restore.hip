@@ -11,6 +11,10 @@
 // the reads had before it: after k_restore_index the container is unpacked, validated and inverted (k_reorder.hip), the
 // record sizes are scanned through the inverse and k_fq_format_ordered reads line inv[i] for record i -- no second pass over
 // the text.
+// bfq_fastq_restore_grouped* restore an archive block by block: rs_groups() cuts the members of the inputs into groups that
+// decode on their own (one per block of a sharded run), the arena is reserved once for the largest group of the range, and
+// every group goes through the pipeline above on its slices of the inputs; its text leaves the device from one of two
+// buffers while the next group is decoded into the streams' space.
 #include <string.h>
 #include <stdio.h>
 #include <sys/mman.h>
@@ -167,6 +171,168 @@ extern "C" int64_t bfq_fastq_restore_bound(const uint8_t *h_dna, uint64_t dna_le
     } catch (const BfqError &) { return -1; }
 }
 
+// ---- the group plan -----------------------------------------------------------------------------------------------------
+// one member at byte `pos` of an input: its bytes, its raw bytes, the reads it states (~0: none); a BFQEBWT1 member counts
+// as one member of `rows` raw bytes
+struct RsMember { u64 len = 0, raw = 0, reads = ~0ull; bool ebwt = false; };
+static RsMember rs_member(const RsSrc &s, u64 pos, const char *what, u64 *maxMember, u64 *nameExtra)
+{
+    RsMember m;
+    const u8 *p = s.h + pos;
+    const u64 avail = s.len - pos;
+    try {
+        if (avail >= 8 && !memcmp(p, "BFQEBWT1", 8)) {
+            const BfqError bad{BFQ_E_ARG, "damaged BFQEBWT1 stream"};
+            if (avail < 40) throw bad;
+            const u64 n = rs_get64(p + 8), N = rs_get64(p + 16), symLen = rs_get64(p + 32);
+            if (symLen > avail - 40 || N > n) throw bad;
+            u64 mm = 0;
+            if (rs_walk(RsSrc{p + 40, symLen}, "eBWT symbols", &mm, nullptr) != n) throw bad;
+            const u64 pm = bfq_codec_member_len(p + 40 + symLen, avail - 40 - symLen);
+            if (bfq_codec_raw_len(p + 40 + symLen, pm) != n) throw bad;
+            m.len = 40 + symLen + pm; m.raw = n; m.reads = N; m.ebwt = true;
+        } else {
+            m.len = bfq_codec_member_len(p, avail);
+            m.raw = bfq_codec_raw_len(p, m.len);
+            if (!memcmp(p, "BFQNAME1", 8)) {
+                const u64 x = bfq_names_decode_extra(p, m.len, maxMember);
+                if (nameExtra && x > *nameExtra) *nameExtra = x;
+            }
+            if (m.len >= 72 && !memcmp(p, "BFQDNAC1", 8) && rs_get64(p + 16) <= m.raw) m.reads = rs_get64(p + 16);
+        }
+    } catch (const BfqError &e) {
+        char b[96];
+        snprintf(b, sizeof b, ": not a container at byte %llu (", (unsigned long long)pos);
+        throw BfqError{BFQ_E_ARG, std::string(what) + b + e.msg + ")"};
+    }
+    if (!m.len || m.raw > (1ull << 46)) throw BfqError{BFQ_E_ARG, std::string(what) + ": not a container (raw length)"};
+    if (m.raw > *maxMember) *maxMember = m.raw;
+    return m;
+}
+
+// a group of the plan: what the caller sees, and what sizes its share of the arena
+struct RsGroup {
+    bfq_restore_group g;
+    u64 nD = 0, nQ = 0;                     // members
+    bool ebwt = false;
+    u64 maxMember = 0, hdrMember = 0, nameExtra = 0;   // as in RsPlan, for this group
+    RsPlan plan(bool haveHdr) const
+    {
+        RsPlan P;
+        P.ebwt = ebwt; P.rawD = P.rawQ = g.raw_stream; P.rawH = g.raw_hdr;
+        P.maxMember = maxMember; P.hdrMember = hdrMember; P.nameExtra = nameExtra;
+        const u64 byBytes = g.raw_stream + 1;
+        P.readsBound = g.reads != ~0ull && g.reads < byBytes ? g.reads + 1 : byBytes;
+        P.textBound = g.text_bound;
+        return P;
+    }
+};
+
+static u64 rs_rest(const RsSrc &s, u64 pos, const char *what)          // raw bytes of the members from `pos` on
+{
+    u64 raw = 0, mm = 0;
+    while (pos < s.len) { const RsMember m = rs_member(s, pos, what, &mm, nullptr); raw += m.raw; pos += m.len; }
+    return raw;
+}
+
+static std::vector<RsGroup> rs_groups(const RsSrc &dna, const RsSrc &qs, const RsSrc &hdr, bool haveHdr)
+{
+    if (!dna.h || !qs.h) throw BfqError{BFQ_E_ARG, "null argument"};
+    for (const auto &pr : {std::make_pair(&dna, "dna"), std::make_pair(&qs, "qs"), std::make_pair(&hdr, "hdr")})
+        if ((pr.first != &hdr || haveHdr) && (!pr.first->h || !pr.first->len))
+            throw BfqError{BFQ_E_ARG, std::string(pr.second) + ": not a container (empty input)"};
+    std::vector<RsGroup> G;
+    u64 pD = 0, pQ = 0, totD = 0, totQ = 0;
+    auto unequal = [&]() {
+        char b[200];
+        snprintf(b, sizeof b, "the DNA members decode to %llu bytes, the quality members to %llu: not of the same collection",
+                 (unsigned long long)(totD + rs_rest(dna, pD, "dna")), (unsigned long long)(totQ + rs_rest(qs, pQ, "qs")));
+        return BfqError{BFQ_E_ARG, b};
+    };
+    while (pD < dna.len || pQ < qs.len) {
+        RsGroup r;
+        memset(&r.g, 0, sizeof r.g);
+        r.g.dna_off = pD; r.g.qs_off = pQ;
+        u64 rawD = 0, rawQ = 0, reads = 0;
+        auto takeD = [&]() {
+            if (pD >= dna.len) throw unequal();
+            const RsMember m = rs_member(dna, pD, "dna", &r.maxMember, &r.nameExtra);
+            pD += m.len; rawD += m.raw; totD += m.raw; r.nD++;
+            r.ebwt = r.ebwt || m.ebwt;
+            reads = (reads == ~0ull || m.reads == ~0ull) ? ~0ull : reads + m.reads;
+        };
+        auto takeQ = [&]() {
+            if (pQ >= qs.len) throw unequal();
+            const RsMember m = rs_member(qs, pQ, "qs", &r.maxMember, &r.nameExtra);
+            if (m.ebwt) throw BfqError{BFQ_E_ARG, "qs: a BFQEBWT1 member in the quality input"};
+            pQ += m.len; rawQ += m.raw; totQ += m.raw; r.nQ++;
+        };
+        takeD(); takeQ();
+        while (rawD != rawQ) { if (rawD < rawQ) takeD(); else takeQ(); }
+        if (r.ebwt && (r.nD != 1 || r.nQ != 1)) {
+            char b[200];
+            snprintf(b, sizeof b, "group %llu: one DNA member and one quality member of the same raw length expected where the DNA member is a BFQEBWT1",
+                     (unsigned long long)G.size());
+            throw BfqError{BFQ_E_ARG, b};
+        }
+        r.g.dna_len = pD - r.g.dna_off; r.g.qs_len = pQ - r.g.qs_off;
+        r.g.raw_stream = rawD; r.g.reads = reads;
+        G.push_back(r);
+    }
+    if (haveHdr) {
+        u64 pH = 0, k = 0;
+        while (pH < hdr.len) {
+            RsGroup scratch;
+            RsGroup &r = k < G.size() ? G[k] : scratch;
+            const RsMember m = rs_member(hdr, pH, "hdr", &r.hdrMember, &r.nameExtra);
+            if (m.ebwt) throw BfqError{BFQ_E_ARG, "hdr: a BFQEBWT1 member in the header input"};
+            if (k < G.size()) { r.g.hdr_off = pH; r.g.hdr_len = m.len; r.g.raw_hdr = m.raw; if (!r.ebwt) r.maxMember = std::max(r.maxMember, r.hdrMember); }
+            pH += m.len; k++;
+        }
+        if (k != G.size()) {
+            char b[240];
+            snprintf(b, sizeof b, "hdr: %llu header members for %llu groups of DNA and quality members: the header stream was not cut with the blocks; "
+                                  "restore the archive in one piece", (unsigned long long)k, (unsigned long long)G.size());
+            throw BfqError{BFQ_E_ARG, b};
+        }
+    }
+    for (auto &r : G) {                                           // the bound of rs_plan, group by group
+        const u64 byBytes = r.g.raw_stream + 1;
+        const u64 rb = r.g.reads != ~0ull && r.g.reads < byBytes ? r.g.reads + 1 : byBytes;
+        r.g.text_bound = 2 * r.g.raw_stream + 2 + 2 * rb + (haveHdr ? r.g.raw_hdr + 1 : 2 * rb);
+    }
+    return G;
+}
+
+extern "C" int64_t bfq_fastq_restore_groups(const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                            const uint8_t *h_hdr, uint64_t hdr_len, bfq_restore_group *groups, uint64_t cap,
+                                            char *why, int why_cap)
+{
+    if (why && why_cap > 0) why[0] = 0;
+    try {
+        const std::vector<RsGroup> G = rs_groups(RsSrc{h_dna, dna_len}, RsSrc{h_qs, qs_len}, RsSrc{h_hdr, hdr_len}, h_hdr != nullptr);
+        for (u64 k = 0; groups && k < G.size() && k < cap; k++) groups[k] = G[k].g;
+        return (int64_t)G.size();
+    } catch (const BfqError &e) {
+        if (why && why_cap > 0) snprintf(why, (size_t)why_cap, "%s", e.msg.c_str());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        if (why && why_cap > 0) snprintf(why, (size_t)why_cap, "host out of memory");
+        return BFQ_E_NOMEM;
+    }
+}
+
+extern "C" int64_t bfq_stream_members(const uint8_t *h_in, uint64_t len)
+{
+    try {
+        int64_t k = 0;
+        u64 mm = 0;
+        const RsSrc s{h_in, len};
+        for (u64 pos = 0; h_in && pos < len; k++) pos += rs_member(s, pos, "stream", &mm, nullptr).len;
+        return k;
+    } catch (const BfqError &) { return -1; }
+}
+
 // all members of `s` into d_out (raw bytes in all); d_z: room for the compressed bytes
 static void rs_decode(bfq_ctx *c, const RsSrc &s, u8 *d_z, u8 *d_out, u64 raw)
 {
@@ -185,6 +351,30 @@ static size_t rs_index_bytes(const RsPlan &P, bool ordered)
     // line ends of three streams, roff, hStart, hLen, sizes, recOff per read; chunk counts of the line index and of the scans;
     // ordered: the container's payload, the unpacked permutation, its inverse (8 bytes each) and the sizes in output order
     return (ordered ? 64 + 32 : 64) * (size_t)(P.readsBound + 64) + 3 * 32 * (size_t)((std::max(P.rawD, std::max(P.rawQ, P.rawH)) >> 12) + 64) + (1u << 20);
+}
+
+// what k_restore_index found, as the error of the call.  base: reads before the first one of these streams (a group of an
+// archive), where: what to add to the sentence (the group)
+static BfqError rs_read_error(u64 err, u64 nD, u64 nQ, u64 nH, u64 N, u64 base, const char *where)
+{
+    const unsigned long long i = base + (err >> 3);
+    char b[320];
+    switch ((u32)(err & 7)) {
+    case RS_LEN:
+        snprintf(b, sizeof b, "read %llu%s: its DNA line and its quality line differ in length (streams of different collections?)", i, where);
+        break;
+    case RS_LONG:
+        snprintf(b, sizeof b, "read %llu%s: line longer than BFQ_MAX_READ_LEN (%d)", i, where, BFQ_MAX_READ_LEN);
+        break;
+    case RS_COUNT:
+        snprintf(b, sizeof b, "read %llu%s has no partner: the DNA stream has %llu lines, the quality stream %llu", i, where, (unsigned long long)nD,
+                 (unsigned long long)nQ);
+        break;
+    default:
+        snprintf(b, sizeof b, "read %llu%s: the header stream has %llu lines for %llu reads", i, where, (unsigned long long)nH, (unsigned long long)N);
+        break;
+    }
+    return BfqError{BFQ_E_ARG, b};
 }
 
 // sink: where the text goes once it is known to be good.  put(d_text, len) is called at most once.
@@ -254,26 +444,7 @@ static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const Rs
     HIP_CHECK(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipMemcpyAsync(&ol, recOff + N, 8, hipMemcpyDeviceToHost, c->stream));
     c->sync();
-    if (err != RS_NONE) {
-        const unsigned long long i = err >> 3;
-        char b[256];
-        switch ((u32)(err & 7)) {
-        case RS_LEN:
-            snprintf(b, sizeof b, "read %llu: its DNA line and its quality line differ in length (streams of different collections?)", i);
-            break;
-        case RS_LONG:
-            snprintf(b, sizeof b, "read %llu: line longer than BFQ_MAX_READ_LEN (%d)", i, BFQ_MAX_READ_LEN);
-            break;
-        case RS_COUNT:
-            snprintf(b, sizeof b, "read %llu has no partner: the DNA stream has %llu lines, the quality stream %llu", i, (unsigned long long)nD,
-                     (unsigned long long)nQ);
-            break;
-        default:
-            snprintf(b, sizeof b, "read %llu: the header stream has %llu lines for %llu reads", i, (unsigned long long)nH, (unsigned long long)N);
-            break;
-        }
-        throw BfqError{BFQ_E_ARG, b};
-    }
+    if (err != RS_NONE) throw rs_read_error(err, nD, nQ, nH, N, 0, "");
     const u64 *inv = nullptr;
     if (permz) {
         u64 PN = 0;
@@ -416,4 +587,257 @@ extern "C" int bfq_fastq_restore_ordered_fd(bfq_ctx *c, int dna_fd, uint64_t dna
                                             int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads)
 {
     return rs_run_fd(c, dna_fd, dna_len, qs_fd, qs_len, hdr_fd, hdr_len, true, perm_fd, permz_len, out_fd, out_len, n_reads);
+}
+
+// ---- the grouped restore ------------------------------------------------------------------------------------------------
+// where the texts of the groups go.  put(d_text, off, len, buf): the bytes of text buffer `buf` to offset `off` of the output,
+// in the background where the destination allows it; wait(buf): the transfer that last read that buffer is over.
+struct RsGroupSink {
+    u64 cap = ~0ull;
+    std::function<void(u64)> sized;                 // the output is known to reach this far (before the group is formatted)
+    std::function<void(const u8 *, u64, u64, int)> put;
+    std::function<void(int)> wait;
+};
+
+// arena bytes of one group beside the two text buffers: its decoded streams, then its compressed members and the codec's
+// workspace or its index, whichever is larger (the eBWT-domain form: what the walk reserves)
+static size_t rs_group_need(const RsGroup &r, const RsSrc &dna, bool haveHdr)
+{
+    const RsPlan P = r.plan(haveHdr);
+    const size_t afterDecode = rs_index_bytes(P, false) + 4096;
+    if (r.ebwt) {
+        const size_t hdrPart = haveHdr ? P.rawH + r.g.hdr_len + bfq_codec_workspace(std::max(P.rawH, P.hdrMember)) + P.nameExtra + 8192 : 0;
+        return r.g.raw_stream ? bfq_ebwt_decode_need(dna.h + r.g.dna_off, r.g.dna_len, r.g.qs_len, afterDecode + hdrPart + 4096, true) : afterDecode + hdrPart + 8192;
+    }
+    const size_t streams = (size_t)2 * r.g.raw_stream + r.g.raw_hdr + 3 * 320;
+    const size_t decode = (size_t)r.g.dna_len + r.g.qs_len + r.g.hdr_len + 3 * 320 + bfq_codec_workspace(P.maxMember) + P.nameExtra;
+    return streams + std::max(decode, afterDecode);
+}
+
+static void restore_grouped_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const RsSrc &hdr, bool haveHdr, const std::vector<RsGroup> &G,
+                                 u64 first, u64 count, const RsGroupSink &sink, uint64_t *out_len, uint64_t *n_reads)
+{
+    if (out_len) *out_len = 0;
+    if (n_reads) *n_reads = 0;
+    const u64 end = first + count;
+    // one reservation, from the largest group of the range
+    size_t needMax = 0, textMax = 0, worst = 0;
+    u64 worstK = first;
+    for (u64 k = first; k < end; k++) {
+        const size_t need = rs_group_need(G[k], dna, haveHdr), text = (size_t)G[k].g.text_bound + 4096;
+        needMax = std::max(needMax, need); textMax = std::max(textMax, text);
+        if (need + 2 * text > worst) { worst = need + 2 * text; worstK = k; }
+    }
+    bfq_phase("alloc");
+    try { c->reserve(needMax + 2 * textMax + (64u << 20)); }
+    catch (const BfqError &e) {
+        if (e.code != BFQ_E_NOMEM) throw;
+        char b[160];
+        snprintf(b, sizeof b, " (sized by group %llu, the largest of groups %llu..%llu)", (unsigned long long)worstK, (unsigned long long)first,
+                 (unsigned long long)(end - 1));
+        throw BfqError{BFQ_E_NOMEM, e.msg + b};
+    }
+    c->call.arenaHeld = true;
+    u8 *text[2] = {c->alloc<u8>(textMax), c->alloc<u8>(textMax)};
+    const size_t base = c->mark();
+    // reads before the range: known where every earlier DNA member states them
+    u64 readsBefore = 0;
+    bool baseKnown = true;
+    for (u64 k = 0; k < first; k++) { if (G[k].g.reads == ~0ull) baseKnown = false; else readsBefore += G[k].g.reads; }
+    u64 off = 0, reads = 0;
+    for (u64 k = first; k < end; k++) {
+        const RsGroup &r = G[k];
+        const int buf = (int)((k - first) & 1);
+        const RsSrc gD{dna.h + r.g.dna_off, r.g.dna_len}, gQ{qs.h + r.g.qs_off, r.g.qs_len};
+        const RsSrc gH{haveHdr ? hdr.h + r.g.hdr_off : nullptr, haveHdr ? r.g.hdr_len : 0};
+        const u64 raw = r.g.raw_stream, rawH = r.g.raw_hdr;
+        c->release(base);
+        u8 *dD = nullptr, *dQ = nullptr, *dH = nullptr;
+        if (r.ebwt) {
+            EbwtLines e;
+            bfq_phase("gpu");
+            bfq_ebwt_decode_lines(c, gD.h, gD.len, gQ.h, gQ.len, nullptr, nullptr, ~0ull, nullptr, nullptr, 0, &e);
+            if (!e.n) { e.dna = c->alloc<u8>(64); e.qs = c->alloc<u8>(64); }
+            dD = e.dna; dQ = e.qs;
+            if (haveHdr) {
+                dH = c->alloc<u8>(rawH + 64);
+                const size_t mk = c->mark();
+                rs_decode(c, gH, c->alloc<u8>(gH.len + 64), dH, rawH);
+                c->release(mk);
+            }
+        } else {
+            c->zeroCounters();
+            dD = c->alloc<u8>(raw + 64); dQ = c->alloc<u8>(raw + 64);
+            if (haveHdr) dH = c->alloc<u8>(rawH + 64);
+            const size_t mk = c->mark();
+            u8 *zD = c->alloc<u8>(gD.len + 64), *zQ = c->alloc<u8>(gQ.len + 64), *zH = haveHdr ? c->alloc<u8>(gH.len + 64) : nullptr;
+            bfq_phase("read_h2d");
+            rs_decode(c, gD, zD, dD, raw);
+            bfq_phase("gpu");
+            rs_decode(c, gQ, zQ, dQ, raw);
+            if (haveHdr) rs_decode(c, gH, zH, dH, rawH);
+            c->release(mk);
+        }
+        bfq_phase("gpu");
+        u64 nD = 0, nQ = 0, nH = 0;
+        const u64 *endD = bfq_line_index(c, dD, raw, &nD);
+        const u64 *endQ = bfq_line_index(c, dQ, raw, &nQ);
+        const u64 *endH = haveHdr ? bfq_line_index(c, dH, rawH, &nH) : nullptr;
+        const u64 N = std::min(nD, nQ);
+        u64 *roff = c->alloc<u64>(N + 2), *recOff = c->alloc<u64>(N + 2);
+        u64 *hStart = haveHdr ? c->alloc<u64>(N + 1) : nullptr;
+        u32 *hLen = haveHdr ? c->alloc<u32>(N + 1) : nullptr, *sizes = c->alloc<u32>(N + 1);
+        unsigned long long *d_err = (unsigned long long *)c->alloc<u64>(1);
+        HIP_CHECK(hipMemsetAsync(d_err, 0xFF, 8, c->stream));
+        KLAUNCH(c, K_RESTORE, (haveHdr ? 48.0 : 28.0) * (double)N, k_restore_index, bfq_grid(N ? N : 1, 256), 256, endD, nD, endQ, nQ, endH, nH,
+                haveHdr ? 1 : 0, roff, hStart, hLen, sizes, d_err);
+        bfq_exscan_u32(c, sizes, recOff, N, recOff + N);
+        u64 err = RS_NONE, ol = 0;
+        // the last byte of every stream of a group inside the archive: a line end, or a read was cut in two
+        u8 last[3] = {'\n', '\n', '\n'};
+        const bool inside = k + 1 < G.size();
+        HIP_CHECK(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipMemcpyAsync(&ol, recOff + N, 8, hipMemcpyDeviceToHost, c->stream));
+        if (inside && raw) {
+            HIP_CHECK(hipMemcpyAsync(&last[0], dD + raw - 1, 1, hipMemcpyDeviceToHost, c->stream));
+            HIP_CHECK(hipMemcpyAsync(&last[1], dQ + raw - 1, 1, hipMemcpyDeviceToHost, c->stream));
+        }
+        if (inside && haveHdr && rawH) HIP_CHECK(hipMemcpyAsync(&last[2], dH + rawH - 1, 1, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        c->profCollect();
+        for (int q = 0; q < 3; q++)
+            if (last[q] != '\n') {
+                char b[320];
+                snprintf(b, sizeof b, "group %llu: its %s stream does not end with a line end: the members were not cut at reads; restore the archive in one piece",
+                         (unsigned long long)k, q == 0 ? "DNA" : q == 1 ? "quality" : "header");
+                throw BfqError{BFQ_E_ARG, b};
+            }
+        if (err != RS_NONE) {
+            char w[96];
+            if (baseKnown) snprintf(w, sizeof w, " (read %llu of group %llu)", (unsigned long long)(err >> 3), (unsigned long long)k);
+            else snprintf(w, sizeof w, " of group %llu", (unsigned long long)k);
+            throw rs_read_error(err, nD, nQ, nH, N, baseKnown ? readsBefore + reads : 0, w);
+        }
+        if (ol > (u64)G[k].g.text_bound) throw BfqError{BFQ_E_ARG, "damaged container (a group holds more reads than its DNA members state)"};
+        if (off + ol > sink.cap) throw BfqError{BFQ_E_ARG, "output buffer smaller than the FASTQ text (see bfq_fastq_restore_groups: the sum of text_bound)"};
+        if (sink.sized) sink.sized(off + ol);
+        sink.wait(buf);                                          // the transfer of two groups ago read this buffer
+        bfq_fastq_format_lines(c, dD, dQ, roff, dH, hStart, hLen, recOff, N, ol, text[buf]);
+        sink.put(text[buf], off, ol, buf);
+        off += ol; reads += N;
+    }
+    sink.wait(0); sink.wait(1);
+    c->sync();
+    c->profCollect();
+    if (out_len) *out_len = off;
+    if (n_reads) *n_reads = reads;
+}
+
+// the range [first, first + count) inside a plan of G groups; count ~0: to the end
+static void rs_range(u64 G, u64 first, uint64_t *count)
+{
+    if (first >= G || (*count != ~0ull && (*count > G || first + *count > G))) {
+        char b[200];
+        snprintf(b, sizeof b, "groups %llu.. (count %lld) are outside the plan of %llu groups", (unsigned long long)first, (long long)*count, (unsigned long long)G);
+        throw BfqError{BFQ_E_ARG, b};
+    }
+    if (*count == ~0ull) *count = G - first;
+}
+
+extern "C" int bfq_fastq_restore_grouped(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                         const uint8_t *h_hdr, uint64_t hdr_len, uint64_t first, uint64_t count, uint8_t *h_out,
+                                         uint64_t cap, uint64_t *out_len, uint64_t *n_reads)
+{
+    if (out_len) *out_len = 0;
+    if (n_reads) *n_reads = 0;
+    return guarded(c, [&] {
+        if (!h_dna || !h_qs || (!h_out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
+        const RsSrc dna{h_dna, dna_len}, qs{h_qs, qs_len}, hdr{h_hdr, hdr_len};
+        const std::vector<RsGroup> G = rs_groups(dna, qs, hdr, h_hdr != nullptr);
+        rs_range(G.size(), first, &count);
+        // a pinned destination: direct DMA on the copy stream, behind the formatting kernel; each buffer has the event of the
+        // copy that last read it
+        const bool pinned = h_out && bfq_is_pinned(h_out);
+        ScopedEvent formatted, copied[2];
+        bool used[2] = {false, false};
+        RsGroupSink sink;
+        sink.cap = cap;
+        sink.put = [&](const u8 *d_text, u64 off, u64 len, int buf) {
+            bfq_phase("d2h_write");
+            if (pinned) {
+                if (!len) return;
+                HIP_CHECK(hipEventRecord(formatted, c->stream));
+                HIP_CHECK(hipStreamWaitEvent(c->copy(), formatted, 0));
+                HIP_CHECK(hipMemcpyAsync(h_out + off, d_text, len, hipMemcpyDeviceToHost, c->copy()));
+                HIP_CHECK(hipEventRecord(copied[buf], c->copy()));
+                used[buf] = true;
+            } else {
+                bfq_download(c, h_out + off, d_text, len);      // pageable: in place when this returns (small pieces: queued on the stream)
+                c->sync();
+            }
+        };
+        sink.wait = [&](int buf) {
+            if (used[buf]) HIP_CHECK(hipEventSynchronize(copied[buf]));
+            used[buf] = false;
+        };
+        try { restore_grouped_core(c, dna, qs, hdr, h_hdr != nullptr, G, first, count, sink, out_len, n_reads); }
+        catch (...) {
+            if (c->copyStream) (void)hipStreamSynchronize(c->copyStream);   // the events go with this frame
+            if (out_len) *out_len = 0;
+            if (n_reads) *n_reads = 0;
+            throw;
+        }
+    });
+}
+
+extern "C" int bfq_fastq_restore_grouped_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                            uint64_t first, uint64_t count, int out_fd, uint64_t *out_len, uint64_t *n_reads)
+{
+    if (out_len) *out_len = 0;
+    if (n_reads) *n_reads = 0;
+    return guarded(c, [&] {
+        if (dna_fd < 0 || qs_fd < 0 || out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
+        const bool haveHdr = hdr_fd >= 0;
+        RsMap mD, mQ, mH;
+        const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
+        const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
+        OutFile of;
+        bool opened = false;
+        try {
+            const std::vector<RsGroup> G = rs_groups(dna, qs, hdr, haveHdr);
+            rs_range(G.size(), first, &count);
+            u64 bound = 0, certain = 0;
+            for (u64 k = first; k < first + count; k++) { bound += G[k].g.text_bound; certain += 2 * G[k].g.raw_stream; }
+            of.open(out_fd, bound + 4096, certain);
+            opened = true;
+            c->call.writeHint = (size_t)bound;
+            RsGroupSink sink;
+            sink.sized = [&](u64 len) {
+                if (of.m && len > bfq_outmap_len(of.m)) throw BfqError{BFQ_E_IO, "output mapping smaller than the FASTQ text"};
+                if (of.m) bfq_outmap_extend(of.m, len);
+            };
+            // the background writers know one wait, for everything queued: it is made before a text is queued, so that the
+            // text before it travels beside the decoding, the index and the formatting of this one
+            sink.put = [&](const u8 *d_text, u64 off, u64 len, int) {
+                bfq_phase("d2h_write");
+                bfq_write_wait(c);
+                bfq_write_async(c, of.at(off), d_text, len);
+            };
+            sink.wait = [&](int) {};
+            uint64_t ol = 0;
+            restore_grouped_core(c, dna, qs, hdr, haveHdr, G, first, count, sink, &ol, n_reads);
+            bfq_phase("d2h_write");
+            bfq_write_wait(c);
+            if (out_len) *out_len = ol;
+            opened = false;
+            if (!of.close(ol)) throw BfqError{BFQ_E_IO, "cannot size the output file"};
+        } catch (...) {
+            if (opened) { try { bfq_write_wait(c); } catch (...) {} }
+            else { of.fd = out_fd; of.m = bfq_outmap_take(out_fd, 0); }   // (a mapping the caller registered goes with the file's contents)
+            of.close(0);
+            if (out_len) *out_len = 0;
+            if (n_reads) *n_reads = 0;
+            throw;
+        }
+    });
 }

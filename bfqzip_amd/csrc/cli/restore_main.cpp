@@ -1,53 +1,122 @@
 // restore_main.cpp -- the way back from the compressed streams to a FASTQ file (not a tool of the reference, which leaves
 // this to `7z x` / `bsc d` + `paste`):
-//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM] -o OUT.fq [-V]
+//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] -o OUT.fq [-V]
 // The inputs are what `bsc e`, bfq_fastq_job.compress_streams = 1 / 2 / 3 and parallel.py --compress write
 // (include/bfqzip_hip.h, bfq_fastq_restore_fd).  -P PERM: the BFQPERM1 file `bfq_reorder -P` / `parallel.py --keep-order`
-// wrote for the run: the records come back in the order of the original file (bfq_fastq_restore_ordered_fd).  Exit status 0 on success; 1 with the library's message otherwise, and then
+// wrote for the run: the records come back in the order of the original file (bfq_fastq_restore_ordered_fd).
+// -g: block by block (bfq_fastq_restore_grouped_fd): the members of the inputs are cut into groups that decode on their own
+// -- one per block of a sharded run -- and the device holds one group at a time, so the archive may be larger than the
+// device; several BFQEBWT1 members are taken.  -G FIRST[:COUNT]: only those groups.  -l: the plan of the groups, one line
+// each, and nothing else: no GPU is touched and no output is created.  -g / -G with -P is a usage error: records in the
+// original order draw on all groups at once.  Exit status 0 on success; 1 with the library's message otherwise, and then
 // OUT.fq is left empty.
 #include <unistd.h>
 #include <sys/mman.h>
+#include <vector>
 #include "cli_common.h"
 
 static int usage(const char *argv0)
 {
-    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM] -o OUT.fq [-V]\n"
+    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] -o OUT.fq [-V]\n"
                     "  -d <arg>  container(s) of the DNA stream (OUT.fq.dna; BFQDNAC1 / BFQRANS2 members, or one BFQEBWT1) (REQUIRED)\n"
                     "  -q <arg>  container(s) of the quality stream (OUT.fq.qs) (REQUIRED)\n"
                     "  -H <arg>  container(s) of the header stream (OUT.h); without it every header line is \"@\"\n"
                     "  -P <arg>  BFQPERM1 file of the reordering the collection went through: the text in the order before it\n"
+                    "  -g        block by block: one group of members (a block of a sharded run) on the device at a time\n"
+                    "  -G <arg>  FIRST[:COUNT]: only these groups of the plan (COUNT omitted: to the end)\n"
+                    "  -l        print the plan of the groups and exit (no GPU, no output file; -o not needed)\n"
                     "  -o <arg>  output FASTQ (REQUIRED)\n"
                     "  -V        phase timeline on stderr\n", argv0);
     return 1;
+}
+
+// -l: index, members of the three inputs, compressed bytes, raw bytes, reads (? where a DNA member states none), text bound
+static int list_groups(const InFile &fd, const InFile &fq, const InFile *fh)
+{
+    auto map = [](const InFile &f) { return f.size ? mmap(nullptr, f.size, PROT_READ, MAP_PRIVATE, f.fd, 0) : MAP_FAILED; };
+    void *md = map(fd), *mq = map(fq), *mh = fh ? map(*fh) : MAP_FAILED;
+    const uint8_t *pd = md != MAP_FAILED ? (const uint8_t *)md : nullptr, *pq = mq != MAP_FAILED ? (const uint8_t *)mq : nullptr;
+    const uint8_t *ph = mh != MAP_FAILED ? (const uint8_t *)mh : nullptr;
+    static const uint8_t none = 0;
+    if (!pd) pd = &none;                                                   // (an empty file: the library says so)
+    if (!pq) pq = &none;
+    if (fh && !ph) ph = &none;
+    char why[512];
+    int64_t G = bfq_fastq_restore_groups(pd, fd.size, pq, fq.size, ph, fh ? fh->size : 0, nullptr, 0, why, (int)sizeof why);
+    std::vector<bfq_restore_group> g((size_t)(G > 0 ? G : 0));
+    if (G > 0) G = bfq_fastq_restore_groups(pd, fd.size, pq, fq.size, ph, fh ? fh->size : 0, g.data(), (uint64_t)G, why, (int)sizeof why);
+    if (G < 0) { fprintf(stderr, "bfq_restore: %s\n", why); return 1; }
+    printf("# group  members(dna qs hdr)  compressed  raw  reads  text_bound\n");
+    for (int64_t k = 0; k < G; k++) {
+        const bfq_restore_group &r = g[(size_t)k];
+        char reads[32];
+        if (r.reads == ~0ull) snprintf(reads, sizeof reads, "?");
+        else snprintf(reads, sizeof reads, "%llu", (unsigned long long)r.reads);
+        printf("%lld  %lld %lld %lld  %llu  %llu  %s  %llu\n", (long long)k, (long long)bfq_stream_members(pd + r.dna_off, r.dna_len),
+               (long long)bfq_stream_members(pq + r.qs_off, r.qs_len), (long long)(ph ? bfq_stream_members(ph + r.hdr_off, r.hdr_len) : 0),
+               (unsigned long long)(r.dna_len + r.qs_len + r.hdr_len), (unsigned long long)(2 * r.raw_stream + r.raw_hdr), reads,
+               (unsigned long long)r.text_bound);
+    }
+    printf("%lld groups\n", (long long)G);
+    return 0;
 }
 
 int main(int argc, char **argv)
 {
     bfq_phase("start");
     std::string dna, qs, hdr, perm, output;
+    bool grouped = false, list = false;
+    uint64_t first = 0, count = ~0ull;
     int opt;
-    while ((opt = getopt(argc, argv, "d:q:H:P:o:Vh")) != -1) {
+    while ((opt = getopt(argc, argv, "d:q:H:P:o:gG:lVh")) != -1) {
         switch (opt) {
         case 'd': dna = optarg; break;
         case 'q': qs = optarg; break;
         case 'H': hdr = optarg; break;
         case 'P': perm = optarg; break;
         case 'o': output = optarg; break;
+        case 'g': grouped = true; break;
+        case 'G': {
+            char *e = nullptr;
+            grouped = true;
+            first = strtoull(optarg, &e, 10);
+            if (e == optarg || (*e && *e != ':')) return usage(argv[0]);
+            if (*e == ':') { const char *q = e + 1; count = strtoull(q, &e, 10); if (e == q || *e) return usage(argv[0]); }
+            break;
+        }
+        case 'l': list = true; break;
         case 'V': bfq_phase_enable(1); break;
         default: return usage(argv[0]);
         }
     }
-    if (dna.empty() || qs.empty() || output.empty()) return usage(argv[0]);
+    if (dna.empty() || qs.empty() || (output.empty() && !list)) return usage(argv[0]);
+    if ((grouped || list) && !perm.empty()) {
+        fprintf(stderr, "bfq_restore: -g / -G / -l do not go with the permutation -P %s: records in the original order draw on all groups at once; "
+                        "restore the archive in one piece (without -g)\n", perm.c_str());
+        return usage(argv[0]);
+    }
     InFile fd, fq, fh, fp;
     if (!fd.open(dna) || !fq.open(qs) || (!hdr.empty() && !fh.open(hdr)) || (!perm.empty() && !fp.open(perm))) { fprintf(stderr, "bfq_restore: cannot read the inputs\n"); return 1; }
+    if (list) return list_groups(fd, fq, hdr.empty() ? nullptr : &fh);
     OutFile outText;
     if (!outText.open(output)) { perror("bfq_restore"); return 1; }
     {   // the bound of the text from the container headers: the output's pages are prepared while the GPU starts up
         auto map = [](const InFile &f) { return f.size ? mmap(nullptr, f.size, PROT_READ, MAP_PRIVATE, f.fd, 0) : MAP_FAILED; };
         void *md = map(fd), *mq = map(fq), *mh = hdr.empty() ? MAP_FAILED : map(fh);
         int64_t bound = -1;
-        if (md != MAP_FAILED && mq != MAP_FAILED && (hdr.empty() || mh != MAP_FAILED))
-            bound = bfq_fastq_restore_bound((const uint8_t *)md, fd.size, (const uint8_t *)mq, fq.size, hdr.empty() ? nullptr : (const uint8_t *)mh, fh.size);
+        if (md != MAP_FAILED && mq != MAP_FAILED && (hdr.empty() || mh != MAP_FAILED)) {
+            if (!grouped)
+                bound = bfq_fastq_restore_bound((const uint8_t *)md, fd.size, (const uint8_t *)mq, fq.size, hdr.empty() ? nullptr : (const uint8_t *)mh, fh.size);
+            else {                                                         // the plan's text bounds over the range; what is wrong with it the library says below
+                const int64_t G = bfq_fastq_restore_groups((const uint8_t *)md, fd.size, (const uint8_t *)mq, fq.size,
+                                                           hdr.empty() ? nullptr : (const uint8_t *)mh, fh.size, nullptr, 0, nullptr, 0);
+                std::vector<bfq_restore_group> g((size_t)(G > 0 ? G : 0));
+                if (G > 0) (void)bfq_fastq_restore_groups((const uint8_t *)md, fd.size, (const uint8_t *)mq, fq.size,
+                                                          hdr.empty() ? nullptr : (const uint8_t *)mh, fh.size, g.data(), (uint64_t)G, nullptr, 0);
+                bound = 0;
+                for (uint64_t k = first; k < (uint64_t)(G > 0 ? G : 0) && k - first < count; k++) bound += (int64_t)g[(size_t)k].text_bound;
+            }
+        }
         if (md != MAP_FAILED) munmap(md, fd.size);
         if (mq != MAP_FAILED) munmap(mq, fq.size);
         if (mh != MAP_FAILED) munmap(mh, fh.size);
@@ -59,7 +128,8 @@ int main(int argc, char **argv)
     bfq_ctx *c = create_on_free_gpu("bfq_restore", &P);
     if (!c) return 1;
     uint64_t outLen = 0, reads = 0;
-    const int rc = perm.empty() ? bfq_fastq_restore_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, outText.fd, &outLen, &reads)
+    const int rc = grouped ? bfq_fastq_restore_grouped_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, first, count, outText.fd, &outLen, &reads)
+                   : perm.empty() ? bfq_fastq_restore_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, outText.fd, &outLen, &reads)
                                 : bfq_fastq_restore_ordered_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, fp.fd, fp.size,
                                                                outText.fd, &outLen, &reads);
     if (rc) {

@@ -330,6 +330,44 @@ def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fas
     return tot
 
 
+def restore_files(eng, comm, dna_path, qs_path, hdr_path, out_path, log=None):
+    """The way back of run_files(.., compress=True) on as many GPUs as it was written with: the three .bsc files are mapped,
+    every rank computes the group plan from the container headers (eng.host.restore_groups: one group per block), group k
+    goes to rank k mod world (eng.fastq_restore(.., groups=(k, 1))), after every round the text lengths are all-gathered
+    (one integer per rank) and every rank writes its text at its final offset.  No payload collective, nothing per read on
+    the host.  hdr_path may be None ("@" lines).  The two mates of a paired run are two invocations.  Returns this rank's
+    totals {"groups", "reads", "bytes"} with "bytes_all" = the length of the whole text."""
+    host = eng.host
+    dna, qs = map_file(dna_path), map_file(qs_path)
+    hdr = map_file(hdr_path) if hdr_path is not None else None
+    plan = host.restore_groups(dna, qs, hdr)
+    if comm.rank == 0:
+        open(out_path, "wb").close()
+    comm.barrier()
+    fd = os.open(out_path, os.O_RDWR)
+    tot = {"groups": 0, "reads": 0, "bytes": 0}
+    cursor = 0
+    try:
+        rounds = (len(plan) + comm.world - 1) // comm.world
+        for rd in range(rounds):
+            k = rd * comm.world + comm.rank
+            text, n = None, 0
+            if k < len(plan):
+                text, n = eng.fastq_restore(dna, qs, hdr, groups=(k, 1))
+                tot["groups"] += 1; tot["reads"] += n; tot["bytes"] += len(text)
+                if log:
+                    log(f"group {k + 1}/{len(plan)}: {n} reads, {len(text)} bytes")
+            allsz = comm.all_gather_i64(np.array([len(text) if text is not None else 0], np.int64)).reshape(-1)
+            if text is not None and len(text):
+                pwrite_all(fd, text, cursor + int(allsz[:comm.rank].sum()), host)
+            cursor += int(allsz.sum())
+    finally:
+        os.close(fd)
+    comm.barrier()
+    tot["bytes_all"] = cursor
+    return tot
+
+
 def deal_piles(counts, world):
     """The two-symbol piles (first 1..5, second 1..5; a second symbol 0 = suffixes of one base: never in a cluster) dealt to
     the ranks, largest first to the least loaded rank: [[(s, s2), ...] per rank] -- the same list on every rank."""
@@ -519,7 +557,9 @@ def main(argv=None):
     The multi-GPU counterpart of `BFQzip_parallel.py in.fastq [in2.fastq -p] -o OUT -t n -0` (same flags, same
     block split, same output names: OUT<ext> or OUT_1<ext> / OUT_2<ext>), one block per GPU at a time.  --m2 / --m3
     additionally write the streams BFQzip.py cuts with sed (<fastq>.dna, <fastq>.qs; --m3: OUT.h and header lines
-    kept).  Without torchrun it runs all blocks on GPU 0."""
+    kept).  Without torchrun it runs all blocks on GPU 0.
+    `... -m bfqzip_amd.parallel --restore DNA.bsc QS.bsc [HDR.bsc] -o OUT.fq` is the way back of a --compress run
+    (restore_files)."""
     import argparse
     import torch
     from . import api
@@ -554,8 +594,14 @@ def main(argv=None):
                          "FASTQ text back in input order (streams and --compress containers stay in run order: bfq_restore -P)")
     ap.add_argument("--reorder-k", type=int, default=21, help="k-mer length of --reorder 2 (8..32)")
     ap.add_argument("--seed", type=int, default=0, help="seed of --reorder 1")
+    ap.add_argument("--restore", action="store_true",
+                    help="the way back: the inputs are DNA.bsc QS.bsc [HDR.bsc] of a --compress run, -o OUT.fq the FASTQ file to write; "
+                         "group k of the archive (one per block) is restored by rank k mod world")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.restore and (len(a.input) not in (2, 3) or not a.out):
+        print("=== ERROR ===\n--restore DNA.bsc QS.bsc [HDR.bsc] -o OUT.fq", file=sys.stderr)
+        return 1
     if a.paired and len(a.input) != 2:
         print("=== ERROR ===\npaired end mode", file=sys.stderr)
         return 1
@@ -583,6 +629,14 @@ def main(argv=None):
         par["v"] = ord(a.rv)
     eng = api.Engine(local, **par)
     log = (lambda m: print(f"[rank {comm.rank}] {m}", flush=True)) if a.v else None
+    if a.restore:
+        tot = restore_files(eng, comm, a.input[0], a.input[1], a.input[2] if len(a.input) == 3 else None, a.out, log=log)
+        if a.v:
+            print(f"[rank {comm.rank}] {tot}", flush=True)
+        eng.close()
+        if dist:
+            dist.destroy_process_group()
+        return 0
     perm_path = reordered_names(a.input[:1], a.reorder)[0] + ".perm" if (a.keep_order and a.reorder) else None
     keep = dict(perm_path=perm_path) if perm_path else {}
     a.input = reorder_inputs(eng, comm, a.input, a.reorder, k=a.reorder_k, seed=a.seed, paired=a.paired, log=log, **keep)

@@ -426,6 +426,51 @@ int bfq_fastq_restore(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const 
                       const uint8_t *h_hdr, uint64_t hdr_len, uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads);
 int bfq_fastq_restore_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len,
                          int hdr_fd, uint64_t hdr_len, int out_fd, uint64_t *out_len, uint64_t *n_reads);
+/* ---- the way back, block by block.  The members of one block of a sharded run (parallel.py --compress appends one container
+ * per block to every .bsc) decode independently of every other block: an archive is a sequence of GROUPS, and the grouped
+ * calls restore one group after another in an arena sized by the largest group instead of by the whole archive.
+ *   bfq_fastq_restore_groups: the plan.  Host only (no context, no GPU), reads the container headers and decodes nothing.
+ *     The DNA and the quality input are walked with one cursor each; a group takes one member of each and then further
+ *     members of whichever side has decoded to fewer bytes until both have decoded to the same number, and ends there (the
+ *     finest cut; a group of raw length 0 is a block of no reads).  A BFQEBWT1 member is one DNA member of `rows` raw bytes
+ *     with ONE quality member of the same raw length beside it.  A header input must have exactly one member per group.
+ *     Returns the number of groups G and fills min(G, cap) entries; a negative BFQ_E_* with the reason in `why` (why_cap
+ *     bytes, may be NULL) when the totals of the two inputs never meet ("not of the same collection"), bytes are no member,
+ *     an input is empty or the header members do not count G.
+ *   bfq_stream_members: number of members in [h_in, h_in + len) (a BFQEBWT1 member counts once); -1: bytes that are no member.
+ *   bfq_fastq_restore_grouped / _fd: groups [first, first + count) of the plan (count = ~0: to the end), their texts
+ *     concatenated from offset 0 of the output; for every archive both calls accept, (0, ~0) writes byte for byte what
+ *     bfq_fastq_restore writes, and the groups restored one at a time concatenate to the same bytes.  Several BFQEBWT1
+ *     members (the outputs of several compress_streams = 2 / 3 jobs back to back) are restored here, one per group.
+ *     Device memory, reserved once before the first group from the LARGEST group of the range: its decoded streams + two
+ *     text buffers of its text bound + the larger of (its compressed members + the codec's workspace for its largest
+ *     member) and its index + 64 MiB; above ws_cap_mib: BFQ_E_NOMEM naming that group and the cap.  The text of group g
+ *     leaves the device (background writers of the file form; direct DMA into a pinned h_out) while group g + 1 is decoded;
+ *     the two text buffers alternate.  Every group but the archive's last must end each of its non-empty decoded streams with
+ *     '\n' (a line index would otherwise give the cut line a newline of its own and split a read): else BFQ_E_ARG naming
+ *     the group and the stream.  A read the validator refuses is named by its index in the archive (the reads of the earlier
+ *     groups plus its index in the group -- when first > 0, where every earlier DNA member states its reads) and the group.
+ *     Whatever the plan can refuse (also: first >= G, first + count > G) is refused before a byte is written.  On any
+ *     failure *out_len = 0; the file form leaves out_fd empty; a MEMORY destination may have been written up to the failing
+ *     group.  No BFQPERM1 permutation here: records in the original order draw on all groups at once. */
+typedef struct bfq_restore_group {
+    uint64_t dna_off, dna_len;     /* this group's members inside the DNA input (bytes)        */
+    uint64_t qs_off,  qs_len;
+    uint64_t hdr_off, hdr_len;     /* 0, 0 without a header input                               */
+    uint64_t raw_stream;           /* decoded bytes of its DNA members = of its quality members */
+    uint64_t raw_hdr;
+    uint64_t reads;                /* where every DNA member states it (BFQDNAC1, BFQEBWT1), else ~0 */
+    uint64_t text_bound;           /* as bfq_fastq_restore_bound, for this group                */
+} bfq_restore_group;
+int64_t bfq_fastq_restore_groups(const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                 const uint8_t *h_hdr, uint64_t hdr_len,
+                                 bfq_restore_group *groups, uint64_t cap, char *why, int why_cap);
+int64_t bfq_stream_members(const uint8_t *h_in, uint64_t len);
+int bfq_fastq_restore_grouped(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                              const uint8_t *h_hdr, uint64_t hdr_len, uint64_t first, uint64_t count,
+                              uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads);
+int bfq_fastq_restore_grouped_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                 uint64_t first, uint64_t count, int out_fd, uint64_t *out_len, uint64_t *n_reads);
 /* ---- reads of a FASTQ in another order (the pre-pass of `BFQzip_parallel.py --reorder {1,2}`, :35,59-75,389-437, which shells
  * out to randomFASTQ.py / SPRING's reorder-only tool): FASTQ text in -> the same records, verbatim, in a new order out.  A
  * sharded run cuts the input into blocks of consecutive reads; reads of one locus brought together end up in one block and
