@@ -18,13 +18,14 @@
 #include "bfq_synth.h"
 #include "bfq_device.h"
 #include "bfq_rank.h"
+#include "bfq_posbin.h"
 
 const char *const BFQ_KERNEL_NAMES[K_NUM] = {
     "k_text_from_reads", "k_pack3", "k_build_keys", "k_radix_hist", "k_scan", "k_radix_scatter", "k_huge_round",
     "k_cluster_big", "k_refine_chunk", "k_refine_big", "k_emit_bwt", "k_lf_count", "k_lf_build", "k_lcp_flags",
     "k_cluster", "k_invert_count", "k_invert", "k_synth", "k_fastq", "k_bfs", "k_codec", "misc",
     "k_restore_index", "k_fq_format_lines", "k_reorder_keys", "k_reorder_gather",
-    "k_fq_format_ordered", "k_perm_pack", "k_perm_invert"};
+    "k_fq_format_ordered", "k_perm_pack", "k_perm_invert", "k_posbin_l1", "k_posbin_l2", "k_posbin_apply"};
 
 static thread_local std::string g_createErr;
 
@@ -285,6 +286,13 @@ extern "C" int64_t bfq_prof_trace(bfq_ctx *c, float *ms, uint64_t cap)
     return (int64_t)c->profTrace.size();
 }
 extern "C" int bfq_prof_count(bfq_ctx *c) { (void)c; return K_NUM; }
+extern "C" int bfq_posbin_geometry(uint64_t n_rows, uint64_t *window, int *bin_shift)
+{
+    const int s = bfq_posbin_shift(n_rows);
+    if (window) *window = BFQ_PB_W;
+    if (bin_shift) *bin_shift = s;
+    return s >= 0 ? BFQ_OK : BFQ_E_ARG;
+}
 extern "C" int bfq_prof_get(bfq_ctx *c, int idx, char *name, int cap, double *ms, uint64_t *launches, double *bytes)
 {
     if (!c || idx < 0 || idx >= K_NUM) return BFQ_E_ARG;
@@ -576,6 +584,37 @@ static void steps34_positions(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, 
     if (N) KLAUNCH(c, K_MISC, 4.0 * (double)(n - N), k_lines_strip, bfq_grid(N, 16), 256, (const u8 *)dna, (const u8 *)qs, d_roff, N, d_out_bases, d_out_quals);
 }
 
+// ---- the same without the random stores ("position bins", the default of the device-resident entry point): k_cluster
+// leaves its edits beside the rows (one byte each for the smoothed quality and the replaced base), and the rows -- position,
+// symbol, quality: all in the sort record's payload -- go back to text order by a two-level partition on the position and
+// one LDS placement per window (k_posbin.hip).  Streams 36 bytes per row in coalesced runs where k_lf_build + k_invert
+// fetched one random 64-byte sector per base.  Arena: text + (w1, w2) words kept (8.5 n), flags and edits 3 n, level-1
+// records 8 n -- below the 24 n of the sort buffers that step 1 has just given back (ws_need() is unchanged).
+static size_t posbins_room_needed(u64 n)
+{
+    const size_t pb = bfq_posbins_need(n);
+    if (pb == ~(size_t)0) return pb;
+    return pb + 3 * (n + 64 + 256) + 24 * (n / 256 + 8) + (1u << 20);   // + flags, the two edit arrays, k_cluster's tables
+}
+static void steps34_posbins(bfq_ctx *c, const u64 *d_roff, u8 *d_out_bases, u8 *d_out_quals)
+{
+    const u64 n = c->n, N = c->N;
+    if (!n) return;
+    u8 *editQual = c->alloc<u8>(n + 64), *repl = c->alloc<u8>(n + 64);
+    HIP_CHECK(hipMemcpyAsync(editQual, c->d_qual, n, hipMemcpyDeviceToDevice, c->stream));
+    HIP_CHECK(hipMemsetAsync(repl, 0, n + 64, c->stream));
+    {
+        const size_t mk = c->mark();
+        u8 *in = c->alloc<u8>(n + 64);
+        bfq_lcp_flags(c, c->d_lcp, n, c->P.K, in);
+        ClusterPos pm{c->call.d_w12, c->call.d_text3, nullptr, nullptr, c->P.B, editQual, repl};
+        RankIndex none{nullptr, n};
+        bfq_clusters(c, none, c->d_bwt, c->d_qual, in, n, &pm);
+        c->release(mk);
+    }
+    bfq_posbins(c, const_cast<u64 *>(c->call.d_w12), repl, editQual, n, d_roff, N, c->P.B, d_out_bases, d_out_quals);
+}
+
 // ---- the whole path under a workspace cap (the counterpart of bfq_ext's pile files, bfq_ext.cpp:190-348, and
 // of its lock-step inversion, decode.cpp:499-966): what bounds a block is the eBWT-sized state -- 24 B of sort records, the
 // 8-byte LF entry, the eBWT / QS / LCP arrays.  None of it is needed all at once.  The suffixes are cut into piles by their
@@ -650,11 +689,18 @@ extern "C" int bfq_run_reads_device(bfq_ctx *c, const uint8_t *d_bases, const ui
         reserve_step1(c, total + N, N, 0);
         c->zeroCounters();
         const u64 *roff = (const u64 *)d_read_off;
-        c->call.keepRecs = !c->call.capped && !c->call.piles && c->env.posMode;   // position mode
+        const bool fused = !c->call.capped && !c->call.piles;
+        const bool posBins = fused && !c->env.posMode && c->env.posBins && bfq_posbin_shift(total + N) >= 0;
+        c->call.keepRecs = fused && (c->env.posMode || posBins);   // position mode / position bins: the rows keep their positions
         if (c->call.capped) run_capped_reads(c, d_bases, d_quals, roff, N, total, d_out_bases, d_out_quals);
         else {
             bfq_step1_device(c, d_bases, d_quals, roff, N, total, c->P.term, st);
-            if (c->call.keepRecs) steps34_positions(c, d_bases, d_quals, roff, d_out_bases, d_out_quals);
+            if (posBins && total + N && c->ws.room() < posbins_room_needed(total + N)) {   // no room: the LF table after all
+                c->release(c->call.keepMark);
+                c->call.keepRecs = false;
+            }
+            if (c->call.keepRecs && posBins) steps34_posbins(c, roff, d_out_bases, d_out_quals);
+            else if (c->call.keepRecs) steps34_positions(c, d_bases, d_quals, roff, d_out_bases, d_out_quals);
             else steps234_device(c, (u64 *)d_read_off, d_out_bases, d_out_quals);
         }
         finish_call(c, st);

@@ -29,7 +29,7 @@ enum BfqKernel {
     K_TEXT = 0, K_PACK, K_KEYS, K_RADIX_HIST, K_SCAN, K_RADIX_SCATTER, K_HUGE_ROUND, K_CLUSTER_BIG,
     K_REFINE_WAVE, K_REFINE_BIG, K_EMIT, K_RANK_BUILD, K_RANK_FINAL, K_LCP_FLAGS, K_CLUSTER,
     K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER,
-    K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_NUM
+    K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_POSBIN_L1, K_POSBIN_L2, K_POSBIN_APPLY, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -383,7 +383,9 @@ void bfq_lcp_from_bwt(bfq_ctx *c, const u8 *bwt, u64 n, u64 N, int term, u16 *lc
                       const u64 *rankGiven = nullptr, u64 ringEntries = 0);
 // pm != nullptr: position mode -- no LF table (R.lfq may be null): edits go to the output line streams at the text position
 // each row's sort record carries (k_cluster.hip)
-struct ClusterPos { const u64 *w12; const u64 *text3; u8 *outSym, *outQual; int B; };
+// outSym == nullptr: the edits stay row-local instead -- the smoothed quality replaces editQual[row] (unbinned), a replaced
+// base goes to repl[row] -- and the position bins carry every row to its text position afterwards (k_posbin.hip)
+struct ClusterPos { const u64 *w12; const u64 *text3; u8 *outSym, *outQual; int B; u8 *editQual = nullptr, *repl = nullptr; };
 // rm != nullptr: rank mode -- no LF table either: LF from the rank blocks, qualities edited in place (qual == the array the
 // statistics are read from), replaced bases into repl[] (k_compact.hip)
 struct ClusterRank { const u64 *rankBlk; u64 F[6]; u8 *qual, *repl; };
@@ -401,6 +403,10 @@ void bfq_fixed_offsets(bfq_ctx *c, u64 N, u64 L, u64 *d_roff);   // d_roff[i] = 
 void bfq_invert(bfq_ctx *c, const RankIndex &R, u64 N, const u64 *d_roff, int B, u8 *out_bases, u8 *out_quals, u64 first = 0,
                 u64 count = ~0ull, bool lines = false);
 bool bfq_is_pinned(const void *p);
+// the rows back in text order by position bins instead of LF walks (k_posbin.hip): w12 = the sorted records' (w1, w2) words
+// (overwritten), repl / editQual = k_cluster's row-local edits; the reads go out back to back (read i at roff[i])
+size_t bfq_posbins_need(u64 n);                   // arena bytes it takes; ~0: more rows than two partition levels hold
+void bfq_posbins(bfq_ctx *c, u64 *w12, const u8 *repl, const u8 *editQual, u64 n, const u64 *d_roff, u64 N, int B, u8 *outSym, u8 *outQual);
 
 void bfq_synth_launch(bfq_ctx *c, const bfq_synth *s, u8 *d_bases, u8 *d_quals, u64 *d_roff);
 u8 *bfq_synth_headers(bfq_ctx *c, const bfq_synth *s, u64 *len);   // k_synth.hip

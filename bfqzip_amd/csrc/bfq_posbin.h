@@ -1,0 +1,46 @@
+// bfq_posbin.h -- geometry of the position-bin inversion (k_posbin.hip): plain C++, shared by host and device code.
+//
+// Row order -> text order is a permutation in which every text position occurs exactly once, so a radix partition on the
+// position needs no counting pass: bin b of level 1 holds the positions [b << s1, (b + 1) << s1) and therefore exactly that
+// many records, its base is arithmetic.  Level 2 cuts every level-1 bin into windows of BFQ_PB_W positions the same way, and
+// one workgroup per window places the window's records in LDS and writes the window out in one piece.
+#pragma once
+#include "bfq_common.h"
+
+#define BFQ_PB_WSHIFT 15                          // window: 32 Ki text positions (two 32 KiB byte arrays in LDS)
+#define BFQ_PB_W (1u << BFQ_PB_WSHIFT)
+#define BFQ_PB_MAX_BINS 512                       // bins of one partition level (LDS counters; ~8 records per bin and 4096-record tile)
+#define BFQ_PB_MAX_SHIFT (BFQ_PB_WSHIFT + 9)      // a level-1 bin is at most 512 windows: 2^33 rows in all
+
+// level-1 bin shift for n rows: the smallest s >= BFQ_PB_WSHIFT with at most BFQ_PB_MAX_BINS bins; -1: too many rows for two levels
+BFQ_HD int bfq_posbin_shift(u64 n)
+{
+    if (!n) return BFQ_PB_WSHIFT;
+    int s = BFQ_PB_WSHIFT;
+    while (s <= BFQ_PB_MAX_SHIFT && ((n - 1) >> s) + 1 > (u64)BFQ_PB_MAX_BINS) s++;
+    return s <= BFQ_PB_MAX_SHIFT ? s : -1;
+}
+BFQ_HD u64 bfq_posbin_bins(u64 n, int shift) { return n ? ((n - 1) >> shift) + 1 : 0; }     // bins (or windows) of 2^shift positions
+// records of bin b = positions in it
+BFQ_HD u64 bfq_posbin_cap(u64 n, int shift, u64 b)
+{
+    const u64 lo = b << shift;
+    if (lo >= n) return 0;
+    return n - lo < (1ull << shift) ? n - lo : (1ull << shift);
+}
+// the records: level 1 writes bfq_pack_val(position, final symbol code, final quality) (8 bytes), level 2 the position inside
+// the window | code << 15 | quality << 18 (4 bytes)
+BFQ_HD u32 bfq_posbin_rec4(u64 v) { return (u32)(bfq_val_pos(v) & (BFQ_PB_W - 1u)) | (bfq_val_code(v) << BFQ_PB_WSHIFT) | (bfq_val_qual(v) << (BFQ_PB_WSHIFT + 3)); }
+
+// Terminated-text coordinates: read i stands at roff[i] + i, its terminator at roff[i + 1] + i.  Number of terminators
+// strictly before position q = index of the read q lies in (a terminator belongs to the read it ends); q - that = where
+// q's symbol goes when the reads are written back to back.
+BFQ_HD u64 bfq_posbin_reads_before(const u64 *roff, u64 N, u64 q)
+{
+    u64 lo = 0, hi = N;                           // first i in [0, N] with roff[i + 1] + i >= q
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);
+        if (roff[mid + 1] + mid < q) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}

@@ -71,6 +71,8 @@ struct ClusterArgs {
     const u64 *text3;       // packed text (bfq_common.h)
     u8 *outSym, *outQual;   // OUT.fq.dna / OUT.fq.qs layout = terminated text coordinates (read i at roff[i] + i, then '\n')
     int B;
+    // ... or, with outSym == nullptr, stay row-local in editQual[] / repl[] as in rank mode below (but editQual[] is a copy:
+    // the statistics still read qual[]); the position bins move them afterwards (k_posbin.hip)
     // rank mode (rankBlk != nullptr; neither an LF table nor sort records): a given eBWT under a workspace cap
     // (k_compact.hip).  LF(row) is answered on demand from the 64-byte rank blocks, smoothed qualities replace qual[] in
     // place and replaced bases go to repl[] (0 = untouched) -- the reference's own arrangement: QUAL[] edited in place,
@@ -100,14 +102,14 @@ __device__ __forceinline__ u64 row_pos(const ClusterArgs &a, u64 j)      // text
 }
 __device__ __forceinline__ void set_qual(const ClusterArgs &a, u64 j, int newqs)
 {
-    if (a.w12) { const u32 q = (u32)newqs & 0xFFu; a.outQual[row_pos(a, j) - 1] = (u8)(a.B ? bfq_bin8(q) : q); }
-    else if (a.rankBlk) a.editQual[j] = (u8)newqs;
+    if (a.w12 && a.outQual) { const u32 q = (u32)newqs & 0xFFu; a.outQual[row_pos(a, j) - 1] = (u8)(a.B ? bfq_bin8(q) : q); }
+    else if (a.w12 || a.rankBlk) a.editQual[j] = (u8)newqs;
     else lfq_set_qual(a.R.lfq, j, (u32)newqs & 0xFFu);
 }
 __device__ __forceinline__ void set_mod(const ClusterArgs &a, u64 j, u8 sym)
 {
-    if (a.w12) a.outSym[row_pos(a, j) - 1] = sym;
-    else if (a.rankBlk) a.repl[j] = sym;
+    if (a.w12 && a.outSym) a.outSym[row_pos(a, j) - 1] = sym;
+    else if (a.w12 || a.rankBlk) a.repl[j] = sym;
     else lfq_set_repl(a.R.lfq, j, bfq_base_code(a.bwt[j]), bfq_base_code(sym));
 }
 // the symbol that precedes the eBWT symbol of row j: bwt[LF(j)] (bfq_int.cpp:545-560,577); row j holds a base
@@ -560,7 +562,7 @@ void bfq_clusters(bfq_ctx *c, const RankIndex &R, const u8 *bwt, const u8 *qual,
     if (!n) return;
     ClusterArgs a;
     a.R = R; a.bwt = bwt; a.qual = qual; a.in = in; a.n = n;
-    a.rankBlk = rm ? rm->rankBlk : nullptr; a.editQual = rm ? rm->qual : nullptr; a.repl = rm ? rm->repl : nullptr;
+    a.rankBlk = rm ? rm->rankBlk : nullptr; a.editQual = rm ? rm->qual : pm ? pm->editQual : nullptr; a.repl = rm ? rm->repl : pm ? pm->repl : nullptr;
     for (int s = 0; s < 6; s++) a.F[s] = rm ? rm->F[s] : 0;
     a.w12 = pm ? pm->w12 : nullptr; a.text3 = pm ? pm->text3 : nullptr;
     a.outSym = pm ? pm->outSym : nullptr; a.outQual = pm ? pm->outQual : nullptr; a.B = pm ? pm->B : 0;

@@ -571,6 +571,10 @@ int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, ui
 int  bfq_prof_enable(bfq_ctx *c, int on);
 void bfq_prof_reset(bfq_ctx *c);
 int  bfq_prof_count(bfq_ctx *c);
+/* introspection: how bfq_run_reads_device() brings n_rows rows (bases + reads) back to text order by position bins --
+ * the window (text positions per workgroup of the last stage) and the shift of a first-level bin (2^shift positions).
+ * BFQ_E_ARG (bin_shift -1): more rows than two partition levels hold; such a call inverts by LF walks. */
+int  bfq_posbin_geometry(uint64_t n_rows, uint64_t *window, int *bin_shift);
 int  bfq_prof_get(bfq_ctx *c, int idx, char *name, int name_cap, double *total_ms,
                   uint64_t *launches, double *alg_bytes_total);
 /* per-launch durations (ms, launch order, since the last reset) of ONE kernel chosen by its bfq_prof_get index (-1: none):
