@@ -32,6 +32,7 @@ SYMBOLS = [
     "bfq_fastq_reorder_keep", "bfq_fastq_reorder_keep_fd", "bfq_fastq_unreorder", "bfq_fastq_unreorder_fd",
     "bfq_fastq_restore_ordered", "bfq_fastq_restore_ordered_fd",
     "bfq_fastq_restore_groups", "bfq_stream_members", "bfq_fastq_restore_grouped", "bfq_fastq_restore_grouped_fd",
+    "bfq_fastq_compare", "bfq_fastq_compare_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -72,6 +73,25 @@ class ReorderOpts(C.Structure):
 class RestoreGroup(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("dna_off", "dna_len", "qs_off", "qs_len", "hdr_off", "hdr_len", "raw_stream", "raw_hdr",
                                           "reads", "text_bound")]
+
+
+CMP_SYMS = 6
+CMP_POS = 512
+
+
+class CompareDiff(C.Structure):
+    _fields_ = [("read", C.c_uint64), ("pos", C.c_uint32), ("base_a", C.c_uint8), ("base_b", C.c_uint8), ("qual_a", C.c_uint8), ("qual_b", C.c_uint8)]
+
+
+COMPARE_SCALARS = ("n_reads", "total_bases", "n_diffs", "reads_changed", "reads_bases_changed", "reads_quals_changed", "bases_changed",
+                   "quals_changed", "quals_raised", "quals_lowered", "qual_abs_sum", "qual_sq_sum", "qual_abs_max", "first_changed_read",
+                   "headers_same", "headers_dropped", "headers_changed")
+COMPARE_ARRAYS = (("subst", CMP_SYMS * CMP_SYMS), ("qual_hist_a", 256), ("qual_hist_b", 256), ("changed_base_qual_hist", 256),
+                  ("pos_len", CMP_POS), ("pos_bases", CMP_POS), ("pos_quals", CMP_POS), ("pos_abs", CMP_POS))
+
+
+class CompareReport(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in COMPARE_SCALARS] + [(k, C.c_uint64 * n) for k, n in COMPARE_ARRAYS] + [("reserved", C.c_uint64 * 8)]
 
 
 class FastqJob(C.Structure):
@@ -210,6 +230,8 @@ def lib():
         L.bfq_fastq_restore_grouped.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, u64, vp, u64, pu64, pu64]
         L.bfq_fastq_restore_grouped_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, u64, u64, C.c_int, pu64, pu64]
         L.bfq_stream_compress_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+        L.bfq_fastq_compare.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(TextPart), C.c_int, vp, u64, C.POINTER(CompareReport), vp, u64]
+        L.bfq_fastq_compare_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.POINTER(CompareReport), vp, u64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]
         L.bfq_prof_reset.argtypes = [vp]

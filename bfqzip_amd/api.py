@@ -114,6 +114,44 @@ class FileRange:
 
 
 ALL_GROUPS = (1 << 64) - 1
+NO_READ = (1 << 64) - 1
+
+DIFF_DTYPE = np.dtype([("read", "<u8"), ("pos", "<u4"), ("base_a", "u1"), ("base_b", "u1"), ("qual_a", "u1"), ("qual_b", "u1")])
+
+
+class CompareReport:
+    """What Engine.fastq_compare found (bfq_compare_report): the scalar fields as ints (first_changed_read: NO_READ when
+    nothing differs), subst as a 6 x 6 uint64 array ([class of A's base][class of B's], classes A C G N T other), the
+    histograms and position profiles as uint64 arrays, .diffs the listed positions as a structured array (DIFF_DTYPE, in
+    (read, pos) order), .identical = no base and no quality differs."""
+
+    def __init__(self, raw, diffs):
+        for k in _lib.COMPARE_SCALARS:
+            setattr(self, k, int(getattr(raw, k)))
+        for k, n in _lib.COMPARE_ARRAYS:
+            setattr(self, k, np.array(getattr(raw, k), np.uint64))
+        self.subst = self.subst.reshape(_lib.CMP_SYMS, _lib.CMP_SYMS)
+        self.diffs = diffs
+
+    @property
+    def identical(self):
+        return self.n_diffs == 0
+
+    def as_dict(self):
+        """Plain ints and lists (JSON): the scalars (first_changed_read None when nothing differs), identical, subst as six
+        rows, the histograms, and the position profiles cut after the last bin that holds a position."""
+        d = {k: getattr(self, k) for k in _lib.COMPARE_SCALARS}
+        if d["first_changed_read"] == NO_READ:
+            d["first_changed_read"] = None
+        d["identical"] = self.identical
+        d["subst"] = [[int(v) for v in row] for row in self.subst]
+        for k in ("qual_hist_a", "qual_hist_b", "changed_base_qual_hist"):
+            d[k] = [int(v) for v in getattr(self, k)]
+        nz = np.flatnonzero(self.pos_len)
+        n = int(nz[-1]) + 1 if len(nz) else 0
+        for k in ("pos_len", "pos_bases", "pos_quals", "pos_abs"):
+            d[k] = [int(v) for v in getattr(self, k)[:n]]
+        return d
 
 
 def restore_groups(dna, qs, hdr=None):
@@ -653,6 +691,47 @@ class Engine:
         def call(fin, sizes, n, fout, fperm, ol, nr):
             self._ck(self.L.bfq_fastq_unreorder_fd(self.h, fin, sizes, n, fperm, os.fstat(fperm).st_size, fout, ol, C.byref(nr)))
         return self._reorder_files(inputs, outputs, perm_path, False, call)
+
+    # ---- what a run changed: two FASTQ texts compared on the GPU (bfq_fastq_compare)
+    def fastq_compare(self, a_parts, b_parts, perm=None, max_diffs=0, diffs_out=None):
+        """A ("before") against B ("after"), each a list of 1..4 texts taken as one: a CompareReport.  perm: the BFQPERM1
+        container of the run that gave B its order (record j of B pairs with record perm[j] of A; every read index reported
+        is A's).  max_diffs: list that many differing positions at most (.diffs).  diffs_out: a DIFF_DTYPE array of at least
+        max_diffs entries to fill; .diffs is a view of it.  Texts that do not pair (record counts, a read's length), a bad
+        permutation or malformed text raise BfqError and leave diffs_out untouched."""
+        pa, pb = [_u8(p) for p in a_parts], [_u8(p) for p in b_parts]
+
+        def parts(arrs):
+            tp = (_lib.TextPart * max(len(arrs), 1))()
+            for i, x in enumerate(arrs):
+                tp[i].data = x.ctypes.data if len(x) else None
+                tp[i].len = len(x)
+            return tp
+        z = _u8(perm) if perm is not None else None
+        buf = diffs_out if diffs_out is not None else np.zeros(max(int(max_diffs), 1), DIFF_DTYPE)
+        assert buf.dtype == DIFF_DTYPE and len(buf) >= max_diffs
+        raw = _lib.CompareReport()
+        self._ck(self.L.bfq_fastq_compare(self.h, parts(pa), len(pa), parts(pb), len(pb), _ptr(z) if z is not None else None,
+                                          len(z) if z is not None else 0, C.byref(raw), _ptr(buf) if max_diffs else None, int(max_diffs)))
+        return CompareReport(raw, buf[:min(int(raw.n_diffs), int(max_diffs))])
+
+    def fastq_compare_files(self, a_path, b_path, perm_path=None, max_diffs=0):
+        """fastq_compare on named files (bfq_fastq_compare_fd)."""
+        import os
+        fds = []
+        try:
+            for p in (a_path, b_path, perm_path):
+                fds.append(os.open(p, os.O_RDONLY) if p is not None else -1)
+            size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
+            buf = np.zeros(max(int(max_diffs), 1), DIFF_DTYPE)
+            raw = _lib.CompareReport()
+            self._ck(self.L.bfq_fastq_compare_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]), C.byref(raw),
+                                                 _ptr(buf) if max_diffs else None, int(max_diffs)))
+            return CompareReport(raw, buf[:min(int(raw.n_diffs), int(max_diffs))])
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
 
     # ---- the permutation as a container (host only)
     @staticmethod

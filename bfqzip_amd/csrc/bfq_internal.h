@@ -29,7 +29,8 @@ enum BfqKernel {
     K_TEXT = 0, K_PACK, K_KEYS, K_RADIX_HIST, K_SCAN, K_RADIX_SCATTER, K_HUGE_ROUND, K_CLUSTER_BIG,
     K_REFINE_WAVE, K_REFINE_BIG, K_EMIT, K_RANK_BUILD, K_RANK_FINAL, K_LCP_FLAGS, K_CLUSTER,
     K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER,
-    K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_POSBIN_L1, K_POSBIN_L2, K_POSBIN_APPLY, K_NUM
+    K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_POSBIN_L1, K_POSBIN_L2, K_POSBIN_APPLY,
+    K_CMP_CHECK, K_CMP_COMPARE, K_CMP_EMIT, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -450,3 +451,11 @@ void bfq_reorder_gather(bfq_ctx *c, const RoText &t, const u64 *perm, const u64 
 void bfq_perm_pack(bfq_ctx *c, const u64 *perm, u64 N, u64 *d_words);                            // d_words: bfq_perm_words() of them
 u64 bfq_perm_unpack_invert(bfq_ctx *c, const u64 *d_words, u64 N, u64 *perm, u64 *inv);         // the first offending position, ~0: none; synchronises
 void bfq_reorder_sizes(bfq_ctx *c, const u64 *order, const RoText *mates, int nmates, u64 N, u64 *const *sizes);   // sizes[p][j] = size of record order[j]
+
+// two FASTQ texts compared where they lie (k_compare.hip; bfq_compare.hip drives them).  inv == nullptr: read i of A pairs with
+// read i of B, else with read inv[i].  d_rep: a zeroed report on the device whose first_changed_read is all-ones.
+struct CmpText { const u8 *buf; const FqRec *rec; };
+void bfq_compare_check(bfq_ctx *c, CmpText A, CmpText B, const u64 *inv, u64 N, bfq_compare_report *d_rep, u64 *d_badRead);   // *d_badRead preset to all-ones
+void bfq_compare_pass(bfq_ctx *c, CmpText A, CmpText B, const u64 *inv, u64 N, u64 total, bfq_compare_report *d_rep, u32 *readDiffs);
+void bfq_compare_emit(bfq_ctx *c, CmpText A, CmpText B, const u64 *inv, u64 N, u64 total, const u32 *readDiffs, const u64 *diffOff, u64 cap,
+                      bfq_compare_diff *d_out);

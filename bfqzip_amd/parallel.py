@@ -232,6 +232,25 @@ def restore_order(eng, comm, outputs, perm_path, log=None):
     comm.barrier()
 
 
+def write_reports(eng, comm, before, outputs, log=None):
+    """--report after the run: rank 0 compares every merged FASTQ output with the input it came from, in the same order
+    (eng.fastq_compare_files), and writes `<output fastq>.report.json` (the keys of CompareReport.as_dict()), one per mate,
+    after the barrier that ends the writes.  Returns the report names."""
+    import json
+    comm.barrier()
+    paths = [o + ".report.json" for o in outputs]
+    if comm.rank == 0:
+        for src, o, p in zip(before, outputs, paths):
+            rep = eng.fastq_compare_files(src, o)
+            with open(p, "w") as f:
+                json.dump(rep.as_dict(), f)
+                f.write("\n")
+            if log:
+                log(f"report: {o} against {src}: {rep.n_diffs} differing positions in {rep.reads_changed} of {rep.n_reads} reads -> {p}")
+    comm.barrier()
+    return paths
+
+
 KINDS = ("fastq", "dna", "qs", "hdr")
 
 
@@ -594,6 +613,9 @@ def main(argv=None):
                          "FASTQ text back in input order (streams and --compress containers stay in run order: bfq_restore -P)")
     ap.add_argument("--reorder-k", type=int, default=21, help="k-mer length of --reorder 2 (8..32)")
     ap.add_argument("--seed", type=int, default=0, help="seed of --reorder 1")
+    ap.add_argument("--report", action="store_true",
+                    help="after the run, compare every merged FASTQ output with the input in the same order on the GPU and write "
+                         "<output fastq>.report.json (needs the uncompressed merged FASTQ text: not with --streams-only or --compress)")
     ap.add_argument("--restore", action="store_true",
                     help="the way back: the inputs are DNA.bsc QS.bsc [HDR.bsc] of a --compress run, -o OUT.fq the FASTQ file to write; "
                          "group k of the archive (one per block) is restored by rank k mod world")
@@ -607,6 +629,9 @@ def main(argv=None):
         return 1
     if a.m3:
         a.headers = True
+    if a.report and (a.restore or ((a.m2 or a.m3) and a.streams_only) or (a.compress and not a.m0 and not a.glob)):
+        print("=== ERROR ===\n--report compares the merged FASTQ text: not with --restore, --streams-only or --compress", file=sys.stderr)
+        return 1
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
     if torch.cuda.device_count():
@@ -639,6 +664,7 @@ def main(argv=None):
         return 0
     perm_path = reordered_names(a.input[:1], a.reorder)[0] + ".perm" if (a.keep_order and a.reorder) else None
     keep = dict(perm_path=perm_path) if perm_path else {}
+    original = list(a.input)
     a.input = reorder_inputs(eng, comm, a.input, a.reorder, k=a.reorder_k, seed=a.seed, paired=a.paired, log=log, **keep)
     names = output_names(a.input, a.out, a.paired)                   # after the replacement, as define_basename() in the reference
     streams = a.m2 or a.m3
@@ -656,6 +682,8 @@ def main(argv=None):
             restore_order(eng, comm, [n["fastq"] for n in names], perm_path, log=log)
         if log and comm.rank == 0 and (streams or compress):
             log(f"keep-order: the {'containers' if compress else 'raw streams'} stay in run order; pass {perm_path} to bfq_restore -P")
+    if a.report:                                                     # against what is in the outputs' order: the originals unless the run reordered for good
+        write_reports(eng, comm, original if (perm_path or not a.reorder) else a.input, [n["fastq"] for n in names], log=log)
     if a.v:
         print(f"[rank {comm.rank}] {tot}", flush=True)
     eng.close()

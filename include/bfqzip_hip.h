@@ -562,6 +562,55 @@ int bfq_fastq_restore_ordered(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len
                               uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads);
 int bfq_fastq_restore_ordered_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
                                  int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads);
+/* ---- what a run did to the data: two FASTQ texts compared on the device, A "before" and B "after" (k_compare.hip;
+ * tests/compare_model.py states it in Python).  The reference leaves this question to a bwa + GATK pipeline downstream.
+ * Inputs: each text is 1..BFQ_MAX_PARTS parts taken as one text, in order; a part without its final newline gets one, as in
+ *   bfq_fastq_run_job; the part boundaries of A and B need not correspond.  Records are four lines; a CR before LF is dropped
+ *   from lines 1, 2 and 4 of both texts.  Malformed text of either input: the code and message of bfq_fastq_run, prefixed by
+ *   "A: " or "B: ".
+ * Pairing: read i of A with read i of B.  With h_permz / perm_fd (a BFQPERM1 container: what bfq_fastq_reorder_keep writes for
+ *   the run that produced B's order) record j of B is compared with record perm[j] of A.  Every read index the call reports
+ *   (first_changed_read, bfq_compare_diff.read, messages) is A's.  The container is validated and inverted on the device as in
+ *   bfq_fastq_restore_ordered, with its refusals: another N (both numbers named), a bad entry (first offending position named).
+ * Refusals, BFQ_E_ARG unless said otherwise; *rep is zeroed and h_diffs untouched then: the record counts differ (both are
+ *   named); a read's sequence length differs between A and B (the smallest such A index and both lengths are named).  Device
+ *   memory: the two texts + about 160 bytes of index per read + 16 bytes per diff record asked for (min(cap_diffs, the bases
+ *   the text can hold)), reserved once; above ws_cap_mib: BFQ_E_NOMEM with the size in the message.  An input pair larger than
+ *   device memory is not split.
+ * Counting: a position differs when the base bytes differ, the quality bytes differ, or both (n_diffs).  bases_changed counts
+ *   byte inequality ('a' against 'A' is a change); reads_*_changed count the reads with at least one such position.  d =
+ *   (int) qual_b - (int) qual_a: quals_raised d > 0, quals_lowered d < 0, qual_abs_sum / qual_sq_sum / qual_abs_max over |d|.
+ *   pos_len[p] = compared positions that fall in bin p: the denominator of pos_bases (base changed), pos_quals (quality
+ *   changed) and pos_abs (sum of |d|).
+ * Headers: a header is the header line without its line end.  same: equal bytes; dropped: B's header is exactly "@" and A's
+ *   is not (what a run without --headers writes); changed: any other inequality.  The three sum to n_reads.
+ * Diff list: the first min(n_diffs, cap_diffs) differing positions in ascending (read, pos) go to h_diffs; nothing is written
+ *   beyond them.  cap_diffs = 0 with h_diffs = NULL is the plain report.
+ * Every sum is an integer sum: the report is exact and does not depend on the launch geometry.
+ *   bfq_fastq_compare   : host buffers (pinned: direct DMA); h_permz NULL / permz_len 0: no permutation
+ *   bfq_fastq_compare_fd: open files; perm_fd < 0: no permutation */
+#define BFQ_CMP_SYMS 6      /* classes of a base byte: A C G N T (the project's order) = 0..4, every other byte = 5 */
+#define BFQ_CMP_POS  512    /* position bins: position p of a read counts in bin min(p, 511) */
+typedef struct bfq_compare_diff { uint64_t read; uint32_t pos; uint8_t base_a, base_b, qual_a, qual_b; } bfq_compare_diff; /* 16 bytes */
+typedef struct bfq_compare_report {
+    uint64_t n_reads, total_bases;
+    uint64_t n_diffs;                 /* positions where the base or the quality differs */
+    uint64_t reads_changed, reads_bases_changed, reads_quals_changed;
+    uint64_t bases_changed, quals_changed, quals_raised, quals_lowered;
+    uint64_t qual_abs_sum, qual_sq_sum, qual_abs_max;      /* of d = (int) qual_b - (int) qual_a */
+    uint64_t first_changed_read;      /* smallest read index with a difference, UINT64_MAX: none */
+    uint64_t headers_same, headers_dropped, headers_changed;
+    uint64_t subst[BFQ_CMP_SYMS * BFQ_CMP_SYMS];           /* [6 * class(base_a) + class(base_b)], every position: sums to total_bases */
+    uint64_t qual_hist_a[256], qual_hist_b[256];           /* every quality byte of A / of B */
+    uint64_t changed_base_qual_hist[256];                  /* qual_a at the positions whose base changed */
+    uint64_t pos_len[BFQ_CMP_POS], pos_bases[BFQ_CMP_POS], pos_quals[BFQ_CMP_POS], pos_abs[BFQ_CMP_POS];
+    uint64_t reserved[8];
+} bfq_compare_report;
+int bfq_fastq_compare   (bfq_ctx *c, const bfq_text_part *a, int na, const bfq_text_part *b, int nb,
+                         const uint8_t *h_permz, uint64_t permz_len,
+                         bfq_compare_report *rep, bfq_compare_diff *h_diffs, uint64_t cap_diffs);
+int bfq_fastq_compare_fd(bfq_ctx *c, int a_fd, uint64_t a_len, int b_fd, uint64_t b_len, int perm_fd, uint64_t permz_len,
+                         bfq_compare_report *rep, bfq_compare_diff *h_diffs, uint64_t cap_diffs);
 /* device-resident form (input and output in device memory): bfq_stream_reserve(len) sizes the workspace once */
 int bfq_stream_reserve(bfq_ctx *c, uint64_t len);
 int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
