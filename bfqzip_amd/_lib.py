@@ -33,6 +33,7 @@ SYMBOLS = [
     "bfq_fastq_restore_ordered", "bfq_fastq_restore_ordered_fd",
     "bfq_fastq_restore_groups", "bfq_stream_members", "bfq_fastq_restore_grouped", "bfq_fastq_restore_grouped_fd",
     "bfq_fastq_compare", "bfq_fastq_compare_fd",
+    "bfq_bgzf_probe", "bfq_bgzf_index", "bfq_bgzf_inflate", "bfq_bgzf_inflate_device", "bfq_bgzf_inflate_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -73,6 +74,10 @@ class ReorderOpts(C.Structure):
 class RestoreGroup(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("dna_off", "dna_len", "qs_off", "qs_len", "hdr_off", "hdr_len", "raw_stream", "raw_hdr",
                                           "reads", "text_bound")]
+
+
+class BgzfMember(C.Structure):
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("out_len", C.c_uint32)]
 
 
 CMP_SYMS = 6
@@ -232,6 +237,11 @@ def lib():
         L.bfq_stream_compress_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_fastq_compare.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(TextPart), C.c_int, vp, u64, C.POINTER(CompareReport), vp, u64]
         L.bfq_fastq_compare_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.POINTER(CompareReport), vp, u64]
+        L.bfq_bgzf_probe.argtypes = [vp, u64]
+        L.bfq_bgzf_index.argtypes = [vp, u64, C.POINTER(BgzfMember), u64, pu64, pu64, pu64]
+        L.bfq_bgzf_inflate.argtypes = [vp, vp, u64, vp, u64, pu64]
+        L.bfq_bgzf_inflate_device.argtypes = [vp, vp, u64, vp, u64, pu64]
+        L.bfq_bgzf_inflate_fd.argtypes = [vp, C.c_int, u64, C.c_int, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]
         L.bfq_prof_reset.argtypes = [vp]

@@ -183,8 +183,48 @@ def restore_groups(dna, qs, hdr=None):
     return out
 
 
+class BgzfIndexError(BfqError):
+    """bgzf_index met a member header it refuses: `members` well-formed members stand before it, it starts at byte `bad_off`."""
+
+    def __init__(self, code, members, bad_off):
+        super().__init__(code, f"not a BGZF member: member {members} at byte {bad_off}")
+        self.members, self.bad_off = members, bad_off
+
+
+def bgzf_probe(blob):
+    """True when the bytes begin with a well-formed BGZF member header (a FASTQ text never does)."""
+    blob = _u8(blob)
+    return bool(len(blob)) and bool(_lib.lib().bfq_bgzf_probe(_ptr(blob), len(blob)))
+
+
+def bgzf_index(blob):
+    """The directory of a BGZF file: ([(in_off, out_off, in_len, out_len) per member], raw length); BgzfIndexError when a
+    member header is refused."""
+    blob = _u8(blob)
+    L = _lib.lib()
+    n, raw, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = L.bfq_bgzf_index(_ptr(blob), len(blob), None, 0, C.byref(n), C.byref(raw), C.byref(bad))
+    if rc != 0:
+        raise BgzfIndexError(rc, int(n.value), int(bad.value))
+    m = (_lib.BgzfMember * max(int(n.value), 1))()
+    L.bfq_bgzf_index(_ptr(blob), len(blob), m, int(n.value), C.byref(n), C.byref(raw), C.byref(bad))
+    return [(int(e.in_off), int(e.out_off), int(e.in_len), int(e.out_len)) for e in m[:int(n.value)]], int(raw.value)
+
+
+def text_len(a):
+    """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
+    a = _u8(a)
+    if len(a) >= 2 and a[0] == 0x1F and a[1] == 0x8B:
+        raw = C.c_uint64(0)
+        if _lib.lib().bfq_bgzf_index(_ptr(a), len(a), None, 0, None, C.byref(raw), None) == 0:
+            return int(raw.value) + 1                              # (+ the newline a part may lack)
+    return len(a)
+
+
 class HostText:
     """Host-side text helpers of libbfqhip.so (no GPU involved)."""
+    bgzf_probe = staticmethod(bgzf_probe)
+    bgzf_index = staticmethod(bgzf_index)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -279,7 +319,7 @@ class Engine:
             cap = min(len(bwt), len(qs), len(lcp) if lcp is not None else len(bwt))
             want_lcp = lcp is not None
         else:
-            cap = len(buf) // 2 + 1
+            cap = text_len(buf) // 2 + 1
             bwt = np.empty(cap, np.uint8); qs = np.empty(cap, np.uint8)
             lcp = np.empty(cap, np.uint16) if want_lcp else None
         n = C.c_uint64(0); N = C.c_uint64(0)
@@ -290,7 +330,7 @@ class Engine:
     def fastq_run(self, text, keep_headers=False):
         """The whole path on the bytes of a FASTQ file -> (smoothed FASTQ bytes, stats)."""
         buf = np.frombuffer(text, np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
-        out = np.empty(len(buf) + 16, np.uint8)
+        out = np.empty(text_len(buf) + 16, np.uint8)
         ol = C.c_uint64(0)
         st = _lib.Stats()
         self._ck(self.L.bfq_fastq_run(self.h, _ptr(buf), len(buf), 1 if keep_headers else 0, _ptr(out), len(out),
@@ -301,7 +341,7 @@ class Engine:
         """The whole path with the result as the streams of BFQzip.py --m2/--m3 (BFQzip.py:19-21,192-251):
         (OUT.fq.dna bytes, OUT.fq.qs bytes, OUT.h bytes or None, stats)."""
         buf = np.frombuffer(text, np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
-        cap = len(buf) + 16
+        cap = text_len(buf) + 16
         dna = np.empty(cap, np.uint8); qs = np.empty(cap, np.uint8)
         hdr = np.empty(cap, np.uint8) if want_headers else None
         sl = C.c_uint64(0); hl = C.c_uint64(0)
@@ -325,7 +365,7 @@ class Engine:
         for i, a in enumerate(arrs):
             tp[i].data = a.ctypes.data if len(a) else None
             tp[i].len = len(a)
-        inlen = sum(len(a) for a in arrs)
+        inlen = sum(text_len(a) for a in arrs)                  # (a BGZF part: its raw length)
         out = out or {}
 
         def buf(key, want, size):
@@ -516,6 +556,42 @@ class Engine:
         ol = C.c_uint64(0)
         self._ck(self.L.bfq_stream_decompress(self.h, _ptr(blob), len(blob), _ptr(out), len(out), C.byref(ol)))
         return out[:int(ol.value)]
+
+    def bgzf_inflate(self, blob, out=None):
+        """The text of a bgzip-compressed (BGZF) file, inflated on the GPU (bfq_bgzf_inflate) as a uint8 array.  `out`: a uint8
+        array to fill (e.g. PinnedBuffer.array) of at least the raw length (HostText.bgzf_index); the result is a view of it.
+        A damaged file raises BfqError (BFQ_E_ARG: "damaged BGZF input: member <i> at byte <off>: <reason>"); plain gzip is
+        refused by name."""
+        blob = _u8(blob)
+        if out is None:
+            raw, n = C.c_uint64(0), C.c_uint64(0)
+            self.L.bfq_bgzf_index(_ptr(blob), len(blob), None, 0, C.byref(n), C.byref(raw), None)   # (a refused header: the call below words it)
+            out = np.empty(max(int(raw.value), 1), np.uint8)
+        ol = C.c_uint64(0)
+        self._ck(self.L.bfq_bgzf_inflate(self.h, _ptr(blob), len(blob), _ptr(out), len(out), C.byref(ol)))
+        return out[:int(ol.value)]
+
+    def bgzf_inflate_device(self, blob, d_out, cap):
+        """bfq_bgzf_inflate_device: the text at the device address d_out (cap bytes); returns its length."""
+        blob = _u8(blob)
+        ol = C.c_uint64(0)
+        self._ck(self.L.bfq_bgzf_inflate_device(self.h, _ptr(blob), len(blob), C.c_void_p(d_out), cap, C.byref(ol)))
+        return int(ol.value)
+
+    def bgzf_inflate_files(self, src, dst=None):
+        """bfq_bgzf_inflate_fd on named files; dst None: inflate and verify only.  Returns the length of the text."""
+        import os
+        fds = []
+        try:
+            fds.append(os.open(src, os.O_RDONLY))
+            fds.append(os.open(dst, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) if dst is not None else -1)
+            ol = C.c_uint64(0)
+            self._ck(self.L.bfq_bgzf_inflate_fd(self.h, fds[0], os.fstat(fds[0]).st_size, fds[1], C.byref(ol)))
+            return int(ol.value)
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
 
     def ebwt_decode(self, bwtz, qsz, out=None):
         """The line streams (dna, qs) of a pair of eBWT-domain containers (fastq_job(compress=2)); returns (dna, qs, n_reads)."""

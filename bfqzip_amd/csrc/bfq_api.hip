@@ -26,7 +26,7 @@ const char *const BFQ_KERNEL_NAMES[K_NUM] = {
     "k_cluster", "k_invert_count", "k_invert", "k_synth", "k_fastq", "k_bfs", "k_codec", "misc",
     "k_restore_index", "k_fq_format_lines", "k_reorder_keys", "k_reorder_gather",
     "k_fq_format_ordered", "k_perm_pack", "k_perm_invert", "k_posbin_l1", "k_posbin_l2", "k_posbin_apply",
-    "k_cmp_check", "k_cmp_compare", "k_cmp_emit"};
+    "k_cmp_check", "k_cmp_compare", "k_cmp_emit", "k_bgzf_inflate"};
 
 static thread_local std::string g_createErr;
 
@@ -933,34 +933,24 @@ u8 *bfq_ctx::textBuf(size_t bytes)
 
 // Uploads the parts back to back (a part that does not end in '\n' gets one, so that no record straddles two
 // parts); pstart[p] = offset of part p in the device text, pstart[nparts] = its length.
-struct TextSrc { HostRef ref; u64 len; };
-static bool src_ends_with_newline(const TextSrc &t)
+// (measured and placed by the shared pair of bfq_bgzf.hip: a part may be BGZF, and is then inflated into the text)
+static u8 *text_place(bfq_ctx *c, const TextSrc *parts, TextMeasure &M, u64 *pstart)
 {
-    if (!t.len) return true;
-    if (t.ref.ptr) return ((const u8 *)t.ref.ptr)[t.len - 1] == (u8)'\n';
-    u8 b = 0;
-    if (pread(t.ref.fd, &b, 1, (off_t)(t.ref.off + t.len - 1)) != 1) throw BfqError{BFQ_E_IO, "cannot read the input file"};
-    return b == (u8)'\n';
+    bfq_phase("alloc");
+    // the compressed bytes of a BGZF part need a home before the arena is sized: the tail of the text buffer
+    const u64 stageOff = (M.bound + 64 + 255) & ~255ull;
+    u8 *d_fq = c->textBuf(M.anyBgzf() ? stageOff + M.stage : M.bound + 64);
+    bfq_phase("read_h2d");
+    bfq_text_put(c, parts, &M, d_fq, d_fq + stageOff, pstart);
+    return d_fq;
 }
 static u8 *fastq_upload_and_reserve(bfq_ctx *c, const TextSrc *parts, int nparts, std::vector<u64> &pstart, size_t extraWs = 0, bool allowCapped = true)
 {
     pstart.assign(nparts + 1, 0);
-    std::vector<u8> addNl(nparts, 0);
-    u64 len = 0;
-    for (int p = 0; p < nparts; p++) {
-        if (parts[p].len && parts[p].ref.null()) throw BfqError{BFQ_E_ARG, "null FASTQ text"};
-        pstart[p] = len;
-        len += parts[p].len;
-        if (!src_ends_with_newline(parts[p])) { addNl[p] = 1; len++; }
-    }
-    pstart[nparts] = len;
-    bfq_phase("alloc");
-    u8 *d_fq = c->textBuf(len + 64);
-    bfq_phase("read_h2d");
-    for (int p = 0; p < nparts; p++) {
-        bfq_upload(c, d_fq + pstart[p], parts[p].ref, parts[p].len);
-        if (addNl[p]) HIP_CHECK(hipMemsetAsync(d_fq + pstart[p] + parts[p].len, '\n', 1, c->stream));
-    }
+    TextMeasure M;
+    bfq_text_measure(parts, nparts, &M);
+    u8 *d_fq = text_place(c, parts, M, pstart.data());
+    const u64 len = pstart[nparts];
     bfq_phase("alloc");
     c->reserve(16 * (len / 4096 + 16) + (64u << 20));
     bfq_phase("gpu");
@@ -1025,12 +1015,14 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
     // The outputs are sized to their bound (rows <= bytes / 2) and pre-faulted in the background -- from the moment the tool
     // opened them (bfq_output_prefault) or from here: by the time the first pile is sorted the page-cache pages exist and the
     // copy out of the staging buffers runs at memcpy speed.
-    const u64 capRows = len / 2 + 64, est = bfq_fastq_rows_estimate(fastq_fd, len);
     OutFile ob, oq, ol;
-    ob.open(bwt_fd, capRows, est);
-    oq.open(qs_fd, capRows, est);
-    if (wantLcp) ol.open(lcp_fd, capRows * (u64)lcp_bytes, est * (u64)lcp_bytes);
     u64 n = 0;
+    auto openOutputs = [&](u64 textBound, u64 est) {
+        const u64 capRows = textBound / 2 + 64;
+        ob.open(bwt_fd, capRows, est);
+        oq.open(qs_fd, capRows, est);
+        if (wantLcp) ol.open(lcp_fd, capRows * (u64)lcp_bytes, est * (u64)lcp_bytes);
+    };
     // HBM of this process, and why it is cut into pieces: the driver scrubs freed HBM at ~30 GB/s and the NEXT process's
     // allocations wait for it (profiles/microbench/alloc_after_exit.hip; profiles/r3/dropin_phases.md: bfq_int waited 1.3-4.3 s
     // behind a gsufsort that had held 102 GiB).  So every piece is as small as its contents and goes back the moment it is dead:
@@ -1046,13 +1038,14 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
         if (ok && !(a && b && l)) throw BfqError{BFQ_E_IO, "cannot size the output files"};
     };
     try {
-        bfq_phase("alloc");
-        const bool addNl = !src_ends_with_newline(text);
-        const u64 tl = len + (addNl ? 1 : 0);
-        u8 *d_fq = c->textBuf(tl + 64);
-        bfq_phase("read_h2d");
-        bfq_upload(c, d_fq, text.ref, len);
-        if (addNl) HIP_CHECK(hipMemsetAsync(d_fq + len, '\n', 1, c->stream));
+        // a BGZF file: every size follows from its raw length, which the measure gives (host only: headers and trailers)
+        TextMeasure M;
+        try { bfq_text_measure(&text, 1, &M); }
+        catch (...) { openOutputs(len, 0); throw; }             // (the outputs of a refused input are cut to nothing below)
+        openOutputs(M.bound, bfq_fastq_rows_estimate(fastq_fd, len));
+        u64 ps[2];
+        u8 *d_fq = text_place(c, &text, M, ps);
+        const u64 tl = ps[1];
         bfq_phase("alloc");
         c->reserve(16 * (tl / 4096 + 16) + (64u << 20));
         bfq_phase("gpu");

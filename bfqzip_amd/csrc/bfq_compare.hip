@@ -12,17 +12,8 @@
 #include "bfq_device.h"
 #include "bfq_perm.h"
 
-struct CmpSrc { HostRef ref; u64 len; };
-struct CmpInput { const CmpSrc *parts; int nparts; u64 len; u8 addNl[BFQ_MAX_PARTS]; };
-
-static bool cmp_ends_with_newline(const CmpSrc &t)
-{
-    if (!t.len) return true;
-    if (t.ref.ptr) return ((const u8 *)t.ref.ptr)[t.len - 1] == (u8)'\n';
-    u8 b = 0;
-    if (pread(t.ref.fd, &b, 1, (off_t)(t.ref.off + t.len - 1)) != 1) throw BfqError{BFQ_E_IO, "cannot read the input file"};
-    return b == (u8)'\n';
-}
+using CmpSrc = TextSrc;
+struct CmpInput { const CmpSrc *parts; int nparts; u64 len; TextMeasure M; };   // len: a bound once measured, the length once placed
 
 static void cmp_nomem(bfq_ctx *c, size_t need)
 {
@@ -32,24 +23,20 @@ static void cmp_nomem(bfq_ctx *c, size_t need)
     throw BfqError{BFQ_E_NOMEM, b};
 }
 
-// the length a text has on the device: a part that lacks its final newline gets one
+// the length a text has on the device (the shared pair of bfq_bgzf.hip: a part that lacks its final newline gets one, a
+// BGZF part is inflated); what is refused is passed on with the input's name in front
 static void cmp_measure(CmpInput &in, const char *which)
 {
-    in.len = 0;
-    for (int p = 0; p < in.nparts; p++) {
-        if (in.parts[p].len && in.parts[p].ref.null()) throw BfqError{BFQ_E_ARG, std::string(which) + ": null FASTQ text"};
-        in.addNl[p] = cmp_ends_with_newline(in.parts[p]) ? 0 : 1;
-        in.len += in.parts[p].len + in.addNl[p];
-    }
+    try { bfq_text_measure(in.parts, in.nparts, &in.M); }
+    catch (const BfqError &e) { if (e.code != BFQ_E_ARG) throw; throw BfqError{e.code, std::string(which) + ": " + e.msg}; }
+    in.len = in.M.bound;
 }
-static void cmp_upload(bfq_ctx *c, const CmpInput &in, u8 *d_dst)
+static void cmp_upload(bfq_ctx *c, CmpInput &in, const char *which, u8 *d_dst, u8 *d_stage)
 {
-    u64 at = 0;
-    for (int p = 0; p < in.nparts; p++) {
-        bfq_upload(c, d_dst + at, in.parts[p].ref, in.parts[p].len);
-        at += in.parts[p].len;
-        if (in.addNl[p]) { HIP_CHECK(hipMemsetAsync(d_dst + at, '\n', 1, c->stream)); at++; }
-    }
+    u64 ps[BFQ_MAX_PARTS + 1];
+    try { bfq_text_put(c, in.parts, &in.M, d_dst, d_stage, ps); }
+    catch (const BfqError &e) { if (e.code != BFQ_E_ARG) throw; throw BfqError{e.code, std::string(which) + ": " + e.msg}; }
+    in.len = ps[in.nparts];
 }
 // the record index of one text; what the parser refuses is passed on with the input's name in front
 static void cmp_index(bfq_ctx *c, const char *which, const u8 *d_text, u64 len, DevFastq *fq)
@@ -68,12 +55,13 @@ static void compare_core(bfq_ctx *c, CmpInput A, CmpInput B, const u8 *h_permz, 
     if (havePerm && !bfq_perm_header(h_permz, permzLen, &PN, nullptr, nullptr))
         throw BfqError{BFQ_E_ARG, "perm: not a BFQPERM1 container (magic, entry width, length or padding)"};
     const u64 offB = (A.len + 64 + 255) & ~255ull, sum = offB + ((B.len + 64 + 255) & ~255ull);   // every text 256-byte aligned and padded
-    if (c->wsLimit() && sum > c->wsLimit()) cmp_nomem(c, sum);
+    const u64 stage = std::max(A.M.stage, B.M.stage);           // a BGZF part's compressed bytes: behind both texts
+    if (c->wsLimit() && sum + stage > c->wsLimit()) cmp_nomem(c, sum + stage);
     bfq_phase("alloc");
-    u8 *d_a = c->textBuf(sum + 64), *d_b = d_a + offB;
+    u8 *d_a = c->textBuf(sum + stage + 64), *d_b = d_a + offB;
     bfq_phase("read_h2d");
-    cmp_upload(c, A, d_a);
-    cmp_upload(c, B, d_b);
+    cmp_upload(c, A, "A", d_a, d_a + sum);
+    cmp_upload(c, B, "B", d_b, d_a + sum);
     bfq_phase("alloc");
     const u64 maxLen = std::max(A.len, B.len);
     c->reserve(16 * (maxLen / 4096 + 16) + (64u << 20));
@@ -179,7 +167,7 @@ extern "C" int bfq_fastq_compare(bfq_ctx *c, const bfq_text_part *a, int na, con
         CmpSrc sa[BFQ_MAX_PARTS], sb[BFQ_MAX_PARTS];
         for (int p = 0; p < na; p++) sa[p] = CmpSrc{HostRef::mem(a[p].data), a[p].len};
         for (int p = 0; p < nb; p++) sb[p] = CmpSrc{HostRef::mem(b[p].data), b[p].len};
-        CmpInput A{sa, na, 0, {0}}, B{sb, nb, 0, {0}};
+        CmpInput A{sa, na, 0, {}}, B{sb, nb, 0, {}};
         try { compare_core(c, A, B, h_permz, permz_len, h_permz != nullptr || permz_len != 0, rep, h_diffs, cap_diffs); }
         catch (...) { memset(rep, 0, sizeof *rep); throw; }
     });
@@ -205,7 +193,7 @@ extern "C" int bfq_fastq_compare_fd(bfq_ctx *c, int a_fd, uint64_t a_len, int b_
             if (got != permz_len) throw BfqError{BFQ_E_ARG, "perm: the file is shorter than permz_len"};
         }
         const CmpSrc sa{HostRef::file(a_fd), a_len}, sb{HostRef::file(b_fd), b_len};
-        CmpInput A{&sa, 1, 0, {0}}, B{&sb, 1, 0, {0}};
+        CmpInput A{&sa, 1, 0, {}}, B{&sb, 1, 0, {}};
         try { compare_core(c, A, B, permz.data(), permz_len, perm_fd >= 0, rep, h_diffs, cap_diffs); }
         catch (...) { memset(rep, 0, sizeof *rep); throw; }
     });

@@ -27,6 +27,7 @@
 #include "bfq_internal_host.h"
 #include "bfq_reorder.h"
 #include "bfq_perm.h"
+#include "bfq_bgzf.h"
 
 static double now_s()
 {
@@ -476,35 +477,47 @@ bool bfq_outmap_close(bfq_outmap *m, uint64_t final_len)
 // ---------------------------------------------------------------- what a tool can do before the GPU is even initialised
 // eBWT rows of a FASTQ file, estimated from the complete records among its first bytes (0.98 of it: the estimate sizes the
 // background pre-fault of the outputs before the file has been parsed; a wrong guess costs time, never correctness)
+static double rows_per_byte(const uint8_t *b, size_t want)
+{
+    uint64_t rows = 0, used = 0;
+    size_t pos = 0;
+    for (;;) {
+        size_t e[4], p = pos;
+        int k = 0;
+        for (; k < 4; k++) {
+            const void *q = p < want ? memchr(b + p, '\n', want - p) : nullptr;
+            if (!q) break;
+            e[k] = (size_t)((const uint8_t *)q - b);
+            p = e[k] + 1;
+        }
+        if (k < 4) break;
+        size_t L = e[1] - (e[0] + 1);
+        if (L && b[e[1] - 1] == '\r') L--;
+        rows += L + 1;
+        used = p;
+        pos = p;
+    }
+    double rpb = used ? (double)rows / (double)used : 0.45;
+    return rpb > 0.5 ? 0.5 : rpb;
+}
+// (a BGZF file: from the records of its first member, inflated here with the text the kernel runs, and that member's ratio)
 extern "C" uint64_t bfq_fastq_rows_estimate(int fd, uint64_t len)
 {
     const size_t want = (size_t)(len < (1u << 20) ? len : (1u << 20));
     if (!want || fd < 0) return 0;
     std::vector<uint8_t> b(want);
-    double rpb = 0.45;
-    if (pread(fd, b.data(), want, 0) == (ssize_t)want) {
-        uint64_t rows = 0, used = 0;
-        size_t pos = 0;
-        for (;;) {
-            size_t e[4], p = pos;
-            int k = 0;
-            for (; k < 4; k++) {
-                const void *q = p < want ? memchr(b.data() + p, '\n', want - p) : nullptr;
-                if (!q) break;
-                e[k] = (size_t)((const uint8_t *)q - b.data());
-                p = e[k] + 1;
-            }
-            if (k < 4) break;
-            size_t L = e[1] - (e[0] + 1);
-            if (L && b[e[1] - 1] == '\r') L--;
-            rows += L + 1;
-            used = p;
-            pos = p;
-        }
-        if (used) rpb = (double)rows / (double)used;
+    if (pread(fd, b.data(), want, 0) != (ssize_t)want) return (uint64_t)(0.45 * (double)len * 0.98);
+    if (want >= 2 && b[0] == 0x1F && b[1] == 0x8B) {
+        bfq_bgzf_hdr h;
+        if (bfq_bgzf_member_header(b.data(), want, &h) != BFQ_BGZF_OK || !h.isize) return 0;
+        std::vector<uint8_t> text(h.isize);
+        std::vector<bfq_bgzf_tables> T(1);
+        u32 crcTab[256];
+        for (u32 i = 0; i < 256; i++) crcTab[i] = bfq_crc32_entry(i);
+        if (bfq_bgzf_inflate_payload(b.data() + h.payOff, h.payLen, text.data(), h.isize, h.crc, T.data(), crcTab, 0, 1) != BFQ_BGZF_OK) return 0;
+        return (uint64_t)(rows_per_byte(text.data(), text.size()) * (double)len * ((double)h.isize / (double)h.total) * 0.98);
     }
-    if (rpb > 0.5) rpb = 0.5;
-    return (uint64_t)(rpb * (double)len * 0.98);
+    return (uint64_t)(rows_per_byte(b.data(), want) * (double)len * 0.98);
 }
 
 // A tool opens its outputs first thing and registers them here; the entry point that later gets the same descriptor finds

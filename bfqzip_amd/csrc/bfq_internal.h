@@ -30,7 +30,7 @@ enum BfqKernel {
     K_REFINE_WAVE, K_REFINE_BIG, K_EMIT, K_RANK_BUILD, K_RANK_FINAL, K_LCP_FLAGS, K_CLUSTER,
     K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER,
     K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_POSBIN_L1, K_POSBIN_L2, K_POSBIN_APPLY,
-    K_CMP_CHECK, K_CMP_COMPARE, K_CMP_EMIT, K_NUM
+    K_CMP_CHECK, K_CMP_COMPARE, K_CMP_EMIT, K_BGZF, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -204,6 +204,24 @@ struct HostRef {
 };
 void bfq_upload(bfq_ctx *c, void *d_dst, HostRef src, size_t len);
 void bfq_download(bfq_ctx *c, HostRef dst, const void *d_src, size_t len);
+// A text source of a call -- memory or an open file -- measured and placed (bfq_bgzf.hip).  A FASTQ text cannot begin with
+// 1f 8b: a source that does is taken as BGZF, its members are inflated into the device text instead of uploaded, and every
+// size that follows from a source's length follows from its raw length.
+//   bfq_text_measure: per part, whether it is BGZF, its raw length, its directory; bound = what the parts take on the device at
+//     most (a part that lacks its final newline gets one; whether a BGZF part does is known only once it is inflated: room is
+//     left); stage = bytes of staging behind the text that the BGZF parts need (compressed bytes, directory, status), 0: none.
+//   bfq_text_put: the parts back to back at d_dst; pstart[p] = where part p starts, pstart[nparts] = the length of the text.
+struct TextSrc { HostRef ref; u64 len; };
+struct TextMeasure {
+    struct Part { bool bgzf = false; u64 raw = 0; u8 addNl = 0; std::vector<bfq_bgzf_member> dir; };
+    Part part[BFQ_MAX_PARTS];
+    int nparts = 0;
+    u64 bound = 0, stage = 0;
+    bool anyBgzf() const { return stage != 0; }
+};
+void bfq_text_measure(const TextSrc *parts, int nparts, TextMeasure *M);
+void bfq_text_put(bfq_ctx *c, const TextSrc *parts, TextMeasure *M, u8 *d_dst, u8 *d_stage, u64 *pstart);
+bool bfq_text_is_gzip(const TextSrc &t);        // begins with 1f 8b (the entry points that do not take BGZF refuse by it)
 void bfq_upload(bfq_ctx *c, void *d_dst, const void *h_src, size_t len);
 void bfq_download(bfq_ctx *c, void *h_dst, const void *d_src, size_t len);
 // background writes: the bytes [d_src, d_src + len) as they are once the work queued so far on the context's stream has

@@ -76,6 +76,8 @@ static void ro_lengths(const RoSrc *src, int np, u64 *tl)
 {
     for (int p = 0; p < np; p++) {
         if (src[p].len && src[p].ref.null()) throw BfqError{BFQ_E_ARG, "null FASTQ text"};
+        if (bfq_text_is_gzip(TextSrc{src[p].ref, src[p].len}))
+            throw BfqError{BFQ_E_ARG, "a bgzip-compressed (BGZF) input is not reordered as it is: inflate first (bfq_bgzf_inflate, bfq_bgzf -d)"};
         tl[p] = src[p].len + (ro_ends_with_newline(src[p]) ? 0 : 1);
     }
 }

@@ -1,9 +1,10 @@
 // builder_main.cpp -- drop-in for the reference's step-1 tools, over libbfqhip.so:
-//   gsufsort <in.fastq> --bwt --qs -o <OUT>                        (BFQzip.py:184)
+//   gsufsort <in.fastq | in.fastq.gz (BGZF)> --bwt --qs -o <OUT>   (BFQzip.py:184)
 //       -> <OUT>.bwt, <OUT>.bwt.qs   (terminator '#')
 //   eGap <in.fastq> --em --mem <MB> --qs -o <OUT> --lcp --lbytes 1  (BFQzip_ext.py:172-177)
 //       -> <OUT>.bwt (terminator byte 0), <OUT>.bwt.qs, <OUT>.<lbytes>.lcp
 // Exit status 0 on success, 1 on any error (the drivers check it, BFQzip.py:328-336).
+#include <sys/mman.h>
 #include "cli_common.h"
 
 int main(int argc, char **argv)
@@ -46,7 +47,14 @@ int main(int argc, char **argv)
     if (!ok) { fprintf(stderr, "%s: cannot create outputs for %s\n", tool, out.c_str()); return 1; }
     // the outputs' pages are allocated and zeroed by helper threads from now on -- beside the lease, the start of the HIP
     // runtime, the upload and the sort (a failure here only means they are written the slow way)
-    const uint64_t est = bfq_fastq_rows_estimate(buf.fd, buf.size), capRows = buf.size / 2 + 64;
+    uint64_t textLen = buf.size;                 // a bgzip-compressed input: the bounds follow from its raw length
+    if (void *m = buf.size ? mmap(nullptr, buf.size, PROT_READ, MAP_PRIVATE, buf.fd, 0) : MAP_FAILED; m != MAP_FAILED) {
+        uint64_t members = 0, raw = 0, bad = 0;
+        if (bfq_bgzf_probe((const uint8_t *)m, buf.size) && bfq_bgzf_index((const uint8_t *)m, buf.size, nullptr, 0, &members, &raw, &bad) == 0)
+            textLen = raw + 1;
+        munmap(m, buf.size);
+    }
+    const uint64_t est = bfq_fastq_rows_estimate(buf.fd, buf.size), capRows = textLen / 2 + 64;
     (void)bfq_output_prefault(bwt.fd, capRows, est);
     (void)bfq_output_prefault(qs.fd, capRows, est);
     if (wantLcp) (void)bfq_output_prefault(lcpf.fd, capRows * (uint64_t)lbytes, est * (uint64_t)lbytes);

@@ -40,6 +40,8 @@ extern "C" int bfq_glob_begin(bfq_ctx *c, const bfq_text_part *parts, int nparts
         std::vector<u8> addNl(nparts, 0);
         for (int p = 0; p < nparts; p++) {
             if (parts[p].len && !parts[p].data) throw BfqError{BFQ_E_ARG, "null FASTQ text"};
+            if (bfq_text_is_gzip(TextSrc{HostRef::mem(parts[p].data), parts[p].len}))
+                throw BfqError{BFQ_E_ARG, "a bgzip-compressed (BGZF) part is not taken in global mode: inflate first (bfq_bgzf_inflate, bfq_bgzf -d)"};
             len += parts[p].len;
             if (parts[p].len && parts[p].data[parts[p].len - 1] != (u8)'\n') { addNl[p] = 1; len++; }
         }

@@ -178,6 +178,42 @@ def output_names(inputs, out, paired):
     return [{"fastq": f, "dna": f + ".dna", "qs": f + ".qs", "hdr": b + ".h"} for f, b in zip(fq, base)]
 
 
+def inflated_name(path, out):
+    """Where a bgzip-compressed input is inflated to: beside the outputs (the directory of -o, else the input's), the name
+    without its .gz / .bgz and with .inflated in front of the extension (in.fastq.gz -> in.inflated.fastq)."""
+    base = os.path.basename(path)
+    for z in (".gz", ".bgz", ".bgzf"):
+        if base.endswith(z):
+            base = base[:-len(z)]
+            break
+    root, ext = os.path.splitext(base)
+    return os.path.join(os.path.dirname(out) if out else os.path.dirname(path), root + ".inflated" + ext)
+
+
+def inflate_inputs(eng, comm, inputs, out="", log=None):
+    """A bgzip-compressed (BGZF) input is inflated on the GPU to a plain file beside the outputs before the line index is
+    built (eng.bgzf_inflate_files), by rank 0, and the run goes on with that file: returns (the new input list, the files
+    written).  The blocks are cut by line number, which a compressed file does not give: one extra trip of the text through
+    the file system."""
+    new, tmp = [], []
+    for p in inputs:
+        with open(p, "rb") as f:
+            head = f.read(2)
+        if head[:2] != b"\x1f\x8b":
+            new.append(p)
+            continue
+        q = inflated_name(p, out)
+        if comm.rank == 0:
+            n = eng.bgzf_inflate_files(p, q)                        # (plain gzip, a damaged file: the library's message)
+            if log:
+                log(f"inflate: {p} -> {q}, {n} bytes")
+        new.append(q)
+        tmp.append(q)
+    if tmp:
+        comm.barrier()
+    return new, tmp
+
+
 def reordered_names(inputs, mode):
     """Where --reorder puts its intermediate files: <root>.reordered<ext> (mode 2, BFQzip_parallel.py:398) or
     <root>.random<ext> (mode 1, :421) beside every input."""
@@ -619,6 +655,8 @@ def main(argv=None):
     ap.add_argument("--restore", action="store_true",
                     help="the way back: the inputs are DNA.bsc QS.bsc [HDR.bsc] of a --compress run, -o OUT.fq the FASTQ file to write; "
                          "group k of the archive (one per block) is restored by rank k mod world")
+    ap.add_argument("--keep-inflated", action="store_true",
+                    help="a bgzip-compressed input is inflated to <name>.inflated<ext> beside the outputs first: keep that file")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
     if a.restore and (len(a.input) not in (2, 3) or not a.out):
@@ -662,6 +700,7 @@ def main(argv=None):
         if dist:
             dist.destroy_process_group()
         return 0
+    a.input, inflated = inflate_inputs(eng, comm, a.input, a.out, log=log)
     perm_path = reordered_names(a.input[:1], a.reorder)[0] + ".perm" if (a.keep_order and a.reorder) else None
     keep = dict(perm_path=perm_path) if perm_path else {}
     original = list(a.input)
@@ -684,6 +723,11 @@ def main(argv=None):
             log(f"keep-order: the {'containers' if compress else 'raw streams'} stay in run order; pass {perm_path} to bfq_restore -P")
     if a.report:                                                     # against what is in the outputs' order: the originals unless the run reordered for good
         write_reports(eng, comm, original if (perm_path or not a.reorder) else a.input, [n["fastq"] for n in names], log=log)
+    if inflated and not a.keep_inflated:
+        comm.barrier()
+        if comm.rank == 0:
+            for q in inflated:
+                os.remove(q)
     if a.v:
         print(f"[rank {comm.rank}] {tot}", flush=True)
     eng.close()

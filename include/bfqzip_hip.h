@@ -611,6 +611,49 @@ int bfq_fastq_compare   (bfq_ctx *c, const bfq_text_part *a, int na, const bfq_t
                          bfq_compare_report *rep, bfq_compare_diff *h_diffs, uint64_t cap_diffs);
 int bfq_fastq_compare_fd(bfq_ctx *c, int a_fd, uint64_t a_len, int b_fd, uint64_t b_len, int perm_fd, uint64_t permz_len,
                          bfq_compare_report *rep, bfq_compare_diff *h_diffs, uint64_t cap_diffs);
+/* ---- bgzip-compressed input: BGZF inflated on the device (k_bgzf.hip; the format and every bound: csrc/bfq_bgzf.h).
+ * A BGZF file (bgzip, htslib, BCL Convert) is a chain of independent gzip members of at most 64 KiB in and out; each states
+ * its size in its header ('B','C' subfield) and its CRC32 and raw size (ISIZE) in its trailer, so the place of every
+ * member's text is known before a byte is decoded.  One wave64 inflates one member: stored, fixed and dynamic blocks.
+ * There is no host inflate.  Plain gzip -- one member, no blocks to inflate side by side -- is refused with a message of its
+ * own that says to recompress with bgzip.
+ *   bfq_bgzf_probe : 1 when h begins with a well-formed BGZF member header, else 0.  A FASTQ text begins with '@', never
+ *     with 1f 8b.  Host only.
+ *   bfq_bgzf_index : the directory -- member i lies at [in_off, in_off + in_len) and inflates to [out_off, out_off + out_len)
+ *     of the text; *raw_len = the length of the text = the sum of the ISIZE fields.  Fills min(*n_members, cap) entries; m may
+ *     be NULL to size.  BFQ_E_ARG when a member header is refused: *n_members = the members before it, *raw_len theirs,
+ *     *bad_off = where the refused member starts.  A file need not end with the 28-byte EOF member.  Host only.
+ *   bfq_bgzf_inflate* : the text of h_in[0, len).  Capacity: cap >= the raw length (bfq_bgzf_index) -- every size that follows
+ *     from an input's length follows from its RAW length when the input is BGZF; a smaller cap is BFQ_E_ARG, nothing written.
+ *     Device memory: the compressed bytes + 24 bytes per member (+ the text, for the host and file forms), in the workspace.
+ *       bfq_bgzf_inflate        : host buffer out (pinned: direct DMA)
+ *       bfq_bgzf_inflate_device : device buffer out; the text never exists on the host
+ *       bfq_bgzf_inflate_fd     : open files; out_fd < 0: inflate and verify only
+ * Refusals: BFQ_E_ARG, bfq_last_error() = "damaged BGZF input: member <i> at byte <off>: <reason>", the lowest failing member
+ *   of the file, one reason per rule: header (not gzip; FLG != 4; a subfield past XLEN; no BC subfield; member size below
+ *   XLEN + 20 or past the end of the input; ISIZE > 65536) and payload (bits needed past the payload; output past ISIZE; a
+ *   distance before the member's first byte; over-subscribed or incomplete code lengths -- the single one-bit distance code
+ *   and the empty distance set of a literal-only block stand; symbols 286 / 287 / 30 / 31; no end-of-block code; a repeat with
+ *   nothing before it or past HLIT + HDIST; HLIT > 286 or HDIST > 30; stored LEN != ~NLEN or past the payload; block type 3;
+ *   length != ISIZE; CRC32 mismatch; payload bytes after the final block).  A refused member writes nothing outside its own
+ *   [out_off, out_off + out_len); the output of a refused call is undefined in the members' ranges and untouched beyond the raw
+ *   length.  The context stays usable.
+ * Transparent input: a text source that begins with 1f 8b is taken as BGZF wherever these take FASTQ text -- memory or
+ *   descriptor -- and is inflated into the device text instead of uploaded: bfq_fastq_run, bfq_fastq_run_streams,
+ *   bfq_fastq_run_job (any part, mixed with plain parts), bfq_fastq_build_ebwt, bfq_fastq_build_ebwt_fd, both sides of
+ *   bfq_fastq_compare*.  A part that lacks its final newline gets one, as a plain part does.  Capacity rules: wherever a
+ *   comment above says that the input length ("len", "the input length", "len / 2 + 64") is enough for an output or bounds
+ *   it, read the RAW length + 1 per BGZF part (bfq_bgzf_index) for such a source: eBWT / QS rows <= (raw + 1) / 2 + 64, the
+ *   streams <= raw + 1 each, the FASTQ text <= raw + 16 + 5 per part; bfq_fastq_rows_estimate() estimates from the first
+ *   member.  Refusals of such a source: as bfq_bgzf_inflate ("A: " / "B: " in front in the compare).
+ * bfq_fastq_reorder* and bfq_glob_begin do not take BGZF parts: BFQ_E_ARG with a message that says "inflate first". */
+typedef struct bfq_bgzf_member { uint64_t in_off, out_off; uint32_t in_len, out_len; } bfq_bgzf_member;
+int bfq_bgzf_probe(const uint8_t *h, uint64_t len);
+int bfq_bgzf_index(const uint8_t *h_in, uint64_t len, bfq_bgzf_member *m, uint64_t cap, uint64_t *n_members,
+                   uint64_t *raw_len, uint64_t *bad_off);
+int bfq_bgzf_inflate(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+int bfq_bgzf_inflate_device(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
+int bfq_bgzf_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, int out_fd, uint64_t *out_len);
 /* device-resident form (input and output in device memory): bfq_stream_reserve(len) sizes the workspace once */
 int bfq_stream_reserve(bfq_ctx *c, uint64_t len);
 int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
