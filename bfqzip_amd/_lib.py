@@ -34,6 +34,8 @@ SYMBOLS = [
     "bfq_fastq_restore_groups", "bfq_stream_members", "bfq_fastq_restore_grouped", "bfq_fastq_restore_grouped_fd",
     "bfq_fastq_compare", "bfq_fastq_compare_fd",
     "bfq_bgzf_probe", "bfq_bgzf_index", "bfq_bgzf_inflate", "bfq_bgzf_inflate_device", "bfq_bgzf_inflate_fd",
+    "bfq_bgzf_deflate_bound", "bfq_bgzf_deflate_host", "bfq_bgzf_deflate", "bfq_bgzf_deflate_device", "bfq_bgzf_deflate_fd",
+    "bfq_fastq_restore_bgzf_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -242,6 +244,13 @@ def lib():
         L.bfq_bgzf_inflate.argtypes = [vp, vp, u64, vp, u64, pu64]
         L.bfq_bgzf_inflate_device.argtypes = [vp, vp, u64, vp, u64, pu64]
         L.bfq_bgzf_inflate_fd.argtypes = [vp, C.c_int, u64, C.c_int, pu64]
+        L.bfq_bgzf_deflate_bound.restype = u64
+        L.bfq_bgzf_deflate_bound.argtypes = [u64]
+        L.bfq_bgzf_deflate_host.argtypes = [vp, u64, C.c_int, vp, u64, pu64]
+        L.bfq_bgzf_deflate.argtypes = [vp, vp, u64, C.c_int, vp, u64, pu64]
+        L.bfq_bgzf_deflate_device.argtypes = [vp, vp, u64, C.c_int, vp, u64, pu64]
+        L.bfq_bgzf_deflate_fd.argtypes = [vp, C.c_int, u64, C.c_int, C.c_int, pu64]
+        L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]
         L.bfq_prof_reset.argtypes = [vp]

@@ -211,6 +211,24 @@ def bgzf_index(blob):
     return [(int(e.in_off), int(e.out_off), int(e.in_len), int(e.out_len)) for e in m[:int(n.value)]], int(raw.value)
 
 
+def bgzf_deflate_bound(n):
+    """bfq_bgzf_deflate_bound: the bytes the BGZF form of a text of n bytes takes at most (n + 31 per member of 65 280 + 28)."""
+    return int(_lib.lib().bfq_bgzf_deflate_bound(int(n)))
+
+
+def bgzf_deflate_model(text, level=1):
+    """The BGZF form of a text by the host form of the writer (bfq_bgzf_deflate_host: one thread, no GPU) as a uint8 array:
+    the statement of the format -- Engine.bgzf_deflate gives the same bytes.  level 0: every member stored."""
+    text = _u8(text)
+    L = _lib.lib()
+    out = np.empty(bgzf_deflate_bound(len(text)), np.uint8)
+    ol = C.c_uint64(0)
+    rc = L.bfq_bgzf_deflate_host(_ptr(text) if len(text) else None, len(text), int(level), _ptr(out), len(out), C.byref(ol))
+    if rc != 0:
+        raise BfqError(rc, "bgzf_deflate_model: level other than 0 / 1, or an input that is already compressed (1f 8b)")
+    return out[:int(ol.value)]
+
+
 def text_len(a):
     """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
     a = _u8(a)
@@ -225,6 +243,8 @@ class HostText:
     """Host-side text helpers of libbfqhip.so (no GPU involved)."""
     bgzf_probe = staticmethod(bgzf_probe)
     bgzf_index = staticmethod(bgzf_index)
+    bgzf_deflate_bound = staticmethod(bgzf_deflate_bound)
+    bgzf_deflate_model = staticmethod(bgzf_deflate_model)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -593,6 +613,39 @@ class Engine:
                 if fd >= 0:
                     os.close(fd)
 
+    def bgzf_deflate(self, text, level=1, out=None):
+        """The BGZF form (.fq.gz as bgzip writes it: members of 65 280 bytes, the EOF member) of a text, deflated on the GPU
+        (bfq_bgzf_deflate), as a uint8 array; the same bytes as HostText.bgzf_deflate_model.  level 0: every member stored.
+        `out`: a uint8 array to fill, of at least HostText.bgzf_deflate_bound(len(text)); the result is a view of it.  A
+        smaller one, another level or a text that is already compressed (1f 8b) raise BfqError (BFQ_E_ARG), nothing written."""
+        text = _u8(text)
+        if out is None:
+            out = np.empty(bgzf_deflate_bound(len(text)), np.uint8)
+        ol = C.c_uint64(0)
+        self._ck(self.L.bfq_bgzf_deflate(self.h, _ptr(text) if len(text) else None, len(text), int(level), _ptr(out), len(out), C.byref(ol)))
+        return out[:int(ol.value)]
+
+    def bgzf_deflate_device(self, d_in, n, level=1):
+        """bfq_bgzf_deflate_device: the BGZF form of the n bytes of text at the device address d_in, as a uint8 array."""
+        out = np.empty(bgzf_deflate_bound(n), np.uint8)
+        ol = C.c_uint64(0)
+        self._ck(self.L.bfq_bgzf_deflate_device(self.h, C.c_void_p(d_in), int(n), int(level), _ptr(out), len(out), C.byref(ol)))
+        return out[:int(ol.value)]
+
+    def bgzf_deflate_files(self, src, dst, level=1):
+        """bfq_bgzf_deflate_fd on named files; returns the length of the BGZF file."""
+        import os
+        fds = []
+        try:
+            fds.append(os.open(src, os.O_RDONLY))
+            fds.append(os.open(dst, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            ol = C.c_uint64(0)
+            self._ck(self.L.bfq_bgzf_deflate_fd(self.h, fds[0], os.fstat(fds[0]).st_size, int(level), fds[1], C.byref(ol)))
+            return int(ol.value)
+        finally:
+            for fd in fds:
+                os.close(fd)
+
     def ebwt_decode(self, bwtz, qsz, out=None):
         """The line streams (dna, qs) of a pair of eBWT-domain containers (fastq_job(compress=2)); returns (dna, qs, n_reads)."""
         bwtz, qsz = _u8(bwtz), _u8(qsz)
@@ -647,13 +700,17 @@ class Engine:
                                               _ptr(out), len(out), C.byref(ol), C.byref(nr)))
         return out[:int(ol.value)], int(nr.value)
 
-    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None, grouped=False):
+    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None, grouped=False, bgzf=False, level=1):
         """bfq_fastq_restore_fd on named files (hdr_path may be None); returns (bytes written, n_reads).  perm_path: the
         BFQPERM1 file of the reordering (bfq_fastq_restore_ordered_fd): the text in the order before it.  grouped: True or
-        (first, count) as fastq_restore's `groups` (bfq_fastq_restore_grouped_fd); not with perm_path."""
+        (first, count) as fastq_restore's `groups` (bfq_fastq_restore_grouped_fd); not with perm_path.  bgzf: out_path is
+        written as BGZF (bfq_fastq_restore_bgzf_fd: the text is deflated on the device at `level` and never crosses to the
+        host); the bytes written are the compressed ones; not with grouped."""
         import os
         if grouped and perm_path is not None:
             raise ValueError("fastq_restore_files: grouped and perm_path do not go together")
+        if grouped and bgzf:
+            raise ValueError("fastq_restore_files: grouped and bgzf do not go together (the grouped restore writes plain text)")
         fds = []
         try:
             for p in (dna_path, qs_path, hdr_path, perm_path):
@@ -661,7 +718,11 @@ class Engine:
             fds.append(os.open(out_path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
             ol, nr = C.c_uint64(0), C.c_uint64(0)
             size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
-            if grouped:
+            if bgzf:
+                raw = C.c_uint64(0)
+                self._ck(self.L.bfq_fastq_restore_bgzf_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
+                                                          fds[3], size(fds[3]), int(level), fds[4], C.byref(ol), C.byref(raw), C.byref(nr)))
+            elif grouped:
                 first, count = (0, None) if grouped is True else grouped
                 self._ck(self.L.bfq_fastq_restore_grouped_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
                                                              int(first), ALL_GROUPS if count is None else int(count), fds[4],

@@ -72,6 +72,7 @@ BfqEnv bfq_env_read()
         e.prefaultPause = geti("BFQ_PREFAULT_PAUSE", 0) != 0;
         e.compactWin = getu("BFQ_COMPACT_WIN", 0);
         e.compactRing = getu("BFQ_COMPACT_RING", 0);
+        e.bgzfBatch = getu("BFQ_BGZF_BATCH", 0);
         e.dnaStatic = geti("BFQ_DNA_STATIC", 0);
         e.dnacK = geti("BFQ_DNAC_K", 0); e.dnacH = geti("BFQ_DNAC_H", 0); e.dnacW = geti("BFQ_DNAC_W", 0); e.dnacSkip = geti("BFQ_DNAC_TSKIP", -1);
         return e;

@@ -35,6 +35,7 @@ struct BfqEnv {
     unsigned long long compactRing = 0; // BFQ_COMPACT_RING: entries of the interval refinement's ring queue there (default: what the cap leaves; small values test the chunked levels / the move to host memory)
     unsigned long long compactWin = 0;  // BFQ_COMPACT_WIN: rows of the LCP file in flight there (default 64 Mi; small values test the windowing)
     bool prefaultPause = false;     // BFQ_PREFAULT_PAUSE=1: output files are not allocated while an input file is being read (default: both at once)
+    unsigned long long bgzfBatch = 0;   // BFQ_BGZF_BATCH: text bytes per batch of the BGZF writer (rounded down to whole members of 65 280; 0: chosen from the arena)
     bool noOutmap = false;          // BFQ_NO_OUTMAP: the tools write their outputs with pwrite instead of through a mapping (test knob)
 };
 BfqEnv bfq_env_read();

@@ -382,6 +382,7 @@ struct RsSink {
     u64 cap = ~0ull;
     std::function<void(u64)> sized;                 // the length of the text is known (before it is formatted)
     std::function<void(const u8 *, u64)> put;
+    std::function<size_t(u64)> extraWs;             // arena bytes put() takes above a text of at most this length (unset: none)
 };
 
 // permz != nullptr: the records leave in the order before the reordering whose BFQPERM1 container this is
@@ -392,7 +393,7 @@ static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const Rs
     if (n_reads) *n_reads = 0;
     RsPlan P;
     rs_plan(dna, qs, hdr, haveHdr, P);
-    const size_t afterDecode = rs_index_bytes(P, permz != nullptr) + P.textBound + 4096;
+    const size_t afterDecode = rs_index_bytes(P, permz != nullptr) + P.textBound + 4096 + (sink.extraWs ? sink.extraWs(P.textBound) : 0);
     u8 *dD = nullptr, *dQ = nullptr, *dH = nullptr;
     u64 lenD = P.rawD, lenQ = P.rawQ;
     if (P.ebwt) {
@@ -587,6 +588,47 @@ extern "C" int bfq_fastq_restore_ordered_fd(bfq_ctx *c, int dna_fd, uint64_t dna
                                             int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads)
 {
     return rs_run_fd(c, dna_fd, dna_len, qs_fd, qs_len, hdr_fd, hdr_len, true, perm_fd, permz_len, out_fd, out_len, n_reads);
+}
+
+// The text deflated where it lies (bfq_deflate.hip): the FASTQ text never crosses to the host.
+size_t bfq_deflate_need(bfq_ctx *c, u64 len, bool hostSrc, size_t beside);
+u64 bfq_deflate_core(bfq_ctx *c, const u8 *d_text, HostRef h_src, u64 len, int level, HostRef dst, bool held, size_t beside);
+
+extern "C" int bfq_fastq_restore_bgzf_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                         int perm_fd, uint64_t permz_len, int level, int out_fd, uint64_t *out_len, uint64_t *raw_len,
+                                         uint64_t *n_reads)
+{
+    if (out_len) *out_len = 0;
+    if (raw_len) *raw_len = 0;
+    if (n_reads) *n_reads = 0;
+    return guarded(c, [&] {
+        if (dna_fd < 0 || qs_fd < 0 || out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
+        if (level != 0 && level != 1) throw BfqError{BFQ_E_ARG, "level: 0 (every member stored) or 1 (the compressor)"};
+        const bool haveHdr = hdr_fd >= 0, ordered = perm_fd >= 0;
+        RsMap mD, mQ, mH, mP;
+        struct stat st;
+        if (ordered && fstat(perm_fd, &st) == 0 && S_ISREG(st.st_mode) && (u64)st.st_size < permz_len) permz_len = (u64)st.st_size;
+        const RsSrc permz{ordered ? mP.open(perm_fd, permz_len) : nullptr, ordered ? permz_len : 0};
+        const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
+        const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
+        try {
+            u64 zl = 0;
+            RsSink sink;
+            sink.extraWs = [&](u64 bound) { return bfq_deflate_need(c, bound, false, 0); };
+            sink.put = [&](const u8 *d_text, u64 len) { zl = bfq_deflate_core(c, d_text, HostRef{}, len, level, HostRef::file(out_fd, 0), true, 0); };
+            uint64_t ol = 0;
+            restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads, ordered ? &permz : nullptr);
+            if (ftruncate(out_fd, (off_t)zl) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, "cannot size the output file"};
+            if (out_len) *out_len = zl;
+            if (raw_len) *raw_len = ol;
+        } catch (...) {
+            if (ftruncate(out_fd, 0) != 0) {}
+            if (out_len) *out_len = 0;
+            if (raw_len) *raw_len = 0;
+            if (n_reads) *n_reads = 0;
+            throw;
+        }
+    });
 }
 
 // ---- the grouped restore ------------------------------------------------------------------------------------------------

@@ -1,5 +1,7 @@
-// bgzf_main.cpp -- bgzip-compressed FASTQ to text on the GPU (not a tool of the reference, which takes plain text only):
+// bgzf_main.cpp -- bgzip-compressed FASTQ to text and back on the GPU (not a tool of the reference, which takes plain text only):
 //     bfq_bgzf -d IN.fq.gz -o OUT.fq [-V]     inflate
+//     bfq_bgzf -c IN.fq -o OUT.fq.gz [-0] [-V]  deflate: BGZF members of 65 280 bytes and the EOF member (bfq_bgzf_deflate_fd);
+//                                             -0: every member stored.  An input that is already compressed is refused.
 //     bfq_bgzf -t IN.fq.gz                    inflate and verify (every member's length and CRC32), writing nothing
 //     bfq_bgzf -l IN.fq.gz                    members, raw length, ratio: no GPU is touched
 // The input is BGZF (bgzip, htslib, BCL Convert): include/bfqzip_hip.h, bfq_bgzf_inflate_fd.  Plain gzip is refused with a
@@ -12,9 +14,11 @@
 
 static int usage(const char *argv0)
 {
-    fprintf(stderr, "usage: %s -d IN.fq.gz -o OUT.fq [-V] | -t IN.fq.gz | -l IN.fq.gz\n"
+    fprintf(stderr, "usage: %s -d IN.fq.gz -o OUT.fq [-V] | -c IN.fq -o OUT.fq.gz [-0] [-V] | -t IN.fq.gz | -l IN.fq.gz\n"
                     "  -d <arg>  bgzip-compressed (BGZF) input to inflate (with -o)\n"
-                    "  -o <arg>  output text\n"
+                    "  -c <arg>  text to compress into BGZF (with -o)\n"
+                    "  -0        with -c: every member stored\n"
+                    "  -o <arg>  output (text with -d, BGZF with -c)\n"
                     "  -t <arg>  inflate and verify only: no output is written\n"
                     "  -l <arg>  print members, compressed and raw length, ratio, and exit (no GPU)\n"
                     "  -V        phase timeline on stderr\n", argv0);
@@ -47,10 +51,11 @@ int main(int argc, char **argv)
     bfq_phase("start");
     std::string input, output;
     char mode = 0;
-    int opt;
-    while ((opt = getopt(argc, argv, "d:t:l:o:Vh")) != -1) {
+    int opt, level = 1;
+    while ((opt = getopt(argc, argv, "d:c:t:l:o:0Vh")) != -1) {
         switch (opt) {
-        case 'd': case 't': case 'l':
+        case '0': level = 0; break;
+        case 'd': case 'c': case 't': case 'l':
             if (mode) return usage(argv[0]);
             mode = (char)opt; input = optarg; break;
         case 'o': output = optarg; break;
@@ -58,22 +63,24 @@ int main(int argc, char **argv)
         default: return usage(argv[0]);
         }
     }
-    if (!mode || (mode == 'd') != !output.empty()) return usage(argv[0]);
+    const bool writes = mode == 'd' || mode == 'c';
+    if (!mode || writes != !output.empty() || (level == 0 && mode != 'c')) return usage(argv[0]);
     InFile in;
     if (!in.open(input)) { fprintf(stderr, "bfq_bgzf: cannot read %s\n", input.c_str()); return 1; }
     if (mode == 'l') return list_members(in, input);
     OutFile out;
-    if (mode == 'd' && !out.open(output)) { perror("bfq_bgzf"); return 1; }
+    if (writes && !out.open(output)) { perror("bfq_bgzf"); return 1; }
     bfq_params P;
     bfq_default_params(&P);
     bfq_ctx *c = create_on_free_gpu("bfq_bgzf", &P);
     if (!c) return 1;
     uint64_t outLen = 0;
-    const int rc = bfq_bgzf_inflate_fd(c, in.fd, in.size, mode == 'd' ? out.fd : -1, &outLen);
+    const int rc = mode == 'c' ? bfq_bgzf_deflate_fd(c, in.fd, in.size, level, out.fd, &outLen)
+                               : bfq_bgzf_inflate_fd(c, in.fd, in.size, mode == 'd' ? out.fd : -1, &outLen);
     if (rc) {
         fprintf(stderr, "bfq_bgzf: %s: %s\n", input.c_str(), bfq_last_error(c));
         bfq_destroy(c);
-        if (mode == 'd' && ftruncate(out.fd, 0) != 0) perror("bfq_bgzf");
+        if (writes && ftruncate(out.fd, 0) != 0) perror("bfq_bgzf");
         return 1;
     }
     bfq_phase("teardown");
@@ -82,6 +89,7 @@ int main(int argc, char **argv)
     bfq_destroy(c);
     if (!closed) { perror("bfq_bgzf"); return 1; }
     bfq_phase_report("bfq_bgzf");
-    printf("%llu bytes%s\n", (unsigned long long)outLen, mode == 't' ? " verified" : "");
+    if (mode == 'c') printf("%llu bytes -> %llu bytes\n", (unsigned long long)in.size, (unsigned long long)outLen);
+    else printf("%llu bytes%s\n", (unsigned long long)outLen, mode == 't' ? " verified" : "");
     return 0;
 }

@@ -1,6 +1,6 @@
 // restore_main.cpp -- the way back from the compressed streams to a FASTQ file (not a tool of the reference, which leaves
 // this to `7z x` / `bsc d` + `paste`):
-//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] -o OUT.fq [-V]
+//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z] -o OUT.fq [-V]
 // The inputs are what `bsc e`, bfq_fastq_job.compress_streams = 1 / 2 / 3 and parallel.py --compress write
 // (include/bfqzip_hip.h, bfq_fastq_restore_fd).  -P PERM: the BFQPERM1 file `bfq_reorder -P` / `parallel.py --keep-order`
 // wrote for the run: the records come back in the order of the original file (bfq_fastq_restore_ordered_fd).
@@ -8,7 +8,8 @@
 // -- one per block of a sharded run -- and the device holds one group at a time, so the archive may be larger than the
 // device; several BFQEBWT1 members are taken.  -G FIRST[:COUNT]: only those groups.  -l: the plan of the groups, one line
 // each, and nothing else: no GPU is touched and no output is created.  -g / -G with -P is a usage error: records in the
-// original order draw on all groups at once.  Exit status 0 on success; 1 with the library's message otherwise, and then
+// original order draw on all groups at once.  -z: OUT.fq is written as BGZF (.fq.gz: bfq_fastq_restore_bgzf_fd, the text is
+// deflated on the device and never crosses to the host), with and without -P; not with -g / -G.  Exit status 0 on success; 1 with the library's message otherwise, and then
 // OUT.fq is left empty.
 #include <unistd.h>
 #include <sys/mman.h>
@@ -17,7 +18,7 @@
 
 static int usage(const char *argv0)
 {
-    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] -o OUT.fq [-V]\n"
+    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z] -o OUT.fq [-V]\n"
                     "  -d <arg>  container(s) of the DNA stream (OUT.fq.dna; BFQDNAC1 / BFQRANS2 members, or one BFQEBWT1) (REQUIRED)\n"
                     "  -q <arg>  container(s) of the quality stream (OUT.fq.qs) (REQUIRED)\n"
                     "  -H <arg>  container(s) of the header stream (OUT.h); without it every header line is \"@\"\n"
@@ -25,6 +26,7 @@ static int usage(const char *argv0)
                     "  -g        block by block: one group of members (a block of a sharded run) on the device at a time\n"
                     "  -G <arg>  FIRST[:COUNT]: only these groups of the plan (COUNT omitted: to the end)\n"
                     "  -l        print the plan of the groups and exit (no GPU, no output file; -o not needed)\n"
+                    "  -z        write the output as BGZF (OUT.fq.gz), deflated on the GPU; not with -g / -G\n"
                     "  -o <arg>  output FASTQ (REQUIRED)\n"
                     "  -V        phase timeline on stderr\n", argv0);
     return 1;
@@ -65,10 +67,10 @@ int main(int argc, char **argv)
 {
     bfq_phase("start");
     std::string dna, qs, hdr, perm, output;
-    bool grouped = false, list = false;
+    bool grouped = false, list = false, bgzf = false;
     uint64_t first = 0, count = ~0ull;
     int opt;
-    while ((opt = getopt(argc, argv, "d:q:H:P:o:gG:lVh")) != -1) {
+    while ((opt = getopt(argc, argv, "d:q:H:P:o:gG:lzVh")) != -1) {
         switch (opt) {
         case 'd': dna = optarg; break;
         case 'q': qs = optarg; break;
@@ -85,6 +87,7 @@ int main(int argc, char **argv)
             break;
         }
         case 'l': list = true; break;
+        case 'z': bgzf = true; break;
         case 'V': bfq_phase_enable(1); break;
         default: return usage(argv[0]);
         }
@@ -93,6 +96,11 @@ int main(int argc, char **argv)
     if ((grouped || list) && !perm.empty()) {
         fprintf(stderr, "bfq_restore: -g / -G / -l do not go with the permutation -P %s: records in the original order draw on all groups at once; "
                         "restore the archive in one piece (without -g)\n", perm.c_str());
+        return usage(argv[0]);
+    }
+    if (bgzf && grouped) {
+        fprintf(stderr, "bfq_restore: -z does not go with -g / -G: the grouped restore writes plain text; restore the archive in one piece (without -g), "
+                        "or compress the text afterwards (bfq_bgzf -c)\n");
         return usage(argv[0]);
     }
     InFile fd, fq, fh, fp;
@@ -121,14 +129,16 @@ int main(int argc, char **argv)
         if (mq != MAP_FAILED) munmap(mq, fq.size);
         if (mh != MAP_FAILED) munmap(mh, fh.size);
         if (bound < 0) { fprintf(stderr, "bfq_restore: the inputs are not containers (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQNAME1 / BFQQUAL1 / BFQEBWT1)\n"); outText.close(); return 1; }
-        if (bound >= (64 << 20)) (void)bfq_output_prefault(outText.fd, (uint64_t)bound + 4096, (uint64_t)bound / 2);
+        if (bound >= (64 << 20) && !bgzf) (void)bfq_output_prefault(outText.fd, (uint64_t)bound + 4096, (uint64_t)bound / 2);
     }
     bfq_params P;
     bfq_default_params(&P);
     bfq_ctx *c = create_on_free_gpu("bfq_restore", &P);
     if (!c) return 1;
-    uint64_t outLen = 0, reads = 0;
-    const int rc = grouped ? bfq_fastq_restore_grouped_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, first, count, outText.fd, &outLen, &reads)
+    uint64_t outLen = 0, reads = 0, rawLen = 0;
+    const int rc = bgzf ? bfq_fastq_restore_bgzf_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd, fp.size, 1,
+                                                    outText.fd, &outLen, &rawLen, &reads)
+                   : grouped ? bfq_fastq_restore_grouped_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, first, count, outText.fd, &outLen, &reads)
                    : perm.empty() ? bfq_fastq_restore_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, outText.fd, &outLen, &reads)
                                 : bfq_fastq_restore_ordered_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, fp.fd, fp.size,
                                                                outText.fd, &outLen, &reads);
@@ -143,6 +153,7 @@ int main(int argc, char **argv)
     bfq_destroy(c);
     if (!closed) { perror("bfq_restore"); return 1; }
     bfq_phase_report("bfq_restore");
-    printf("%llu reads, %llu bytes\n", (unsigned long long)reads, (unsigned long long)outLen);
+    if (bgzf) printf("%llu reads, %llu bytes -> %llu bytes\n", (unsigned long long)reads, (unsigned long long)rawLen, (unsigned long long)outLen);
+    else printf("%llu reads, %llu bytes\n", (unsigned long long)reads, (unsigned long long)outLen);
     return 0;
 }

@@ -654,6 +654,42 @@ int bfq_bgzf_index(const uint8_t *h_in, uint64_t len, bfq_bgzf_member *m, uint64
 int bfq_bgzf_inflate(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
 int bfq_bgzf_inflate_device(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
 int bfq_bgzf_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, int out_fd, uint64_t *out_len);
+/* ---- bgzip-compressed output: BGZF members deflated on the device (k_deflate.hip; the format and every bound:
+ * csrc/bfq_deflate.h).  A text of len bytes is cut at multiples of 65 280 bytes (htslib's member size; the cut depends on
+ * nothing else); every piece becomes one BGZF member -- htslib's 18-byte header, a raw deflate payload, CRC32 and ISIZE --
+ * and the 28-byte EOF member ends the file (an empty text gives exactly those 28 bytes).  Any gzip reader takes the result
+ * (htslib, zcat, Python's gzip), and bfq_bgzf_inflate* and every transparent input above do.
+ *   payload : matches inside the member only (distance <= 32 768, length 3..258), found through one hash slot per position
+ *     and a distance-1 probe, taken greedily where they are estimated to cost fewer bits than their literals; one dynamic
+ *     block (code lengths limited to 15, the code-length code to 7, the header run-length coded).  A member whose coded form
+ *     would be no shorter than the stored form is one stored block: a member is at most its piece + 31 bytes, and
+ *       bfq_bgzf_deflate_bound(len) = len + 31 * ceil(len / 65280) + 28       (host arithmetic; what callers size buffers with)
+ *   The output is deterministic: the same text gives the same bytes on every run, with any batch size and grid, and
+ *   bfq_bgzf_deflate_host -- the host form of csrc/bfq_deflate.h: one thread, no context, no GPU -- gives the same bytes as
+ *   the kernel.  It is the statement of the format and what the tests compare with; NO entry point falls back to it: a call
+ *   that cannot run on the device fails.
+ *   level : 0 = every member stored, 1 = the compressor; anything else is BFQ_E_ARG.
+ *   cap   : cap < bfq_bgzf_deflate_bound(len) is BFQ_E_ARG, nothing written.
+ *   An input that begins with 1f 8b is refused (BFQ_E_ARG: "the input is already compressed ...").
+ *       bfq_bgzf_deflate        : host text in, host buffer out
+ *       bfq_bgzf_deflate_device : device text in (d_in), host buffer out; the text never exists on the host
+ *       bfq_bgzf_deflate_fd     : open files (out_fd is sized to *out_len)
+ *   The host-memory and file forms work in batches of text: whole members, a default chosen from the arena (6144 members,
+ *   fewer under a workspace cap), BFQ_BGZF_BATCH = bytes of text per batch overrides it.  Device memory: one batch of text, a
+ *   worst-case slot per member of the batch, 255 KiB of tokens per workgroup of the launch (at most 1536) and two output
+ *   buffers -- it does not grow with len.  The output of a batch leaves through the background writers while the next batch
+ *   is uploaded and deflated.
+ *   bfq_fastq_restore_bgzf_fd : bfq_fastq_restore_fd (perm_fd < 0) or bfq_fastq_restore_ordered_fd (perm_fd >= 0) with the
+ *     text deflated where it lies: out_fd receives the BGZF file, *out_len its length, *raw_len the length of the text.  The
+ *     FASTQ text never crosses to the host.  The grouped restore has no such form. */
+uint64_t bfq_bgzf_deflate_bound(uint64_t len);
+int bfq_bgzf_deflate_host(const uint8_t *h_in, uint64_t len, int level, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+int bfq_bgzf_deflate(bfq_ctx *c, const uint8_t *h_in, uint64_t len, int level, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+int bfq_bgzf_deflate_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, int level, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+int bfq_bgzf_deflate_fd(bfq_ctx *c, int in_fd, uint64_t len, int level, int out_fd, uint64_t *out_len);
+int bfq_fastq_restore_bgzf_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                              int perm_fd, uint64_t permz_len, int level, int out_fd, uint64_t *out_len, uint64_t *raw_len,
+                              uint64_t *n_reads);
 /* device-resident form (input and output in device memory): bfq_stream_reserve(len) sizes the workspace once */
 int bfq_stream_reserve(bfq_ctx *c, uint64_t len);
 int bfq_stream_compress_device(bfq_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
