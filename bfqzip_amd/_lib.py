@@ -36,6 +36,8 @@ SYMBOLS = [
     "bfq_bgzf_probe", "bfq_bgzf_index", "bfq_bgzf_inflate", "bfq_bgzf_inflate_device", "bfq_bgzf_inflate_fd",
     "bfq_bgzf_deflate_bound", "bfq_bgzf_deflate_host", "bfq_bgzf_deflate", "bfq_bgzf_deflate_device", "bfq_bgzf_deflate_fd",
     "bfq_fastq_restore_bgzf_fd",
+    "bfq_gzip_probe", "bfq_gzip_measure", "bfq_gzip_inflate", "bfq_gzip_inflate_device", "bfq_gzip_inflate_fd", "bfq_gzip_inflate_host",
+    "bfq_gzip_host_error",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -80,6 +82,17 @@ class RestoreGroup(C.Structure):
 
 class BgzfMember(C.Structure):
     _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("out_len", C.c_uint32)]
+
+
+class GzipStats(C.Structure):
+    """bfq_gzip_stats: members, pieces, decoders started, decoders of the chain, candidates the chain ran past, decoders discarded"""
+    _fields_ = [(k, C.c_uint64) for k in ("members", "pieces", "decoders", "chain", "skipped", "discarded")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "GzipStats(%s)" % ", ".join("%s=%d" % kv for kv in self.as_dict().items())
 
 
 CMP_SYMS = 6
@@ -250,6 +263,15 @@ def lib():
         L.bfq_bgzf_deflate.argtypes = [vp, vp, u64, C.c_int, vp, u64, pu64]
         L.bfq_bgzf_deflate_device.argtypes = [vp, vp, u64, C.c_int, vp, u64, pu64]
         L.bfq_bgzf_deflate_fd.argtypes = [vp, C.c_int, u64, C.c_int, C.c_int, pu64]
+        pgs = C.POINTER(GzipStats)
+        L.bfq_gzip_probe.argtypes = [vp, u64]
+        L.bfq_gzip_measure.argtypes = [vp, vp, u64, u64, pu64, pu64, pgs]
+        L.bfq_gzip_inflate.argtypes = [vp, vp, u64, u64, vp, u64, pu64, pgs]
+        L.bfq_gzip_inflate_device.argtypes = [vp, vp, u64, u64, vp, u64, pu64, pgs]
+        L.bfq_gzip_inflate_fd.argtypes = [vp, C.c_int, u64, u64, C.c_int, pu64, pgs]
+        L.bfq_gzip_inflate_host.argtypes = [vp, u64, u64, vp, u64, pu64, pgs]
+        L.bfq_gzip_host_error.restype = C.c_char_p
+        L.bfq_gzip_host_error.argtypes = []
         L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]

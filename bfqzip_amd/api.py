@@ -229,6 +229,39 @@ def bgzf_deflate_model(text, level=1):
     return out[:int(ol.value)]
 
 
+def gzip_probe(blob):
+    """True when the bytes begin with a well-formed gzip member header (bfq_gzip_probe): plain gzip or BGZF."""
+    blob = _u8(blob)
+    return bool(len(blob)) and bool(_lib.lib().bfq_gzip_probe(_ptr(blob), len(blob)))
+
+
+def _gzip_raise(rc, msg, needed):
+    e = BfqError(rc, msg)
+    e.needed = int(needed)                                         # the raw length, when the buffer was too small for it; else 0
+    raise e
+
+
+def gzip_inflate_host(blob, chunk=0, out=None):
+    """(text, stats) of a gzip file by the host form of the side-by-side inflate (bfq_gzip_inflate_host: the steps of
+    csrc/bfq_gzip.h by one thread, no GPU): the statement of the algorithm -- Engine.gzip_inflate gives the same bytes and the
+    same stats.  `out`: a uint8 array to fill; one that is too small raises BfqError with .needed = the raw length and is
+    left untouched.  A damaged file raises BfqError ("damaged gzip input: member <i> at byte <off>: <reason>")."""
+    blob = _u8(blob)
+    L = _lib.lib()
+    st, ol = _lib.GzipStats(), C.c_uint64(0)
+    if out is None:
+        rc = L.bfq_gzip_inflate_host(_ptr(blob) if len(blob) else None, len(blob), int(chunk), None, 0, C.byref(ol), C.byref(st))
+        if rc == 0:
+            return np.empty(0, np.uint8), st
+        if not ol.value:
+            _gzip_raise(rc, L.bfq_gzip_host_error().decode(), 0)
+        out = np.empty(int(ol.value), np.uint8)
+    rc = L.bfq_gzip_inflate_host(_ptr(blob) if len(blob) else None, len(blob), int(chunk), _ptr(out), len(out), C.byref(ol), C.byref(st))
+    if rc != 0:
+        _gzip_raise(rc, L.bfq_gzip_host_error().decode(), ol.value)
+    return out[:int(ol.value)], st
+
+
 def text_len(a):
     """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
     a = _u8(a)
@@ -245,6 +278,8 @@ class HostText:
     bgzf_index = staticmethod(bgzf_index)
     bgzf_deflate_bound = staticmethod(bgzf_deflate_bound)
     bgzf_deflate_model = staticmethod(bgzf_deflate_model)
+    gzip_probe = staticmethod(gzip_probe)
+    gzip_inflate_host = staticmethod(gzip_inflate_host)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -608,6 +643,55 @@ class Engine:
             ol = C.c_uint64(0)
             self._ck(self.L.bfq_bgzf_inflate_fd(self.h, fds[0], os.fstat(fds[0]).st_size, fds[1], C.byref(ol)))
             return int(ol.value)
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+    # ---- plain gzip: one deflate stream per member, inflated side by side (bfq_gzip_*, csrc/bfq_gzip.h)
+    def _gzip_ck(self, rc, ol):
+        if rc != 0:
+            _gzip_raise(rc, self.L.bfq_last_error(self.h).decode(), ol.value)
+
+    def gzip_measure(self, blob, chunk=0):
+        """bfq_gzip_measure: (raw length, members, stats) of a gzip file from the candidate search and the counting pass alone."""
+        blob = _u8(blob)
+        raw, n, st = C.c_uint64(0), C.c_uint64(0), _lib.GzipStats()
+        self._ck(self.L.bfq_gzip_measure(self.h, _ptr(blob) if len(blob) else None, len(blob), int(chunk), C.byref(raw), C.byref(n), C.byref(st)))
+        return int(raw.value), int(n.value), st
+
+    def gzip_inflate(self, blob, out=None, chunk=0):
+        """(text, stats) of a gzip file -- what gzip, pigz and `cat a.gz b.gz` write, BGZF included -- inflated on the GPU
+        (bfq_gzip_inflate); the text is a uint8 array.  `out`: a uint8 array to fill, the text is a view of it; without one
+        the file is measured first (gzip_measure).  chunk: bytes per piece, a power of two >= 512, 0 = the default.  An `out`
+        below the raw length raises BfqError with .needed = that length and is left untouched; a damaged file raises BfqError
+        (BFQ_E_ARG: "damaged gzip input: member <i> at byte <off>: <reason>")."""
+        blob = _u8(blob)
+        if out is None:
+            out = np.empty(max(self.gzip_measure(blob, chunk)[0], 1), np.uint8)
+        ol, st = C.c_uint64(0), _lib.GzipStats()
+        self._gzip_ck(self.L.bfq_gzip_inflate(self.h, _ptr(blob) if len(blob) else None, len(blob), int(chunk), _ptr(out), len(out), C.byref(ol),
+                                              C.byref(st)), ol)
+        return out[:int(ol.value)], st
+
+    def gzip_inflate_device(self, blob, d_out, cap, chunk=0):
+        """bfq_gzip_inflate_device: the text at the device address d_out (cap bytes); returns (its length, stats)."""
+        blob = _u8(blob)
+        ol, st = C.c_uint64(0), _lib.GzipStats()
+        self._gzip_ck(self.L.bfq_gzip_inflate_device(self.h, _ptr(blob) if len(blob) else None, len(blob), int(chunk), C.c_void_p(d_out), cap,
+                                                     C.byref(ol), C.byref(st)), ol)
+        return int(ol.value), st
+
+    def gzip_inflate_files(self, src, dst=None, chunk=0):
+        """bfq_gzip_inflate_fd on named files; dst None: inflate and verify only.  Returns (the length of the text, stats)."""
+        import os
+        fds = []
+        try:
+            fds.append(os.open(src, os.O_RDONLY))
+            fds.append(os.open(dst, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) if dst is not None else -1)
+            ol, st = C.c_uint64(0), _lib.GzipStats()
+            self._gzip_ck(self.L.bfq_gzip_inflate_fd(self.h, fds[0], os.fstat(fds[0]).st_size, int(chunk), fds[1], C.byref(ol), C.byref(st)), ol)
+            return int(ol.value), st
         finally:
             for fd in fds:
                 if fd >= 0:

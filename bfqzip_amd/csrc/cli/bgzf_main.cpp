@@ -4,8 +4,13 @@
 //                                             -0: every member stored.  An input that is already compressed is refused.
 //     bfq_bgzf -t IN.fq.gz                    inflate and verify (every member's length and CRC32), writing nothing
 //     bfq_bgzf -l IN.fq.gz                    members, raw length, ratio: no GPU is touched
-// The input is BGZF (bgzip, htslib, BCL Convert): include/bfqzip_hip.h, bfq_bgzf_inflate_fd.  Plain gzip is refused with a
-// message that says to recompress with bgzip.  The tools that take FASTQ (gsufsort, bfq_compare, ...) take a BGZF file as it
+//     bfq_bgzf -g -d IN.fq.gz -o OUT.fq [-V]  plain gzip (gzip, pigz, bcl2fastq, `cat a.gz b.gz`; BGZF too): the deflate streams
+//     bfq_bgzf -g -t IN.fq.gz                 are inflated side by side (bfq_gzip_inflate_fd, csrc/bfq_gzip.h); -t verifies
+//     bfq_bgzf -g -l IN.fq.gz                 every member's CRC32 and length; -l prints members, compressed and raw bytes,
+//                                             pieces, chain length and skipped candidates (on the GPU: a gzip file has no
+//                                             directory to read them from)
+// Without -g the input is BGZF (bgzip, htslib, BCL Convert): include/bfqzip_hip.h, bfq_bgzf_inflate_fd, and plain gzip is
+// refused with a message that says to recompress with bgzip.  The tools that take FASTQ (gsufsort, bfq_compare, ...) take a BGZF file as it
 // is; this one is for the ones that do not (bfq_reorder, the multi-GPU driver's line index).  Exit status 0 on success; 1 with
 // the library's message on a damaged file, and then OUT.fq is left empty.
 #include <unistd.h>
@@ -14,13 +19,14 @@
 
 static int usage(const char *argv0)
 {
-    fprintf(stderr, "usage: %s -d IN.fq.gz -o OUT.fq [-V] | -c IN.fq -o OUT.fq.gz [-0] [-V] | -t IN.fq.gz | -l IN.fq.gz\n"
+    fprintf(stderr, "usage: %s [-g] -d IN.fq.gz -o OUT.fq [-V] | -c IN.fq -o OUT.fq.gz [-0] [-V] | [-g] -t IN.fq.gz | [-g] -l IN.fq.gz\n"
                     "  -d <arg>  bgzip-compressed (BGZF) input to inflate (with -o)\n"
                     "  -c <arg>  text to compress into BGZF (with -o)\n"
                     "  -0        with -c: every member stored\n"
                     "  -o <arg>  output (text with -d, BGZF with -c)\n"
                     "  -t <arg>  inflate and verify only: no output is written\n"
                     "  -l <arg>  print members, compressed and raw length, ratio, and exit (no GPU)\n"
+                    "  -g        with -d, -t, -l: the input is plain gzip (any gzip file), inflated side by side; -l runs on the GPU\n"
                     "  -V        phase timeline on stderr\n", argv0);
     return 1;
 }
@@ -52,9 +58,11 @@ int main(int argc, char **argv)
     std::string input, output;
     char mode = 0;
     int opt, level = 1;
-    while ((opt = getopt(argc, argv, "d:c:t:l:o:0Vh")) != -1) {
+    bool gzip = false;
+    while ((opt = getopt(argc, argv, "d:c:t:l:o:0gVh")) != -1) {
         switch (opt) {
         case '0': level = 0; break;
+        case 'g': gzip = true; break;
         case 'd': case 'c': case 't': case 'l':
             if (mode) return usage(argv[0]);
             mode = (char)opt; input = optarg; break;
@@ -64,19 +72,26 @@ int main(int argc, char **argv)
         }
     }
     const bool writes = mode == 'd' || mode == 'c';
-    if (!mode || writes != !output.empty() || (level == 0 && mode != 'c')) return usage(argv[0]);
+    if (!mode || writes != !output.empty() || (level == 0 && mode != 'c') || (gzip && mode == 'c')) return usage(argv[0]);
     InFile in;
     if (!in.open(input)) { fprintf(stderr, "bfq_bgzf: cannot read %s\n", input.c_str()); return 1; }
-    if (mode == 'l') return list_members(in, input);
+    if (mode == 'l' && !gzip) return list_members(in, input);
     OutFile out;
     if (writes && !out.open(output)) { perror("bfq_bgzf"); return 1; }
     bfq_params P;
     bfq_default_params(&P);
     bfq_ctx *c = create_on_free_gpu("bfq_bgzf", &P);
     if (!c) return 1;
-    uint64_t outLen = 0;
-    const int rc = mode == 'c' ? bfq_bgzf_deflate_fd(c, in.fd, in.size, level, out.fd, &outLen)
-                               : bfq_bgzf_inflate_fd(c, in.fd, in.size, mode == 'd' ? out.fd : -1, &outLen);
+    uint64_t outLen = 0, members = 0;
+    bfq_gzip_stats gs = {};
+    int rc;
+    if (gzip && mode == 'l') {
+        void *m = in.size ? mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0) : MAP_FAILED;
+        rc = bfq_gzip_measure(c, m != MAP_FAILED ? (const uint8_t *)m : nullptr, m != MAP_FAILED ? in.size : 0, 0, &outLen, &members, &gs);
+        if (m != MAP_FAILED) munmap(m, in.size);
+    } else if (gzip) rc = bfq_gzip_inflate_fd(c, in.fd, in.size, 0, mode == 'd' ? out.fd : -1, &outLen, &gs);
+    else rc = mode == 'c' ? bfq_bgzf_deflate_fd(c, in.fd, in.size, level, out.fd, &outLen)
+                          : bfq_bgzf_inflate_fd(c, in.fd, in.size, mode == 'd' ? out.fd : -1, &outLen);
     if (rc) {
         fprintf(stderr, "bfq_bgzf: %s: %s\n", input.c_str(), bfq_last_error(c));
         bfq_destroy(c);
@@ -89,7 +104,11 @@ int main(int argc, char **argv)
     bfq_destroy(c);
     if (!closed) { perror("bfq_bgzf"); return 1; }
     bfq_phase_report("bfq_bgzf");
-    if (mode == 'c') printf("%llu bytes -> %llu bytes\n", (unsigned long long)in.size, (unsigned long long)outLen);
+    if (mode == 'l')
+        printf("%llu members, %llu bytes compressed, %llu bytes raw, %llu pieces, chain %llu, %llu candidates skipped\n", (unsigned long long)members,
+               (unsigned long long)in.size, (unsigned long long)outLen, (unsigned long long)gs.pieces, (unsigned long long)gs.chain,
+               (unsigned long long)gs.skipped);
+    else if (mode == 'c') printf("%llu bytes -> %llu bytes\n", (unsigned long long)in.size, (unsigned long long)outLen);
     else printf("%llu bytes%s\n", (unsigned long long)outLen, mode == 't' ? " verified" : "");
     return 0;
 }

@@ -190,11 +190,12 @@ def inflated_name(path, out):
     return os.path.join(os.path.dirname(out) if out else os.path.dirname(path), root + ".inflated" + ext)
 
 
-def inflate_inputs(eng, comm, inputs, out="", log=None):
+def inflate_inputs(eng, comm, inputs, out="", log=None, gunzip=False):
     """A bgzip-compressed (BGZF) input is inflated on the GPU to a plain file beside the outputs before the line index is
     built (eng.bgzf_inflate_files), by rank 0, and the run goes on with that file: returns (the new input list, the files
     written).  The blocks are cut by line number, which a compressed file does not give: one extra trip of the text through
-    the file system."""
+    the file system.  gunzip (--gunzip): an input that is gzip but not BGZF goes through eng.gzip_inflate_files, its deflate
+    streams inflated side by side; without it such a file keeps the library's refusal."""
     new, tmp = [], []
     for p in inputs:
         with open(p, "rb") as f:
@@ -203,7 +204,15 @@ def inflate_inputs(eng, comm, inputs, out="", log=None):
             new.append(p)
             continue
         q = inflated_name(p, out)
-        if comm.rank == 0:
+        if gunzip:
+            from . import api
+            with open(p, "rb") as f:
+                gunzip_this = not api.bgzf_probe(f.read(1 << 17))   # (a whole first member: at most 64 KiB)
+        if comm.rank == 0 and gunzip and gunzip_this:
+            n, st = eng.gzip_inflate_files(p, q)                    # (a damaged file: the library's message)
+            if log:
+                log(f"gunzip: {st}")
+        elif comm.rank == 0:
             n = eng.bgzf_inflate_files(p, q)                        # (plain gzip, a damaged file: the library's message)
             if log:
                 log(f"inflate: {p} -> {q}, {n} bytes")
@@ -657,6 +666,9 @@ def main(argv=None):
                          "group k of the archive (one per block) is restored by rank k mod world")
     ap.add_argument("--keep-inflated", action="store_true",
                     help="a bgzip-compressed input is inflated to <name>.inflated<ext> beside the outputs first: keep that file")
+    ap.add_argument("--gunzip", action="store_true",
+                    help="a .gz input that is gzip but not BGZF (gzip, pigz, bcl2fastq) is inflated on the GPU too, its deflate streams "
+                         "side by side; without this such a file is refused")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
     if a.restore and (len(a.input) not in (2, 3) or not a.out):
@@ -700,7 +712,7 @@ def main(argv=None):
         if dist:
             dist.destroy_process_group()
         return 0
-    a.input, inflated = inflate_inputs(eng, comm, a.input, a.out, log=log)
+    a.input, inflated = inflate_inputs(eng, comm, a.input, a.out, log=log, gunzip=a.gunzip)
     perm_path = reordered_names(a.input[:1], a.reorder)[0] + ".perm" if (a.keep_order and a.reorder) else None
     keep = dict(perm_path=perm_path) if perm_path else {}
     original = list(a.input)

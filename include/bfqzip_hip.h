@@ -654,6 +654,54 @@ int bfq_bgzf_index(const uint8_t *h_in, uint64_t len, bfq_bgzf_member *m, uint64
 int bfq_bgzf_inflate(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
 int bfq_bgzf_inflate_device(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *d_out, uint64_t cap, uint64_t *out_len);
 int bfq_bgzf_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, int out_fd, uint64_t *out_len);
+/* ---- plain gzip input: one long deflate stream per member, inflated side by side on the device (k_gzip.hip; the format,
+ * the algorithm and every bound: csrc/bfq_gzip.h).  What gzip, pigz, bcl2fastq and `cat a.gz b.gz` write: any number of
+ * RFC 1952 members (FEXTRA, FNAME, FCOMMENT, FHCRC with its CRC16 checked; reserved FLG bits refused), zero bytes allowed
+ * after the last one.  A member has no directory, so the work is found and proved instead of read:
+ *   1 the compressed bytes are cut into pieces of `chunk` bytes; in every piece after the first the device looks for the
+ *     first bit offset that passes the block-start rule (BFINAL 0, BTYPE 2, a dynamic header that passes every check of the
+ *     inflate): the piece's candidate;
+ *   2 pass 1: one decoder per candidate (and one at the first member's first block) runs block by block and counts, until a
+ *     block ends exactly on a later candidate (its landing), the stream ends, or an error.  The host walks the landings from
+ *     piece 0: the chain.  Decoders off the chain started on false candidates and are discarded; correctness rests on the
+ *     chain and on every member's CRC32, never on a candidate;
+ *   3 pass 2: the chain's decoders write 16-bit symbols (a byte, or a marker for a byte of the unknown 32 KiB in front of the
+ *     decoder); one workgroup resolves the 32 KiB window in front of every chain decoder in order; one streaming pass turns
+ *     symbols into bytes; every member's CRC32 and length (mod 2^32) are checked against its trailer.
+ *   chunk : a power of two >= 512; 0 = the default (131 072, or $BFQ_GZIP_CHUNK); anything else is BFQ_E_ARG.
+ *   bfq_gzip_probe   : 1 when h begins with a well-formed gzip member header (BGZF included), else 0.  Host only.
+ *   bfq_gzip_measure : steps 1-2 only: *raw_len = the length of the text, *n_members, *stats.  CRC32 and far distances are
+ *     not checked by it.
+ *   bfq_gzip_inflate* : the text.  cap < the raw length: BFQ_E_ARG, nothing written, *out_len = the length needed (every other
+ *     failure leaves *out_len = 0).  Device memory, in the workspace: the compressed bytes, 56 bytes per piece, 2 x the raw
+ *     length of symbols, 32 KiB per chain decoder, 24 bytes per member (+ the text, for the host and file forms).
+ *       bfq_gzip_inflate        : host buffer out
+ *       bfq_gzip_inflate_device : device buffer out
+ *       bfq_gzip_inflate_fd     : open files; out_fd < 0: inflate and verify only
+ *   bfq_gzip_inflate_host : the same steps by one thread, with no context and no GPU: the same bytes and the same *stats as
+ *     the device gives.  It states the algorithm and is what the tests compare with; NO entry point falls back to it.
+ *   stats (may be NULL): members, pieces, decoders started, decoders of the chain, candidates the chain ran past, decoders
+ *     discarded.
+ * A BGZF file is a gzip file and goes through the same general path here; bfq_bgzf_* stays the fast way for it.
+ * Refusals: BFQ_E_ARG, bfq_last_error() = "damaged gzip input: member <i> at byte <off>: <reason>" (<off>: where the member's
+ *   header begins).  A structural error -- header or deflate data, the reasons of bfq_bgzf_inflate where the rule is the same,
+ *   and: reserved flag bits, header CRC16, a header field past the end, trailing bytes that are neither zero nor a member, the
+ *   input ending inside a trailer -- at the lowest place in the stream is named first; CRC32 and length mismatches only when
+ *   there is none, lowest member first.  bfq_gzip_inflate_host returns BFQ_E_ARG and leaves the same message in
+ *   bfq_gzip_host_error() (of the calling thread's last call).  The text of a refused call is undefined; the context stays usable.
+ * The entry points that take FASTQ text keep reading 1f 8b as BGZF and keep refusing plain gzip: their buffers are sized
+ * from a raw length that is known before any GPU work, which plain gzip cannot give.  Inflate first. */
+typedef struct bfq_gzip_stats { uint64_t members, pieces, decoders, chain, skipped, discarded; } bfq_gzip_stats;
+int bfq_gzip_probe(const uint8_t *h, uint64_t len);
+int bfq_gzip_measure(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint64_t chunk, uint64_t *raw_len, uint64_t *n_members, bfq_gzip_stats *stats);
+int bfq_gzip_inflate(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint64_t chunk, uint8_t *h_out, uint64_t cap, uint64_t *out_len,
+                     bfq_gzip_stats *stats);
+int bfq_gzip_inflate_device(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint64_t chunk, uint8_t *d_out, uint64_t cap, uint64_t *out_len,
+                            bfq_gzip_stats *stats);
+int bfq_gzip_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, uint64_t chunk, int out_fd, uint64_t *out_len, bfq_gzip_stats *stats);
+int bfq_gzip_inflate_host(const uint8_t *h_in, uint64_t len, uint64_t chunk, uint8_t *h_out, uint64_t cap, uint64_t *out_len,
+                          bfq_gzip_stats *stats);
+const char *bfq_gzip_host_error(void);
 /* ---- bgzip-compressed output: BGZF members deflated on the device (k_deflate.hip; the format and every bound:
  * csrc/bfq_deflate.h).  A text of len bytes is cut at multiples of 65 280 bytes (htslib's member size; the cut depends on
  * nothing else); every piece becomes one BGZF member -- htslib's 18-byte header, a raw deflate payload, CRC32 and ISIZE --
