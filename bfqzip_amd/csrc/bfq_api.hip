@@ -294,6 +294,12 @@ extern "C" int bfq_posbin_geometry(uint64_t n_rows, uint64_t *window, int *bin_s
     if (bin_shift) *bin_shift = s;
     return s >= 0 ? BFQ_OK : BFQ_E_ARG;
 }
+extern "C" int bfq_radix_geometry(uint64_t n_rows, uint64_t *tile_rows, uint64_t *block_rows)
+{
+    if (tile_rows) *tile_rows = BFQ_RS_TILE;
+    if (block_rows) *block_rows = bfq_radix_block_elems(n_rows);
+    return BFQ_OK;
+}
 extern "C" int bfq_prof_get(bfq_ctx *c, int idx, char *name, int cap, double *ms, uint64_t *launches, double *bytes)
 {
     if (!c || idx < 0 || idx >= K_NUM) return BFQ_E_ARG;
@@ -428,13 +434,23 @@ void bfq_step1_device(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u6
     B.w0 = c->alloc<u32>(n + 16);
     B.w12 = c->alloc<u64>(n + 16);
     if (bfq_env().trace) fprintf(stderr, "[bfq] sort buffers: A.w12 %p A.w0 %p B.w0 %p B.w12 %p (arena %p)\n", (void *)A.w12, (void *)A.w0, (void *)B.w0, (void *)B.w12, (void *)c->ws.base);
-    // k_build_keys writes the records to B, the byte text lying in A (dead before the sort's first scatter writes there)
-    u8 *T8 = (u8 *)A.w0, *Q8 = (u8 *)A.w12;
+    // The sort's first pass makes the records itself from the text (k_radix.hip), counted beforehand by k_build_keys' counting
+    // form: text -> A -> B -> A -> B -> A.  The byte text lies in B, where pass 0 does not write and which is dead before
+    // pass 1 does.  BFQ_FUSEKEYS=0 (and a single row): k_build_keys writes the records to B, the byte text lying in A (dead
+    // before the sort's first scatter writes there), and all five passes stream.
+    const bool fuse = c->env.fuseKeys && n >= 2;
+    u8 *T8 = fuse ? (u8 *)B.w0 : (u8 *)A.w0, *Q8 = fuse ? (u8 *)B.w12 : (u8 *)A.w12;
     bfq_build_text(c, d_bases, d_quals, d_roff, N, n, T8, Q8, text3, nwords);
     u32 *hist0 = c->alloc<u32>(256 * ceil_div(n, bfq_radix_block_elems(n)));
     static_assert(BFQ_KEY_PASSES & 1, "an odd number of passes ends in the other buffer");
-    bfq_build_keys(c, T8, Q8, text3, n, B, hist0);
-    bfq_radix_sort(c, B, A, n, BFQ_KEY_PASSES, hist0);  // B -> A -> B -> A -> B -> A
+    if (fuse) {
+        const KeySrc gen{T8, Q8, text3};
+        bfq_count_keys(c, text3, n, hist0);
+        bfq_radix_sort(c, B, A, n, BFQ_KEY_PASSES, hist0, &gen);   // text -> A -> B -> A -> B -> A
+    } else {
+        bfq_build_keys(c, T8, Q8, text3, n, B, hist0);
+        bfq_radix_sort(c, B, A, n, BFQ_KEY_PASSES, hist0);  // B -> A -> B -> A -> B -> A
+    }
     c->release(mB);                                     // the big-segment list reuses the B buffers
     bfq_refine(c, A, text3, n, c->d_lcp, st);
     bfq_emit_bwt(c, A, n, termOut, c->d_bwt, c->d_qual, c->d_gcnt);

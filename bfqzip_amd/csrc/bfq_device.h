@@ -83,9 +83,8 @@ __device__ __forceinline__ u64 bfq_wave_incscan64(u64 v)
 
 // the same through the LDS crossbar (ds_bpermute): fewer live registers than the DPP sequence, for
 // kernels at their VGPR limit (k_radix_scatter)
-__device__ __forceinline__ u32 bfq_wave_incscan32_bp(u32 v)
+__device__ __forceinline__ u32 bfq_wave_incscan32_bp(u32 v, u32 lane)   // lane: the caller's copy of bfq_lane()
 {
-    u32 lane = bfq_lane();
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         u32 t = (u32)__builtin_amdgcn_ds_bpermute(((int)lane - d) << 2, (int)v);
@@ -93,6 +92,8 @@ __device__ __forceinline__ u32 bfq_wave_incscan32_bp(u32 v)
     }
     return v;
 }
+
+__device__ __forceinline__ u32 bfq_wave_incscan32_bp(u32 v) { return bfq_wave_incscan32_bp(v, bfq_lane()); }
 
 // exclusive scan over a 256-thread workgroup; sh must hold 4 entries; returns the
 // exclusive prefix, *total = workgroup sum.  Contains two __syncthreads().

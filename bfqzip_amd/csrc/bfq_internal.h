@@ -309,6 +309,7 @@ static inline unsigned bfq_grid(u64 items, u64 perBlock)
 
 // the suffix records being sorted: three 32-bit arrays (layout: bfq_common.h)
 struct SortRec { u32 *w0; u64 *w12; };   // w12 = w2 << 32 | w1
+struct KeySrc { const u8 *T8, *Q8; const u64 *text3; };   // what the records of the unsorted rows are a function of: byte text, its qualities, packed text
 
 // ---- stage entry points (each in its own .hip file) --------------------------------
 // scan: out[i] = sum(in[0..i)) ; T in {u8,u32,u64}; total (device u64) optional
@@ -370,7 +371,8 @@ static inline u64 bfq_radix_block_elems(u64 n)
 }
 void bfq_build_keys(bfq_ctx *c, const u8 *T8, const u8 *Q8, const u64 *text3, u64 n, SortRec out, u32 *hist0);   // hist0: [256][ceil(n / bfq_radix_block_elems(n))]
 // LSD radix sort of the records on their 48-bit key; result ends in A
-SortRec bfq_radix_sort(bfq_ctx *c, SortRec in, SortRec tmp, u64 n, int passes = BFQ_KEY_PASSES, const u32 *hist0 = nullptr);   // returns the buffer holding the result (in: even passes, tmp: odd); fewer passes = low digits only; hist0: pass-0 counts already made
+void bfq_count_keys(bfq_ctx *c, const u64 *text3, u64 n, u32 *hist0);   // hist0 alone, no records: for a sort whose first pass generates them
+SortRec bfq_radix_sort(bfq_ctx *c, SortRec in, SortRec tmp, u64 n, int passes = BFQ_KEY_PASSES, const u32 *hist0 = nullptr, const KeySrc *gen = nullptr);   // returns the buffer holding the result (in: even passes, tmp: odd); fewer passes = low digits only; hist0: pass-0 counts already made; gen: pass 0 makes the records of rows = text positions itself and does not read `in`
 // tie refinement: sorts vals inside equal-key segments by the remaining suffix, fills lcp
 void bfq_refine(bfq_ctx *c, SortRec rec, const u64 *text3, u64 n, u16 *lcp, bfq_stats *st);
 // segments above BFQ_HUGE_SEG rows (listed by k_refine_big): whole-device radix rounds on the following symbols

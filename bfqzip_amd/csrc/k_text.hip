@@ -1,11 +1,17 @@
 // k_text.hip -- reads -> terminated text of symbol codes -> 3-bit packed text ->
-// (21-symbol key, payload) pairs, one per suffix.  Pure streaming kernels.
+// (16-symbol key, payload) records, one per suffix.  Pure streaming kernels.
+//
+// k_build_keys has two forms.  The one-piece step 1 runs the counting form: it reads the packed text alone and leaves only
+// the digit counts of the sort's first pass, which then makes the records itself (k_radix.hip, bfq_keyrec.h) -- the 12 B/row
+// array is neither written here nor read there.  The writing form (records to memory, counts on the way) serves
+// BFQ_FUSEKEYS=0 and single-row collections.
 //
 // Replaces the input stage of the absent step-1 tool (call site BFQzip.py:178-189):
 // the text is the read collection with one terminator per read, no global end
 // marker (gsufsort built with TERMINATOR=0, reference Makefile:18).
 #include "bfq_internal.h"
 #include "bfq_device.h"
+#include "bfq_keyrec.h"
 
 // 16 lanes per read, 8 bytes per lane and step (unaligned 8-byte loads/stores are fine on gfx950):
 // symbol codes + qualities into terminated text order
@@ -85,8 +91,11 @@ __global__ __launch_bounds__(256) void k_pack3(const u8 *__restrict__ T8, u64 n,
 }
 
 // 4 consecutive suffixes per thread: 16-symbol key + payload (position, previous symbol, its quality) as
-// 12-byte records; the previous symbols / qualities arrive by one 4-byte load each, the records leave as
-// one 16-byte (w0) and two 16-byte (w12) stores
+// 12-byte records (bfq_keyrec.h builds them); the previous symbols / qualities arrive by one 4-byte load each, the
+// records leave as one 16-byte (w0) and two 16-byte (w12) stores.
+// COUNT: the counting-only form for the sort's generating first pass (k_radix.hip), which makes the records itself:
+// same blocks, same hist0 layout, reads the packed text only and stores nothing but the histogram.
+template <bool COUNT>
 __global__ __launch_bounds__(256) void k_build_keys(const u8 *__restrict__ T8, const u8 *__restrict__ Q8,
                                                     const u64 *__restrict__ text3, u64 n, SortRec out, u32 *__restrict__ hist0,
                                                     u64 nblocks, u64 blockElems)
@@ -108,8 +117,10 @@ __global__ __launch_bounds__(256) void k_build_keys(const u8 *__restrict__ T8, c
         u32 o0 = (u32)(p0 - w0 * BFQ_SYMS_PER_WORD);
         for (; p0 < bend; p0 += 1024) {
             u32 c4 = 0, q4 = 0;                                       // codes / qualities of text positions p0-1 .. p0+2
-            if (p0 >= 1 && p0 + 3 <= n) { c4 = *(const u32 *)(T8 + p0 - 1); q4 = *(const u32 *)(Q8 + p0 - 1); }
-            else for (int k = 0; k < 4; k++) { u64 t = p0 + k; if (t >= 1 && t - 1 < n) { c4 |= (u32)T8[t - 1] << (8 * k); q4 |= (u32)Q8[t - 1] << (8 * k); } }
+            if (!COUNT) {
+                if (p0 >= 1 && p0 + 3 <= n) { c4 = *(const u32 *)(T8 + p0 - 1); q4 = *(const u32 *)(Q8 + p0 - 1); }
+                else for (int k = 0; k < 4; k++) { u64 t = p0 + k; if (t >= 1 && t - 1 < n) { c4 |= (u32)T8[t - 1] << (8 * k); q4 |= (u32)Q8[t - 1] << (8 * k); } }
+            }
             const u64 *t3 = text3 + bfq_t3_at(w0);
             u64 t0 = t3[0], t1 = t3[1], t2 = t3[2];                   // 4 windows span at most 3 words
             u32 rw0[4];
@@ -119,23 +130,20 @@ __global__ __launch_bounds__(256) void k_build_keys(const u8 *__restrict__ T8, c
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 u64 a = (wd == w0) ? t0 : t1, bnext = (wd == w0) ? t1 : t2;
-                u32 o3 = o * 3u;
-                u64 hi = (a << o3) & BFQ_M63;
-                u64 lo = o3 ? (bnext >> (63u - o3)) : 0ull;
-                u64 sk = bfq_skey_of(bfq_mask_key(hi | lo));
-                u32 pc = (c4 >> (8 * k)) & 0xFFu;
-                u32 pq = pc ? (q4 >> (8 * k)) & 0xFFu : (u32)'#';
-                u64 pay = bfq_pack_val(p0 + k, pc, pq);
-                rw0[k] = bfq_rec_w0(sk);
-                rw12[k] = ((u64)bfq_rec_w2(pay) << 32) | bfq_rec_w1(sk, pay);
-                if (p0 + k < n) atomicAdd(&wh[w][(u32)sk & 255u], 1u);   // digit 0 of the LSD sort = low byte of the key
+                u32 d0;
+                if (COUNT) d0 = bfq_keyrec_digit0(a, bnext, o);
+                else {
+                    bfq_keyrec(a, bnext, o, p0 + k, (c4 >> (8 * k)) & 0xFFu, (q4 >> (8 * k)) & 0xFFu, &rw0[k], &rw12[k]);
+                    d0 = (u32)rw12[k] >> 24;
+                }
+                if (p0 + k < n) atomicAdd(&wh[w][d0], 1u);             // digit 0 of the LSD sort = low byte of the key
                 if (++o == BFQ_SYMS_PER_WORD) { o = 0; wd++; }
             }
-            if (p0 + 4 <= n) {
+            if (!COUNT && p0 + 4 <= n) {
                 *(uint4 *)(out.w0 + p0) = make_uint4(rw0[0], rw0[1], rw0[2], rw0[3]);
                 *(ulonglong2 *)(out.w12 + p0) = make_ulonglong2(rw12[0], rw12[1]);
                 *(ulonglong2 *)(out.w12 + p0 + 2) = make_ulonglong2(rw12[2], rw12[3]);
-            } else {
+            } else if (!COUNT) {
                 for (int k = 0; p0 + k < n; k++) { out.w0[p0 + k] = rw0[k]; out.w12[p0 + k] = rw12[k]; }
             }
             w0 += sw; o0 += so;
@@ -170,5 +178,15 @@ void bfq_build_keys(bfq_ctx *c, const u8 *T8, const u8 *Q8, const u64 *text3, u6
     if (!n) return;
     const u64 be = bfq_radix_block_elems(n);
     const u64 nb = ceil_div(n, be);
-    KLAUNCH(c, K_KEYS, 14.5 * (double)n, k_build_keys, bfq_grid(nb, 1), 256, T8, Q8, text3, n, out, hist0, nb, be);
+    KLAUNCH(c, K_KEYS, 14.5 * (double)n, k_build_keys<false>, bfq_grid(nb, 1), 256, T8, Q8, text3, n, out, hist0, nb, be);
+}
+
+// the digit counts alone: 8/21 bytes of packed text per row in (a third more with the sectors' repeats), 1 KiB per block out
+void bfq_count_keys(bfq_ctx *c, const u64 *text3, u64 n, u32 *hist0)
+{
+    if (!n) return;
+    const u64 be = bfq_radix_block_elems(n);
+    const u64 nb = ceil_div(n, be);
+    KLAUNCH(c, K_KEYS, 0.51 * (double)n + 1024.0 * (double)nb, k_build_keys<true>, bfq_grid(nb, 1), 256, (const u8 *)nullptr, (const u8 *)nullptr, text3, n,
+            SortRec{}, hist0, nb, be);
 }

@@ -751,6 +751,9 @@ int  bfq_prof_count(bfq_ctx *c);
  * the window (text positions per workgroup of the last stage) and the shift of a first-level bin (2^shift positions).
  * BFQ_E_ARG (bin_shift -1): more rows than two partition levels hold; such a call inverts by LF walks. */
 int  bfq_posbin_geometry(uint64_t n_rows, uint64_t *window, int *bin_shift);
+/* introspection: how the suffix sort cuts n_rows rows -- the rows of a scatter tile and of a radix block (a whole number of
+ * tiles, which one workgroup runs through one after the other; fewer tiles for smaller collections). */
+int  bfq_radix_geometry(uint64_t n_rows, uint64_t *tile_rows, uint64_t *block_rows);
 int  bfq_prof_get(bfq_ctx *c, int idx, char *name, int name_cap, double *total_ms,
                   uint64_t *launches, double *alg_bytes_total);
 /* per-launch durations (ms, launch order, since the last reset) of ONE kernel chosen by its bfq_prof_get index (-1: none):
