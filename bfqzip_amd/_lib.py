@@ -38,6 +38,8 @@ SYMBOLS = [
     "bfq_fastq_restore_bgzf_fd",
     "bfq_gzip_probe", "bfq_gzip_measure", "bfq_gzip_inflate", "bfq_gzip_inflate_device", "bfq_gzip_inflate_fd", "bfq_gzip_inflate_host",
     "bfq_gzip_host_error",
+    "bfq_bam_default_opts", "bfq_bam_probe", "bfq_bam_measure", "bfq_bam_to_fastq", "bfq_bam_to_fastq_device", "bfq_bam_to_fastq_fd",
+    "bfq_bam_to_fastq_host", "bfq_bam_host_error",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -93,6 +95,26 @@ class GzipStats(C.Structure):
 
     def __repr__(self):
         return "GzipStats(%s)" % ", ".join("%s=%d" % kv for kv in self.as_dict().items())
+
+
+class BamOpts(C.Structure):
+    """bfq_bam_opts: exclude_flags, mate_suffix, default_qual, split, paired_check, piece (0: the default)"""
+    _fields_ = [(k, C.c_uint32) for k in ("exclude_flags", "mate_suffix", "default_qual", "split", "paired_check", "piece")] + [("reserved", C.c_uint32 * 2)]
+
+
+class BamStats(C.Structure):
+    """bfq_bam_stats: records of the file, written[3], skipped, reversed, no_qual, clamped_quals, n_ref, header_bytes, pieces, walkers,
+    dead, repaired, rounds"""
+    _fields_ = [("records", C.c_uint64), ("written", C.c_uint64 * 3)] + [(k, C.c_uint64) for k in (
+        "skipped", "reversed", "no_qual", "clamped_quals", "n_ref", "header_bytes", "pieces", "walkers", "dead", "repaired", "rounds")]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["written"] = [int(v) for v in self.written]
+        return {k: v if k == "written" else int(v) for k, v in d.items()}
+
+    def __repr__(self):
+        return "BamStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
 
 
 CMP_SYMS = 6
@@ -272,6 +294,17 @@ def lib():
         L.bfq_gzip_inflate_host.argtypes = [vp, u64, u64, vp, u64, pu64, pgs]
         L.bfq_gzip_host_error.restype = C.c_char_p
         L.bfq_gzip_host_error.argtypes = []
+        pbo, pbs, a3 = C.POINTER(BamOpts), C.POINTER(BamStats), C.POINTER(u64)
+        L.bfq_bam_default_opts.restype = None
+        L.bfq_bam_default_opts.argtypes = [pbo]
+        L.bfq_bam_probe.argtypes = [vp, u64]
+        L.bfq_bam_measure.argtypes = [vp, vp, u64, pbo, a3, a3, pbs]
+        L.bfq_bam_to_fastq.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, a3, a3, pbs]
+        L.bfq_bam_to_fastq_device.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, a3, a3, pbs]
+        L.bfq_bam_to_fastq_fd.argtypes = [vp, C.c_int, u64, pbo, C.POINTER(C.c_int), a3, a3, pbs]
+        L.bfq_bam_to_fastq_host.argtypes = [vp, u64, pbo, C.POINTER(vp), a3, a3, a3, pbs]
+        L.bfq_bam_host_error.restype = C.c_char_p
+        L.bfq_bam_host_error.argtypes = []
         L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_radix_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(u64)]

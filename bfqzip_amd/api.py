@@ -262,6 +262,54 @@ def gzip_inflate_host(blob, chunk=0, out=None):
     return out[:int(ol.value)], st
 
 
+def bam_opts(exclude_flags=0x900, mate_suffix=1, default_qual=1, split=0, paired_check=0, piece=0):
+    """bfq_bam_opts (include/bfqzip_hip.h); the defaults are bfq_bam_default_opts'."""
+    o = _lib.BamOpts()
+    o.exclude_flags, o.mate_suffix, o.default_qual, o.split, o.paired_check, o.piece = (int(exclude_flags), int(mate_suffix), int(default_qual), int(split),
+                                                                                      int(paired_check), int(piece))
+    return o
+
+
+def bam_probe(blob):
+    """True for a BAM file (bfq_bam_probe): the inflated stream itself ("BAM\\1"), or BGZF whose first member inflates to one."""
+    blob = _u8(blob)
+    return bool(len(blob)) and bool(_lib.lib().bfq_bam_probe(_ptr(blob), len(blob)))
+
+
+def _bam_raise(rc, msg, needed):
+    e = BfqError(rc, msg)
+    e.needed = [int(v) for v in needed]                            # the three lengths, when a buffer was too small; else zeros
+    raise e
+
+
+def _bam_outs(outs):
+    ptrs = (C.c_void_p * 3)(*[o.ctypes.data if len(o) else None for o in outs])
+    caps = (C.c_uint64 * 3)(*[len(o) for o in outs])
+    return ptrs, caps
+
+
+def bam_to_fastq_host(raw, outs=None, **opts):
+    """(texts[3], stats) of the INFLATED stream of a BAM file by the host form of the conversion (bfq_bam_to_fastq_host: the
+    steps of csrc/bfq_bam.h by one thread, no GPU): the statement of the algorithm -- Engine.bam_to_fastq gives the same bytes
+    and the same stats.  opts: bam_opts().  `outs`: three uint8 arrays to fill; one that is too small raises BfqError with
+    .needed = the three lengths and all are left untouched.  Refusals raise BfqError ("damaged BAM input: ...")."""
+    raw = _u8(raw)
+    L = _lib.lib()
+    O, st = bam_opts(**opts), _lib.BamStats()
+    ol, nr = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+    src = _ptr(raw) if len(raw) else None
+    if outs is None:
+        rc = L.bfq_bam_to_fastq_host(src, len(raw), C.byref(O), None, None, ol, nr, C.byref(st))
+        if rc != 0:
+            _bam_raise(rc, L.bfq_bam_host_error().decode(), ol)
+        outs = [np.empty(int(v), np.uint8) for v in ol]
+    ptrs, caps = _bam_outs(outs)
+    rc = L.bfq_bam_to_fastq_host(src, len(raw), C.byref(O), ptrs, caps, ol, nr, C.byref(st))
+    if rc != 0:
+        _bam_raise(rc, L.bfq_bam_host_error().decode(), ol)
+    return [o[:int(n)] for o, n in zip(outs, ol)], st
+
+
 def text_len(a):
     """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
     a = _u8(a)
@@ -280,6 +328,8 @@ class HostText:
     bgzf_deflate_model = staticmethod(bgzf_deflate_model)
     gzip_probe = staticmethod(gzip_probe)
     gzip_inflate_host = staticmethod(gzip_inflate_host)
+    bam_probe = staticmethod(bam_probe)
+    bam_to_fastq_host = staticmethod(bam_to_fastq_host)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -692,6 +742,58 @@ class Engine:
             ol, st = C.c_uint64(0), _lib.GzipStats()
             self._gzip_ck(self.L.bfq_gzip_inflate_fd(self.h, fds[0], os.fstat(fds[0]).st_size, int(chunk), fds[1], C.byref(ol), C.byref(st)), ol)
             return int(ol.value), st
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+    # ---- BAM records to FASTQ text (bfq_bam_*, csrc/bfq_bam.h)
+    def _bam_ck(self, rc, ol):
+        if rc != 0:
+            _bam_raise(rc, self.L.bfq_last_error(self.h).decode(), ol)
+
+    def bam_measure(self, blob, **opts):
+        """bfq_bam_measure: (the three text lengths, the three read counts, stats) of a BAM file; nothing is written."""
+        blob = _u8(blob)
+        O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        self._bam_ck(self.L.bfq_bam_measure(self.h, _ptr(blob) if len(blob) else None, len(blob), C.byref(O), ol, nr, C.byref(st)), ol)
+        return [int(v) for v in ol], [int(v) for v in nr], st
+
+    def bam_to_fastq(self, blob, outs=None, **opts):
+        """(texts[3], stats) of a BAM file -- BGZF as samtools, GATK and DRAGEN write it, or the inflated stream itself --
+        converted on the GPU (bfq_bam_to_fastq); the texts are uint8 arrays: output 0, and with split=1 READ1-only records in
+        1 and READ2-only records in 2.  opts: bam_opts() (exclude_flags, mate_suffix, default_qual, split, paired_check,
+        piece).  `outs`: three uint8 arrays to fill; without them the file is measured first.  A buffer below its text raises
+        BfqError with .needed = the three lengths and nothing is written; a damaged or unpaired file raises BfqError
+        ("damaged BAM input: record <i> at byte <off>: <reason>", "unpaired BAM input: pair <k>: ...")."""
+        blob = _u8(blob)
+        if outs is None:
+            outs = [np.empty(v, np.uint8) for v in self.bam_measure(blob, **dict(opts, paired_check=0))[0]]
+        O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        ptrs, caps = _bam_outs(outs)
+        self._bam_ck(self.L.bfq_bam_to_fastq(self.h, _ptr(blob) if len(blob) else None, len(blob), C.byref(O), ptrs, caps, ol, nr, C.byref(st)), ol)
+        return [o[:int(n)] for o, n in zip(outs, ol)], st
+
+    def bam_to_fastq_device(self, blob, d_outs, caps, **opts):
+        """bfq_bam_to_fastq_device: the texts at the three device addresses d_outs (caps bytes each); returns (lengths, read counts, stats)."""
+        blob = _u8(blob)
+        O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        ptrs, cp = (C.c_void_p * 3)(*[int(p) if p else None for p in d_outs]), (C.c_uint64 * 3)(*[int(v) for v in caps])
+        self._bam_ck(self.L.bfq_bam_to_fastq_device(self.h, _ptr(blob) if len(blob) else None, len(blob), C.byref(O), ptrs, cp, ol, nr, C.byref(st)), ol)
+        return [int(v) for v in ol], [int(v) for v in nr], st
+
+    def bam_to_fastq_files(self, src, dsts=(None, None, None), **opts):
+        """bfq_bam_to_fastq_fd on named files: dsts = the paths of outputs 0, 1, 2 (None: not written; all None: convert and
+        verify only).  Returns (lengths, read counts, stats)."""
+        import os
+        fds = []
+        try:
+            fds.append(os.open(src, os.O_RDONLY))
+            for d in dsts:
+                fds.append(os.open(d, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) if d is not None else -1)
+            O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+            self._bam_ck(self.L.bfq_bam_to_fastq_fd(self.h, fds[0], os.fstat(fds[0]).st_size, C.byref(O), (C.c_int * 3)(*fds[1:4]), ol, nr, C.byref(st)), ol)
+            return [int(v) for v in ol], [int(v) for v in nr], st
         finally:
             for fd in fds:
                 if fd >= 0:

@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <sys/mman.h>
 #include <algorithm>
+#include <functional>
 #include "bfq_internal.h"
 #include "bfq_bgzf.h"
 
@@ -44,7 +45,8 @@ extern "C" int bfq_bgzf_index(const uint8_t *h_in, uint64_t len, bfq_bgzf_member
 
 // The text of h_in[0, len) at d_out (cap bytes; nullptr: in the arena, behind the compressed bytes).  Returns the raw length
 // and, through *where, the place of the text.
-static u64 bgzf_inflate_core(bfq_ctx *c, const u8 *h_in, u64 len, u8 *d_out, u64 cap, u8 **where)
+// `more`: bytes to reserve behind the text for the caller's own allocations, from the raw length.
+static u64 bgzf_inflate_core(bfq_ctx *c, const u8 *h_in, u64 len, u8 *d_out, u64 cap, u8 **where, const std::function<size_t(u64)> *more = nullptr)
 {
     if (!h_in && len) throw BfqError{BFQ_E_ARG, "null argument"};
     u64 n = 0, raw = 0, bad = 0;
@@ -61,7 +63,7 @@ static u64 bgzf_inflate_core(bfq_ctx *c, const u8 *h_in, u64 len, u8 *d_out, u64
     bfq_bgzf_walk(h_in, len, dir.data(), n, &n, &raw, &bad);
     const u64 used = hr ? bad : len;
     bfq_phase("alloc");
-    c->reserve((size_t)used + 24 * (size_t)n + (d_out ? 0 : (size_t)raw) + (1u << 20));
+    c->reserve((size_t)used + 24 * (size_t)n + (d_out ? 0 : (size_t)raw) + (more ? (*more)(raw) : 0) + (1u << 20));
     u8 *d_in = c->alloc<u8>(used + 16);
     bfq_bgzf_member *d_dir = c->alloc<bfq_bgzf_member>(n + 1);
     u64 *d_status = c->alloc<u64>(1);
@@ -80,6 +82,12 @@ static u64 bgzf_inflate_core(bfq_ctx *c, const u8 *h_in, u64 len, u8 *d_out, u64
     if (hr) bgzf_refuse(n, bad, hr);
     *where = d_out;
     return raw;
+}
+
+// bfq_bam.hip: the inflated stream of a BGZF file in the arena, with room for more(raw) bytes behind it
+u64 bfq_bgzf_inflate_arena(bfq_ctx *c, const u8 *h_in, u64 len, const std::function<size_t(u64)> &more, u8 **where)
+{
+    return bgzf_inflate_core(c, h_in, len, nullptr, ~0ull, where, &more);
 }
 
 extern "C" int bfq_bgzf_inflate(bfq_ctx *c, const uint8_t *h_in, uint64_t len, uint8_t *h_out, uint64_t cap, uint64_t *out_len)

@@ -1,0 +1,107 @@
+// bam_main.cpp -- BAM (unaligned or aligned) to FASTQ text on the GPU (not a tool of the reference, which takes plain text only):
+//     bfq_bam -i IN.bam -o OUT.fq [-F MASK] [-n] [-v Q] [-C PIECE] [-V]             every kept record, in file order
+//     bfq_bam -i IN.bam -1 OUT_1.fq -2 OUT_2.fq [-0 OTHER.fq] [-c] [...]            READ1 / READ2 / the rest; -c: the pairing check
+//     bfq_bam -t IN.bam                                                             convert and verify, writing nothing
+//     bfq_bam -l IN.bam                                                             the header counts and the statistics as JSON
+// include/bfqzip_hip.h, bfq_bam_to_fastq_fd: the records' text is this project's definition, modelled on the defaults of
+// `samtools fastq` (-F 0x900; /1 and /2 unless -n; absent qualities as -v Q, default 1).  Exit status 0 on success; 1 with
+// the library's message on a damaged or unpaired file, and then the outputs are left empty.
+#include <unistd.h>
+#include <sys/mman.h>
+#include "cli_common.h"
+
+static int usage(const char *argv0)
+{
+    fprintf(stderr, "usage: %s -i IN.bam -o OUT.fq | -1 OUT_1.fq -2 OUT_2.fq [-0 OTHER.fq] [-c] [-F MASK] [-n] [-v Q] [-C PIECE] [-V] | -t IN.bam | -l IN.bam\n"
+                    "  -i <arg>  BAM input (BGZF, or the inflated stream itself)\n"
+                    "  -o <arg>  one FASTQ output: every kept record in file order\n"
+                    "  -1 -2 <arg>  split: READ1-only and READ2-only records; -0 <arg>: the rest (dropped without it)\n"
+                    "  -c        with -1 -2: refuse unless the k-th names of both files are equal (collated input)\n"
+                    "  -F <arg>  leave out records with any of these flag bits (default 0x900)\n"
+                    "  -n        no /1 and /2 behind the names\n"
+                    "  -v <arg>  quality given to reads without qualities (default 1)\n"
+                    "  -C <arg>  bytes per piece of the stream (default 65536)\n"
+                    "  -t <arg>  convert and verify only: no output is written\n"
+                    "  -l <arg>  print references, header bytes, records and the statistics as JSON\n"
+                    "  -V        phase timeline on stderr\n", argv0);
+    return 1;
+}
+
+int main(int argc, char **argv)
+{
+    bfq_phase("start");
+    std::string input, outName[3];
+    char mode = 0;
+    bfq_bam_opts O;
+    bfq_bam_default_opts(&O);
+    int opt;
+    bool single = false;                                           // -o was given
+    while ((opt = getopt(argc, argv, "i:t:l:o:0:1:2:cF:nv:C:Vh")) != -1) {
+        switch (opt) {
+        case 'i': case 't': case 'l':
+            if (mode) return usage(argv[0]);
+            mode = (char)opt; input = optarg; break;
+        case 'o': case '0':
+            if (!outName[0].empty()) return usage(argv[0]);
+            outName[0] = optarg; single = opt == 'o'; if (opt == '0') O.split = 1; break;
+        case '1': outName[1] = optarg; O.split = 1; break;
+        case '2': outName[2] = optarg; O.split = 1; break;
+        case 'c': O.paired_check = 1; break;
+        case 'F': O.exclude_flags = (uint32_t)strtoul(optarg, nullptr, 0); break;
+        case 'n': O.mate_suffix = 0; break;
+        case 'v': O.default_qual = (uint32_t)strtoul(optarg, nullptr, 10); break;
+        case 'C': O.piece = (uint32_t)strtoul(optarg, nullptr, 10); break;
+        case 'V': bfq_phase_enable(1); break;
+        default: return usage(argv[0]);
+        }
+    }
+    const bool anyOut = !outName[0].empty() || !outName[1].empty() || !outName[2].empty();
+    if (!mode || (mode != 'i' && anyOut) || (mode == 'i' && !anyOut)) return usage(argv[0]);
+    if (mode == 'i' && (single ? O.split != 0 : outName[1].empty() || outName[2].empty())) return usage(argv[0]);
+    if (O.paired_check && !O.split) return usage(argv[0]);
+    InFile in;
+    if (!in.open(input)) { fprintf(stderr, "bfq_bam: cannot read %s\n", input.c_str()); return 1; }
+    OutFile out[3];
+    int fds[3] = {-1, -1, -1};
+    for (int o = 0; o < 3; o++)
+        if (!outName[o].empty()) {
+            if (!out[o].open(outName[o])) { perror("bfq_bam"); return 1; }
+            fds[o] = out[o].fd;
+        }
+    bfq_params P;
+    bfq_default_params(&P);
+    bfq_ctx *c = create_on_free_gpu("bfq_bam", &P);
+    if (!c) return 1;
+    uint64_t outLen[3] = {0, 0, 0}, nReads[3] = {0, 0, 0};
+    bfq_bam_stats S = {};
+    int rc;
+    if (mode == 'l') {
+        void *m = in.size ? mmap(nullptr, in.size, PROT_READ, MAP_PRIVATE, in.fd, 0) : MAP_FAILED;
+        rc = bfq_bam_measure(c, m != MAP_FAILED ? (const uint8_t *)m : nullptr, m != MAP_FAILED ? in.size : 0, &O, outLen, nReads, &S);
+        if (m != MAP_FAILED) munmap(m, in.size);
+    } else rc = bfq_bam_to_fastq_fd(c, in.fd, in.size, &O, fds, outLen, nReads, &S);
+    if (rc) {
+        fprintf(stderr, "bfq_bam: %s: %s\n", input.c_str(), bfq_last_error(c));
+        bfq_destroy(c);
+        for (int o = 0; o < 3; o++)
+            if (fds[o] >= 0 && ftruncate(fds[o], 0) != 0) perror("bfq_bam");
+        return 1;
+    }
+    bfq_phase("teardown");
+    trace_kernel_times(c, "bfq_bam");
+    bool closed = true;
+    for (int o = 0; o < 3; o++) closed = out[o].close() && closed;
+    bfq_destroy(c);
+    if (!closed) { perror("bfq_bam"); return 1; }
+    bfq_phase_report("bfq_bam");
+    typedef unsigned long long ull;
+    if (mode == 'l')
+        printf("{\"n_ref\": %llu, \"header_bytes\": %llu, \"records\": %llu, \"written\": [%llu, %llu, %llu], \"bytes\": [%llu, %llu, %llu], \"skipped\": %llu, "
+               "\"reversed\": %llu, \"no_qual\": %llu, \"clamped_quals\": %llu, \"pieces\": %llu, \"walkers\": %llu, \"dead\": %llu, \"repaired\": %llu, \"rounds\": %llu}\n",
+               (ull)S.n_ref, (ull)S.header_bytes, (ull)S.records, (ull)S.written[0], (ull)S.written[1], (ull)S.written[2], (ull)outLen[0], (ull)outLen[1], (ull)outLen[2],
+               (ull)S.skipped, (ull)S.reversed, (ull)S.no_qual, (ull)S.clamped_quals, (ull)S.pieces, (ull)S.walkers, (ull)S.dead, (ull)S.repaired, (ull)S.rounds);
+    else
+        printf("%llu records: %llu + %llu + %llu reads, %llu + %llu + %llu bytes%s\n", (ull)S.records, (ull)nReads[0], (ull)nReads[1], (ull)nReads[2], (ull)outLen[0],
+               (ull)outLen[1], (ull)outLen[2], mode == 't' ? " verified" : "");
+    return 0;
+}

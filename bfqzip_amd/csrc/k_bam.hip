@@ -1,0 +1,71 @@
+// k_bam.hip -- BAM records to FASTQ text on the device: the candidate search, the counting walk, the placing walk and the
+// pairing check.  The text of every step is bfq_bam.h's (the same that runs on the host under sanitizers); the host side
+// that orders them is bfq_bam.hip.  No workgroup waits for another; all launches are booked under the BGZF kernel class.
+#include "bfq_internal.h"
+#include "bfq_device.h"
+#include "bfq_bam.h"
+
+#define BAM_WAVES 4
+
+// Candidates and the counting walk.  Schedule as built: one wave64 per piece, four pieces per 256-thread workgroup.  The wave
+// goes through its piece 64 offsets at a time -- every lane tries the record-start rule at one offset; nearly all fail on
+// the four bytes of the block size -- and takes the lowest that passes (ballot).  From there all lanes hop together
+// (bfq_bam_walk: uniform control flow, the same loads in every lane) and share only the quality bytes, lane-consecutive,
+// for the count of clamped values.  Lane 0 writes the piece's record.  `only` != NONE: the walk of that one piece from
+// `from` (a repair round).
+__global__ __launch_bounds__(64 * BAM_WAVES) void k_bam_walk(const u8 *__restrict__ s, u64 len, u64 hdrEnd, u64 piece, u64 np, u32 nref, bfq_bam_opts O,
+                                                              u64 only, u64 from, bfq_bam_piece *recs)
+{
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const bool repair = only != BFQ_BAM_NONE;
+    for (u64 k = repair ? (wave == 0 ? only : np) : (u64)blockIdx.x * BAM_WAVES + wave; k < np; k += repair ? np : (u64)gridDim.x * BAM_WAVES) {
+        const u64 lo = hdrEnd + k * piece, hi = lo + piece < len ? lo + piece : len;
+        u64 start = only != BFQ_BAM_NONE ? from : k ? BFQ_BAM_NONE : hdrEnd;
+        for (u64 at = lo; start == BFQ_BAM_NONE && at < hi; at += 64) {
+            const u64 o = at + lane;
+            const u64 hit = __ballot(o < hi && bfq_bam_candidate(s, len, o, nref));
+            if (hit) start = at + (u64)(__ffsll((long long)hit) - 1);
+        }
+        bfq_bam_piece P{};
+        P.start = BFQ_BAM_NONE;
+        if (start != BFQ_BAM_NONE) {
+            const u64 mine = bfq_bam_walk(s, len, start, hi, nref, O, lane, 64, &P);
+            P.clamped = bfq_wave_incscan64(mine);                  // (lane 63 holds the wave's sum)
+            P.clamped = __shfl(P.clamped, 63);
+        }
+        if (lane == 0) recs[k] = P;
+    }
+}
+
+// The placing walk.  Schedule as built: one wave64 per piece of the chain, four per workgroup.  The wave hops over its
+// records as the counting walk did and writes every kept record's text at the place the prefix sums gave it: lane i takes
+// bytes i, i + 64, ... of the name, of the bases (a nibble each) and of the qualities, so a wave's stores are 64
+// consecutive bytes and no lane writes a record alone.  A wave writes its own [byteBase, byteBase + bytes) and nothing else.
+__global__ __launch_bounds__(64 * BAM_WAVES) void k_bam_place(const u8 *__restrict__ s, u64 len, const bfq_bam_job *__restrict__ jobs, u64 nj, u32 nref,
+                                                               bfq_bam_opts O, bfq_bam_outs out)
+{
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    for (u64 j = (u64)blockIdx.x * BAM_WAVES + wave; j < nj; j += (u64)gridDim.x * BAM_WAVES) bfq_bam_place(s, len, jobs[j], nref, O, out, lane, 64);
+}
+
+// The pairing check.  Schedule as built: one thread per pair; the lowest pair whose names differ by atomicMin.
+__global__ __launch_bounds__(256) void k_bam_pairs(const u8 *__restrict__ s, const u64 *__restrict__ a, const u64 *__restrict__ b, u64 n, u64 *firstBad)
+{
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+        if (!bfq_bam_same_name(s, a[i], b[i])) atomicMin((unsigned long long *)firstBad, (unsigned long long)i);
+}
+
+void bfq_bam_launch_walk(bfq_ctx *c, const u8 *d_s, u64 len, u64 hdrEnd, u64 piece, u64 np, u32 nref, const bfq_bam_opts &O, u64 only, u64 from,
+                         bfq_bam_piece *d_recs)
+{
+    KLAUNCH(c, K_BGZF, only == BFQ_BAM_NONE ? len : piece, k_bam_walk, only == BFQ_BAM_NONE ? bfq_grid(np, BAM_WAVES) : 1u, 64 * BAM_WAVES, d_s, len, hdrEnd, piece,
+            np, nref, O, only, from, d_recs);
+}
+void bfq_bam_launch_place(bfq_ctx *c, const u8 *d_s, u64 len, const bfq_bam_job *d_jobs, u64 nj, u32 nref, const bfq_bam_opts &O, const bfq_bam_outs &out, u64 bytes)
+{
+    if (nj) KLAUNCH(c, K_BGZF, len + bytes, k_bam_place, bfq_grid(nj, BAM_WAVES), 64 * BAM_WAVES, d_s, len, d_jobs, nj, nref, O, out);
+}
+void bfq_bam_launch_pairs(bfq_ctx *c, const u8 *d_s, const u64 *d_a, const u64 *d_b, u64 n, u64 *d_firstBad)
+{
+    if (n) KLAUNCH(c, K_BGZF, n * 80, k_bam_pairs, bfq_grid(n, 256), 256, d_s, d_a, d_b, n, d_firstBad);
+}

@@ -223,6 +223,40 @@ def inflate_inputs(eng, comm, inputs, out="", log=None, gunzip=False):
     return new, tmp
 
 
+def bam_names(path, out, split):
+    """Where --bam converts a BAM input to: beside the outputs (the directory of -o, else the input's), <name>.fastq, or
+    <name>_1.fastq and <name>_2.fastq for the one file of a paired run."""
+    root = os.path.splitext(os.path.basename(path))[0]
+    d = os.path.dirname(out) if out else os.path.dirname(path)
+    return [os.path.join(d, root + tag + ".fastq") for tag in (("_1", "_2") if split else ("",))]
+
+
+def convert_bam_inputs(eng, comm, inputs, out="", paired=False, log=None):
+    """--bam: an input for which api.bam_probe holds is converted to FASTQ text on the GPU (eng.bam_to_fastq_files) by rank 0
+    before the line index is built, as inflate_inputs does for .gz, and the run goes on with that file: returns (the new
+    input list, the files written).  With -p and a single BAM input the file is split by its READ1 / READ2 flags, with the
+    pairing check (records that are neither are left out), and the run goes on as a two-file paired run."""
+    from . import api
+    new, tmp = [], []
+    for p in inputs:
+        with open(p, "rb") as f:
+            is_bam = api.bam_probe(f.read(1 << 17))                 # (a whole first member: at most 64 KiB)
+        if not is_bam:
+            new.append(p)
+            continue
+        split = paired and len(inputs) == 1
+        q = bam_names(p, out, split)
+        if comm.rank == 0:                                          # (a damaged or unpaired file: the library's message)
+            n, reads, st = eng.bam_to_fastq_files(p, (None, q[0], q[1]) if split else (q[0], None, None), split=int(split), paired_check=int(split))
+            if log:
+                log(f"bam: {p} -> {q}, {reads} reads, {st}")
+        new += q
+        tmp += q
+    if tmp:
+        comm.barrier()
+    return new, tmp
+
+
 def reordered_names(inputs, mode):
     """Where --reorder puts its intermediate files: <root>.reordered<ext> (mode 2, BFQzip_parallel.py:398) or
     <root>.random<ext> (mode 1, :421) beside every input."""
@@ -669,12 +703,15 @@ def main(argv=None):
     ap.add_argument("--gunzip", action="store_true",
                     help="a .gz input that is gzip but not BGZF (gzip, pigz, bcl2fastq) is inflated on the GPU too, its deflate streams "
                          "side by side; without this such a file is refused")
+    ap.add_argument("--bam", action="store_true",
+                    help="a BAM input (unaligned or aligned) is converted to <name>.fastq beside the outputs on the GPU first "
+                         "(--keep-inflated keeps it); with -p one BAM file is split into <name>_1.fastq / <name>_2.fastq with the pairing check")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
     if a.restore and (len(a.input) not in (2, 3) or not a.out):
         print("=== ERROR ===\n--restore DNA.bsc QS.bsc [HDR.bsc] -o OUT.fq", file=sys.stderr)
         return 1
-    if a.paired and len(a.input) != 2:
+    if a.paired and len(a.input) != 2 and not (a.bam and len(a.input) == 1):
         print("=== ERROR ===\npaired end mode", file=sys.stderr)
         return 1
     if a.m3:
@@ -712,7 +749,14 @@ def main(argv=None):
         if dist:
             dist.destroy_process_group()
         return 0
+    converted = []
+    if a.bam:
+        a.input, converted = convert_bam_inputs(eng, comm, a.input, a.out, paired=a.paired, log=log)
+        if a.paired and len(a.input) != 2:
+            print("=== ERROR ===\npaired end mode", file=sys.stderr)
+            return 1
     a.input, inflated = inflate_inputs(eng, comm, a.input, a.out, log=log, gunzip=a.gunzip)
+    inflated = converted + inflated
     perm_path = reordered_names(a.input[:1], a.reorder)[0] + ".perm" if (a.keep_order and a.reorder) else None
     keep = dict(perm_path=perm_path) if perm_path else {}
     original = list(a.input)

@@ -702,6 +702,72 @@ int bfq_gzip_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, uint64_t chunk, int
 int bfq_gzip_inflate_host(const uint8_t *h_in, uint64_t len, uint64_t chunk, uint8_t *h_out, uint64_t cap, uint64_t *out_len,
                           bfq_gzip_stats *stats);
 const char *bfq_gzip_host_error(void);
+/* ---- BAM input: the records of a BAM file as FASTQ text, made on the device (k_bam.hip; the format, the record check, the
+ * record-start rule and every bound: csrc/bfq_bam.h).  Unaligned BAM (GATK, DRAGEN, instrument software) and aligned BAM
+ * alike.  A BAM file is a BGZF file: bfq_bgzf_inflate puts its inflated stream into device memory; a source that begins
+ * with "BAM\1" itself is taken as that stream and uploaded as it is.  Records are length-prefixed, so the work is found
+ * and proved as for plain gzip:
+ *   1 the stream behind the header (walked on the host, any size, up to 2^20 references) is cut into pieces of opts.piece
+ *     bytes; in every piece behind the first the device looks for the lowest offset that passes the record-start rule (a
+ *     well-formed record with pos, next_pos >= -1 and a printable name, followed by another or by the end): a heuristic;
+ *   2 one walker per piece hops from record to record up to the first record at or behind the piece's end (its landing),
+ *     checks every record and counts records, kept records and text bytes per output;
+ *   3 the host walks the landings from the header's end: the chain.  A piece whose walker did not start at the chain's
+ *     landing (a false start, even one that fell back into step; or no walker) is walked again from there, one round
+ *     each.  Exactness rests on the chain: every record on it has passed the record check;
+ *   4 prefix sums of the chain's counts place every piece's text; a second walk writes it, a wave64 per piece, the lanes
+ *     sharing each record's bytes.
+ * What a record becomes (this project's definition, modelled on the defaults of `samtools fastq`; parity with samtools is
+ * not pinned by a test):  flag & exclude_flags != 0: left out.  "@name" ["/1" | "/2" with mate_suffix, where exactly one of
+ * READ1 0x40 / READ2 0x80 is set] \n sequence (=ACMGRSVTWYHKDBN) \n + \n phred + 33 \n.  Flag 0x10: reverse complement
+ * (=TGKCYSBAWRDMHVN) and reversed qualities.  A quality above 93 is written '~' (clamped_quals); absent qualities (0xFF)
+ * become default_qual + 33 (no_qual counts the records).  split: READ1-only records to output 1, READ2-only to output 2,
+ * the rest to output 0 -- else everything to output 0 -- each in file order.  paired_check (needs split): refused unless
+ * outputs 1 and 2 hold the same number of records and their k-th names are equal (compared on the device):
+ * "unpaired BAM input: pair <k>: <what>; collate the file by name first".  A kept record is l_read_name + 2 l_seq + 5
+ * bytes of text, + 2 with a suffix.
+ *   opts (NULL: the defaults): exclude_flags 0x900, mate_suffix 1, default_qual 1 (0..93), split 0, paired_check 0,
+ *     piece 0 = the default (65 536; 64 .. 2^30).  The texts and all statistics but pieces .. rounds do not depend on piece.
+ *   bfq_bam_probe   : 1 for "BAM\1", or a BGZF file whose first member inflates to a text that begins so (inflated on the
+ *     host), else 0.  Host only.
+ *   bfq_bam_measure : steps 1-3: exact out_len[3], n_reads[3] and *stats; nothing is written.
+ *   bfq_bam_to_fastq* : the texts.  A cap[k] below the measured length: BFQ_E_ARG, nothing written, out_len[] = the lengths
+ *     needed (every other failure leaves them 0).  Device memory, in the workspace: the compressed bytes, the inflated
+ *     stream, 168 bytes per piece, 8 bytes per record of outputs 1 and 2 with paired_check, and -- for the host and file
+ *     forms -- 4/3 of the stream for the texts.
+ *       bfq_bam_to_fastq        : host buffers out
+ *       bfq_bam_to_fastq_device : device buffers out; the text never exists on the host
+ *       bfq_bam_to_fastq_fd     : open files; an out_fd[k] < 0 is not written
+ *   bfq_bam_to_fastq_host : the same steps by one thread on the INFLATED stream raw[0, raw_len), with no context and no
+ *     GPU: the same bytes and the same *stats.  It states the algorithm and is what the tests compare with; NO entry point
+ *     falls back to it.  Its message: bfq_bam_host_error() (of the calling thread's last call).
+ *   stats (may be NULL): records of the file, written[3], skipped (excluded), reversed, no_qual, clamped_quals (of the kept
+ *     records), n_ref, header_bytes, pieces, walkers started by the rule (piece 0's included), dead (walkers that met a
+ *     record failing the check), repaired (pieces walked again), rounds (1 + repaired).
+ * Refusals: BFQ_E_ARG, "damaged BAM input: record <i> at byte <off of the inflated stream>: <reason>" for a record that
+ *   fails the check on the chain (block size below 32 / above 2^24 / past the end of the stream -- a stream that ends inside
+ *   a record --, l_read_name 0, the fields not fitting the block, a name without its NUL or with one inside, a reference
+ *   index outside [-1, n_ref)); BFQ_E_TOO_LONG with the same words for l_seq > BFQ_MAX_READ_LEN; "damaged BAM input: header at
+ *   byte <off>: <reason>"; a refusal of the BGZF layer keeps the BGZF message.  With paired_check the device form may have
+ *   written text before the names are refused; the host and file forms write nothing.  The context stays usable.
+ * The entry points that take FASTQ text keep reading 1f 8b as BGZF-compressed FASTQ: BAM is taken by these calls only. */
+typedef struct bfq_bam_opts { uint32_t exclude_flags, mate_suffix, default_qual, split, paired_check, piece, reserved[2]; } bfq_bam_opts;
+typedef struct bfq_bam_stats {
+    uint64_t records, written[3], skipped, reversed, no_qual, clamped_quals, n_ref, header_bytes, pieces, walkers, dead, repaired, rounds;
+} bfq_bam_stats;
+void bfq_bam_default_opts(bfq_bam_opts *o);
+int bfq_bam_probe(const uint8_t *h, uint64_t len);
+int bfq_bam_measure(bfq_ctx *c, const uint8_t *h_in, uint64_t len, const bfq_bam_opts *opts, uint64_t out_len[3], uint64_t n_reads[3],
+                    bfq_bam_stats *stats);
+int bfq_bam_to_fastq(bfq_ctx *c, const uint8_t *h_in, uint64_t len, const bfq_bam_opts *opts, uint8_t *const h_out[3], const uint64_t cap[3],
+                     uint64_t out_len[3], uint64_t n_reads[3], bfq_bam_stats *stats);
+int bfq_bam_to_fastq_device(bfq_ctx *c, const uint8_t *h_in, uint64_t len, const bfq_bam_opts *opts, uint8_t *const d_out[3], const uint64_t cap[3],
+                            uint64_t out_len[3], uint64_t n_reads[3], bfq_bam_stats *stats);
+int bfq_bam_to_fastq_fd(bfq_ctx *c, int in_fd, uint64_t len, const bfq_bam_opts *opts, const int out_fd[3], uint64_t out_len[3],
+                        uint64_t n_reads[3], bfq_bam_stats *stats);
+int bfq_bam_to_fastq_host(const uint8_t *raw, uint64_t raw_len, const bfq_bam_opts *opts, uint8_t *const h_out[3], const uint64_t cap[3],
+                          uint64_t out_len[3], uint64_t n_reads[3], bfq_bam_stats *stats);
+const char *bfq_bam_host_error(void);
 /* ---- bgzip-compressed output: BGZF members deflated on the device (k_deflate.hip; the format and every bound:
  * csrc/bfq_deflate.h).  A text of len bytes is cut at multiples of 65 280 bytes (htslib's member size; the cut depends on
  * nothing else); every piece becomes one BGZF member -- htslib's 18-byte header, a raw deflate payload, CRC32 and ISIZE --
