@@ -40,6 +40,7 @@ SYMBOLS = [
     "bfq_gzip_host_error",
     "bfq_bam_default_opts", "bfq_bam_probe", "bfq_bam_measure", "bfq_bam_to_fastq", "bfq_bam_to_fastq_device", "bfq_bam_to_fastq_fd",
     "bfq_bam_to_fastq_host", "bfq_bam_host_error",
+    "bfq_bam_patch_host", "bfq_bam_patch_device", "bfq_bam_patch", "bfq_bam_patch_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -98,8 +99,8 @@ class GzipStats(C.Structure):
 
 
 class BamOpts(C.Structure):
-    """bfq_bam_opts: exclude_flags, mate_suffix, default_qual, split, paired_check, piece (0: the default)"""
-    _fields_ = [(k, C.c_uint32) for k in ("exclude_flags", "mate_suffix", "default_qual", "split", "paired_check", "piece")] + [("reserved", C.c_uint32 * 2)]
+    """bfq_bam_opts: exclude_flags, mate_suffix, default_qual, split, paired_check, piece (0: the default), check_names (bfq_bam_patch* only)"""
+    _fields_ = [(k, C.c_uint32) for k in ("exclude_flags", "mate_suffix", "default_qual", "split", "paired_check", "piece", "check_names", "reserved")]
 
 
 class BamStats(C.Structure):
@@ -115,6 +116,20 @@ class BamStats(C.Structure):
 
     def __repr__(self):
         return "BamStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
+
+
+class BamPatchStats(C.Structure):
+    """bfq_bam_patch_stats: records of the file, patched[3], skipped, reversed, reads_changed, bases_changed, quals_changed, unknown_bases,
+    kept_high_quals, kept_absent, raw_len, pieces, repaired"""
+    _fields_ = [("records", C.c_uint64), ("patched", C.c_uint64 * 3)] + [(k, C.c_uint64) for k in (
+        "skipped", "reversed", "reads_changed", "bases_changed", "quals_changed", "unknown_bases", "kept_high_quals", "kept_absent", "raw_len", "pieces",
+        "repaired")]
+
+    def as_dict(self):
+        return {k: [int(v) for v in self.patched] if k == "patched" else int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "BamPatchStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
 
 
 CMP_SYMS = 6
@@ -305,6 +320,11 @@ def lib():
         L.bfq_bam_to_fastq_host.argtypes = [vp, u64, pbo, C.POINTER(vp), a3, a3, a3, pbs]
         L.bfq_bam_host_error.restype = C.c_char_p
         L.bfq_bam_host_error.argtypes = []
+        pps, i3 = C.POINTER(BamPatchStats), C.POINTER(C.c_int)
+        L.bfq_bam_patch_host.argtypes = [vp, u64, pbo, C.POINTER(vp), a3, vp, u64, pps]
+        L.bfq_bam_patch_device.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, vp, u64, pu64, pps]
+        L.bfq_bam_patch.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, C.c_int, vp, u64, pu64, pps]
+        L.bfq_bam_patch_fd.argtypes = [vp, C.c_int, u64, pbo, i3, C.c_int, C.c_int, pu64, pps]
         L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_radix_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(u64)]

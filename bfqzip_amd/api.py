@@ -262,9 +262,10 @@ def gzip_inflate_host(blob, chunk=0, out=None):
     return out[:int(ol.value)], st
 
 
-def bam_opts(exclude_flags=0x900, mate_suffix=1, default_qual=1, split=0, paired_check=0, piece=0):
-    """bfq_bam_opts (include/bfqzip_hip.h); the defaults are bfq_bam_default_opts'."""
+def bam_opts(exclude_flags=0x900, mate_suffix=1, default_qual=1, split=0, paired_check=0, piece=0, check_names=0):
+    """bfq_bam_opts (include/bfqzip_hip.h); the defaults are bfq_bam_default_opts'.  check_names: bam_patch* only."""
     o = _lib.BamOpts()
+    o.check_names = int(check_names)
     o.exclude_flags, o.mate_suffix, o.default_qual, o.split, o.paired_check, o.piece = (int(exclude_flags), int(mate_suffix), int(default_qual), int(split),
                                                                                       int(paired_check), int(piece))
     return o
@@ -310,6 +311,44 @@ def bam_to_fastq_host(raw, outs=None, **opts):
     return [o[:int(n)] for o, n in zip(outs, ol)], st
 
 
+def _bam_patch_raise(rc, msg, needed):
+    e = BfqError(rc, msg)
+    e.needed = int(needed)                                         # the capacity needed, when the buffer was too small; else 0
+    raise e
+
+
+_EMPTY_TEXT = np.zeros(1, np.uint8)                                # where an empty text (present, unlike None) points
+
+
+def _bam_texts(texts):
+    """the three texts of a bam_patch call (None: absent; fewer than three: the rest absent) as pointer and length arrays"""
+    texts = [None if t is None else _u8(t) for t in list(texts) + [None] * (3 - len(texts))]
+    if len(texts) != 3:
+        raise ValueError("bam_patch: at most three texts")
+    ptrs = (C.c_void_p * 3)(*[None if t is None else (t if len(t) else _EMPTY_TEXT).ctypes.data for t in texts])
+    lens = (C.c_uint64 * 3)(*[0 if t is None else len(t) for t in texts])
+    return texts, ptrs, lens
+
+
+def bam_patch_host(stream, texts, out=None, **opts):
+    """(the patched stream, stats) of the INFLATED stream of a BAM file with the reads of up to three FASTQ texts written
+    back into it, by the host form (bfq_bam_patch_host: the steps of csrc/bfq_bam_patch.h by one thread, no GPU): the
+    statement of the algorithm -- Engine.bam_patch_device gives the same bytes and the same stats.  texts[k] (None: absent)
+    meets output k of bam_to_fastq with the same opts (bam_opts(); check_names=1 compares the names too).  `out`: a uint8 array
+    of at least len(stream) to fill.  Refusals raise BfqError ("BAM patch: ...", "FASTQ: ...", "damaged BAM input: ...") and
+    write nothing."""
+    stream = _u8(stream)
+    L = _lib.lib()
+    keep, ptrs, lens = _bam_texts(texts)
+    if out is None:
+        out = np.empty(len(stream), np.uint8)
+    O, st = bam_opts(**opts), _lib.BamPatchStats()
+    rc = L.bfq_bam_patch_host(_ptr(stream) if len(stream) else None, len(stream), C.byref(O), ptrs, lens, _ptr(out) if len(out) else None, len(out), C.byref(st))
+    if rc != 0:
+        _bam_patch_raise(rc, L.bfq_bam_host_error().decode(), st.raw_len)
+    return out[:len(stream)], st
+
+
 def text_len(a):
     """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
     a = _u8(a)
@@ -330,6 +369,7 @@ class HostText:
     gzip_inflate_host = staticmethod(gzip_inflate_host)
     bam_probe = staticmethod(bam_probe)
     bam_to_fastq_host = staticmethod(bam_to_fastq_host)
+    bam_patch_host = staticmethod(bam_patch_host)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -794,6 +834,62 @@ class Engine:
             O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
             self._bam_ck(self.L.bfq_bam_to_fastq_fd(self.h, fds[0], os.fstat(fds[0]).st_size, C.byref(O), (C.c_int * 3)(*fds[1:4]), ol, nr, C.byref(st)), ol)
             return [int(v) for v in ol], [int(v) for v in nr], st
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+    # ---- FASTQ texts back into their BAM (bfq_bam_patch*, csrc/bfq_bam_patch.h)
+    def bam_patch(self, blob, texts, level=1, out=None, **opts):
+        """(the BAM file, stats): `blob` -- a BAM file as bam_to_fastq takes it -- with the sequence and quality lines of up
+        to three FASTQ texts written back into the records they came from, patched on the GPU and compressed there
+        (bfq_bam_patch); a uint8 array.  texts[k] (None: absent, its records stay) meets output k of bam_to_fastq with the same
+        opts: bam_opts(), check_names=1 compares the names too.  level: as bgzf_deflate.  `out`: a uint8 array to fill; one
+        below HostText.bgzf_deflate_bound(the stream's length) raises BfqError with .needed = that bound, nothing written;
+        without one it is sized from the file's directory.  Refusals raise BfqError (BFQ_E_ARG: "BAM patch: text <k> ...", "FASTQ: ...",
+        "damaged BAM input: ...").  An index of the input does not fit the result; MD / NM tags go stale where a base changed."""
+        blob = _u8(blob)
+        keep, ptrs, lens = _bam_texts(texts)
+        if out is None:
+            out = np.empty(bgzf_deflate_bound(text_len(blob)), np.uint8)    # (the directory gives the stream's length)
+        O, st, ol = bam_opts(**opts), _lib.BamPatchStats(), C.c_uint64(0)
+        rc = self.L.bfq_bam_patch(self.h, _ptr(blob) if len(blob) else None, len(blob), C.byref(O), ptrs, lens, int(level), _ptr(out) if len(out) else None,
+                                  len(out), C.byref(ol), C.byref(st))
+        if rc != 0:
+            _bam_patch_raise(rc, self.L.bfq_last_error(self.h).decode(), ol.value)
+        return out[:int(ol.value)], st
+
+    def bam_patch_device(self, blob, d_texts, text_lens, d_out, cap, **opts):
+        """bfq_bam_patch_device: the texts at the device addresses d_texts (None / 0: absent), the patched INFLATED stream at
+        the device address d_out (cap bytes), not compressed; returns (its length, stats).  A cap below that length raises
+        BfqError with .needed = the length, nothing written."""
+        blob = _u8(blob)
+        ptrs = (C.c_void_p * 3)(*[int(p) if p else None for p in d_texts])
+        lens = (C.c_uint64 * 3)(*[int(v) for v in text_lens])
+        O, st, rl = bam_opts(**opts), _lib.BamPatchStats(), C.c_uint64(0)
+        rc = self.L.bfq_bam_patch_device(self.h, _ptr(blob) if len(blob) else None, len(blob), C.byref(O), ptrs, lens, C.c_void_p(d_out), int(cap), C.byref(rl),
+                                         C.byref(st))
+        if rc != 0:
+            _bam_patch_raise(rc, self.L.bfq_last_error(self.h).decode(), rl.value)
+        return int(rl.value), st
+
+    def bam_patch_files(self, src, texts, dst, level=1, **opts):
+        """bfq_bam_patch_fd on named files: the BAM file src with the FASTQ files texts[k] (None: absent) in it, written to dst
+        (left empty on a refusal).  Returns (the length of dst, stats)."""
+        import os
+        texts = list(texts) + [None] * (3 - len(texts))
+        fds = []
+        try:
+            fds.append(os.open(src, os.O_RDONLY))
+            for t in texts[:3]:
+                fds.append(os.open(t, os.O_RDONLY) if t is not None else -1)
+            fds.append(os.open(dst, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            O, st, ol = bam_opts(**opts), _lib.BamPatchStats(), C.c_uint64(0)
+            rc = self.L.bfq_bam_patch_fd(self.h, fds[0], os.fstat(fds[0]).st_size, C.byref(O), (C.c_int * 3)(*fds[1:4]), int(level), fds[4], C.byref(ol),
+                                         C.byref(st))
+            if rc != 0:
+                _bam_patch_raise(rc, self.L.bfq_last_error(self.h).decode(), ol.value)
+            return int(ol.value), st
         finally:
             for fd in fds:
                 if fd >= 0:

@@ -26,6 +26,7 @@
 #include "../../include/bfqzip_hip.h"
 #include <stdio.h>
 #include <string.h>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -352,22 +353,35 @@ inline bool bfq_bam_pair_counts(const bfq_bam_stats &S, bfq_bam_err *E)
     return false;
 }
 
-// The host form: the same steps by one thread on the inflated stream s[0, len).  O: resolved options.  out[k] / cap[k]: the
-// three texts (measure: not touched).  Returns 0, 1 = refused (*E), 2 = a capacity below the measured length (outLen: the
-// lengths needed; nothing written).
-inline int bfq_bam_host(const u8 *s, u64 len, const bfq_bam_opts &O, u8 *const out[3], const u64 cap[3], bool measure, u64 outLen[3], u64 nReads[3],
-                        bfq_bam_stats *S, bfq_bam_err *E)
+// What steps 1-3 leave on the device side: the stream in the arena (d_s, raw bytes) and the chain.  bfq_bam.hip's, declared
+// here for the two host files of the BAM calls (bfq_bam.hip, bfq_bam_patch.hip):
+//   bfq_bam_chain_device  steps 1-3: the stream of h_in[0, len) into the arena -- reserved there, once, with more(raw length)
+//                         bytes beside the stream --, the header, the counting walk, the chain; *stats (may be null) is set
+//                         before a damaged file is refused
+//   bfq_bam_refuse        throws the refusal that *E words;  bfq_bam_opts_of: the resolved options of a call, or throws
+//   bfq_bam_host_error_set  the calling thread's bfq_bam_host_error()
+struct bfq_bam_chain_dev { u8 *d_s = nullptr; u64 raw = 0, hdrEnd = 0; u32 nref = 0; std::vector<bfq_bam_piece> P; std::vector<bfq_bam_job> jobs; bfq_bam_stats S; };
+void bfq_bam_chain_device(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts &O, const std::function<size_t(u64)> &more, bfq_bam_stats *stats,
+                          bfq_bam_chain_dev *C);
+void bfq_bam_refuse(const bfq_bam_err &E);
+bfq_bam_opts bfq_bam_opts_of(const bfq_bam_opts *in);
+void bfq_bam_host_error_set(const std::string &msg);
+
+// Steps 1-3 by one thread on the inflated stream s[0, len): the header, the candidates and the counting walk, the chain.
+// O: resolved options.  Fills P, jobs, *S and -- returning false -- *E.  Shared by both directions' host forms.
+inline bool bfq_bam_host_chain(const u8 *s, u64 len, const bfq_bam_opts &O, u32 *nrefOut, u64 *hdrEndOut, std::vector<bfq_bam_piece> &P,
+                               std::vector<bfq_bam_job> &jobs, bfq_bam_stats *S, bfq_bam_err *E)
 {
     *S = bfq_bam_stats{};
     *E = bfq_bam_err{};
-    outLen[0] = outLen[1] = outLen[2] = nReads[0] = nReads[1] = nReads[2] = 0;
     u32 nref = 0;
     u64 hdrEnd = 0, bad = 0;
     const int hr = bfq_bam_header([&](u64 off, u64 n, u8 *dst) { memcpy(dst, s + off, (size_t)n); }, len, &nref, &hdrEnd, &bad);
-    if (hr) { E->reason = hr; E->header = true; E->off = bad; return 1; }
+    if (hr) { E->reason = hr; E->header = true; E->off = bad; return false; }
     S->n_ref = nref; S->header_bytes = hdrEnd;
+    *nrefOut = nref; *hdrEndOut = hdrEnd;
     const u64 piece = O.piece, np = bfq_bam_pieces(len, hdrEnd, piece);
-    std::vector<bfq_bam_piece> P(np);
+    P.assign(np, bfq_bam_piece{});
     for (u64 k = 0; k < np; k++) {
         const u64 lo = hdrEnd + k * piece, hi = lo + piece < len ? lo + piece : len;
         u64 cand = k ? BFQ_BAM_NONE : hdrEnd;
@@ -376,7 +390,6 @@ inline int bfq_bam_host(const u8 *s, u64 len, const bfq_bam_opts &O, u8 *const o
         if (cand == BFQ_BAM_NONE) { P[k] = bfq_bam_piece{}; P[k].start = BFQ_BAM_NONE; continue; }
         P[k].clamped = bfq_bam_walk(s, len, cand, hi, nref, O, 0, 1, &P[k]);
     }
-    std::vector<bfq_bam_job> jobs;
     bfq_bam_chain(P, hdrEnd, len, piece, [&](u64 k, u64 start) {
         bfq_bam_piece w;
         const u64 hi = hdrEnd + (k + 1) * piece < len ? hdrEnd + (k + 1) * piece : len;
@@ -384,7 +397,22 @@ inline int bfq_bam_host(const u8 *s, u64 len, const bfq_bam_opts &O, u8 *const o
         w.clamped = cl;
         return w;
     }, jobs, S, E);
-    if (E->reason) return 1;
+    return E->reason == 0;
+}
+
+// The host form: the same steps by one thread on the inflated stream s[0, len).  O: resolved options.  out[k] / cap[k]: the
+// three texts (measure: not touched).  Returns 0, 1 = refused (*E), 2 = a capacity below the measured length (outLen: the
+// lengths needed; nothing written).
+inline int bfq_bam_host(const u8 *s, u64 len, const bfq_bam_opts &O, u8 *const out[3], const u64 cap[3], bool measure, u64 outLen[3], u64 nReads[3],
+                        bfq_bam_stats *S, bfq_bam_err *E)
+{
+    outLen[0] = outLen[1] = outLen[2] = nReads[0] = nReads[1] = nReads[2] = 0;
+    u32 nref = 0;
+    u64 hdrEnd = 0;
+    std::vector<bfq_bam_piece> P;
+    std::vector<bfq_bam_job> jobs;
+    if (!bfq_bam_host_chain(s, len, O, &nref, &hdrEnd, P, jobs, S, E)) return 1;
+    const u64 piece = O.piece;
     bfq_bam_totals(P, jobs, hdrEnd, piece, outLen);
     for (int o = 0; o < 3; o++) nReads[o] = S->written[o];
     if (measure) return 0;

@@ -36,6 +36,8 @@ static bfq_bam_opts bam_opts(const bfq_bam_opts *in)
     return O;
 }
 static bool is_gzip(const u8 *h, u64 len) { return len >= 2 && h[0] == 0x1F && h[1] == 0x8B; }
+void bfq_bam_refuse(const bfq_bam_err &E) { bam_refuse(E); }                       // (declared in bfq_bam.h, for bfq_bam_patch.hip)
+bfq_bam_opts bfq_bam_opts_of(const bfq_bam_opts *in) { return bam_opts(in); }
 
 extern "C" void bfq_bam_default_opts(bfq_bam_opts *o)
 {
@@ -59,6 +61,7 @@ extern "C" int bfq_bam_probe(const uint8_t *h, uint64_t len)
 
 static thread_local std::string g_bamHostErr;
 extern "C" const char *bfq_bam_host_error(void) { return g_bamHostErr.c_str(); }
+void bfq_bam_host_error_set(const std::string &msg) { g_bamHostErr = msg; }
 extern "C" int bfq_bam_to_fastq_host(const uint8_t *raw, uint64_t raw_len, const bfq_bam_opts *opts, uint8_t *const h_out[3], const uint64_t cap[3],
                                      uint64_t out_len[3], uint64_t n_reads[3], bfq_bam_stats *stats)
 {
@@ -89,19 +92,10 @@ extern "C" int bfq_bam_to_fastq_host(const uint8_t *raw, uint64_t raw_len, const
     }
 }
 
-enum BamMode { BAM_MEASURE, BAM_DEVICE, BAM_ARENA };
-// The texts of h_in[0, len) at d_out[] (BAM_DEVICE) or in the arena (BAM_ARENA; *where), or steps 1-3 only (BAM_MEASURE).
-// outLen / nReads: set once the chain stands, also when a capacity is then found short (*isShort).
-static void bam_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *opts, BamMode mode, u8 *const d_out[3], const u64 cap[3], u64 outLen[3],
-                     u64 nReads[3], bfq_bam_stats *stats, u8 *where[3], bool *isShort)
+// Steps 1-3, shared by both directions (bfq_bam.h states what it leaves).
+void bfq_bam_chain_device(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts &O, const std::function<size_t(u64)> &more, bfq_bam_stats *stats, bfq_bam_chain_dev *C)
 {
     if (!h_in && len) throw BfqError{BFQ_E_ARG, "null argument"};
-    const bfq_bam_opts O = bam_opts(opts);
-    const std::function<size_t(u64)> more = [&](u64 raw) {
-        const size_t np = (size_t)(raw / O.piece + 2);
-        return np * (sizeof(bfq_bam_piece) + sizeof(bfq_bam_job) + 8) + (O.paired_check ? (size_t)raw / 4 + 1024 : 0) +
-               (mode == BAM_ARENA ? (size_t)BFQ_BAM_TEXT_BOUND(raw) + 1024 : 0) + 8192;
-    };
     u8 *d_s = nullptr;
     u64 raw = len;
     if (is_gzip(h_in, len)) raw = bfq_bgzf_inflate_arena(c, h_in, len, more, &d_s);
@@ -113,7 +107,8 @@ static void bam_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *op
         bfq_upload(c, d_s, h_in, len);
         bfq_phase("gpu");
     }
-    bfq_bam_stats S{};
+    bfq_bam_stats &S = C->S;
+    S = bfq_bam_stats{};
     bfq_bam_err E;
     u32 nref = 0;
     u64 hdrEnd = 0, bad = 0;
@@ -126,19 +121,43 @@ static void bam_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *op
     const u64 piece = O.piece, np = bfq_bam_pieces(raw, hdrEnd, piece);
     bfq_bam_piece *d_recs = c->alloc<bfq_bam_piece>(np);
     bfq_bam_launch_walk(c, d_s, raw, hdrEnd, piece, np, nref, O, BFQ_BAM_NONE, 0, d_recs);
-    std::vector<bfq_bam_piece> P(np);
+    std::vector<bfq_bam_piece> &P = C->P;
+    P.resize(np);
     HIP_CHECK(hipMemcpyAsync(P.data(), d_recs, sizeof(bfq_bam_piece) * np, hipMemcpyDeviceToHost, c->stream));
     c->sync();
-    std::vector<bfq_bam_job> jobs;
     bfq_bam_chain(P, hdrEnd, raw, piece, [&](u64 k, u64 start) {
         bfq_bam_piece w;
         bfq_bam_launch_walk(c, d_s, raw, hdrEnd, piece, np, nref, O, k, start, d_recs);
         HIP_CHECK(hipMemcpyAsync(&w, d_recs + k, sizeof w, hipMemcpyDeviceToHost, c->stream));
         c->sync();
         return w;
-    }, jobs, &S, &E);
+    }, C->jobs, &S, &E);
     if (stats) *stats = S;
     if (E.reason) { c->profCollect(); bam_refuse(E); }
+    C->d_s = d_s; C->raw = raw; C->nref = nref; C->hdrEnd = hdrEnd;
+}
+
+enum BamMode { BAM_MEASURE, BAM_DEVICE, BAM_ARENA };
+// The texts of h_in[0, len) at d_out[] (BAM_DEVICE) or in the arena (BAM_ARENA; *where), or steps 1-3 only (BAM_MEASURE).
+// outLen / nReads: set once the chain stands, also when a capacity is then found short (*isShort).
+static void bam_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *opts, BamMode mode, u8 *const d_out[3], const u64 cap[3], u64 outLen[3],
+                     u64 nReads[3], bfq_bam_stats *stats, u8 *where[3], bool *isShort)
+{
+    const bfq_bam_opts O = bam_opts(opts);
+    const std::function<size_t(u64)> more = [&](u64 raw) {
+        const size_t np = (size_t)(raw / O.piece + 2);
+        return np * (sizeof(bfq_bam_piece) + sizeof(bfq_bam_job) + 8) + (O.paired_check ? (size_t)raw / 4 + 1024 : 0) +
+               (mode == BAM_ARENA ? (size_t)BFQ_BAM_TEXT_BOUND(raw) + 1024 : 0) + 8192;
+    };
+    bfq_bam_chain_dev C;
+    bfq_bam_chain_device(c, h_in, len, O, more, stats, &C);
+    u8 *const d_s = C.d_s;
+    const u64 raw = C.raw, hdrEnd = C.hdrEnd, piece = O.piece;
+    const u32 nref = C.nref;
+    const std::vector<bfq_bam_piece> &P = C.P;
+    const std::vector<bfq_bam_job> &jobs = C.jobs;
+    const bfq_bam_stats &S = C.S;
+    bfq_bam_err E;
     bfq_bam_totals(P, jobs, hdrEnd, piece, outLen);
     for (int o = 0; o < 3; o++) nReads[o] = S.written[o];
     if (mode == BAM_MEASURE) { c->profCollect(); return; }

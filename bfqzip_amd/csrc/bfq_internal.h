@@ -318,6 +318,10 @@ void bfq_exscan_u32(bfq_ctx *c, const u32 *in, u64 *out, u64 n, u64 *d_total);
 void bfq_exscan_u64(bfq_ctx *c, const u64 *in, u64 *out, u64 n, u64 *d_total);
 
 u64 *bfq_line_index(bfq_ctx *c, const u8 *d_buf, u64 len, u64 *nlines);   // k_fastq.hip: positions of the line ends (arena)
+// bfq_deflate.hip: the BGZF form of a text that lies on the device (d_text) or on the host (h_src) to dst; held: the arena is
+// the caller's, sized with bfq_deflate_need() beside what it holds.  Returns the length of the output.
+size_t bfq_deflate_need(bfq_ctx *c, u64 len, bool hostSrc, size_t beside);
+u64 bfq_deflate_core(bfq_ctx *c, const u8 *d_text, HostRef h_src, u64 len, int level, HostRef dst, bool held, size_t beside);
 u64 bfq_fastq_count_lines(bfq_ctx *c, const u8 *d_buf, u64 len);          // k_fastq.hip: newlines + 1
 // stream codec (k_codec.hip)
 u64 bfq_codec_bound(u64 n);

@@ -2,10 +2,15 @@
 //     bfq_bam -i IN.bam -o OUT.fq [-F MASK] [-n] [-v Q] [-C PIECE] [-V]             every kept record, in file order
 //     bfq_bam -i IN.bam -1 OUT_1.fq -2 OUT_2.fq [-0 OTHER.fq] [-c] [...]            READ1 / READ2 / the rest; -c: the pairing check
 //     bfq_bam -t IN.bam                                                             convert and verify, writing nothing
+//     bfq_bam -i IN.bam -u OUT.bam -o TEXT.fq | -1 T_1.fq -2 T_2.fq [-0 T_0.fq] [-N] [-L 0|1] [...]
+//                                                                                   the way back: IN.bam with the reads of the texts in it
 //     bfq_bam -l IN.bam                                                             the header counts and the statistics as JSON
 // include/bfqzip_hip.h, bfq_bam_to_fastq_fd: the records' text is this project's definition, modelled on the defaults of
 // `samtools fastq` (-F 0x900; /1 and /2 unless -n; absent qualities as -v Q, default 1).  Exit status 0 on success; 1 with
 // the library's message on a damaged or unpaired file, and then the outputs are left empty.
+// With -u the FASTQ options name the texts to READ (bfq_bam_patch_fd): their sequence and quality lines go back into the SEQ
+// and QUAL fields of the records they came from -- -F, -n, -v, -C as on the run that made the texts --, everything else stays
+// byte for byte and OUT.bam is compressed on the device.  One line with the statistics; on a refusal OUT.bam is left empty.
 #include <unistd.h>
 #include <sys/mman.h>
 #include "cli_common.h"
@@ -13,6 +18,7 @@
 static int usage(const char *argv0)
 {
     fprintf(stderr, "usage: %s -i IN.bam -o OUT.fq | -1 OUT_1.fq -2 OUT_2.fq [-0 OTHER.fq] [-c] [-F MASK] [-n] [-v Q] [-C PIECE] [-V] | -t IN.bam | -l IN.bam\n"
+                    "       %s -i IN.bam -u OUT.bam -o TEXT.fq | -1 T_1.fq -2 T_2.fq [-0 T_0.fq] [-N] [-L 0|1] [-F MASK] [-n] [-v Q] [-C PIECE] [-V]\n"
                     "  -i <arg>  BAM input (BGZF, or the inflated stream itself)\n"
                     "  -o <arg>  one FASTQ output: every kept record in file order\n"
                     "  -1 -2 <arg>  split: READ1-only and READ2-only records; -0 <arg>: the rest (dropped without it)\n"
@@ -23,20 +29,62 @@ static int usage(const char *argv0)
                     "  -C <arg>  bytes per piece of the stream (default 65536)\n"
                     "  -t <arg>  convert and verify only: no output is written\n"
                     "  -l <arg>  print references, header bytes, records and the statistics as JSON\n"
-                    "  -V        phase timeline on stderr\n", argv0);
+                    "  -u <arg>  the way back: write IN.bam with the reads of the FASTQ files (-o | -1 -2 [-0], now inputs) in it\n"
+                    "  -N        with -u: refuse unless every read's name is its record's\n"
+                    "  -L <arg>  with -u: 0 = stored members, 1 = compressed (default 1)\n"
+                    "  -V        phase timeline on stderr\n", argv0, argv0);
     return 1;
+}
+
+// -u: IN.bam with the reads of the texts in it, to OUT.bam
+static int patch(const std::string &input, const std::string text[3], const std::string &outName, const bfq_bam_opts &O, int level)
+{
+    InFile in, tin[3];
+    if (!in.open(input)) { fprintf(stderr, "bfq_bam: cannot read %s\n", input.c_str()); return 1; }
+    int fds[3] = {-1, -1, -1};
+    for (int k = 0; k < 3; k++)
+        if (!text[k].empty()) {
+            if (!tin[k].open(text[k])) { fprintf(stderr, "bfq_bam: cannot read %s\n", text[k].c_str()); return 1; }
+            fds[k] = tin[k].fd;
+        }
+    OutFile out;
+    if (!out.open(outName)) { perror("bfq_bam"); return 1; }
+    bfq_params P;
+    bfq_default_params(&P);
+    bfq_ctx *c = create_on_free_gpu("bfq_bam", &P);
+    if (!c) return 1;
+    uint64_t outLen = 0;
+    bfq_bam_patch_stats S = {};
+    if (bfq_bam_patch_fd(c, in.fd, in.size, &O, fds, level, out.fd, &outLen, &S)) {
+        fprintf(stderr, "bfq_bam: %s: %s\n", input.c_str(), bfq_last_error(c));
+        bfq_destroy(c);
+        if (ftruncate(out.fd, 0) != 0) perror("bfq_bam");
+        return 1;
+    }
+    bfq_phase("teardown");
+    trace_kernel_times(c, "bfq_bam");
+    const bool closed = out.close();
+    bfq_destroy(c);
+    if (!closed) { perror("bfq_bam"); return 1; }
+    bfq_phase_report("bfq_bam");
+    typedef unsigned long long ull;
+    printf("%llu records: %llu + %llu + %llu patched, %llu skipped, %llu reads changed (%llu bases, %llu qualities), %llu unknown bases, %llu high qualities and "
+           "%llu absent kept; %llu bytes of stream, %llu bytes written\n", (ull)S.records, (ull)S.patched[0], (ull)S.patched[1], (ull)S.patched[2], (ull)S.skipped,
+           (ull)S.reads_changed, (ull)S.bases_changed, (ull)S.quals_changed, (ull)S.unknown_bases, (ull)S.kept_high_quals, (ull)S.kept_absent, (ull)S.raw_len, (ull)outLen);
+    return 0;
 }
 
 int main(int argc, char **argv)
 {
     bfq_phase("start");
-    std::string input, outName[3];
+    std::string input, outName[3], patchName;
+    int level = 1;
     char mode = 0;
     bfq_bam_opts O;
     bfq_bam_default_opts(&O);
     int opt;
     bool single = false;                                           // -o was given
-    while ((opt = getopt(argc, argv, "i:t:l:o:0:1:2:cF:nv:C:Vh")) != -1) {
+    while ((opt = getopt(argc, argv, "i:t:l:o:0:1:2:cF:nv:C:Vhu:NL:")) != -1) {
         switch (opt) {
         case 'i': case 't': case 'l':
             if (mode) return usage(argv[0]);
@@ -52,6 +100,9 @@ int main(int argc, char **argv)
         case 'v': O.default_qual = (uint32_t)strtoul(optarg, nullptr, 10); break;
         case 'C': O.piece = (uint32_t)strtoul(optarg, nullptr, 10); break;
         case 'V': bfq_phase_enable(1); break;
+        case 'u': patchName = optarg; break;
+        case 'N': O.check_names = 1; break;
+        case 'L': level = atoi(optarg); break;
         default: return usage(argv[0]);
         }
     }
@@ -59,6 +110,8 @@ int main(int argc, char **argv)
     if (!mode || (mode != 'i' && anyOut) || (mode == 'i' && !anyOut)) return usage(argv[0]);
     if (mode == 'i' && (single ? O.split != 0 : outName[1].empty() || outName[2].empty())) return usage(argv[0]);
     if (O.paired_check && !O.split) return usage(argv[0]);
+    if (patchName.empty() ? O.check_names != 0 : mode != 'i' || O.paired_check) return usage(argv[0]);
+    if (!patchName.empty()) return patch(input, outName, patchName, O, level);
     InFile in;
     if (!in.open(input)) { fprintf(stderr, "bfq_bam: cannot read %s\n", input.c_str()); return 1; }
     OutFile out[3];

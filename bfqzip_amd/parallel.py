@@ -706,8 +706,30 @@ def main(argv=None):
     ap.add_argument("--bam", action="store_true",
                     help="a BAM input (unaligned or aligned) is converted to <name>.fastq beside the outputs on the GPU first "
                          "(--keep-inflated keeps it); with -p one BAM file is split into <name>_1.fastq / <name>_2.fastq with the pairing check")
+    ap.add_argument("--bam-out", default="", metavar="PATH",
+                    help="with --bam, one BAM input and a merged FASTQ output: after the run the output text(s) are written back into "
+                         "the SEQ and QUAL fields of the input's records on the GPU and the result goes to PATH (with -p the two texts "
+                         "meet the READ1 / READ2 records; with -H the names are compared); an index of the input does not fit PATH")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.bam_out:
+        why = None
+        if not a.bam or len(a.input) != 1 or a.restore:
+            why = "--bam-out needs --bam and exactly one BAM input"
+        elif ((a.m2 or a.m3) and a.streams_only) or (a.compress and not a.m0):
+            why = "--bam-out patches the merged FASTQ text: not with --streams-only or --compress"
+        elif a.reorder and not a.keep_order:
+            why = "--bam-out needs the reads in file order: --reorder only with --keep-order"
+        if not why:
+            try:
+                with open(a.input[0], "rb") as f:
+                    if not api.bam_probe(f.read(1 << 17)):               # (a whole first member: at most 64 KiB)
+                        why = "--bam-out: the input is no BAM file"
+            except OSError as e:
+                why = f"--bam-out: {e}"
+        if why:
+            print("=== ERROR ===\n" + why, file=sys.stderr)
+            return 1
     if a.restore and (len(a.input) not in (2, 3) or not a.out):
         print("=== ERROR ===\n--restore DNA.bsc QS.bsc [HDR.bsc] -o OUT.fq", file=sys.stderr)
         return 1
@@ -749,7 +771,7 @@ def main(argv=None):
         if dist:
             dist.destroy_process_group()
         return 0
-    converted = []
+    converted, bam_src = [], a.input[0]
     if a.bam:
         a.input, converted = convert_bam_inputs(eng, comm, a.input, a.out, paired=a.paired, log=log)
         if a.paired and len(a.input) != 2:
@@ -779,6 +801,23 @@ def main(argv=None):
             log(f"keep-order: the {'containers' if compress else 'raw streams'} stay in run order; pass {perm_path} to bfq_restore -P")
     if a.report:                                                     # against what is in the outputs' order: the originals unless the run reordered for good
         write_reports(eng, comm, original if (perm_path or not a.reorder) else a.input, [n["fastq"] for n in names], log=log)
+    if a.bam_out:
+        comm.barrier()
+        failed = None
+        if comm.rank == 0:
+            fq = [n["fastq"] for n in names]
+            try:
+                n, st = eng.bam_patch_files(bam_src, (None, fq[0], fq[1]) if a.paired else (fq[0],), a.bam_out, split=int(a.paired), check_names=int(a.headers))
+                if log:
+                    log(f"bam-out: {bam_src} + {' '.join(fq)} -> {a.bam_out}, {n} bytes, {st}")
+            except api.BfqError as e:                                # (a refusal: the library's message; every rank leaves with it)
+                failed = e
+                print(f"=== ERROR ===\n--bam-out: {e}", file=sys.stderr)
+        if comm.all_gather_i64([1 if failed else 0])[0, 0]:
+            eng.close()
+            if dist:
+                dist.destroy_process_group()
+            return 1
     if inflated and not a.keep_inflated:
         comm.barrier()
         if comm.rank == 0:

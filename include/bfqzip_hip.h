@@ -751,7 +751,7 @@ const char *bfq_gzip_host_error(void);
  *   byte <off>: <reason>"; a refusal of the BGZF layer keeps the BGZF message.  With paired_check the device form may have
  *   written text before the names are refused; the host and file forms write nothing.  The context stays usable.
  * The entry points that take FASTQ text keep reading 1f 8b as BGZF-compressed FASTQ: BAM is taken by these calls only. */
-typedef struct bfq_bam_opts { uint32_t exclude_flags, mate_suffix, default_qual, split, paired_check, piece, reserved[2]; } bfq_bam_opts;
+typedef struct bfq_bam_opts { uint32_t exclude_flags, mate_suffix, default_qual, split, paired_check, piece, check_names, reserved; } bfq_bam_opts;
 typedef struct bfq_bam_stats {
     uint64_t records, written[3], skipped, reversed, no_qual, clamped_quals, n_ref, header_bytes, pieces, walkers, dead, repaired, rounds;
 } bfq_bam_stats;
@@ -768,6 +768,59 @@ int bfq_bam_to_fastq_fd(bfq_ctx *c, int in_fd, uint64_t len, const bfq_bam_opts 
 int bfq_bam_to_fastq_host(const uint8_t *raw, uint64_t raw_len, const bfq_bam_opts *opts, uint8_t *const h_out[3], const uint64_t cap[3],
                           uint64_t out_len[3], uint64_t n_reads[3], bfq_bam_stats *stats);
 const char *bfq_bam_host_error(void);
+/* ---- BAM output: "this BAM, with the reads of these FASTQ texts in it" (k_bam_patch.hip; the definition in full, the two
+ * walks and the host form: csrc/bfq_bam_patch.h).  The way back of bfq_bam_to_fastq*: the sequence and quality lines of up
+ * to three plain FASTQ texts are written into the SEQ and QUAL fields of the records they came from; the header, every
+ * other field, every tag and every record that meets no read stay byte for byte, every record keeps its size.
+ *   Inputs: a BAM source as bfq_bam_to_fastq* takes it (BGZF, or the inflated stream itself); opts with the same meaning
+ *     as on the way in; text[k], k = 0, 1, 2.  The i-th kept record of output k -- the record bfq_bam_to_fastq with the same
+ *     options writes as read i of output k -- meets read i of text[k].  A NULL text[k] leaves the records of output k as they
+ *     are (a paired run that dropped the "neither READ1 nor READ2" records); excluded records are never touched.
+ *   The text is plain FASTQ: one that begins with 1f 8b is refused ("inflate the text first").  CR before LF is stripped.
+ *     The header line is used only with opts.check_names (the first word behind piece; 0 keeps the earlier meaning, and the
+ *     way in ignores it): a run without kept headers writes "@" alone.
+ *   Bases: case-insensitive over =ACMGRSVTWYHKDBN to their nibbles; any other byte becomes 15 (N; unknown_bases).  Flag 0x10:
+ *     text base i goes to position l_seq - 1 - i as its complement.  The spare nibble of an odd length keeps its value.
+ *   Qualities: char - 33, reversed under 0x10.  The record's value stays where the text says 93 ('~') and the record holds
+ *     more (kept_high_quals); absent qualities (0xFF) stay absent when every quality of the read is default_qual + 33
+ *     (kept_absent), else all l_seq values are written.  So the texts of the way in, patched back, give the same stream.
+ *   Refusals, all BFQ_E_ARG, nothing written, the context stays usable: "BAM patch: text <k> is compressed ..."; the FASTQ
+ *     refusals ("FASTQ: number of lines is not a multiple of 4", "FASTQ: len(DNA) != len(QS) in a record"); "BAM patch: text
+ *     <k> holds <n> reads, the BAM file holds <m> records for it"; "BAM patch: text <k> read <i>: <n> bases, record <r> at
+ *     byte <off> holds <m>" and, with check_names, "BAM patch: text <k> read <i>: the name differs from that of record <r>
+ *     at byte <off>" (the name: the bytes behind '@' up to the first blank, less the "/1" or "/2" mate_suffix adds) -- of
+ *     the offending records the one that comes first in the file is named, by the device (atomicMin) as by the host form.
+ *     A damaged BAM keeps the messages of the way in.
+ *   The result: a valid BAM with the same header and the same records in the same order with the same sizes.  The BGZF
+ *     layer is this project's (bfq_bgzf_deflate: members cut at 65 280 bytes of stream whatever the input's cut was, the EOF
+ *     member at the end), so an index (.bai, .csi) of the input does NOT fit the output, and the MD and NM tags of an
+ *     aligned record go stale where a base changed: they are copied like every tag.  Parity with an htslib tool is not
+ *     pinned by a test.
+ *       bfq_bam_patch_host   : one thread on the INFLATED stream, no context, no GPU: states the algorithm and is what the
+ *         tests compare with; NO entry point falls back to it.  cap < raw_len: BFQ_E_ARG.  Message: bfq_bam_host_error().
+ *       bfq_bam_patch_device : texts in device memory; the patched inflated stream into d_out_raw (cap < the stream's
+ *         length: BFQ_E_ARG, nothing written, *raw_len = the length needed).  Not compressed.
+ *       bfq_bam_patch        : host texts in, the BGZF-compressed BAM into a host buffer; level as for bfq_bgzf_deflate; a
+ *         cap below bfq_bgzf_deflate_bound(raw length): BFQ_E_ARG, nothing written, *out_len = that bound.
+ *       bfq_bam_patch_fd     : open files; a text_fd[k] < 0 is an absent text; out_fd is sized to *out_len.
+ *     The stream is deflated where it lies: it never crosses to the host uncompressed.  Device memory, in the workspace and
+ *     reserved once: the compressed bytes, the stream, 8 bytes per text line, 232 bytes per piece, the deflate batch; texts
+ *     that are uploaded (or lie at an address that is no multiple of 16) go into the context's text buffer beside it.
+ *   stats (may be NULL): records of the file, patched[k] (records that met a read of text k), skipped (the others), reversed
+ *     (patched, 0x10), reads_changed, bases_changed / quals_changed (positions whose stored value differs from before),
+ *     unknown_bases, kept_high_quals, kept_absent, raw_len, pieces, repaired.  Only the last two depend on opts.piece. */
+typedef struct bfq_bam_patch_stats {
+    uint64_t records, patched[3], skipped, reversed, reads_changed, bases_changed, quals_changed, unknown_bases, kept_high_quals, kept_absent, raw_len,
+             pieces, repaired;
+} bfq_bam_patch_stats;
+int bfq_bam_patch_host(const uint8_t *raw, uint64_t raw_len, const bfq_bam_opts *opts, const uint8_t *const text[3], const uint64_t text_len[3],
+                       uint8_t *out_raw, uint64_t cap, bfq_bam_patch_stats *stats);
+int bfq_bam_patch_device(bfq_ctx *c, const uint8_t *h_in, uint64_t len, const bfq_bam_opts *opts, const uint8_t *const d_text[3],
+                         const uint64_t text_len[3], uint8_t *d_out_raw, uint64_t cap, uint64_t *raw_len, bfq_bam_patch_stats *stats);
+int bfq_bam_patch(bfq_ctx *c, const uint8_t *h_in, uint64_t len, const bfq_bam_opts *opts, const uint8_t *const h_text[3], const uint64_t text_len[3],
+                  int level, uint8_t *h_out, uint64_t cap, uint64_t *out_len, bfq_bam_patch_stats *stats);
+int bfq_bam_patch_fd(bfq_ctx *c, int bam_fd, uint64_t len, const bfq_bam_opts *opts, const int text_fd[3], int level, int out_fd, uint64_t *out_len,
+                     bfq_bam_patch_stats *stats);
 /* ---- bgzip-compressed output: BGZF members deflated on the device (k_deflate.hip; the format and every bound:
  * csrc/bfq_deflate.h).  A text of len bytes is cut at multiples of 65 280 bytes (htslib's member size; the cut depends on
  * nothing else); every piece becomes one BGZF member -- htslib's 18-byte header, a raw deflate payload, CRC32 and ISIZE --

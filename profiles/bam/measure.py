@@ -6,6 +6,12 @@ unaligned BAM file -- flag 4, an RG tag, numpy-vectorised -- wrapped as BGZF at 
   (c) the one-thread host form (bfq_bam_to_fastq_host) on the inflated stream.
 --save BLOB keeps the BAM bytes; --load BLOB --only-bam PIECE runs (a) alone at one piece size from them, three calls: what a
 `rocprofv3 --kernel-trace --stats` run of its own wraps for the per-kernel split.
+--patch measures the way back instead (bfq_bam_patch*): the file's own text with a seeded 2 % of the bases and 10 % of the
+qualities changed goes back into the file,
+  (p1) wall time around bfq_bam_patch_device (text in a device buffer, the patched stream into a device buffer);
+  (p2) wall time around bfq_bam_patch (text in pinned host memory, the compressed BAM into pinned host memory), its size;
+  (f1) the floor of p1: bfq_bgzf_inflate_device alone;  (f2) the floor of p2: that plus bfq_bgzf_deflate_device of the stream;
+the result of p1 converted again and compared with the text it was given.  --only-patch: p1 alone, three calls, for rocprofv3.
 
     python profiles/bam/measure.py --reads 3000000 --out bam_measure.json"""
 import argparse
@@ -58,6 +64,69 @@ def ubam_stream(text, L):
     return b"".join(parts)
 
 
+def measure_patch(a, eng, pin, d_text, n, res):
+    """the way back: see the module's text"""
+    import torch
+    eng.bam_to_fastq_device(pin.array, [d_text.data_ptr(), 0, 0], [n, 0, 0])
+    g = torch.Generator(device="cuda").manual_seed(1)
+    t = d_text[:n]
+    nl = torch.nonzero(t == 10).flatten()
+    line = torch.zeros(n, dtype=torch.int32, device="cuda")
+    line[nl[:-1] + 1] = 1
+    line = torch.cumsum(line, 0) % 4                                # which line of its record a byte is in
+    r = torch.rand(n, generator=g, device="cuda")
+    base = (line == 1) & (t != 10) & (r < 0.02)
+    qual = (line == 3) & (t != 10) & (r < 0.10)
+    t[base] = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device="cuda")[torch.randint(0, 4, (int(base.sum()),), generator=g, device="cuda")]
+    t[qual] = torch.randint(35, 74, (int(qual.sum()),), generator=g, device="cuda").to(torch.uint8)
+    del line, r, base, qual, nl
+    raw = api.text_len(pin.array) - 1
+    d_raw = torch.empty(raw + 64, dtype=torch.uint8, device="cuda")
+    call_dev = lambda: eng.bam_patch_device(pin.array, [d_text.data_ptr(), 0, 0], [n, 0, 0], d_raw.data_ptr(), raw)
+    if a.only_patch:
+        for _ in range(3):
+            call_dev()
+        return
+    _, st = call_dev()                                              # warm-up: arena, staging buffers
+    back = torch.empty(n + 64, dtype=torch.uint8, device="cuda")
+    eng.bam_to_fastq_device(d_raw[:raw].cpu().numpy(), [back.data_ptr(), 0, 0], [n, 0, 0])
+    assert torch.equal(back[:n], d_text[:n])
+    del back
+    eng.prof_reset()
+    wall, walls = bgzf_measure.best(call_dev)
+    k = eng.prof()["k_bgzf_inflate"]
+    res["stream_bytes"] = raw
+    res["p1_patch_device"] = dict(wall_s=wall, walls=walls, stream_GBps=raw / wall / 1e9, kernels_ms=k["ms"] / 3, launches=k["launches"] / 3, stats=st.as_dict())
+    say("patch_device", wall, k["ms"] / 3, st)
+    text_pin = api.PinnedBuffer(n)
+    text_pin.array[:] = d_text[:n].cpu().numpy()
+    out_pin = api.PinnedBuffer(api.bgzf_deflate_bound(raw))
+    call_host = lambda: eng.bam_patch(pin.array, [text_pin.array[:n]], out=out_pin.array)
+    z, _ = call_host()
+    wall, walls = bgzf_measure.best(call_host)
+    res["p2_patch"] = dict(wall_s=wall, walls=walls, stream_GBps=raw / wall / 1e9, out_bytes=len(z), in_bytes=len(pin.array))
+    say("patch", wall, len(z), len(pin.array))
+    inflate = lambda: eng.bgzf_inflate_device(pin.array, d_raw.data_ptr(), raw)
+    inflate()
+    wall, walls = bgzf_measure.best(inflate)
+    res["f1_inflate_device"] = dict(wall_s=wall, walls=walls)
+    import ctypes as C
+
+    def deflate():                                                  # (into the pinned buffer, as p2 writes: Engine.bgzf_deflate_device allocates its own)
+        ol = C.c_uint64(0)
+        eng._ck(eng.L.bfq_bgzf_deflate_device(eng.h, C.c_void_p(d_raw.data_ptr()), raw, 1, out_pin.array.ctypes.data_as(C.c_void_p), len(out_pin.array), C.byref(ol)))
+    both = lambda: (inflate(), deflate())
+    both()
+    wall, walls = bgzf_measure.best(both)
+    res["f2_inflate_deflate_device"] = dict(wall_s=wall, walls=walls)
+    say("floors", res["f1_inflate_device"]["wall_s"], wall)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=3_000_000)
@@ -66,6 +135,8 @@ def main():
     ap.add_argument("--save", default="")
     ap.add_argument("--load", default="")
     ap.add_argument("--only-bam", type=int, default=-1)
+    ap.add_argument("--patch", action="store_true")
+    ap.add_argument("--only-patch", action="store_true")
     a = ap.parse_args()
     import torch
     eng = api.Engine(0, m=5)
@@ -98,6 +169,8 @@ def main():
         for _ in range(3):
             eng.bam_to_fastq_device(pin.array, outs, caps, piece=a.only_bam)
         return
+    if a.patch or a.only_patch:
+        return measure_patch(a, eng, pin, d_out, n, res)
     # (a) the conversion
     res["a"] = {}
     for piece in [int(c) for c in a.pieces.split(",")]:
