@@ -41,6 +41,8 @@ SYMBOLS = [
     "bfq_bam_default_opts", "bfq_bam_probe", "bfq_bam_measure", "bfq_bam_to_fastq", "bfq_bam_to_fastq_device", "bfq_bam_to_fastq_fd",
     "bfq_bam_to_fastq_host", "bfq_bam_host_error",
     "bfq_bam_patch_host", "bfq_bam_patch_device", "bfq_bam_patch", "bfq_bam_patch_fd",
+    "bfq_ubam_default_opts", "bfq_fastq_to_bam_measure", "bfq_fastq_to_bam_host", "bfq_ubam_host_error", "bfq_fastq_to_bam_device", "bfq_fastq_to_bam",
+    "bfq_fastq_to_bam_fd", "bfq_fastq_restore_bam_fd",
     "bfq_workspace_bytes", "bfq_version",
 ]
 
@@ -130,6 +132,24 @@ class BamPatchStats(C.Structure):
 
     def __repr__(self):
         return "BamPatchStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
+
+
+class UbamOpts(C.Structure):
+    """bfq_ubam_opts: mate_suffix, paired_check, level, reserved; header_text / header_len (NULL: the default header); rg_id (NULL: no tag)"""
+    _fields_ = [(k, C.c_uint32) for k in ("mate_suffix", "paired_check", "level", "reserved")] + [
+        ("header_text", C.c_void_p), ("header_len", C.c_uint64), ("rg_id", C.c_char_p)]
+
+
+class UbamStats(C.Structure):
+    """bfq_ubam_stats: records, written[3], named, comments_dropped, unknown_bases, raw_len, members"""
+    _fields_ = [("records", C.c_uint64), ("written", C.c_uint64 * 3)] + [(k, C.c_uint64) for k in (
+        "named", "comments_dropped", "unknown_bases", "raw_len", "members")]
+
+    def as_dict(self):
+        return {k: [int(v) for v in self.written] if k == "written" else int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "UbamStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
 
 
 CMP_SYMS = 6
@@ -325,6 +345,17 @@ def lib():
         L.bfq_bam_patch_device.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, vp, u64, pu64, pps]
         L.bfq_bam_patch.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, C.c_int, vp, u64, pu64, pps]
         L.bfq_bam_patch_fd.argtypes = [vp, C.c_int, u64, pbo, i3, C.c_int, C.c_int, pu64, pps]
+        puo, pus = C.POINTER(UbamOpts), C.POINTER(UbamStats)
+        L.bfq_ubam_default_opts.restype = None
+        L.bfq_ubam_default_opts.argtypes = [puo]
+        L.bfq_ubam_host_error.restype = C.c_char_p
+        L.bfq_ubam_host_error.argtypes = []
+        L.bfq_fastq_to_bam_measure.argtypes = [vp, C.POINTER(vp), a3, puo, pu64, a3, pus]
+        L.bfq_fastq_to_bam_host.argtypes = [C.POINTER(vp), a3, puo, vp, u64, pu64, pus]
+        L.bfq_fastq_to_bam_device.argtypes = [vp, C.POINTER(vp), a3, puo, vp, u64, pu64, pus]
+        L.bfq_fastq_to_bam.argtypes = [vp, C.POINTER(vp), a3, puo, vp, u64, pu64, pus]
+        L.bfq_fastq_to_bam_fd.argtypes = [vp, i3, puo, C.c_int, pu64, pus]
+        L.bfq_fastq_restore_bam_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, puo, C.c_int, pu64, pus]
         L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_radix_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(u64)]

@@ -349,6 +349,49 @@ def bam_patch_host(stream, texts, out=None, **opts):
     return out[:len(stream)], st
 
 
+def ubam_opts(mate_suffix=1, paired_check=0, level=1, header_text=None, rg_id=None):
+    """(bfq_ubam_opts, what it points to) (include/bfqzip_hip.h); the defaults are bfq_ubam_default_opts'.  header_text: bytes
+    written as the BAM header's text (None: the default header); rg_id: bytes or str, RG:Z:<rg_id> on every record."""
+    o = _lib.UbamOpts()
+    o.mate_suffix, o.paired_check, o.level, o.reserved = int(mate_suffix), int(paired_check), int(level), 0
+    keep = []
+    if header_text is not None:
+        h = np.frombuffer(bytes(header_text) + b"\0", np.uint8)
+        keep.append(h)
+        o.header_text, o.header_len = h.ctypes.data, len(h) - 1
+    if rg_id is not None:
+        o.rg_id = rg_id.encode() if isinstance(rg_id, str) else bytes(rg_id)
+    return o, keep
+
+
+def _ubam_raise(rc, msg, needed):
+    e = BfqError(rc, msg)
+    e.needed = int(needed)                                         # the capacity needed, when the buffer was too small; else 0
+    raise e
+
+
+def fastq_to_bam_host(texts, out=None, **opts):
+    """(the INFLATED stream of an unaligned BAM, stats) made of up to three FASTQ texts by the host form
+    (bfq_fastq_to_bam_host: the steps of csrc/bfq_ubam.h by one thread, no GPU): the statement of the algorithm --
+    Engine.fastq_to_bam_device gives the same bytes and the same stats.  texts[0]: unpaired reads (flag 4); texts[1] and
+    texts[2]: the mates of a paired run (flags 77 and 141, interleaved in front of the reads of texts[0]); None: absent.
+    opts: ubam_opts().  `out`: a uint8 array to fill; one that is too small raises BfqError with .needed = the length,
+    nothing written.  Refusals raise BfqError ("FASTQ to BAM: ...", "FASTQ: ...")."""
+    L = _lib.lib()
+    keep, ptrs, lens = _bam_texts(texts)
+    O, held = ubam_opts(**opts)
+    st, rl = _lib.UbamStats(), C.c_uint64(0)
+    if out is None:
+        rc = L.bfq_fastq_to_bam_host(ptrs, lens, C.byref(O), None, 0, C.byref(rl), C.byref(st))
+        if rc != 0 and not rl.value:
+            _ubam_raise(rc, L.bfq_ubam_host_error().decode(), 0)
+        out = np.empty(int(rl.value), np.uint8)
+    rc = L.bfq_fastq_to_bam_host(ptrs, lens, C.byref(O), _ptr(out) if len(out) else None, len(out), C.byref(rl), C.byref(st))
+    if rc != 0:
+        _ubam_raise(rc, L.bfq_ubam_host_error().decode(), rl.value)
+    return out[:int(rl.value)], st
+
+
 def text_len(a):
     """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
     a = _u8(a)
@@ -370,6 +413,7 @@ class HostText:
     bam_probe = staticmethod(bam_probe)
     bam_to_fastq_host = staticmethod(bam_to_fastq_host)
     bam_patch_host = staticmethod(bam_patch_host)
+    fastq_to_bam_host = staticmethod(fastq_to_bam_host)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -895,6 +939,65 @@ class Engine:
                 if fd >= 0:
                     os.close(fd)
 
+    # ---- FASTQ texts as an unaligned BAM (bfq_fastq_to_bam*, csrc/bfq_ubam.h)
+    def fastq_to_bam_measure(self, texts, **opts):
+        """bfq_fastq_to_bam_measure: (the exact length of the inflated stream, the three read counts, stats without
+        unknown_bases) of up to three host texts; nothing is written."""
+        keep, ptrs, lens = _bam_texts(texts)
+        (O, held), st, rl, nr = ubam_opts(**opts), _lib.UbamStats(), C.c_uint64(0), (C.c_uint64 * 3)()
+        rc = self.L.bfq_fastq_to_bam_measure(self.h, ptrs, lens, C.byref(O), C.byref(rl), nr, C.byref(st))
+        if rc != 0:
+            _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), 0)
+        return int(rl.value), [int(v) for v in nr], st
+
+    def fastq_to_bam(self, texts, out=None, **opts):
+        """(the BAM file, stats): up to three FASTQ texts as an unaligned BAM, the records made on the GPU and compressed there
+        (bfq_fastq_to_bam); a uint8 array.  texts[0]: unpaired reads (flag 4); texts[1] / texts[2]: the mates of a paired run
+        (flags 77 / 141, interleaved, in front of the reads of texts[0]); None: absent.  opts: ubam_opts() (mate_suffix,
+        paired_check, level, header_text, rg_id).  `out`: a uint8 array to fill; one below
+        HostText.bgzf_deflate_bound(the stream's length) raises BfqError with .needed = that bound, nothing written; without
+        one it is sized by fastq_to_bam_measure.  Refusals raise BfqError ("FASTQ to BAM: text <k> ...", "FASTQ: ...")."""
+        keep, ptrs, lens = _bam_texts(texts)
+        if out is None:
+            out = np.empty(bgzf_deflate_bound(self.fastq_to_bam_measure(texts, **opts)[0]), np.uint8)
+        (O, held), st, ol = ubam_opts(**opts), _lib.UbamStats(), C.c_uint64(0)
+        rc = self.L.bfq_fastq_to_bam(self.h, ptrs, lens, C.byref(O), _ptr(out) if len(out) else None, len(out), C.byref(ol), C.byref(st))
+        if rc != 0:
+            _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), ol.value)
+        return out[:int(ol.value)], st
+
+    def fastq_to_bam_device(self, d_texts, text_lens, d_out, cap, **opts):
+        """bfq_fastq_to_bam_device: the texts at the device addresses d_texts (None / 0: absent), the INFLATED stream at the
+        device address d_out (cap bytes), not compressed; returns (its length, stats).  A cap below that length raises
+        BfqError with .needed = the length, nothing written."""
+        ptrs = (C.c_void_p * 3)(*[int(p) if p else None for p in d_texts])
+        lens = (C.c_uint64 * 3)(*[int(v) for v in text_lens])
+        (O, held), st, rl = ubam_opts(**opts), _lib.UbamStats(), C.c_uint64(0)
+        rc = self.L.bfq_fastq_to_bam_device(self.h, ptrs, lens, C.byref(O), C.c_void_p(d_out), int(cap), C.byref(rl), C.byref(st))
+        if rc != 0:
+            _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), rl.value)
+        return int(rl.value), st
+
+    def fastq_to_bam_files(self, texts, dst, **opts):
+        """bfq_fastq_to_bam_fd on named files: the FASTQ files texts[k] (None: absent) as the unaligned BAM dst (left empty
+        on a refusal).  Returns (the length of dst, stats)."""
+        import os
+        texts = list(texts) + [None] * (3 - len(texts))
+        fds = []
+        try:
+            for t in texts[:3]:
+                fds.append(os.open(t, os.O_RDONLY) if t is not None else -1)
+            fds.append(os.open(dst, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            (O, held), st, ol = ubam_opts(**opts), _lib.UbamStats(), C.c_uint64(0)
+            rc = self.L.bfq_fastq_to_bam_fd(self.h, (C.c_int * 3)(*fds[0:3]), C.byref(O), fds[3], C.byref(ol), C.byref(st))
+            if rc != 0:
+                _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), ol.value)
+            return int(ol.value), st
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
     def bgzf_deflate(self, text, level=1, out=None):
         """The BGZF form (.fq.gz as bgzip writes it: members of 65 280 bytes, the EOF member) of a text, deflated on the GPU
         (bfq_bgzf_deflate), as a uint8 array; the same bytes as HostText.bgzf_deflate_model.  level 0: every member stored.
@@ -982,15 +1085,21 @@ class Engine:
                                               _ptr(out), len(out), C.byref(ol), C.byref(nr)))
         return out[:int(ol.value)], int(nr.value)
 
-    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None, grouped=False, bgzf=False, level=1):
+    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None, grouped=False, bgzf=False, level=1, ubam=False, **ubam_kw):
         """bfq_fastq_restore_fd on named files (hdr_path may be None); returns (bytes written, n_reads).  perm_path: the
         BFQPERM1 file of the reordering (bfq_fastq_restore_ordered_fd): the text in the order before it.  grouped: True or
         (first, count) as fastq_restore's `groups` (bfq_fastq_restore_grouped_fd); not with perm_path.  bgzf: out_path is
         written as BGZF (bfq_fastq_restore_bgzf_fd: the text is deflated on the device at `level` and never crosses to the
-        host); the bytes written are the compressed ones; not with grouped."""
+        host); the bytes written are the compressed ones; not with grouped.  ubam: out_path is written as an unaligned BAM
+        (bfq_fastq_restore_bam_fd: the restored text becomes records on the device, unpaired, deflated at `level`; further
+        keywords: ubam_opts()); returns (bytes written, stats.records); not with grouped or bgzf."""
         import os
         if grouped and perm_path is not None:
             raise ValueError("fastq_restore_files: grouped and perm_path do not go together")
+        if ubam and (grouped or bgzf):
+            raise ValueError("fastq_restore_files: ubam does not go together with grouped or bgzf")
+        if ubam_kw and not ubam:
+            raise TypeError("fastq_restore_files: unexpected keywords %s" % sorted(ubam_kw))
         if grouped and bgzf:
             raise ValueError("fastq_restore_files: grouped and bgzf do not go together (the grouped restore writes plain text)")
         fds = []
@@ -1000,7 +1109,12 @@ class Engine:
             fds.append(os.open(out_path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
             ol, nr = C.c_uint64(0), C.c_uint64(0)
             size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
-            if bgzf:
+            if ubam:
+                (O, held), st = ubam_opts(level=level, **ubam_kw), _lib.UbamStats()
+                self._ck(self.L.bfq_fastq_restore_bam_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
+                                                         fds[3], size(fds[3]), C.byref(O), fds[4], C.byref(ol), C.byref(st)))
+                nr.value = st.records
+            elif bgzf:
                 raw = C.c_uint64(0)
                 self._ck(self.L.bfq_fastq_restore_bgzf_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
                                                           fds[3], size(fds[3]), int(level), fds[4], C.byref(ol), C.byref(raw), C.byref(nr)))

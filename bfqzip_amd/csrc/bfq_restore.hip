@@ -631,6 +631,43 @@ extern "C" int bfq_fastq_restore_bgzf_fd(bfq_ctx *c, int dna_fd, uint64_t dna_le
     });
 }
 
+// The restored text turned into unaligned BAM records where it lies, and those deflated where they lie (bfq_ubam.hip).
+size_t bfq_ubam_held_need(bfq_ctx *c, u64 bound, const bfq_ubam_opts *opts);
+u64 bfq_ubam_held(bfq_ctx *c, const u8 *d_text, u64 len, const bfq_ubam_opts *opts, HostRef dst, bfq_ubam_stats *stats);
+
+extern "C" int bfq_fastq_restore_bam_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len, int perm_fd,
+                                        uint64_t permz_len, const bfq_ubam_opts *opts, int out_fd, uint64_t *out_len, bfq_ubam_stats *stats)
+{
+    if (out_len) *out_len = 0;
+    if (stats) *stats = bfq_ubam_stats{};
+    return guarded(c, [&] {
+        if (dna_fd < 0 || qs_fd < 0 || out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
+        const bool haveHdr = hdr_fd >= 0, ordered = perm_fd >= 0;
+        RsMap mD, mQ, mH, mP;
+        struct stat st;
+        if (ordered && fstat(perm_fd, &st) == 0 && S_ISREG(st.st_mode) && (u64)st.st_size < permz_len) permz_len = (u64)st.st_size;
+        const RsSrc permz{ordered ? mP.open(perm_fd, permz_len) : nullptr, ordered ? permz_len : 0};
+        const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
+        const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
+        try {
+            u64 zl = 0;
+            bfq_ubam_stats S{};
+            RsSink sink;
+            sink.extraWs = [&](u64 bound) { return bfq_ubam_held_need(c, bound, opts); };
+            sink.put = [&](const u8 *d_text, u64 len) { zl = bfq_ubam_held(c, d_text, len, opts, HostRef::file(out_fd, 0), &S); };
+            restore_core(c, dna, qs, hdr, haveHdr, sink, nullptr, nullptr, ordered ? &permz : nullptr);
+            if (ftruncate(out_fd, (off_t)zl) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, "cannot size the output file"};
+            if (out_len) *out_len = zl;
+            if (stats) *stats = S;
+        } catch (...) {
+            if (ftruncate(out_fd, 0) != 0) {}
+            if (out_len) *out_len = 0;
+            if (stats) *stats = bfq_ubam_stats{};
+            throw;
+        }
+    });
+}
+
 // ---- the grouped restore ------------------------------------------------------------------------------------------------
 // where the texts of the groups go.  put(d_text, off, len, buf): the bytes of text buffer `buf` to offset `off` of the output,
 // in the background where the destination allows it; wait(buf): the transfer that last read that buffer is over.

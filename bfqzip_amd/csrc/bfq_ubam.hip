@@ -1,0 +1,324 @@
+// bfq_ubam.hip -- unaligned BAM output (include/bfqzip_hip.h, bfq_fastq_to_bam*): the host side of turning FASTQ texts
+// into BAM records.  The definition and both passes are bfq_ubam.h's; the kernels are k_ubam.hip's.  One call:
+//   1  every present text uploaded into the context's text buffer -- or taken where it lies on the device --, its lines
+//      counted there, the arena reserved from the counts, the texts indexed (bfq_line_index)
+//   2  the sizing pass, one lane per read, and an exclusive prefix sum over the sizes in file order: the stream's exact length;
+//      a refusal is the lowest (record, reason) the pass reported
+//   3  the header uploaded, the writing pass
+//   4  bfq_fastq_to_bam / _fd / bfq_fastq_restore_bam_fd: the stream deflated where it lies (bfq_deflate_core): it never
+//      crosses to the host uncompressed
+//   arena   8 bytes per text line (and 12 per 4 KiB of text while they are indexed), 12 bytes per record, the stream -- before
+//           the sizing pass bounded by the texts' bytes + 53 + the tag per read --, the deflate batch; all reserved at once.
+//           Uploaded texts lie in the context's text buffer, beside the arena, like the text of every FASTQ entry point.
+// bfq_fastq_to_bam_host is the host form of bfq_ubam.h, for tests and as the statement of the algorithm: no entry point
+// here falls back to it.
+#include <string.h>
+#include <stdio.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <algorithm>
+#include <functional>
+#include "bfq_internal.h"
+#include "bfq_deflate.h"
+#include "bfq_ubam.h"
+
+static_assert(sizeof(bfq_ubam_stats) == 72 && sizeof(bfq_ubam_opts) == 40 && BFQ_UBAM_PIECE == BFQ_DEFL_PIECE, "the C-ABI's structures; the member size");
+
+void bfq_ubam_launch_size(bfq_ctx *c, const bfq_ubam_job &J, u64 nrec, u32 *d_sizes, u64 *d_firstBad, bfq_ubam_cnt *d_cnt);                   // k_ubam.hip
+void bfq_ubam_launch_write(bfq_ctx *c, const bfq_ubam_job &J, u64 nrec, const u64 *d_off, u8 *d_out, u64 rawLen, bfq_ubam_cnt *d_cnt);
+
+#define UBAM_NL_CHUNK 4096u                                        // (k_fastq.hip's: bfq_line_index takes 12 bytes per chunk)
+#define UBAM_NONE (~0ull)
+
+static void ubam_refuse(const bfq_ubam_err &X) { throw BfqError{bfq_ubam_code(X), bfq_ubam_message(X)}; }
+static bfq_ubam_opts ubam_opts(const bfq_ubam_opts *in)
+{
+    bfq_ubam_opts O;
+    bfq_ubam_err X;
+    if (!bfq_ubam_resolve(in, &O, &X)) ubam_refuse(X);
+    return O;
+}
+
+extern "C" void bfq_ubam_default_opts(bfq_ubam_opts *o) { if (o) bfq_ubam_defaults(o); }
+
+static thread_local std::string g_ubamHostErr;
+extern "C" const char *bfq_ubam_host_error(void) { return g_ubamHostErr.c_str(); }
+
+extern "C" int bfq_fastq_to_bam_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint8_t *out_raw, uint64_t cap,
+                                     uint64_t *raw_len, bfq_ubam_stats *stats)
+{
+    if (raw_len) *raw_len = 0;
+    if (stats) *stats = bfq_ubam_stats{};
+    g_ubamHostErr.clear();
+    try {
+        if (!text || !text_len || !raw_len || (!out_raw && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_ubam_opts O = ubam_opts(opts);
+        const u64 tl[3] = {text[0] ? text_len[0] : 0, text[1] ? text_len[1] : 0, text[2] ? text_len[2] : 0};
+        bfq_ubam_stats S;
+        bfq_ubam_err X;
+        const int r = bfq_ubam_host_form(text, tl, O, out_raw, cap, false, &S, &X);
+        if (r == 2) ubam_refuse(X);
+        *raw_len = S.raw_len;
+        if (r == 3) throw BfqError{BFQ_E_ARG, "output buffer too small for the stream"};
+        if (stats) *stats = S;
+        return BFQ_OK;
+    } catch (const BfqError &e) {
+        g_ubamHostErr = e.msg;
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        g_ubamHostErr = "host out of memory";
+        return BFQ_E_NOMEM;
+    }
+}
+
+// the texts of a call: on the host (h) or on the device (d); neither: absent
+struct UbamTexts { const u8 *h[3] = {nullptr, nullptr, nullptr}, *d[3] = {nullptr, nullptr, nullptr}; u64 len[3] = {0, 0, 0}; };
+// what steps 1-3 leave: the stream in the arena and the counts
+struct UbamStream { u8 *d_s = nullptr; u64 raw = 0; bfq_ubam_stats S{}; };
+
+// arena bytes of steps 1-3 (behind the counting of the lines) for texts of `bytes` bytes and at most `lines` lines in all,
+// of which `texts` are present; + extra(bound of the stream)
+static size_t ubam_need(u64 bytes, u64 lines, u32 texts, size_t hdrLen, size_t tagLen, bool stream, u64 *rawBound)
+{
+    const u64 nrec = lines / 4 + 3;
+    *rawBound = hdrLen + bytes + nrec * (53 + tagLen) + 64;
+    return 8 * (size_t)(lines + 2 * texts) + texts * (12 * (size_t)(bytes / UBAM_NL_CHUNK + 2) + 8192) + 12 * (size_t)(nrec + 2) + 32 * (size_t)(nrec / 4096 + 2) +
+           (stream ? (size_t)*rawBound : 0) + tagLen + (64u << 10);
+}
+
+// Steps 2-3 on texts that stand on the device at 16-byte aligned addresses, in an arena that holds ubam_need() bytes above
+// its top.  sized(raw) runs once the stream's length is known and before anything is written: it throws for a short capacity.
+static void ubam_records(bfq_ctx *c, const u8 *const d_t[3], const u64 len[3], const bool present[3], const bfq_ubam_opts &O, bool measure,
+                         const std::function<void(u64)> &sized, UbamStream *out)
+{
+    bfq_ubam_err R;
+    bfq_ubam_job J{};
+    u64 lines[3] = {0, 0, 0}, reads[3] = {0, 0, 0};
+    for (u32 k = 0; k < 3; k++) {
+        if (!present[k]) continue;
+        J.T.text[k] = d_t[k]; J.T.len[k] = len[k];
+        J.T.lineEnd[k] = bfq_line_index(c, d_t[k], len[k], &lines[k]);
+    }
+    if (!bfq_ubam_counts_ok(lines, present, reads, &R)) { c->profCollect(); ubam_refuse(R); }
+    const std::vector<u8> hdr = bfq_ubam_header(O), tag = bfq_ubam_tag(O);
+    J.npairs = reads[1]; J.n0 = reads[0];
+    J.tagLen = (u32)tag.size(); J.mateSuffix = O.mate_suffix; J.pairedCheck = O.paired_check;
+    const u64 nrec = 2 * J.npairs + J.n0;
+    u8 *d_tag = c->alloc<u8>(tag.size() + 16);
+    if (!tag.empty()) bfq_upload(c, d_tag, tag.data(), tag.size());
+    J.tag = d_tag;
+    u32 *d_sizes = c->alloc<u32>(nrec + 1);
+    u64 *d_off = c->alloc<u64>(nrec + 2);
+    u64 *d_bad = c->alloc<u64>(1);
+    bfq_ubam_cnt *d_cnt = c->alloc<bfq_ubam_cnt>(1);
+    HIP_CHECK(hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(bfq_ubam_cnt), c->stream));
+    bfq_ubam_launch_size(c, J, nrec, d_sizes, d_bad, d_cnt);
+    bfq_exscan_u32(c, d_sizes, d_off, nrec, d_off + nrec);
+    u64 firstBad = UBAM_NONE, total = 0;
+    bfq_ubam_cnt C{};
+    HIP_CHECK(hipMemcpyAsync(&firstBad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(&total, d_off + nrec, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(&C, d_cnt, sizeof C, hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    if (firstBad != UBAM_NONE) {
+        c->profCollect();
+        bfq_ubam_read_err(J, firstBad >> 8, (u32)(firstBad & 0xFFu), &R);
+        ubam_refuse(R);
+    }
+    const u64 raw = hdr.size() + total;
+    bfq_ubam_totals(J, raw, C, &out->S);
+    out->raw = raw;
+    sized(raw);
+    if (measure) { c->profCollect(); return; }
+    u8 *d_s = c->alloc<u8>(raw + 64);
+    bfq_upload(c, d_s, hdr.data(), hdr.size());
+    bfq_ubam_launch_write(c, J, nrec, d_off, d_s + hdr.size(), raw, d_cnt);
+    HIP_CHECK(hipMemcpyAsync(&C, d_cnt, sizeof C, hipMemcpyDeviceToHost, c->stream));
+    c->sync();                                                      // (hdr and tag live till here)
+    c->profCollect();
+    out->S.unknown_bases = C.unknown;
+    out->d_s = d_s;
+}
+
+// Steps 1-3.  extra(bound): arena bytes the caller needs behind them for a stream of at most that length.
+static void ubam_core(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts &O, bool measure, const std::function<size_t(u64)> &extra,
+                      const std::function<void(u64)> &sized, UbamStream *out)
+{
+    bfq_ubam_err R;
+    bool present[3];
+    u32 texts = 0;
+    for (u32 k = 0; k < 3; k++) {
+        present[k] = X.h[k] || X.d[k];
+        if (!present[k]) continue;
+        texts++;
+        u8 first[2] = {0, 0};
+        if (X.len[k] >= 2) {
+            if (X.h[k]) memcpy(first, X.h[k], 2);
+            else { HIP_CHECK(hipMemcpyAsync(first, X.d[k], 2, hipMemcpyDeviceToHost, c->stream)); c->sync(); }
+        }
+        if (!bfq_ubam_gzip_ok(first, X.len[k], k, &R)) ubam_refuse(R);
+    }
+    // Host texts go up first, into the context's text buffer outside the arena, so that every text's lines, which size its
+    // index and the records' arrays, are counted on the device before the arena is reserved.  A device text stays where it
+    // lies unless its address is no multiple of 16 (the line kernels read 16 aligned bytes at a time).
+    const u8 *d_t[3] = {nullptr, nullptr, nullptr};
+    size_t bufNeed = 0, scratch = 0;
+    auto moved = [&](u32 k) { return X.h[k] || ((uintptr_t)X.d[k] & 15u) || !X.len[k]; };
+    for (u32 k = 0; k < 3; k++)
+        if (present[k] && moved(k)) bufNeed += ((size_t)X.len[k] + 16 + 255) & ~(size_t)255;
+    u8 *buf = bufNeed ? c->textBuf(bufNeed) : nullptr;
+    if (bufNeed) bfq_phase("read_h2d");
+    u64 bytes = 0, lines = 0;
+    for (u32 k = 0; k < 3; k++) {
+        if (!present[k]) continue;
+        d_t[k] = X.d[k];
+        if (moved(k)) {
+            if (X.h[k]) bfq_upload(c, buf, X.h[k], X.len[k]);
+            else if (X.len[k]) HIP_CHECK(hipMemcpyAsync(buf, X.d[k], (size_t)X.len[k], hipMemcpyDeviceToDevice, c->stream));
+            d_t[k] = buf;
+            buf += ((size_t)X.len[k] + 16 + 255) & ~(size_t)255;
+        }
+        scratch = std::max(scratch, 12 * (size_t)(X.len[k] / UBAM_NL_CHUNK + 2) + 8192);
+        bytes += X.len[k];
+    }
+    if (scratch) { bfq_phase("alloc"); c->reserve(scratch); bfq_phase("gpu"); }
+    for (u32 k = 0; k < 3; k++)
+        if (present[k]) lines += bfq_fastq_count_lines(c, d_t[k], X.len[k]);
+    const std::vector<u8> hdr = bfq_ubam_header(O), tag = bfq_ubam_tag(O);
+    u64 bound = 0;
+    const size_t need = ubam_need(bytes, lines, texts, hdr.size(), tag.size(), !measure, &bound);
+    bfq_phase("alloc");
+    c->reserve(need + (measure ? 0 : extra(bound)) + (1u << 20));
+    bfq_phase("gpu");
+    ubam_records(c, d_t, X.len, present, O, measure, sized, out);
+}
+
+extern "C" int bfq_fastq_to_bam_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint64_t *raw_len,
+                                        uint64_t n_reads[3], bfq_ubam_stats *stats)
+{
+    if (raw_len) *raw_len = 0;
+    if (n_reads) n_reads[0] = n_reads[1] = n_reads[2] = 0;
+    if (stats) *stats = bfq_ubam_stats{};
+    return guarded(c, [&] {
+        if (!h_text || !text_len || !raw_len) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_ubam_opts O = ubam_opts(opts);
+        UbamTexts X;
+        for (int k = 0; k < 3; k++) { X.h[k] = h_text[k]; X.len[k] = h_text[k] ? text_len[k] : 0; }
+        UbamStream U;
+        ubam_core(c, X, O, true, [](u64) { return (size_t)0; }, [](u64) {}, &U);
+        *raw_len = U.raw;
+        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = U.S.written[k];
+        if (stats) *stats = U.S;
+    });
+}
+
+extern "C" int bfq_fastq_to_bam_device(bfq_ctx *c, const uint8_t *const d_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint8_t *d_out_raw,
+                                       uint64_t cap, uint64_t *raw_len, bfq_ubam_stats *stats)
+{
+    if (raw_len) *raw_len = 0;
+    if (stats) *stats = bfq_ubam_stats{};
+    return guarded(c, [&] {
+        if (!d_text || !text_len || !raw_len || (!d_out_raw && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_ubam_opts O = ubam_opts(opts);
+        UbamTexts X;
+        for (int k = 0; k < 3; k++) { X.d[k] = d_text[k]; X.len[k] = d_text[k] ? text_len[k] : 0; }
+        UbamStream U;
+        ubam_core(c, X, O, false, [](u64) { return (size_t)0; }, [&](u64 raw) {
+            if (cap >= raw) return;
+            *raw_len = raw;
+            c->profCollect();
+            throw BfqError{BFQ_E_ARG, "output buffer too small for the stream"};
+        }, &U);
+        // (the stream is made in the arena and copied out last: a refusal has then written nothing into the caller's buffer)
+        if (U.raw) HIP_CHECK(hipMemcpyAsync(d_out_raw, U.d_s, (size_t)U.raw, hipMemcpyDeviceToDevice, c->stream));
+        c->sync();
+        *raw_len = U.raw;
+        if (stats) *stats = U.S;
+    });
+}
+
+// host texts in, the compressed file out to dst (memory of cap bytes, or a file)
+static void ubam_compressed(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts *opts, HostRef dst, u64 cap, uint64_t *out_len, bfq_ubam_stats *stats)
+{
+    const bfq_ubam_opts O = ubam_opts(opts);
+    UbamStream U;
+    ubam_core(c, X, O, false, [&](u64 bound) { return bfq_deflate_need(c, bound, false, 0) + 4096; }, [&](u64 raw) {
+        if (cap >= bfq_defl_bound(raw)) return;
+        *out_len = bfq_defl_bound(raw);
+        c->profCollect();
+        throw BfqError{BFQ_E_ARG, "output buffer below bfq_bgzf_deflate_bound(raw length)"};
+    }, &U);
+    *out_len = bfq_deflate_core(c, U.d_s, HostRef{}, U.raw, (int)O.level, dst, true, 0);
+    if (stats) *stats = U.S;
+}
+
+extern "C" int bfq_fastq_to_bam(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint8_t *h_out, uint64_t cap,
+                                uint64_t *out_len, bfq_ubam_stats *stats)
+{
+    if (out_len) *out_len = 0;
+    if (stats) *stats = bfq_ubam_stats{};
+    return guarded(c, [&] {
+        if (!h_text || !text_len || !out_len || (!h_out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
+        UbamTexts X;
+        for (int k = 0; k < 3; k++) { X.h[k] = h_text[k]; X.len[k] = h_text[k] ? text_len[k] : 0; }
+        ubam_compressed(c, X, opts, HostRef::mem(h_out), cap, out_len, stats);
+    });
+}
+
+extern "C" int bfq_fastq_to_bam_fd(bfq_ctx *c, const int text_fd[3], const bfq_ubam_opts *opts, int out_fd, uint64_t *out_len, bfq_ubam_stats *stats)
+{
+    if (out_len) *out_len = 0;
+    if (stats) *stats = bfq_ubam_stats{};
+    // the files are mapped, and uploaded from the mappings
+    struct Map {
+        void *p = MAP_FAILED; size_t n = 0;
+        bool open(int fd, size_t len) { n = len; p = len ? mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0) : MAP_FAILED; return !len || p != MAP_FAILED; }
+        ~Map() { if (p != MAP_FAILED) munmap(p, n); }
+    } text[3];
+    return guarded(c, [&] {
+        if (!out_len || !text_fd) throw BfqError{BFQ_E_ARG, "null argument"};
+        if (out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
+        UbamTexts X;
+        static const u8 none = 0;
+        for (int k = 0; k < 3; k++) {
+            if (text_fd[k] < 0) continue;
+            struct stat st;
+            if (fstat(text_fd[k], &st) != 0 || !text[k].open(text_fd[k], (size_t)st.st_size)) throw BfqError{BFQ_E_IO, std::string("cannot map a text file: ") + strerror(errno)};
+            X.h[k] = st.st_size ? (const u8 *)text[k].p : &none;
+            X.len[k] = (u64)st.st_size;
+        }
+        try {
+            ubam_compressed(c, X, opts, HostRef::file(out_fd, 0), ~0ull, out_len, stats);
+            if (ftruncate(out_fd, (off_t)*out_len) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, std::string("cannot size the output file: ") + strerror(errno)};
+        } catch (...) {
+            if (ftruncate(out_fd, 0) != 0) {}
+            *out_len = 0;
+            if (stats) *stats = bfq_ubam_stats{};
+            throw;
+        }
+    });
+}
+
+// For bfq_fastq_restore_bam_fd (bfq_restore.hip), whose arena holds the restored text: the arena bytes the records and the
+// deflate batch take above a text of at most `bound` bytes -- a restored read is at least 6 bytes of text in 4 lines --, and
+// the text at d_text (in that arena) as an unpaired uBAM to dst.  Returns the file's length.
+size_t bfq_ubam_held_need(bfq_ctx *c, u64 bound, const bfq_ubam_opts *opts)
+{
+    const bfq_ubam_opts O = ubam_opts(opts);
+    u64 rawBound = 0;
+    const size_t need = ubam_need(bound, 4 * (bound / 6 + 1), 1, bfq_ubam_header(O).size(), bfq_ubam_tag(O).size(), true, &rawBound);
+    return need + bfq_deflate_need(c, rawBound, false, 0) + 4096;
+}
+u64 bfq_ubam_held(bfq_ctx *c, const u8 *d_text, u64 len, const bfq_ubam_opts *opts, HostRef dst, bfq_ubam_stats *stats)
+{
+    const bfq_ubam_opts O = ubam_opts(opts);
+    const u8 *d_t[3] = {d_text, nullptr, nullptr};
+    const u64 lens[3] = {len, 0, 0};
+    const bool present[3] = {true, false, false};
+    UbamStream U;
+    ubam_records(c, d_t, lens, present, O, false, [](u64) {}, &U);
+    const u64 zl = bfq_deflate_core(c, U.d_s, HostRef{}, U.raw, (int)O.level, dst, true, 0);
+    if (stats) *stats = U.S;
+    return zl;
+}

@@ -4,6 +4,8 @@
 //     bfq_bam -t IN.bam                                                             convert and verify, writing nothing
 //     bfq_bam -i IN.bam -u OUT.bam -o TEXT.fq | -1 T_1.fq -2 T_2.fq [-0 T_0.fq] [-N] [-L 0|1] [...]
 //                                                                                   the way back: IN.bam with the reads of the texts in it
+//     bfq_bam -w OUT.bam -o IN.fq | -1 IN_1.fq -2 IN_2.fq [-0 IN_0.fq] [-T HEADER.sam] [-R RGID] [-c] [-n] [-L 0|1] [-V]
+//                                                                                   FASTQ files as an unaligned BAM (no BAM input)
 //     bfq_bam -l IN.bam                                                             the header counts and the statistics as JSON
 // include/bfqzip_hip.h, bfq_bam_to_fastq_fd: the records' text is this project's definition, modelled on the defaults of
 // `samtools fastq` (-F 0x900; /1 and /2 unless -n; absent qualities as -v Q, default 1).  Exit status 0 on success; 1 with
@@ -11,6 +13,10 @@
 // With -u the FASTQ options name the texts to READ (bfq_bam_patch_fd): their sequence and quality lines go back into the SEQ
 // and QUAL fields of the records they came from -- -F, -n, -v, -C as on the run that made the texts --, everything else stays
 // byte for byte and OUT.bam is compressed on the device.  One line with the statistics; on a refusal OUT.bam is left empty.
+// With -w the FASTQ options name the texts to READ too (bfq_fastq_to_bam_fd): their reads become the records of a new unaligned
+// BAM -- -o alone: flag 4; -1 -2: flags 77 / 141, interleaved, the reads of -0 behind them --, made and compressed on the device.
+// -T: the header's text (as it is; default "@HD VN:1.6 SO:unsorted"), -R: RG:Z:<RGID> on every record, -c: the mates' names
+// are compared, -n: "/1" and "/2" stay on the names.  One line with the statistics; on a refusal OUT.bam is left empty.
 #include <unistd.h>
 #include <sys/mman.h>
 #include "cli_common.h"
@@ -19,6 +25,7 @@ static int usage(const char *argv0)
 {
     fprintf(stderr, "usage: %s -i IN.bam -o OUT.fq | -1 OUT_1.fq -2 OUT_2.fq [-0 OTHER.fq] [-c] [-F MASK] [-n] [-v Q] [-C PIECE] [-V] | -t IN.bam | -l IN.bam\n"
                     "       %s -i IN.bam -u OUT.bam -o TEXT.fq | -1 T_1.fq -2 T_2.fq [-0 T_0.fq] [-N] [-L 0|1] [-F MASK] [-n] [-v Q] [-C PIECE] [-V]\n"
+                    "       %s -w OUT.bam -o IN.fq | -1 IN_1.fq -2 IN_2.fq [-0 IN_0.fq] [-T HEADER.sam] [-R RGID] [-c] [-n] [-L 0|1] [-V]\n"
                     "  -i <arg>  BAM input (BGZF, or the inflated stream itself)\n"
                     "  -o <arg>  one FASTQ output: every kept record in file order\n"
                     "  -1 -2 <arg>  split: READ1-only and READ2-only records; -0 <arg>: the rest (dropped without it)\n"
@@ -32,7 +39,11 @@ static int usage(const char *argv0)
                     "  -u <arg>  the way back: write IN.bam with the reads of the FASTQ files (-o | -1 -2 [-0], now inputs) in it\n"
                     "  -N        with -u: refuse unless every read's name is its record's\n"
                     "  -L <arg>  with -u: 0 = stored members, 1 = compressed (default 1)\n"
-                    "  -V        phase timeline on stderr\n", argv0, argv0);
+                    "  -w <arg>  no BAM input: write the FASTQ files (-o | -1 -2 [-0], now inputs) as this unaligned BAM\n"
+                    "  -T <arg>  with -w: a file whose bytes become the header's text (default: @HD VN:1.6 SO:unsorted)\n"
+                    "  -R <arg>  with -w: the read group: RG:Z:<arg> on every record (and @RG ID:<arg> in the default header)\n"
+                    "            with -w, -c compares the names of the mates, -n keeps /1 and /2 on the names, -L as with -u\n"
+                    "  -V        phase timeline on stderr\n", argv0, argv0, argv0);
     return 1;
 }
 
@@ -74,17 +85,68 @@ static int patch(const std::string &input, const std::string text[3], const std:
     return 0;
 }
 
+// -w: the FASTQ files as an unaligned BAM, to OUT.bam
+static int write_ubam(const std::string text[3], const std::string &outName, const std::string &headerName, const std::string &rg, bool pairedCheck, bool mateSuffix,
+                      int level)
+{
+    InFile tin[3], hin;
+    int fds[3] = {-1, -1, -1};
+    for (int k = 0; k < 3; k++)
+        if (!text[k].empty()) {
+            if (!tin[k].open(text[k])) { fprintf(stderr, "bfq_bam: cannot read %s\n", text[k].c_str()); return 1; }
+            fds[k] = tin[k].fd;
+        }
+    bfq_ubam_opts O;
+    bfq_ubam_default_opts(&O);
+    O.paired_check = pairedCheck ? 1 : 0; O.mate_suffix = mateSuffix ? 1 : 0; O.level = (uint32_t)level;
+    void *hm = MAP_FAILED;
+    static const uint8_t none = 0;
+    if (!headerName.empty()) {
+        if (!hin.open(headerName)) { fprintf(stderr, "bfq_bam: cannot read %s\n", headerName.c_str()); return 1; }
+        hm = hin.size ? mmap(nullptr, hin.size, PROT_READ, MAP_PRIVATE, hin.fd, 0) : MAP_FAILED;
+        if (hin.size && hm == MAP_FAILED) { perror("bfq_bam"); return 1; }
+        O.header_text = hin.size ? (const uint8_t *)hm : &none; O.header_len = hin.size;
+    }
+    if (!rg.empty()) O.rg_id = rg.c_str();
+    OutFile out;
+    if (!out.open(outName)) { perror("bfq_bam"); return 1; }
+    bfq_params P;
+    bfq_default_params(&P);
+    bfq_ctx *c = create_on_free_gpu("bfq_bam", &P);
+    if (!c) return 1;
+    uint64_t outLen = 0;
+    bfq_ubam_stats S = {};
+    if (bfq_fastq_to_bam_fd(c, fds, &O, out.fd, &outLen, &S)) {
+        fprintf(stderr, "bfq_bam: %s: %s\n", outName.c_str(), bfq_last_error(c));
+        bfq_destroy(c);
+        if (ftruncate(out.fd, 0) != 0) perror("bfq_bam");
+        return 1;
+    }
+    if (hm != MAP_FAILED) munmap(hm, hin.size);
+    bfq_phase("teardown");
+    trace_kernel_times(c, "bfq_bam");
+    const bool closed = out.close();
+    bfq_destroy(c);
+    if (!closed) { perror("bfq_bam"); return 1; }
+    bfq_phase_report("bfq_bam");
+    typedef unsigned long long ull;
+    printf("%llu records: %llu + %llu + %llu written, %llu numbered, %llu comments dropped, %llu unknown bases; %llu bytes of stream in %llu members, "
+           "%llu bytes written\n", (ull)S.records, (ull)S.written[0], (ull)S.written[1], (ull)S.written[2], (ull)S.named, (ull)S.comments_dropped,
+           (ull)S.unknown_bases, (ull)S.raw_len, (ull)S.members, (ull)outLen);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     bfq_phase("start");
-    std::string input, outName[3], patchName;
+    std::string input, outName[3], patchName, writeName, headerName, rgId;
     int level = 1;
     char mode = 0;
     bfq_bam_opts O;
     bfq_bam_default_opts(&O);
     int opt;
     bool single = false;                                           // -o was given
-    while ((opt = getopt(argc, argv, "i:t:l:o:0:1:2:cF:nv:C:Vhu:NL:")) != -1) {
+    while ((opt = getopt(argc, argv, "i:t:l:o:0:1:2:cF:nv:C:Vhu:NL:w:T:R:")) != -1) {
         switch (opt) {
         case 'i': case 't': case 'l':
             if (mode) return usage(argv[0]);
@@ -103,10 +165,20 @@ int main(int argc, char **argv)
         case 'u': patchName = optarg; break;
         case 'N': O.check_names = 1; break;
         case 'L': level = atoi(optarg); break;
+        case 'w': writeName = optarg; break;
+        case 'T': headerName = optarg; break;
+        case 'R': rgId = optarg; break;
         default: return usage(argv[0]);
         }
     }
     const bool anyOut = !outName[0].empty() || !outName[1].empty() || !outName[2].empty();
+    if (!writeName.empty()) {                                      // -w: no BAM input; -o | -1 -2 [-0] name the texts to read
+        if (mode || !patchName.empty() || O.check_names || !anyOut || (single && (!outName[1].empty() || !outName[2].empty())) ||
+            outName[1].empty() != outName[2].empty() || (!single && outName[1].empty()) || (O.paired_check && outName[1].empty()))
+            return usage(argv[0]);
+        return write_ubam(outName, writeName, headerName, rgId, O.paired_check != 0, O.mate_suffix != 0, level);
+    }
+    if (!headerName.empty() || !rgId.empty()) return usage(argv[0]);
     if (!mode || (mode != 'i' && anyOut) || (mode == 'i' && !anyOut)) return usage(argv[0]);
     if (mode == 'i' && (single ? O.split != 0 : outName[1].empty() || outName[2].empty())) return usage(argv[0]);
     if (O.paired_check && !O.split) return usage(argv[0]);

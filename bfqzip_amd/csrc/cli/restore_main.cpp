@@ -1,6 +1,6 @@
 // restore_main.cpp -- the way back from the compressed streams to a FASTQ file (not a tool of the reference, which leaves
 // this to `7z x` / `bsc d` + `paste`):
-//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z] -o OUT.fq [-V]
+//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z | -b] -o OUT.fq [-V]
 // The inputs are what `bsc e`, bfq_fastq_job.compress_streams = 1 / 2 / 3 and parallel.py --compress write
 // (include/bfqzip_hip.h, bfq_fastq_restore_fd).  -P PERM: the BFQPERM1 file `bfq_reorder -P` / `parallel.py --keep-order`
 // wrote for the run: the records come back in the order of the original file (bfq_fastq_restore_ordered_fd).
@@ -9,8 +9,10 @@
 // device; several BFQEBWT1 members are taken.  -G FIRST[:COUNT]: only those groups.  -l: the plan of the groups, one line
 // each, and nothing else: no GPU is touched and no output is created.  -g / -G with -P is a usage error: records in the
 // original order draw on all groups at once.  -z: OUT.fq is written as BGZF (.fq.gz: bfq_fastq_restore_bgzf_fd, the text is
-// deflated on the device and never crosses to the host), with and without -P; not with -g / -G.  Exit status 0 on success; 1 with the library's message otherwise, and then
-// OUT.fq is left empty.
+// deflated on the device and never crosses to the host), with and without -P; not with -g / -G.  -b: the output is written as an
+// unaligned BAM instead (OUT.bam: bfq_fastq_restore_bam_fd, the restored text becomes unpaired records on the device and those
+// are deflated there), with and without -P; not with -z, -g / -G.  Exit status 0 on success; 1 with the library's message
+// otherwise, and then OUT.fq is left empty.
 #include <unistd.h>
 #include <sys/mman.h>
 #include <vector>
@@ -18,7 +20,7 @@
 
 static int usage(const char *argv0)
 {
-    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z] -o OUT.fq [-V]\n"
+    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z | -b] -o OUT.fq [-V]\n"
                     "  -d <arg>  container(s) of the DNA stream (OUT.fq.dna; BFQDNAC1 / BFQRANS2 members, or one BFQEBWT1) (REQUIRED)\n"
                     "  -q <arg>  container(s) of the quality stream (OUT.fq.qs) (REQUIRED)\n"
                     "  -H <arg>  container(s) of the header stream (OUT.h); without it every header line is \"@\"\n"
@@ -27,6 +29,7 @@ static int usage(const char *argv0)
                     "  -G <arg>  FIRST[:COUNT]: only these groups of the plan (COUNT omitted: to the end)\n"
                     "  -l        print the plan of the groups and exit (no GPU, no output file; -o not needed)\n"
                     "  -z        write the output as BGZF (OUT.fq.gz), deflated on the GPU; not with -g / -G\n"
+                    "  -b        write the output as an unaligned BAM (OUT.bam), records made and deflated on the GPU; not with -z, -g / -G\n"
                     "  -o <arg>  output FASTQ (REQUIRED)\n"
                     "  -V        phase timeline on stderr\n", argv0);
     return 1;
@@ -67,10 +70,10 @@ int main(int argc, char **argv)
 {
     bfq_phase("start");
     std::string dna, qs, hdr, perm, output;
-    bool grouped = false, list = false, bgzf = false;
+    bool grouped = false, list = false, bgzf = false, ubam = false;
     uint64_t first = 0, count = ~0ull;
     int opt;
-    while ((opt = getopt(argc, argv, "d:q:H:P:o:gG:lzVh")) != -1) {
+    while ((opt = getopt(argc, argv, "d:q:H:P:o:gG:lzbVh")) != -1) {
         switch (opt) {
         case 'd': dna = optarg; break;
         case 'q': qs = optarg; break;
@@ -88,6 +91,7 @@ int main(int argc, char **argv)
         }
         case 'l': list = true; break;
         case 'z': bgzf = true; break;
+        case 'b': ubam = true; break;
         case 'V': bfq_phase_enable(1); break;
         default: return usage(argv[0]);
         }
@@ -101,6 +105,10 @@ int main(int argc, char **argv)
     if (bgzf && grouped) {
         fprintf(stderr, "bfq_restore: -z does not go with -g / -G: the grouped restore writes plain text; restore the archive in one piece (without -g), "
                         "or compress the text afterwards (bfq_bgzf -c)\n");
+        return usage(argv[0]);
+    }
+    if (ubam && (bgzf || grouped)) {
+        fprintf(stderr, "bfq_restore: -b does not go with -z (a BAM file is BGZF already) or with -g / -G (the grouped restore writes plain text)\n");
         return usage(argv[0]);
     }
     InFile fd, fq, fh, fp;
@@ -129,14 +137,17 @@ int main(int argc, char **argv)
         if (mq != MAP_FAILED) munmap(mq, fq.size);
         if (mh != MAP_FAILED) munmap(mh, fh.size);
         if (bound < 0) { fprintf(stderr, "bfq_restore: the inputs are not containers (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQNAME1 / BFQQUAL1 / BFQEBWT1)\n"); outText.close(); return 1; }
-        if (bound >= (64 << 20) && !bgzf) (void)bfq_output_prefault(outText.fd, (uint64_t)bound + 4096, (uint64_t)bound / 2);
+        if (bound >= (64 << 20) && !bgzf && !ubam) (void)bfq_output_prefault(outText.fd, (uint64_t)bound + 4096, (uint64_t)bound / 2);
     }
     bfq_params P;
     bfq_default_params(&P);
     bfq_ctx *c = create_on_free_gpu("bfq_restore", &P);
     if (!c) return 1;
     uint64_t outLen = 0, reads = 0, rawLen = 0;
-    const int rc = bgzf ? bfq_fastq_restore_bgzf_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd, fp.size, 1,
+    bfq_ubam_stats US = {};
+    const int rc = ubam ? bfq_fastq_restore_bam_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd, fp.size, nullptr,
+                                                   outText.fd, &outLen, &US)
+                   : bgzf ? bfq_fastq_restore_bgzf_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd, fp.size, 1,
                                                     outText.fd, &outLen, &rawLen, &reads)
                    : grouped ? bfq_fastq_restore_grouped_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, first, count, outText.fd, &outLen, &reads)
                    : perm.empty() ? bfq_fastq_restore_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, outText.fd, &outLen, &reads)
@@ -153,7 +164,8 @@ int main(int argc, char **argv)
     bfq_destroy(c);
     if (!closed) { perror("bfq_restore"); return 1; }
     bfq_phase_report("bfq_restore");
-    if (bgzf) printf("%llu reads, %llu bytes -> %llu bytes\n", (unsigned long long)reads, (unsigned long long)rawLen, (unsigned long long)outLen);
+    if (ubam) printf("%llu records, %llu bytes of stream -> %llu bytes\n", (unsigned long long)US.records, (unsigned long long)US.raw_len, (unsigned long long)outLen);
+    else if (bgzf) printf("%llu reads, %llu bytes -> %llu bytes\n", (unsigned long long)reads, (unsigned long long)rawLen, (unsigned long long)outLen);
     else printf("%llu reads, %llu bytes\n", (unsigned long long)reads, (unsigned long long)outLen);
     return 0;
 }

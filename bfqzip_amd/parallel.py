@@ -710,8 +710,23 @@ def main(argv=None):
                     help="with --bam, one BAM input and a merged FASTQ output: after the run the output text(s) are written back into "
                          "the SEQ and QUAL fields of the input's records on the GPU and the result goes to PATH (with -p the two texts "
                          "meet the READ1 / READ2 records; with -H the names are compared); an index of the input does not fit PATH")
+    ap.add_argument("--ubam-out", default="", metavar="PATH",
+                    help="with a merged FASTQ output: after the run the output text becomes an unaligned BAM on the GPU of rank 0 "
+                         "and goes to PATH (with -p both merged texts become one paired uBAM, the names compared with -H); "
+                         "not with --bam-out, --restore, --streams-only or --compress")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.ubam_out:
+        why = None
+        if a.bam_out:
+            why = "--ubam-out makes new records, --bam-out patches those of the input: one of them"
+        elif a.restore:
+            why = "--ubam-out follows a run: not with --restore (bfq_restore -b writes a uBAM from the containers)"
+        elif ((a.m2 or a.m3) and a.streams_only) or (a.compress and not a.m0):
+            why = "--ubam-out converts the merged FASTQ text: not with --streams-only or --compress"
+        if why:
+            print("=== ERROR ===\n" + why, file=sys.stderr)
+            return 1
     if a.bam_out:
         why = None
         if not a.bam or len(a.input) != 1 or a.restore:
@@ -813,6 +828,23 @@ def main(argv=None):
             except api.BfqError as e:                                # (a refusal: the library's message; every rank leaves with it)
                 failed = e
                 print(f"=== ERROR ===\n--bam-out: {e}", file=sys.stderr)
+        if comm.all_gather_i64([1 if failed else 0])[0, 0]:
+            eng.close()
+            if dist:
+                dist.destroy_process_group()
+            return 1
+    if a.ubam_out:
+        comm.barrier()
+        failed = None
+        if comm.rank == 0:
+            fq = [n["fastq"] for n in names]
+            try:
+                n, st = eng.fastq_to_bam_files((None, fq[0], fq[1]) if a.paired else (fq[0],), a.ubam_out, paired_check=int(a.paired and a.headers))
+                if log:
+                    log(f"ubam-out: {' '.join(fq)} -> {a.ubam_out}, {n} bytes, {st}")
+            except api.BfqError as e:                                # (a refusal: the library's message; every rank leaves with it)
+                failed = e
+                print(f"=== ERROR ===\n--ubam-out: {e}", file=sys.stderr)
         if comm.all_gather_i64([1 if failed else 0])[0, 0]:
             eng.close()
             if dist:

@@ -821,6 +821,74 @@ int bfq_bam_patch(bfq_ctx *c, const uint8_t *h_in, uint64_t len, const bfq_bam_o
                   int level, uint8_t *h_out, uint64_t cap, uint64_t *out_len, bfq_bam_patch_stats *stats);
 int bfq_bam_patch_fd(bfq_ctx *c, int bam_fd, uint64_t len, const bfq_bam_opts *opts, const int text_fd[3], int level, int out_fd, uint64_t *out_len,
                      bfq_bam_patch_stats *stats);
+/* ---- unaligned BAM output: "these FASTQ texts as an unaligned BAM" (k_ubam.hip; the definition in full, both passes and
+ * the host form: csrc/bfq_ubam.h).  Unlike the patch above it needs no BAM to write into: records are made, not edited.  It
+ * is this project's definition, modelled on the defaults of `samtools import`; parity with an htslib tool is not pinned by a
+ * test.
+ *   Inputs: text[k], k = 0, 1, 2, with the meaning of the outputs of bfq_bam_to_fastq*.  Unpaired: text[0] alone, every
+ *     record flag 4.  Paired: text[1] and text[2] together -- record 2i is read i of text[1] (flag 77), record 2i + 1 read i of
+ *     text[2] (flag 141) --, an optional text[0] behind all pairs (flag 4).  A text that begins with 1f 8b is refused
+ *     ("inflate the text first"); CR before LF is stripped; a last line without its LF counts.
+ *   Name: the bytes behind '@' up to the first blank, tab or line end; the rest of the header line is dropped
+ *     (comments_dropped).  With mate_suffix a trailing "/1" of a text[1] name and "/2" of a text[2] name is removed where at
+ *     least one byte remains.  An empty name ("@" alone: a run without kept headers) becomes the read's 1-based index in
+ *     decimal -- both mates share theirs, the reads of text[0] count on behind the pairs -- (named).  paired_check: the names
+ *     of read i of text[1] and text[2] are compared after the suffix removal.
+ *   Record: refID -1, pos -1, mapq 0, bin 4680, no CIGAR, next_refID -1, next_pos -1, tlen 0.  SEQ: case-insensitive over
+ *     =ACMGRSVTWYHKDBN, any other byte 15 (unknown_bases), the spare nibble of an odd length 0; l_seq may be 0.  QUAL: char - 33,
+ *     always written: absent qualities cannot come back from a text, so BAM -> text -> BAM is an identity only for records
+ *     that held qualities <= 93 and no tags.  Tags: none, or RG:Z:<rg_id> on every record.  A record is 36 + (l_name + 1) +
+ *     ceil(l_seq / 2) + l_seq bytes, + 4 + strlen(rg_id): the stream's length is exact before anything is written.
+ *   Header: header_text[0, header_len) as it is -- the caller's to make valid, e.g. the header text of the original BAM --,
+ *     or with header_text NULL "@HD\tVN:1.6\tSO:unsorted\n" and, with rg_id, "@RG\tID:<rg_id>\n".  n_ref is 0.
+ *   Refusals, nothing written, the context stays usable.  BFQ_E_ARG: "FASTQ to BAM: text <k> is compressed ..."; "FASTQ:
+ *     number of lines is not a multiple of 4"; "FASTQ to BAM: text 1 holds <n> reads, text 2 holds <m>" (one mate text
+ *     absent, or differing counts); "FASTQ: len(DNA) != len(QS) in a record"; "FASTQ to BAM: text <k> read <i>: <reason>" for
+ *     a header line that does not begin with '@', a name above 254 bytes or with a byte outside [!-?A-~], a name that
+ *     differs from its mate's (paired_check), a third line that does not begin with '+', a quality byte outside [33, 126];
+ *     an rg_id that is empty, above 255 bytes or holds a byte outside [ -~]; a level other than 0 or 1.  BFQ_E_TOO_LONG: "...
+ *     read longer than 65000 bases".  Of all offending reads the one whose record would come first in the file is named, by
+ *     the device (one atomicMin) as by the host form.
+ *   The BGZF layer is this project's (bfq_bgzf_deflate: members cut at 65 280 bytes of stream, the EOF member at the end);
+ *   opts.level as for bfq_bgzf_deflate.
+ *       bfq_fastq_to_bam_measure : host texts in; *raw_len = the exact length of the stream, n_reads[3], *stats (without
+ *         unknown_bases, which the writing pass counts); nothing is written.
+ *       bfq_fastq_to_bam_host    : one thread, no context, no GPU, the stream out (not compressed): states the algorithm and
+ *         is what the tests compare with; NO entry point falls back to it.  cap below the length: BFQ_E_ARG, nothing written,
+ *         *raw_len = the length needed.  Message: bfq_ubam_host_error() (of the calling thread's last call).
+ *       bfq_fastq_to_bam_device  : texts in device memory, the stream into d_out_raw, not compressed; cap as above.
+ *       bfq_fastq_to_bam         : host texts in, the BGZF file into a host buffer; a cap below bfq_bgzf_deflate_bound(stream
+ *         length): BFQ_E_ARG, nothing written, *out_len = that bound.
+ *       bfq_fastq_to_bam_fd      : open files; a text_fd[k] < 0 is absent; out_fd is sized to *out_len (0 on a refusal).
+ *       bfq_fastq_restore_bam_fd : bfq_fastq_restore_fd (perm_fd < 0) or bfq_fastq_restore_ordered_fd with the restored text
+ *         turned into records (unpaired) and those deflated where they lie: containers in, uBAM out; the FASTQ text never
+ *         exists on the host.  The grouped restore has no such form; the two archives of a paired run restore to two texts
+ *         and go through bfq_fastq_to_bam_fd.
+ *     The stream is deflated where it lies: it never crosses to the host uncompressed.  Device memory, in the workspace and
+ *     reserved once: 8 bytes per text line (and 12 per 4 KiB of text while they are indexed), 12 bytes per record, the stream,
+ *     the deflate batch; texts that are uploaded (or lie at an address that is no multiple of 16) go into the context's text
+ *     buffer beside it.
+ *   stats (may be NULL): records, written[k] (records made of text k), named, comments_dropped, unknown_bases, raw_len,
+ *     members (of the BGZF file: ceil(raw_len / 65280) + 1). */
+typedef struct bfq_ubam_opts {
+    uint32_t mate_suffix, paired_check, level, reserved;
+    const uint8_t *header_text; uint64_t header_len;
+    const char *rg_id;
+} bfq_ubam_opts;
+typedef struct bfq_ubam_stats { uint64_t records, written[3], named, comments_dropped, unknown_bases, raw_len, members; } bfq_ubam_stats;
+void bfq_ubam_default_opts(bfq_ubam_opts *o);
+int bfq_fastq_to_bam_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint64_t *raw_len,
+                             uint64_t n_reads[3], bfq_ubam_stats *stats);
+int bfq_fastq_to_bam_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint8_t *out_raw, uint64_t cap,
+                          uint64_t *raw_len, bfq_ubam_stats *stats);
+const char *bfq_ubam_host_error(void);
+int bfq_fastq_to_bam_device(bfq_ctx *c, const uint8_t *const d_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint8_t *d_out_raw,
+                            uint64_t cap, uint64_t *raw_len, bfq_ubam_stats *stats);
+int bfq_fastq_to_bam(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint8_t *h_out, uint64_t cap,
+                     uint64_t *out_len, bfq_ubam_stats *stats);
+int bfq_fastq_to_bam_fd(bfq_ctx *c, const int text_fd[3], const bfq_ubam_opts *opts, int out_fd, uint64_t *out_len, bfq_ubam_stats *stats);
+int bfq_fastq_restore_bam_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len, int perm_fd,
+                             uint64_t permz_len, const bfq_ubam_opts *opts, int out_fd, uint64_t *out_len, bfq_ubam_stats *stats);
 /* ---- bgzip-compressed output: BGZF members deflated on the device (k_deflate.hip; the format and every bound:
  * csrc/bfq_deflate.h).  A text of len bytes is cut at multiples of 65 280 bytes (htslib's member size; the cut depends on
  * nothing else); every piece becomes one BGZF member -- htslib's 18-byte header, a raw deflate payload, CRC32 and ISIZE --
