@@ -43,7 +43,7 @@ SYMBOLS = [
     "bfq_bam_patch_host", "bfq_bam_patch_device", "bfq_bam_patch", "bfq_bam_patch_fd",
     "bfq_ubam_default_opts", "bfq_fastq_to_bam_measure", "bfq_fastq_to_bam_host", "bfq_ubam_host_error", "bfq_fastq_to_bam_device", "bfq_fastq_to_bam",
     "bfq_fastq_to_bam_fd", "bfq_fastq_restore_bam_fd",
-    "bfq_workspace_bytes", "bfq_version",
+    "bfq_workspace_bytes", "bfq_workspace_read", "bfq_version",
 ]
 
 
@@ -218,6 +218,8 @@ def lib():
         L.bfq_version.restype = C.c_char_p
         L.bfq_workspace_bytes.restype = C.c_uint64
         L.bfq_workspace_bytes.argtypes = [C.c_void_p]
+        L.bfq_workspace_read.restype = C.c_uint64
+        L.bfq_workspace_read.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         L.bfq_synth_total.restype = C.c_uint64
         vp, u64 = C.c_void_p, C.c_uint64
         L.bfq_pick_device.argtypes = [C.c_char_p, C.c_int]

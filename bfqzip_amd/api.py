@@ -1338,6 +1338,13 @@ class Engine:
     def workspace_bytes(self):
         return int(self.L.bfq_workspace_bytes(self.h))
 
+    def workspace_read(self, off, length):
+        """The workspace's bytes [off, off + length) as they are once the queued work has finished (cut at its end): a test hook
+        (BFQ_POISON)."""
+        out = np.empty(int(length), np.uint8)
+        got = int(self.L.bfq_workspace_read(self.h, int(off), out.ctypes.data, len(out))) if len(out) else 0
+        return out[:got]
+
 
 def reorder_key(seq, k=21):
     """The mode-2 sort key of one sequence line (bfq_reorder_key: host only, no GPU)."""

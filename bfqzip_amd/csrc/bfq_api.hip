@@ -66,6 +66,7 @@ void bfq_ctx::adoptWorkspace(char *p, size_t bytes)
 {
     if (ws.base) { quiesce(); (void)hipFree(ws.base); }
     ws = Arena{p, bytes, 0, ws.peak};
+    poisonWs();
 }
 
 void bfq_ctx::reserve(size_t bytes)
@@ -91,8 +92,8 @@ void bfq_ctx::reserve(size_t bytes)
             (void)hipGetLastError();
             throw BfqError{BFQ_E_NOMEM, b};
         }
-        adoptWorkspace(p, bytes);
-    }
+        adoptWorkspace(p, bytes);                                 // (BFQ_POISON: filled there)
+    } else poisonWs();                                            // the call starts over in what the calls before it left
     ws.release(0);
     d_bwt = d_qual = nullptr; d_lcp = nullptr; d_gcnt = nullptr; n = N = 0;
 }
@@ -201,7 +202,7 @@ extern "C" bfq_ctx *bfq_create(int device, const bfq_params *p)
         c->env = bfq_env_read();
         HIP_CHECK(hipSetDevice(device));
         HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        HIP_CHECK(hipMalloc((void **)&c->d_cnt, sizeof(DevCounters)));
+        if (!bfq_dev_malloc(c, (void **)&c->d_cnt, sizeof(DevCounters))) throw BfqError{BFQ_E_NOMEM, "device counters"};
         memset(c->profMs, 0, sizeof c->profMs); memset(c->profLaunches, 0, sizeof c->profLaunches);
         memset(c->profBytes, 0, sizeof c->profBytes);
         g_bfqHipStarted = true;                                    // (bfq_host.cpp: the output files' populate helpers may map pages now)
@@ -222,8 +223,8 @@ extern "C" bfq_ctx *bfq_create(int device, const bfq_params *p)
             }
             memcpy(&thr[k], &hi, 8);
         }
-        HIP_CHECK(hipMalloc((void **)&c->d_powtab, sizeof pw));
-        HIP_CHECK(hipMalloc((void **)&c->d_qthr, sizeof(double) * c->qthrN));
+        if (!bfq_dev_malloc(c, (void **)&c->d_powtab, sizeof pw) || !bfq_dev_malloc(c, (void **)&c->d_qthr, sizeof(double) * c->qthrN))
+            throw BfqError{BFQ_E_NOMEM, "device tables"};
         HIP_CHECK(hipMemcpy(c->d_powtab, pw, sizeof pw, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(c->d_qthr, thr.data(), sizeof(double) * c->qthrN, hipMemcpyHostToDevice));
         return c;
@@ -263,6 +264,15 @@ extern "C" int bfq_set_params(bfq_ctx *c, const bfq_params *p)
 extern "C" const char *bfq_last_error(bfq_ctx *c) { return c ? c->err.c_str() : "null context"; }
 extern "C" void *bfq_stream(bfq_ctx *c) { return c ? (void *)c->stream : nullptr; }
 extern "C" uint64_t bfq_workspace_bytes(bfq_ctx *c) { return c ? c->ws.cap : 0; }
+extern "C" uint64_t bfq_workspace_read(bfq_ctx *c, uint64_t off, void *dst, uint64_t len)
+{
+    if (!c || !dst || !c->ws.base || off >= c->ws.cap) return 0;
+    if (len > c->ws.cap - off) len = c->ws.cap - off;
+    if (!len || hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    c->quiesce();
+    if (hipMemcpy(dst, c->ws.base + off, len, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return len;
+}
 extern "C" int bfq_prof_enable(bfq_ctx *c, int on) { if (!c) return BFQ_E_ARG; c->profOn = on != 0; return BFQ_OK; }
 extern "C" void bfq_prof_reset(bfq_ctx *c)
 {
@@ -937,9 +947,7 @@ u8 *bfq_ctx::textBuf(size_t bytes)
     if (bytes > textCap) {
         if (d_text) { HIP_CHECK(hipStreamSynchronize(stream)); HIP_CHECK(hipFree(d_text)); d_text = nullptr; textCap = 0; }
         size_t want = (bytes + (bytes >> 4) + 0xFFFFF) & ~(size_t)0xFFFFF;
-        if (hipMalloc((void **)&d_text, want) != hipSuccess) {
-            (void)hipGetLastError();
-            d_text = nullptr;
+        if (!bfq_dev_malloc(this, (void **)&d_text, want)) {     // (BFQ_POISON: filled here, once -- a resident text must survive the calls)
             throw BfqError{BFQ_E_NOMEM, "device buffer for the FASTQ text"};
         }
         textCap = want;
@@ -1069,7 +1077,7 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
         const u64 Nb = nlines / 4 + 1;
         bfq_phase("alloc");
         const size_t parseBytes = (tl + 8192) + 128 * (Nb + 64) + 8 * (nlines + 64) + 16 * (tl / 4096 + 16) + (64u << 20);
-        pws.alloc(parseBytes, "the parsed records");
+        pws.alloc(c, parseBytes, "the parsed records");
         ScopedArena parse(c, pws.p, parseBytes);                // the small arena of the line count comes back below
         bfq_phase("gpu");
         c->zeroCounters();
@@ -1111,7 +1119,7 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
             const u64 nwords = n / BFQ_SYMS_PER_WORD + 3;
             const size_t w3 = (8 * bfq_t3_alloc(nwords) + 255) & ~(size_t)255;
             bfq_phase("alloc");
-            tws.alloc(2 * npad + w3 + 8 * (N + 2) + 4096, "the text arrays");
+            tws.alloc(c, 2 * npad + w3 + 8 * (N + 2) + 4096, "the text arrays");
             bfq_phase("gpu");
             PileText pt{(u8 *)tws.p, (u8 *)tws.p + npad, (u64 *)(tws.p + 2 * npad)};
             u64 *roff2 = (u64 *)(tws.p + 2 * npad + w3);

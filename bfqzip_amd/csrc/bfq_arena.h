@@ -27,11 +27,18 @@ struct Arena {
 
 // Points c->ws at a foreign buffer; the previous arena comes back, `top` included, when the guard goes (or at restore()),
 // after c->quiesce() has waited for the work that may still use the foreign one.  The high-water mark carries over.
+// A context that has a poisonWs() is told of the new arena (bfq_ctx: the BFQ_POISON fill); one without it needs none.
+template <class Ctx> static auto arena_lent(Ctx *c, int) -> decltype(c->poisonWs(), void()) { c->poisonWs(); }
+template <class Ctx> static void arena_lent(Ctx *, long) {}
 template <class Ctx> struct ScopedArenaT {
     Ctx *c;
     Arena prev;
     bool active = true;
-    ScopedArenaT(Ctx *c, char *base, size_t cap) : c(c), prev(c->ws) { c->ws = Arena{base, cap, 0, prev.peak}; }
+    ScopedArenaT(Ctx *c, char *base, size_t cap) : c(c), prev(c->ws)
+    {
+        c->ws = Arena{base, cap, 0, prev.peak};
+        try { arena_lent(c, 0); } catch (...) { c->ws = prev; throw; }   // BFQ_POISON: a lent buffer starts as dirty as the arena does
+    }
     ScopedArenaT(const ScopedArenaT &) = delete; ScopedArenaT &operator=(const ScopedArenaT &) = delete;
     void restore()
     {

@@ -70,6 +70,11 @@ BfqEnv bfq_env_read()
         if (const char *d = getenv("BFQ_LEASE_DIR")) e.leaseDir = d;
         e.noOutmap = getenv("BFQ_NO_OUTMAP") != nullptr;
         e.compact = geti("BFQ_COMPACT", 0) != 0;
+        if (const char *v = getenv("BFQ_POISON")) {
+            char *end = nullptr;
+            const long b = strtol(v, &end, 0);
+            if (*v && end && !*end && b >= 0 && b <= 255) e.poison = (int)b;
+        }
         e.prefaultPause = geti("BFQ_PREFAULT_PAUSE", 0) != 0;
         e.compactWin = getu("BFQ_COMPACT_WIN", 0);
         e.compactRing = getu("BFQ_COMPACT_RING", 0);

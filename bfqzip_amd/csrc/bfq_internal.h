@@ -99,6 +99,13 @@ struct bfq_ctx {
     void wsFree();
     void adoptWorkspace(char *p, size_t bytes);   // frees the arena: this buffer is the arena now, and the context's to free
     void quiesce() { (void)hipStreamSynchronize(stream); }
+    // BFQ_POISON: the byte over the whole arena (a plain memset on the stream, no profiled launch), done when it returns
+    void poisonWs()
+    {
+        if (env.poison < 0 || !ws.base || !ws.cap) return;
+        HIP_CHECK(hipMemsetAsync(ws.base, env.poison, ws.cap, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
     // an arena being allocated on a helper thread while the caller uploads its input (a one-shot tool's 86 GB can land on
     // memory the driver has not cleared yet: 2 s instead of 0); reserve() joins it and takes it over when it is large enough
     void reserveBegin(size_t bytes);
@@ -167,21 +174,31 @@ struct bfq_ctx {
 };
 using ScopedArena = ScopedArenaT<bfq_ctx>;
 
-// one hipMalloc and its hipFree
+// Every device allocation of the library outside the arena is made here (the arena's own two: reserveBegin() and reserve(),
+// bfq_api.hip).  BFQ_POISON: filled with the byte once, before anyone sees it.  false: no memory (the HIP error is cleared).
+static inline bool bfq_dev_malloc(bfq_ctx *c, void **p, size_t bytes)
+{
+    *p = nullptr;
+    if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+    if (c->env.poison >= 0 && bytes) {
+        hipError_t e = hipMemsetAsync(*p, c->env.poison, bytes, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { (void)hipFree(*p); *p = nullptr; throw BfqError{BFQ_E_HIP, std::string("BFQ_POISON fill: ") + hipGetErrorString(e)}; }
+    }
+    return true;
+}
+// one device allocation and its hipFree
 struct DevBuf {
     char *p = nullptr;
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { free(); }
-    bool tryAlloc(size_t bytes)
+    bool tryAlloc(bfq_ctx *c, size_t bytes)
     {
         free();
-        if (hipMalloc((void **)&p, bytes) == hipSuccess) return true;
-        (void)hipGetLastError();
-        p = nullptr;
-        return false;
+        return bfq_dev_malloc(c, (void **)&p, bytes);
     }
-    void alloc(size_t bytes, const char *what) { if (!tryAlloc(bytes)) throw BfqError{BFQ_E_NOMEM, std::string("device buffer for ") + what}; }
+    void alloc(bfq_ctx *c, size_t bytes, const char *what) { if (!tryAlloc(c, bytes)) throw BfqError{BFQ_E_NOMEM, std::string("device buffer for ") + what}; }
     void free() { if (p) (void)hipFree(p); p = nullptr; }
     char *release() { char *q = p; p = nullptr; return q; }   // to another owner
 };

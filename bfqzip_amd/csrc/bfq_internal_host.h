@@ -37,6 +37,8 @@ struct BfqEnv {
     unsigned long long compactWin = 0;  // BFQ_COMPACT_WIN: rows of the LCP file in flight there (default 64 Mi; small values test the windowing)
     bool prefaultPause = false;     // BFQ_PREFAULT_PAUSE=1: output files are not allocated while an input file is being read (default: both at once)
     unsigned long long bgzfBatch = 0;   // BFQ_BGZF_BATCH: text bytes per batch of the BGZF writer (rounded down to whole members of 65 280; 0: chosen from the arena)
+    int poison = -1;                // BFQ_POISON=<byte> (decimal or 0x.., 0-255): the arena is filled with it whenever a call starts over in it, every other
+                                    // device allocation once when it is made (test knob: what a call must not read before it writes); unset: nothing is filled
     bool noOutmap = false;          // BFQ_NO_OUTMAP: the tools write their outputs with pwrite instead of through a mapping (test knob)
 };
 BfqEnv bfq_env_read();

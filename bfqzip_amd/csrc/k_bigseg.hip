@@ -189,7 +189,7 @@ void bfq_refine_huge(bfq_ctx *c, SortRec rec, const u64 *text3, u64 n, u16 *lcp,
         size_t want = fixed + (size_t)std::min<u64>(hc[1], 1ull << 31) * HUGE_BYTES_PER_SLOT;
         size_t most = freeB - freeB / 8;
         if (want > most) want = most;
-        if (slots(want) > cap && side.tryAlloc(want)) {
+        if (slots(want) > cap && side.tryAlloc(c, want)) {
             inSide.emplace(c, side.p, want);
             cap = slots(want);
         }

@@ -330,7 +330,7 @@ struct DqMem {
         const u64 bytes = count * sizeof(Tp) + 256;
         if (c->ws.room() >= bytes + 512) return c->alloc<Tp>(count);
         void *p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); throw BfqError{BFQ_E_NOMEM, "stream codec: no device memory for the context table"}; }
+        if (!bfq_dev_malloc(c, &p, bytes)) throw BfqError{BFQ_E_NOMEM, "stream codec: no device memory for the context table"};
         own.push_back(p);
         return (Tp *)p;
     }

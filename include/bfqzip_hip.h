@@ -949,6 +949,11 @@ int     bfq_prof_trace_select(bfq_ctx *c, int idx);
 int64_t bfq_prof_trace(bfq_ctx *c, float *ms, uint64_t cap);
 
 uint64_t bfq_workspace_bytes(bfq_ctx *c);      /* current device workspace size */
+/* Test hook: waits for the context's stream and copies the workspace's bytes [off, off + len) to dst (host memory), cut at the
+   workspace's end.  Returns the number of bytes copied.  With BFQ_POISON=<byte> in the environment (read by bfq_create and
+   bfq_set_params) the workspace holds that byte everywhere whenever a call starts over in it, and every other device
+   allocation of the library holds it when it is made: what a call reads before it has written it is then not zero. */
+uint64_t bfq_workspace_read(bfq_ctx *c, uint64_t off, void *dst, uint64_t len);
 const char *bfq_version(void);
 
 #ifdef __cplusplus

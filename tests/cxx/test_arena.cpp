@@ -10,6 +10,12 @@ static int g_fail = 0;
 
 struct FakeCtx {
     Arena ws;
+    int syncs = 0, fills = 0;
+    void quiesce() { syncs++; }
+    void poisonWs() { fills++; }                                       // told of every buffer that is lent as the arena
+};
+struct BareCtx {
+    Arena ws;
     int syncs = 0;
     void quiesce() { syncs++; }
 };
@@ -68,9 +74,9 @@ int main()
         ScopedArenaT<FakeCtx> g(&c, other, 4096);
         CHECK(c.ws.base == other && c.ws.cap == 4096 && c.ws.top == 0);
         CHECK((char *)c.ws.alloc(100) == other);
-        CHECK(c.syncs == 0);
+        CHECK(c.syncs == 0 && c.fills == 1);
     }
-    CHECK(same(c.ws, own) && c.syncs == 1);
+    CHECK(same(c.ws, own) && c.syncs == 1 && c.fills == 1);             // ... and not of the one that comes back
     // ... at an early restore(), once,
     {
         ScopedArenaT<FakeCtx> g(&c, other, 4096);
@@ -92,8 +98,16 @@ int main()
     } catch (const BfqError &e) {
         seen = e.code == BFQ_E_NOMEM && same(c.ws, own) && c.syncs == 3;
     }
-    CHECK(seen);
+    CHECK(seen && c.fills == 3);
     CHECK(c.ws.peak >= own.peak);                                      // the high-water mark carries over
+    // a context without poisonWs() is lent a buffer all the same
+    BareCtx bare;
+    bare.ws = a;
+    {
+        ScopedArenaT<BareCtx> g(&bare, other, 4096);
+        CHECK(bare.ws.base == other && (char *)bare.ws.alloc(100) == other && bare.syncs == 0);
+    }
+    CHECK(same(bare.ws, a) && bare.syncs == 1);
 
     free(buf); free(other);
     if (g_fail) { printf("%d checks failed\n", g_fail); return 1; }

@@ -96,6 +96,41 @@ def test_arena_host(tmp_path):
     assert r.returncode == 0, r.stdout.decode()[-2000:]
 
 
+def test_device_allocations_go_through_one_helper():
+    """BFQ_POISON fills what the library allocates on the device: the arena whenever a call starts over in it, everything
+    else in bfq_dev_malloc() (bfq_internal.h).  A hipMalloc anywhere else would dodge the fill: the only calls are the
+    helper's and the arena's own two (bfq_ctx::reserveBegin and bfq_ctx::reserve, bfq_api.hip)."""
+    csrc = os.path.join(ROOT, "bfqzip_amd", "csrc")
+
+    def code(path):
+        text = open(path).read()
+        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+        return re.sub(r"//[^\n]*", "", text)
+
+    def body(text, header):
+        """the function whose definition begins with `header`, down to the closing brace in column 0"""
+        at = text.index(header)
+        return text[at:text.index("\n}", at)]
+
+    allowed = {"bfq_internal.h": ["static inline bool bfq_dev_malloc("], "bfq_api.hip": ["void bfq_ctx::reserveBegin(", "void bfq_ctx::reserve("]}
+    sources = [os.path.join(folder, f) for folder, _, files in os.walk(csrc) for f in sorted(files) if f.endswith((".h", ".hip", ".cpp", ".hpp", ".c"))]
+    assert len(sources) > 60
+    seen = 0
+    for path in sources:
+        text, f = code(path), os.path.basename(path)
+        total = len(re.findall(r"\bhipMalloc\s*\(", text))
+        inside = 0
+        for header in allowed.get(f, []) if os.path.dirname(path) == csrc else []:
+            n = len(re.findall(r"\bhipMalloc\s*\(", body(text, header)))
+            assert n == 1, (f, header, n)
+            inside += n
+        assert total == inside, "%s: %d hipMalloc call(s) outside bfq_dev_malloc() and the arena" % (os.path.relpath(path, ROOT), total - inside)
+        for name in ("hipMallocAsync", "hipMallocManaged", "hipExtMallocWithFlags", "hipMallocPitch", "hipMalloc3D", "hipMemPoolCreate"):   # no side doors
+            assert name not in text, (f, name)
+        seen += inside
+    assert seen == 3
+
+
 # ---- per-GPU lease of the one-shot tools (bfq_device_lease: host only, no GPU needed).  BFQzip_parallel.py:277-285
 # starts n concurrent children; each must end up on a GPU of its own, and never two on one.
 _LEASE_CHILD = r"""
