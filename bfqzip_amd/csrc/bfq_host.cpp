@@ -59,6 +59,7 @@ BfqEnv bfq_env_read()
         e.noLengthGuess = getenv("BFQ_NO_LENGTH_GUESS") != nullptr;
         e.posMode = geti("BFQ_POSMODE", 0) != 0;
         e.posBins = geti("BFQ_POSBINS", 1) != 0;
+        e.posBinWc = geti("BFQ_POSBIN_WC", 1) != 0;
         e.fuseKeys = geti("BFQ_FUSEKEYS", 1) != 0;
         e.ioThreads = geti("BFQ_IO_THREADS", 0);
         e.prefaultThreads = geti("BFQ_PREFAULT_THREADS", -1);

@@ -21,6 +21,7 @@ struct BfqEnv {
     bool noLengthGuess = false;     // BFQ_NO_LENGTH_GUESS: always count read lengths by LF walks
     bool posMode = false;           // BFQ_POSMODE=1: steps 3-4 without LF table (position mode)
     bool posBins = true;            // BFQ_POSBINS=0: the device-resident fused path inverts by LF walks again (A/B runs)
+    bool posBinWc = true;           // BFQ_POSBIN_WC=0: the position bins write per-tile runs at the bin's cursor again, not whole 64-byte chunks (A/B runs)
     bool fuseKeys = true;           // BFQ_FUSEKEYS=0: step 1 in one piece writes the sort records with k_build_keys and streams all five passes again (A/B runs)
     int ioThreads = 0;              // BFQ_IO_THREADS: staging workers (0: by core count)
     int prefaultThreads = -1;       // BFQ_PREFAULT_THREADS: helpers that fault in output mappings (-1: by core count)

@@ -32,6 +32,18 @@ BFQ_HD u64 bfq_posbin_cap(u64 n, int shift, u64 b)
 // the window | code << 15 | quality << 18 (4 bytes)
 BFQ_HD u32 bfq_posbin_rec4(u64 v) { return (u32)(bfq_val_pos(v) & (BFQ_PB_W - 1u)) | (bfq_val_code(v) << BFQ_PB_WSHIFT) | (bfq_val_qual(v) << (BFQ_PB_WSHIFT + 3)); }
 
+// Write-combining (k_posbin_l1_wc; both levels in profiles/microbench/partition_wc.hip): a workgroup carries every bin's
+// incomplete tail from tile to tile and writes whole 64-byte chunks only.  A bin is filled from both ends: whole chunks go up from its base through the head cursor (every claim
+// is a multiple of the chunk, the base is one, so every chunk is aligned), the tails a workgroup is left with go down from the
+// bin's end through the tail cursor.  Bin sizes are exact, so the two regions meet: head + tail = capacity afterwards.
+#define BFQ_PB_CHUNK_BYTES 64u
+BFQ_HD u32 bfq_posbin_chunk(int level) { return BFQ_PB_CHUNK_BYTES / (level == 1 ? 8u : 4u); }     // records per chunk
+// a bin holds `carried` records of the tail and gets `fresh` ones from the tile: records flushed to the head / kept as the tail
+BFQ_HD u32 bfq_posbin_head_claim(u32 carried, u32 fresh, u32 chunk) { return (carried + fresh) / chunk * chunk; }
+BFQ_HD u32 bfq_posbin_tail_kept(u32 carried, u32 fresh, u32 chunk) { return (carried + fresh) % chunk; }
+// slot inside a bin of cap records of the idx-th record the tail cursor handed out (idx < cap)
+BFQ_HD u64 bfq_posbin_tail_slot(u64 cap, u64 idx) { return cap - 1 - idx; }
+
 // Terminated-text coordinates: read i stands at roff[i] + i, its terminator at roff[i + 1] + i.  Number of terminators
 // strictly before position q = index of the read q lies in (a terminator belongs to the read it ends); q - that = where
 // q's symbol goes when the reads are written back to back.

@@ -13,7 +13,8 @@
 // Bin sizes are exact (every position occurs once), so there is no counting pass: a workgroup ranks a tile's records by bin
 // in LDS, takes one atomicAdd per non-empty bin on the bin's global cursor and writes the runs through LDS staging.  Order
 // inside a bin is free.  Every store is checked against the bin's capacity: rows that do not form a permutation of the
-// positions are counted in errInvert instead of being written anywhere.
+// positions are counted in errInvert instead of being written anywhere.  Level 1, whose bins lie far apart, writes whole
+// 64-byte chunks instead of the tile's runs (k_posbin_l1_wc below; BFQ_POSBIN_WC=0: the runs, for A/B runs).
 #include <type_traits>
 #include "bfq_internal.h"
 #include "bfq_device.h"
@@ -27,7 +28,52 @@
 static_assert(BFQ_PB_W % PB_TILE == 0, "a tile lies inside one level-1 bin");
 static_assert(BFQ_PB_MAX_BINS == 2 * PB_THREADS, "two bins per thread in the tile scan");
 
-// LEVEL 1: in = the sorted records' (w1, w2) words, out = u64 records; LEVEL 2: in = level 1's records, out = u32 records
+// level 1's record of a row: x = the sorted record's (w1, w2) words, rp / q = the row's edit bytes
+__device__ __forceinline__ u64 pb_l1_value(u64 x, u32 rp, u32 q, int B, u64 n)
+{
+    const u64 pay = bfq_rec_pay((u32)x, (u32)(x >> 32));
+    const u64 p = bfq_val_pos(pay);                                 // the row's suffix starts at p: its eBWT symbol is text[p - 1]
+    const u32 code = rp ? bfq_base_code((u8)rp) : bfq_val_code(pay);
+    if (B) q = bfq_bin8(q);
+    return bfq_pack_val(p ? p - 1 : n - 1, code & 7u, q);
+}
+
+// LEVEL 1: in = the sorted records' (w1, w2) words, out = u64 records; LEVEL 2: in = level 1's records, out = u32 records.
+// A tile's records into registers: v = the record, lb = its bin relative to binBase (0xFFFF: not to be written, counted in
+// errInvert where it is a live row), rk = its rank among the tile's records of that bin (lcnt: zeroed, a barrier ago)
+template <int LEVEL>
+__device__ __forceinline__ void pb_load_rank(const u64 *__restrict__ in, const u8 *__restrict__ repl, const u8 *__restrict__ editQual, int B, u64 n,
+                                             u64 tbase, u64 binBase, int shiftOut, u32 *lcnt, DevCounters *cnt, u64 (&v)[PB_ITEMS],
+                                             u32 (&lb)[PB_ITEMS], u32 (&rk)[PB_ITEMS])
+{
+    const u32 tid = threadIdx.x;
+    // the arrays are padded by 16 entries and more: a vector load that starts inside them stays inside them
+#pragma unroll
+    for (int r = 0; r < PB_ROUNDS; r++) {
+        const u64 j = tbase + (u64)(r * PB_THREADS + tid) * 4;
+        uint4 a = {0, 0, 0, 0}, b = {0, 0, 0, 0};
+        u32 rp4 = 0, eq4 = 0;
+        if (j < n) {
+            a = *(const uint4 *)(in + j); b = *(const uint4 *)(in + j + 2);
+            if (LEVEL == 1) { rp4 = *(const u32 *)(repl + j); eq4 = *(const u32 *)(editQual + j); }
+        }
+        const u64 x[4] = {((u64)a.y << 32) | a.x, ((u64)a.w << 32) | a.z, ((u64)b.y << 32) | b.x, ((u64)b.w << 32) | b.z};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const u64 val = LEVEL == 1 ? pb_l1_value(x[k], (rp4 >> (8 * k)) & 0xFFu, (eq4 >> (8 * k)) & 0xFFu, B, n) : x[k];
+            const u64 pos = bfq_val_pos(val);
+            const u64 l = (pos >> shiftOut) - binBase;            // (a bin below binBase wraps to a huge value)
+            const bool live = j + k < n;
+            const bool ok = live && pos < n && l < (u64)BFQ_PB_MAX_BINS;
+            if (live && !ok) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
+            v[r * 4 + k] = val;
+            lb[r * 4 + k] = ok ? (u32)l : 0xFFFFu;
+            rk[r * 4 + k] = ok ? atomicAdd(&lcnt[l], 1u) : 0u;
+        }
+    }
+}
+
+// per-tile runs at the bin's cursor (BFQ_POSBIN_WC=0)
 template <int LEVEL>
 __global__ __launch_bounds__(PB_THREADS) void k_posbin_part(const u64 *__restrict__ in, const u8 *__restrict__ repl, const u8 *__restrict__ editQual,
                                                              int B, u64 n, int shiftIn, int shiftOut, u32 *__restrict__ cursor, u32 curStride,
@@ -49,39 +95,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_posbin_part(const u64 *__restric
 
         u64 v[PB_ITEMS];
         u32 lb[PB_ITEMS], rk[PB_ITEMS];
-        // the arrays are padded by 16 entries and more: a vector load that starts inside them stays inside them
-#pragma unroll
-        for (int r = 0; r < PB_ROUNDS; r++) {
-            const u64 j = tbase + (u64)(r * PB_THREADS + tid) * 4;
-            uint4 a = {0, 0, 0, 0}, b = {0, 0, 0, 0};
-            u32 rp4 = 0, eq4 = 0;
-            if (j < n) {
-                a = *(const uint4 *)(in + j); b = *(const uint4 *)(in + j + 2);
-                if (LEVEL == 1) { rp4 = *(const u32 *)(repl + j); eq4 = *(const u32 *)(editQual + j); }
-            }
-            const u64 x[4] = {((u64)a.y << 32) | a.x, ((u64)a.w << 32) | a.z, ((u64)b.y << 32) | b.x, ((u64)b.w << 32) | b.z};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                u64 val = x[k];
-                if (LEVEL == 1) {
-                    const u64 pay = bfq_rec_pay((u32)x[k], (u32)(x[k] >> 32));
-                    const u64 p = bfq_val_pos(pay);                     // the row's suffix starts at p: its eBWT symbol is text[p - 1]
-                    const u32 rp = (rp4 >> (8 * k)) & 0xFFu;
-                    const u32 code = rp ? bfq_base_code((u8)rp) : bfq_val_code(pay);
-                    u32 q = (eq4 >> (8 * k)) & 0xFFu;
-                    if (B) q = bfq_bin8(q);
-                    val = bfq_pack_val(p ? p - 1 : n - 1, code & 7u, q);
-                }
-                const u64 pos = bfq_val_pos(val);
-                const u64 l = (pos >> shiftOut) - binBase;            // (a bin below binBase wraps to a huge value)
-                const bool live = j + k < n;
-                const bool ok = live && pos < n && l < (u64)BFQ_PB_MAX_BINS;
-                if (live && !ok) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
-                v[r * 4 + k] = val;
-                lb[r * 4 + k] = ok ? (u32)l : 0xFFFFu;
-                rk[r * 4 + k] = ok ? atomicAdd(&lcnt[l], 1u) : 0u;
-            }
-        }
+        pb_load_rank<LEVEL>(in, repl, editQual, B, n, tbase, binBase, shiftOut, lcnt, cnt, v, lb, rk);
         __syncthreads();
 
         // thread t: bins 2 t and 2 t + 1 -- where they start in the staged tile, and their runs' places in the global bins
@@ -111,6 +125,154 @@ __global__ __launch_bounds__(PB_THREADS) void k_posbin_part(const u64 *__restric
         }
         __syncthreads();
     }
+}
+
+// Level 1 in whole 64-byte chunks (the default; geometry and cursors: bfq_posbin.h).  The workgroup -- 512 threads, one per
+// bin, 8 records per thread and tile -- keeps every bin's incomplete tail (below C = 8 records) in LDS from tile to tile:
+// left[t * PB_LS + b] is the tail's t-th record of bin b, thread b holds its length in a register.  Per tile a bin's sequence
+// is its tail followed by the tile's records in rank order; the whole chunks of it are claimed on the head cursor and written
+// by groups of C consecutive lanes, the rest is the new tail.  When the workgroup is done, the tails go to the ends of their
+// bins through the downward tail cursor.  The next tile's loads are issued before this tile's LDS work.
+// (Level 2 keeps the runs: its windows lie close together and whole chunks gained nothing there -- DESIGN section 4.)
+#define PW_THREADS 512
+#define PW_ROUNDS (PB_TILE / PW_THREADS / 4)
+#define PW_ITEMS (PW_ROUNDS * 4)
+#define PW_C 8                                      // records per chunk (bfq_posbin_chunk(1))
+#define PB_LS (BFQ_PB_MAX_BINS + 1)                 // (odd stride: a chunk's lanes read its tail records from different banks)
+#define PW_MAXCHUNKS ((PB_TILE + BFQ_PB_MAX_BINS * (PW_C - 1)) / PW_C)
+static_assert(BFQ_PB_MAX_BINS == PW_THREADS && PW_C * 8 == BFQ_PB_CHUNK_BYTES && PW_THREADS % PW_C == 0, "one bin per thread, a chunk by C consecutive lanes");
+
+struct PwRaw { uint4 a[PW_ROUNDS], b[PW_ROUNDS]; u32 rp4[PW_ROUNDS], eq4[PW_ROUNDS]; };
+__device__ __forceinline__ void pw_load(const u64 *__restrict__ in, const u8 *__restrict__ repl, const u8 *__restrict__ editQual, u64 n, u64 tbase, PwRaw &raw)
+{
+    // the arrays are padded by 16 entries and more: a vector load that starts inside them stays inside them
+#pragma unroll
+    for (int r = 0; r < PW_ROUNDS; r++) {
+        const u64 j = tbase + (u64)(r * PW_THREADS + threadIdx.x) * 4;
+        raw.a[r] = raw.b[r] = uint4{0, 0, 0, 0}; raw.rp4[r] = raw.eq4[r] = 0;
+        if (j < n) { raw.a[r] = *(const uint4 *)(in + j); raw.b[r] = *(const uint4 *)(in + j + 2); raw.rp4[r] = *(const u32 *)(repl + j); raw.eq4[r] = *(const u32 *)(editQual + j); }
+    }
+}
+// exclusive scan over the 512 threads; sh holds 8 entries; two barriers
+__device__ __forceinline__ u32 pw_block_exscan32(u32 v, u32 *sh, u32 *total)
+{
+    const u32 lane = bfq_lane(), w = threadIdx.x >> 6;
+    const u32 inc = bfq_wave_incscan32(v);
+    if (lane == 63) sh[w] = inc;
+    __syncthreads();
+    u32 base = 0, tot = 0;
+#pragma unroll
+    for (u32 k = 0; k < PW_THREADS / 64; k++) { const u32 t = sh[k]; base += k < w ? t : 0u; tot += t; }
+    *total = tot;
+    __syncthreads();
+    return base + inc - v;
+}
+__device__ __forceinline__ void pw_tail_out(const u64 *left, u32 b, u32 nl, u64 n, int shiftOut, u32 *tailCur, u64 *out, DevCounters *cnt)
+{
+    if (!nl) return;
+    const u64 cap = bfq_posbin_cap(n, shiftOut, b);
+    const u64 s = atomicAdd(tailCur, nl);
+    for (u32 t = 0; t < nl; t++) {
+        if (s + t < cap) out[((u64)b << shiftOut) + bfq_posbin_tail_slot(cap, s + t)] = left[t * PB_LS + b];
+        else atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
+    }
+}
+
+// (two workgroups per CU -- 72 KiB of LDS each -- are four waves per SIMD: 128 VGPRs)
+__global__ __launch_bounds__(PW_THREADS, 4) void k_posbin_l1_wc(const u64 *__restrict__ in, const u8 *__restrict__ repl, const u8 *__restrict__ editQual, int B, u64 n,
+                                                                int shiftOut, u32 *__restrict__ cursor, u64 *__restrict__ out, u64 ntiles, DevCounters *cnt)
+{
+    constexpr u32 C = PW_C;
+    __shared__ u64 stage[PB_TILE];
+    __shared__ u64 left[(C - 1) * PB_LS];
+    // per bin and tile: lcnt = records; pk0 = start in the staged tile | first chunk << 16; pk1 = tail carried in | whole chunks << 16;
+    // gb = what the head cursor gave; cbin = the bin of every chunk
+    __shared__ u32 lcnt[BFQ_PB_MAX_BINS], pk0[BFQ_PB_MAX_BINS], pk1[BFQ_PB_MAX_BINS], gb[BFQ_PB_MAX_BINS];
+    __shared__ u16 cbin[PW_MAXCHUNKS];
+    __shared__ u32 sh[PW_THREADS / 64];
+    const u32 tid = threadIdx.x;
+    u32 *const head = cursor + (u64)tid * PB_CUR_STRIDE, *const tail = head + 1;     // bin tid's cursors: one 64-byte line
+    u32 nl = 0;                                     // tail of bin tid
+    PwRaw raw;
+    if (blockIdx.x < ntiles) pw_load(in, repl, editQual, n, (u64)blockIdx.x * PB_TILE, raw);
+
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const u64 tbase = tile * PB_TILE;
+        lcnt[tid] = 0;
+        __syncthreads();
+
+        u64 v[PW_ITEMS];
+        u32 lb[PW_ITEMS], rk[PW_ITEMS];
+#pragma unroll
+        for (int r = 0; r < PW_ROUNDS; r++) {
+            const u64 j = tbase + (u64)(r * PW_THREADS + tid) * 4;
+            const uint4 a = raw.a[r], b = raw.b[r];
+            const u64 x[4] = {((u64)a.y << 32) | a.x, ((u64)a.w << 32) | a.z, ((u64)b.y << 32) | b.x, ((u64)b.w << 32) | b.z};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const u64 val = pb_l1_value(x[k], (raw.rp4[r] >> (8 * k)) & 0xFFu, (raw.eq4[r] >> (8 * k)) & 0xFFu, B, n);
+                const u64 pos = bfq_val_pos(val);
+                const u64 l = pos >> shiftOut;
+                const bool live = j + k < n;
+                const bool ok = live && pos < n && l < (u64)BFQ_PB_MAX_BINS;
+                if (live && !ok) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
+                v[r * 4 + k] = val;
+                lb[r * 4 + k] = ok ? (u32)l : 0xFFFFu;
+                rk[r * 4 + k] = ok ? atomicAdd(&lcnt[l], 1u) : 0u;
+            }
+        }
+        if (tile + gridDim.x < ntiles) pw_load(in, repl, editQual, n, (tile + gridDim.x) * PB_TILE, raw);
+        __syncthreads();
+
+        // thread b: where bin b starts in the staged tile, its whole chunks and their place in the global bin
+        const u32 c = lcnt[tid];
+        const u32 h = bfq_posbin_head_claim(nl, c, C), f = h / C;
+        u32 totals;                                 // (records: at most 4096, chunks: fewer -- one scan for both)
+        const u32 ex = pw_block_exscan32(c | (f << 16), sh, &totals);
+        const u32 nchunks = totals >> 16;
+        pk0[tid] = ex; pk1[tid] = nl | (f << 16);
+        if (f) gb[tid] = atomicAdd(head, h);
+        __syncthreads();
+
+        // every chunk has exactly one tile record that names its bin: the one that opens it or, in a chunk the tail opens, rank 0
+#pragma unroll
+        for (int i = 0; i < PW_ITEMS; i++) {
+            if (lb[i] == 0xFFFFu) continue;
+            const u32 p0 = pk0[lb[i]], p1 = pk1[lb[i]];
+            stage[(p0 & 0xFFFFu) + rk[i]] = v[i];
+            const u32 ci = (p1 & 0xFFFFu) + rk[i], ch = ci / C;
+            if (ch < (p1 >> 16) && (ci % C == 0 || rk[i] == 0)) cbin[(p0 >> 16) + ch] = (u16)lb[i];
+        }
+        __syncthreads();
+
+        for (u32 e = tid; e < nchunks * C; e += PW_THREADS) {
+            const u32 ch = e / C, l = cbin[ch];
+            const u32 p0 = pk0[l], carried = pk1[l] & 0xFFFFu;
+            const u32 ci = (ch - (p0 >> 16)) * C + e % C;
+            const u64 rec = ci < carried ? left[ci * PB_LS + l] : stage[(p0 & 0xFFFFu) + ci - carried];
+            const u64 off = (u64)gb[l] + ci;
+            if (off < bfq_posbin_cap(n, shiftOut, l)) out[((u64)l << shiftOut) + off] = rec;
+            else atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
+        }
+        __syncthreads();
+
+        // the new tail: what a bin without a whole chunk carried stays where it is, the tile's records follow it
+        {
+            const u32 r = bfq_posbin_tail_kept(nl, c, C);
+            const u32 s0 = (ex & 0xFFFFu) + h - nl;                     // stage index of the new tail's slot 0
+            for (u32 t = f ? 0u : nl; t < r; t++) left[t * PB_LS + tid] = stage[s0 + t];
+            nl = r;
+        }
+    }
+    pw_tail_out(left, tid, nl, n, shiftOut, tail, out, cnt);
+}
+
+// after level 1: head and tail regions tile every bin exactly (stores beyond a bin's capacity were dropped and counted
+// where they were tried; two regions that overlap inside it show here)
+__global__ void k_posbin_check(const u32 *__restrict__ cursor, u64 nbins, u64 n, int shift, DevCounters *cnt)
+{
+    const u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < nbins && (u64)cursor[b * PB_CUR_STRIDE] + cursor[b * PB_CUR_STRIDE + 1] != bfq_posbin_cap(n, shift, b)) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
 }
 
 #define PA_THREADS 512
@@ -195,6 +357,16 @@ __global__ __launch_bounds__(PA_THREADS, 4) void k_posbin_apply(const u32 *__res
     }
 }
 
+// workgroups of `kernel` that run at once (at most one per tile)
+static unsigned pb_resident(bfq_ctx *c, const void *kernel, int threads, u64 ntiles)
+{
+    int perCu = 0, cus = 0;
+    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kernel, threads, 0));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    const u64 g = (u64)(perCu > 0 ? perCu : 1) * (u64)(cus > 0 ? cus : 1);
+    return (unsigned)(ntiles < g ? ntiles : g);
+}
+
 // the arena bytes bfq_posbins() takes beside what the caller holds (level-1 records, cursors)
 size_t bfq_posbins_need(u64 n)
 {
@@ -213,12 +385,22 @@ void bfq_posbins(bfq_ctx *c, u64 *w12, const u8 *repl, const u8 *editQual, u64 n
     const size_t mk = c->mark();
     const u64 nb1 = bfq_posbin_bins(n, s1), nwin = bfq_posbin_bins(n, BFQ_PB_WSHIFT), ntiles = ceil_div(n, PB_TILE);
     u64 *rec8 = c->alloc<u64>(n + 16);
+    // level 1: head and tail cursor of a bin share its 64-byte line
     u32 *cur = c->alloc<u32>(nb1 * PB_CUR_STRIDE + nwin + 64), *cur2 = cur + nb1 * PB_CUR_STRIDE;
     u32 *rec4 = (u32 *)w12;
     HIP_CHECK(hipMemsetAsync(cur, 0, 4 * (nb1 * PB_CUR_STRIDE + nwin), c->stream));
     const unsigned grid = (unsigned)(ntiles > BFQ_MAX_GRID ? BFQ_MAX_GRID : ntiles);
-    KLAUNCH(c, K_POSBIN_L1, 18.0 * (double)n, k_posbin_part<1>, grid, PB_THREADS, (const u64 *)w12, repl, editQual, B, n, 0, s1, cur,
-            (u32)PB_CUR_STRIDE, (void *)rec8, ntiles, c->d_cnt);
+    if (c->env.posBinWc) {
+        // whole chunks are aligned when the array is: bin bases and head claims are multiples of the chunk
+        if ((uintptr_t)rec8 & (BFQ_PB_CHUNK_BYTES - 1)) throw BfqError{BFQ_E_ARG, "position bins: record array not 64-byte aligned"};
+        // as many workgroups as run at once: a workgroup's tails are written once, at its end
+        KLAUNCH(c, K_POSBIN_L1, 18.0 * (double)n, k_posbin_l1_wc, pb_resident(c, (const void *)k_posbin_l1_wc, PW_THREADS, ntiles), PW_THREADS, (const u64 *)w12, repl,
+                editQual, B, n, s1, cur, rec8, ntiles, c->d_cnt);
+        KLAUNCH(c, K_POSBIN_CHECK, 8.0 * (double)nb1, k_posbin_check, bfq_grid(nb1, 256), 256, (const u32 *)cur, nb1, n, s1, c->d_cnt);
+    } else {
+        KLAUNCH(c, K_POSBIN_L1, 18.0 * (double)n, k_posbin_part<1>, grid, PB_THREADS, (const u64 *)w12, repl, editQual, B, n, 0, s1, cur,
+                (u32)PB_CUR_STRIDE, (void *)rec8, ntiles, c->d_cnt);
+    }
     KLAUNCH(c, K_POSBIN_L2, 12.0 * (double)n, k_posbin_part<2>, grid, PB_THREADS, (const u64 *)rec8, (const u8 *)nullptr, (const u8 *)nullptr, 0, n, s1,
             (int)BFQ_PB_WSHIFT, cur2, 1u, (void *)rec4, ntiles, c->d_cnt);
     const unsigned agrid = (unsigned)(nwin > BFQ_MAX_GRID ? BFQ_MAX_GRID : nwin);
