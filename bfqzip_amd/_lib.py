@@ -120,6 +120,25 @@ class BamStats(C.Structure):
         return "BamStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
 
 
+class BamTagStats(C.Structure):
+    """bfq_bam_tag_stats: tags_written, tags_dropped, tag_bytes (of text)"""
+    _fields_ = [(k, C.c_uint64) for k in ("tags_written", "tags_dropped", "tag_bytes")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "BamTagStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
+
+
+BAM_OPTS_TAGS = 0x31474154                                         # BFQ_BAM_OPTS_TAGS: o.reserved of a BamTagOpts
+
+
+class BamTagOpts(C.Structure):
+    """bfq_bam_tag_opts: o (a BamOpts whose reserved holds BAM_OPTS_TAGS), n_tags (0: every tag), strict, tag[32][2], stats"""
+    _fields_ = [("o", BamOpts), ("n_tags", C.c_uint32), ("strict", C.c_uint32), ("tag", (C.c_uint8 * 2) * 32), ("stats", C.POINTER(BamTagStats))]
+
+
 class BamPatchStats(C.Structure):
     """bfq_bam_patch_stats: records of the file, patched[3], skipped, reversed, reads_changed, bases_changed, quals_changed, unknown_bases,
     kept_high_quals, kept_absent, raw_len, pieces, repaired"""
@@ -150,6 +169,25 @@ class UbamStats(C.Structure):
 
     def __repr__(self):
         return "UbamStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
+
+
+class UbamTagStats(C.Structure):
+    """bfq_ubam_tag_stats: tags_written, fields_dropped, tag_bytes (of stream)"""
+    _fields_ = [(k, C.c_uint64) for k in ("tags_written", "fields_dropped", "tag_bytes")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "UbamTagStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
+
+
+UBAM_OPTS_TAGS = 0x32474154                                        # BFQ_UBAM_OPTS_TAGS: o.reserved of a UbamTagOpts
+
+
+class UbamTagOpts(C.Structure):
+    """bfq_ubam_tag_opts: o (a UbamOpts whose reserved holds UBAM_OPTS_TAGS), n_tags (0: every field), pad, tag[32][2], stats"""
+    _fields_ = [("o", UbamOpts), ("n_tags", C.c_uint32), ("pad", C.c_uint32), ("tag", (C.c_uint8 * 2) * 32), ("stats", C.POINTER(UbamTagStats))]
 
 
 CMP_SYMS = 6
@@ -331,9 +369,10 @@ def lib():
         L.bfq_gzip_inflate_host.argtypes = [vp, u64, u64, vp, u64, pu64, pgs]
         L.bfq_gzip_host_error.restype = C.c_char_p
         L.bfq_gzip_host_error.argtypes = []
-        pbo, pbs, a3 = C.POINTER(BamOpts), C.POINTER(BamStats), C.POINTER(u64)
+        # the options go by address: a BamOpts, or the BamTagOpts / UbamTagOpts that begins with one
+        pbo, pbs, a3 = vp, C.POINTER(BamStats), C.POINTER(u64)
         L.bfq_bam_default_opts.restype = None
-        L.bfq_bam_default_opts.argtypes = [pbo]
+        L.bfq_bam_default_opts.argtypes = [C.POINTER(BamOpts)]
         L.bfq_bam_probe.argtypes = [vp, u64]
         L.bfq_bam_measure.argtypes = [vp, vp, u64, pbo, a3, a3, pbs]
         L.bfq_bam_to_fastq.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, a3, a3, pbs]
@@ -347,9 +386,9 @@ def lib():
         L.bfq_bam_patch_device.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, vp, u64, pu64, pps]
         L.bfq_bam_patch.argtypes = [vp, vp, u64, pbo, C.POINTER(vp), a3, C.c_int, vp, u64, pu64, pps]
         L.bfq_bam_patch_fd.argtypes = [vp, C.c_int, u64, pbo, i3, C.c_int, C.c_int, pu64, pps]
-        puo, pus = C.POINTER(UbamOpts), C.POINTER(UbamStats)
+        puo, pus = vp, C.POINTER(UbamStats)
         L.bfq_ubam_default_opts.restype = None
-        L.bfq_ubam_default_opts.argtypes = [puo]
+        L.bfq_ubam_default_opts.argtypes = [C.POINTER(UbamOpts)]
         L.bfq_ubam_host_error.restype = C.c_char_p
         L.bfq_ubam_host_error.argtypes = []
         L.bfq_fastq_to_bam_measure.argtypes = [vp, C.POINTER(vp), a3, puo, pu64, a3, pus]

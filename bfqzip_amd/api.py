@@ -262,8 +262,35 @@ def gzip_inflate_host(blob, chunk=0, out=None):
     return out[:int(ol.value)], st
 
 
-def bam_opts(exclude_flags=0x900, mate_suffix=1, default_qual=1, split=0, paired_check=0, piece=0, check_names=0):
-    """bfq_bam_opts (include/bfqzip_hip.h); the defaults are bfq_bam_default_opts'.  check_names: bam_patch* only."""
+def _tag_list(tags, what):
+    """the keys of a tag selection: "*" -> [] (every tag), "BC,RX" / b"BC,RX" / a sequence of keys -> [b"BC", b"RX"]"""
+    if isinstance(tags, (str, bytes)):
+        tags = [] if tags in ("*", b"*") else tags.split("," if isinstance(tags, str) else b",")
+    keys = [t.encode() if isinstance(t, str) else bytes(t) for t in tags]
+    if len(keys) > 32 or any(len(k) != 2 for k in keys):
+        raise ValueError("%s: tags: '*', or at most 32 two-byte tags" % what)
+    return keys
+
+
+def _tag_ext(x, keys, stats):
+    x.n_tags = len(keys)
+    for j, k in enumerate(keys):
+        x.tag[j][0], x.tag[j][1] = k[0], k[1]
+    x.stats = C.pointer(stats)
+    x.tag_stats = stats                                            # (kept alive with the options; the call fills it)
+    return x
+
+
+def bam_opts(exclude_flags=0x900, mate_suffix=1, default_qual=1, split=0, paired_check=0, piece=0, check_names=0, tags=None, strict_tags=0):
+    """bfq_bam_opts (include/bfqzip_hip.h); the defaults are bfq_bam_default_opts'.  check_names: bam_patch* only.
+    tags: None, or "*" (every aux tag) or "BC,RX" (those) into the header lines as \\tXX:T:value -- then a bfq_bam_tag_opts
+    comes back, whose .tag_stats (a BamTagStats: tags_written, tags_dropped, tag_bytes) the call fills; the entry points hand
+    it on as stats.tags.  strict_tags: refuse a selected tag that cannot be carried instead of leaving it out."""
+    if tags is not None:
+        x = _tag_ext(_lib.BamTagOpts(), _tag_list(tags, "bam_opts"), _lib.BamTagStats())
+        x.o = bam_opts(exclude_flags, mate_suffix, default_qual, split, paired_check, piece, check_names)
+        x.o.reserved, x.strict = _lib.BAM_OPTS_TAGS, int(strict_tags)
+        return x
     o = _lib.BamOpts()
     o.check_names = int(check_names)
     o.exclude_flags, o.mate_suffix, o.default_qual, o.split, o.paired_check, o.piece = (int(exclude_flags), int(mate_suffix), int(default_qual), int(split),
@@ -297,6 +324,7 @@ def bam_to_fastq_host(raw, outs=None, **opts):
     raw = _u8(raw)
     L = _lib.lib()
     O, st = bam_opts(**opts), _lib.BamStats()
+    st.tags = getattr(O, "tag_stats", None)                         # the tag counts beside the stats (None without tags=): so at every call below
     ol, nr = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
     src = _ptr(raw) if len(raw) else None
     if outs is None:
@@ -349,9 +377,19 @@ def bam_patch_host(stream, texts, out=None, **opts):
     return out[:len(stream)], st
 
 
-def ubam_opts(mate_suffix=1, paired_check=0, level=1, header_text=None, rg_id=None):
+def ubam_opts(mate_suffix=1, paired_check=0, level=1, header_text=None, rg_id=None, tags=None):
     """(bfq_ubam_opts, what it points to) (include/bfqzip_hip.h); the defaults are bfq_ubam_default_opts'.  header_text: bytes
-    written as the BAM header's text (None: the default header); rg_id: bytes or str, RG:Z:<rg_id> on every record."""
+    written as the BAM header's text (None: the default header); rg_id: bytes or str, RG:Z:<rg_id> on every record.
+    tags: None, or "*" (every field XX:T:value of the header lines) or "BC,RX" (those) as aux tags of the records -- then a
+    bfq_ubam_tag_opts comes back, whose .tag_stats (a UbamTagStats: tags_written, fields_dropped, tag_bytes) the call fills;
+    the entry points hand it on as stats.tags."""
+    if tags is not None:
+        x = _tag_ext(_lib.UbamTagOpts(), _tag_list(tags, "ubam_opts"), _lib.UbamTagStats())
+        o, keep = ubam_opts(mate_suffix, paired_check, level, header_text, rg_id)
+        x.o = o
+        x.o.reserved = _lib.UBAM_OPTS_TAGS
+        x.held_rg = o                                              # (rg_id's bytes live with the plain options)
+        return x, keep
     o = _lib.UbamOpts()
     o.mate_suffix, o.paired_check, o.level, o.reserved = int(mate_suffix), int(paired_check), int(level), 0
     keep = []
@@ -381,6 +419,7 @@ def fastq_to_bam_host(texts, out=None, **opts):
     keep, ptrs, lens = _bam_texts(texts)
     O, held = ubam_opts(**opts)
     st, rl = _lib.UbamStats(), C.c_uint64(0)
+    st.tags = getattr(O, "tag_stats", None)
     if out is None:
         rc = L.bfq_fastq_to_bam_host(ptrs, lens, C.byref(O), None, 0, C.byref(rl), C.byref(st))
         if rc != 0 and not rl.value:
@@ -840,6 +879,7 @@ class Engine:
         """bfq_bam_measure: (the three text lengths, the three read counts, stats) of a BAM file; nothing is written."""
         blob = _u8(blob)
         O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        st.tags = getattr(O, "tag_stats", None)
         self._bam_ck(self.L.bfq_bam_measure(self.h, _ptr(blob) if len(blob) else None, len(blob), C.byref(O), ol, nr, C.byref(st)), ol)
         return [int(v) for v in ol], [int(v) for v in nr], st
 
@@ -854,6 +894,7 @@ class Engine:
         if outs is None:
             outs = [np.empty(v, np.uint8) for v in self.bam_measure(blob, **dict(opts, paired_check=0))[0]]
         O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        st.tags = getattr(O, "tag_stats", None)
         ptrs, caps = _bam_outs(outs)
         self._bam_ck(self.L.bfq_bam_to_fastq(self.h, _ptr(blob) if len(blob) else None, len(blob), C.byref(O), ptrs, caps, ol, nr, C.byref(st)), ol)
         return [o[:int(n)] for o, n in zip(outs, ol)], st
@@ -862,6 +903,7 @@ class Engine:
         """bfq_bam_to_fastq_device: the texts at the three device addresses d_outs (caps bytes each); returns (lengths, read counts, stats)."""
         blob = _u8(blob)
         O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        st.tags = getattr(O, "tag_stats", None)
         ptrs, cp = (C.c_void_p * 3)(*[int(p) if p else None for p in d_outs]), (C.c_uint64 * 3)(*[int(v) for v in caps])
         self._bam_ck(self.L.bfq_bam_to_fastq_device(self.h, _ptr(blob) if len(blob) else None, len(blob), C.byref(O), ptrs, cp, ol, nr, C.byref(st)), ol)
         return [int(v) for v in ol], [int(v) for v in nr], st
@@ -876,6 +918,7 @@ class Engine:
             for d in dsts:
                 fds.append(os.open(d, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) if d is not None else -1)
             O, st, ol, nr = bam_opts(**opts), _lib.BamStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+            st.tags = getattr(O, "tag_stats", None)
             self._bam_ck(self.L.bfq_bam_to_fastq_fd(self.h, fds[0], os.fstat(fds[0]).st_size, C.byref(O), (C.c_int * 3)(*fds[1:4]), ol, nr, C.byref(st)), ol)
             return [int(v) for v in ol], [int(v) for v in nr], st
         finally:
@@ -945,6 +988,7 @@ class Engine:
         unknown_bases) of up to three host texts; nothing is written."""
         keep, ptrs, lens = _bam_texts(texts)
         (O, held), st, rl, nr = ubam_opts(**opts), _lib.UbamStats(), C.c_uint64(0), (C.c_uint64 * 3)()
+        st.tags = getattr(O, "tag_stats", None)
         rc = self.L.bfq_fastq_to_bam_measure(self.h, ptrs, lens, C.byref(O), C.byref(rl), nr, C.byref(st))
         if rc != 0:
             _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), 0)
@@ -961,6 +1005,7 @@ class Engine:
         if out is None:
             out = np.empty(bgzf_deflate_bound(self.fastq_to_bam_measure(texts, **opts)[0]), np.uint8)
         (O, held), st, ol = ubam_opts(**opts), _lib.UbamStats(), C.c_uint64(0)
+        st.tags = getattr(O, "tag_stats", None)
         rc = self.L.bfq_fastq_to_bam(self.h, ptrs, lens, C.byref(O), _ptr(out) if len(out) else None, len(out), C.byref(ol), C.byref(st))
         if rc != 0:
             _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), ol.value)
@@ -973,6 +1018,7 @@ class Engine:
         ptrs = (C.c_void_p * 3)(*[int(p) if p else None for p in d_texts])
         lens = (C.c_uint64 * 3)(*[int(v) for v in text_lens])
         (O, held), st, rl = ubam_opts(**opts), _lib.UbamStats(), C.c_uint64(0)
+        st.tags = getattr(O, "tag_stats", None)
         rc = self.L.bfq_fastq_to_bam_device(self.h, ptrs, lens, C.byref(O), C.c_void_p(d_out), int(cap), C.byref(rl), C.byref(st))
         if rc != 0:
             _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), rl.value)
@@ -989,6 +1035,7 @@ class Engine:
                 fds.append(os.open(t, os.O_RDONLY) if t is not None else -1)
             fds.append(os.open(dst, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
             (O, held), st, ol = ubam_opts(**opts), _lib.UbamStats(), C.c_uint64(0)
+            st.tags = getattr(O, "tag_stats", None)
             rc = self.L.bfq_fastq_to_bam_fd(self.h, (C.c_int * 3)(*fds[0:3]), C.byref(O), fds[3], C.byref(ol), C.byref(st))
             if rc != 0:
                 _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), ol.value)
@@ -1111,6 +1158,7 @@ class Engine:
             size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
             if ubam:
                 (O, held), st = ubam_opts(level=level, **ubam_kw), _lib.UbamStats()
+                st.tags = getattr(O, "tag_stats", None)
                 self._ck(self.L.bfq_fastq_restore_bam_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
                                                          fds[3], size(fds[3]), C.byref(O), fds[4], C.byref(ol), C.byref(st)))
                 nr.value = st.records

@@ -6,7 +6,8 @@
 //   4  the chain's jobs up -- the host's prefix sums over the pieces place the text --; the placing walk; the pairing check
 //   arena   the compressed bytes and the stream, 168 bytes per piece, 8 bytes per record of outputs 1 and 2 for the pairing
 //           check and -- unless the caller brings device buffers -- 4/3 of the stream for the texts; all reserved at once,
-//           since growing the arena would lose the stream
+//           since growing the arena would lose the stream.  With tags asked for (bfq_bam_tag_opts): 24 bytes more per piece,
+//           and 5/2 of the stream for the texts (bfq_bam.h derives the bound); a call without them reserves what it did
 // bfq_bam_to_fastq_host is the host form of bfq_bam.h, for tests and as the statement of the algorithm: no entry point here
 // falls back to it.
 #include <string.h>
@@ -22,8 +23,9 @@ static_assert(sizeof(bfq_bam_opts) == 32 && sizeof(bfq_bam_stats) == 120, "the C
 
 u64 bfq_bgzf_inflate_arena(bfq_ctx *c, const u8 *h_in, u64 len, const std::function<size_t(u64)> &more, u8 **where);   // bfq_bgzf.hip
 void bfq_bam_launch_walk(bfq_ctx *c, const u8 *d_s, u64 len, u64 hdrEnd, u64 piece, u64 np, u32 nref, const bfq_bam_opts &O, u64 only, u64 from,
-                         bfq_bam_piece *d_recs);                                                                          // k_bam.hip
-void bfq_bam_launch_place(bfq_ctx *c, const u8 *d_s, u64 len, const bfq_bam_job *d_jobs, u64 nj, u32 nref, const bfq_bam_opts &O, const bfq_bam_outs &out, u64 bytes);
+                         bfq_bam_piece *d_recs, const bfq_bam_tagsel &G, bfq_bam_tagcnt *d_tagc);                           // k_bam.hip
+void bfq_bam_launch_place(bfq_ctx *c, const u8 *d_s, u64 len, const bfq_bam_job *d_jobs, u64 nj, u32 nref, const bfq_bam_opts &O, const bfq_bam_outs &out, u64 bytes,
+                          const bfq_bam_tagsel &G);
 void bfq_bam_launch_pairs(bfq_ctx *c, const u8 *d_s, const u64 *d_a, const u64 *d_b, u64 n, u64 *d_firstBad);
 
 static const char *const BAM_SMALL = "output buffer too small for the FASTQ text";
@@ -34,6 +36,14 @@ static bfq_bam_opts bam_opts(const bfq_bam_opts *in)
     const char *why = nullptr;
     if (!bfq_bam_resolve(in, &O, &why)) throw BfqError{BFQ_E_ARG, why};
     return O;
+}
+// the tag selection of a call (off without the extension) and where its counts go
+static bfq_bam_tagsel bam_tags(const bfq_bam_opts *in, bfq_bam_tag_stats **stats)
+{
+    bfq_bam_tagsel G;
+    const char *why = nullptr;
+    if (!bfq_bam_tags_resolve(in, &G, stats, &why)) throw BfqError{BFQ_E_ARG, why};
+    return G;
 }
 static bool is_gzip(const u8 *h, u64 len) { return len >= 2 && h[0] == 0x1F && h[1] == 0x8B; }
 void bfq_bam_refuse(const bfq_bam_err &E) { bam_refuse(E); }                       // (declared in bfq_bam.h, for bfq_bam_patch.hip)
@@ -71,14 +81,17 @@ extern "C" int bfq_bam_to_fastq_host(const uint8_t *raw, uint64_t raw_len, const
     try {
         if (!out_len || !n_reads || (!raw && raw_len) || (h_out && !cap)) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_bam_opts O = bam_opts(opts);
+        bfq_bam_tag_stats *tagStats = nullptr, TS{};
+        const bfq_bam_tagsel G = bam_tags(opts, &tagStats);
         static const u8 none = 0;
         u8 *const no[3] = {nullptr, nullptr, nullptr};
         const u64 caps[3] = {h_out ? cap[0] : 0, h_out ? cap[1] : 0, h_out ? cap[2] : 0};
         bfq_bam_stats S{};
         bfq_bam_err E;
         u64 ol[3], nr[3];
-        const int r = bfq_bam_host(raw_len ? raw : &none, raw_len, O, h_out ? h_out : no, caps, !h_out, ol, nr, &S, &E);
+        const int r = bfq_bam_host(raw_len ? raw : &none, raw_len, O, h_out ? h_out : no, caps, !h_out, ol, nr, &S, &E, &G, &TS);
         if (stats) *stats = S;
+        if (tagStats) *tagStats = TS;
         if (r == 1) bam_refuse(E);
         for (int o = 0; o < 3; o++) { out_len[o] = ol[o]; n_reads[o] = nr[o]; }
         if (r == 2) throw BfqError{BFQ_E_ARG, BAM_SMALL};
@@ -93,8 +106,11 @@ extern "C" int bfq_bam_to_fastq_host(const uint8_t *raw, uint64_t raw_len, const
 }
 
 // Steps 1-3, shared by both directions (bfq_bam.h states what it leaves).
-void bfq_bam_chain_device(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts &O, const std::function<size_t(u64)> &more, bfq_bam_stats *stats, bfq_bam_chain_dev *C)
+void bfq_bam_chain_device(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts &O, const std::function<size_t(u64)> &more, bfq_bam_stats *stats, bfq_bam_chain_dev *C,
+                          const bfq_bam_tagsel *Gin)
 {
+    bfq_bam_tagsel G{};
+    if (Gin) G = *Gin;
     if (!h_in && len) throw BfqError{BFQ_E_ARG, "null argument"};
     u8 *d_s = nullptr;
     u64 raw = len;
@@ -120,20 +136,25 @@ void bfq_bam_chain_device(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opt
     S.n_ref = nref; S.header_bytes = hdrEnd;
     const u64 piece = O.piece, np = bfq_bam_pieces(raw, hdrEnd, piece);
     bfq_bam_piece *d_recs = c->alloc<bfq_bam_piece>(np);
-    bfq_bam_launch_walk(c, d_s, raw, hdrEnd, piece, np, nref, O, BFQ_BAM_NONE, 0, d_recs);
+    bfq_bam_tagcnt *d_tagc = G.on ? c->alloc<bfq_bam_tagcnt>(np) : nullptr;
+    std::vector<bfq_bam_tagcnt> T(G.on ? np : 0);
+    bfq_bam_launch_walk(c, d_s, raw, hdrEnd, piece, np, nref, O, BFQ_BAM_NONE, 0, d_recs, G, d_tagc);
     std::vector<bfq_bam_piece> &P = C->P;
     P.resize(np);
     HIP_CHECK(hipMemcpyAsync(P.data(), d_recs, sizeof(bfq_bam_piece) * np, hipMemcpyDeviceToHost, c->stream));
+    if (G.on) HIP_CHECK(hipMemcpyAsync(T.data(), d_tagc, sizeof(bfq_bam_tagcnt) * np, hipMemcpyDeviceToHost, c->stream));
     c->sync();
     bfq_bam_chain(P, hdrEnd, raw, piece, [&](u64 k, u64 start) {
         bfq_bam_piece w;
-        bfq_bam_launch_walk(c, d_s, raw, hdrEnd, piece, np, nref, O, k, start, d_recs);
+        bfq_bam_launch_walk(c, d_s, raw, hdrEnd, piece, np, nref, O, k, start, d_recs, G, d_tagc);
         HIP_CHECK(hipMemcpyAsync(&w, d_recs + k, sizeof w, hipMemcpyDeviceToHost, c->stream));
+        if (G.on) HIP_CHECK(hipMemcpyAsync(&T[k], d_tagc + k, sizeof(bfq_bam_tagcnt), hipMemcpyDeviceToHost, c->stream));
         c->sync();
         return w;
     }, C->jobs, &S, &E);
     if (stats) *stats = S;
     if (E.reason) { c->profCollect(); bam_refuse(E); }
+    if (G.on) C->T = bfq_bam_tag_totals(T, C->jobs, hdrEnd, piece);
     C->d_s = d_s; C->raw = raw; C->nref = nref; C->hdrEnd = hdrEnd;
 }
 
@@ -144,13 +165,17 @@ static void bam_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *op
                      u64 nReads[3], bfq_bam_stats *stats, u8 *where[3], bool *isShort)
 {
     const bfq_bam_opts O = bam_opts(opts);
+    bfq_bam_tag_stats *tagStats = nullptr;
+    const bfq_bam_tagsel G = bam_tags(opts, &tagStats);
+    if (tagStats) *tagStats = bfq_bam_tag_stats{};                  // (a refused call leaves them 0)
     const std::function<size_t(u64)> more = [&](u64 raw) {
         const size_t np = (size_t)(raw / O.piece + 2);
-        return np * (sizeof(bfq_bam_piece) + sizeof(bfq_bam_job) + 8) + (O.paired_check ? (size_t)raw / 4 + 1024 : 0) +
-               (mode == BAM_ARENA ? (size_t)BFQ_BAM_TEXT_BOUND(raw) + 1024 : 0) + 8192;
+        return np * (sizeof(bfq_bam_piece) + sizeof(bfq_bam_job) + 8 + (G.on ? sizeof(bfq_bam_tagcnt) : 0)) + (O.paired_check ? (size_t)raw / 4 + 1024 : 0) +
+               (mode == BAM_ARENA ? (size_t)(G.on ? BFQ_BAM_TEXT_BOUND_TAGS(raw) : BFQ_BAM_TEXT_BOUND(raw)) + 1024 : 0) + 8192;
     };
     bfq_bam_chain_dev C;
-    bfq_bam_chain_device(c, h_in, len, O, more, stats, &C);
+    bfq_bam_chain_device(c, h_in, len, O, more, stats, &C, &G);
+    if (tagStats) *tagStats = C.T;
     u8 *const d_s = C.d_s;
     const u64 raw = C.raw, hdrEnd = C.hdrEnd, piece = O.piece;
     const u32 nref = C.nref;
@@ -174,7 +199,7 @@ static void bam_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *op
     bfq_bam_job *d_jobs = c->alloc<bfq_bam_job>(nj + 1);
     u64 *d_bad = c->alloc<u64>(1);
     bfq_upload(c, d_jobs, jobs.data(), sizeof(bfq_bam_job) * nj);
-    bfq_bam_launch_place(c, d_s, raw, d_jobs, nj, nref, O, W, outLen[0] + outLen[1] + outLen[2]);
+    bfq_bam_launch_place(c, d_s, raw, d_jobs, nj, nref, O, W, outLen[0] + outLen[1] + outLen[2], G);
     u64 firstBad = BFQ_BAM_NONE;
     if (O.paired_check) {
         HIP_CHECK(hipMemsetAsync(d_bad, 0xFF, 8, c->stream));

@@ -27,6 +27,27 @@
 //   QUAL: char - 33; a byte below 33 or above 126 is refused.  Qualities are always written: absent qualities cannot come
 //     back from a text, so BAM -> text -> BAM is an identity only for records that held qualities <= 93 and no tags.
 //   Tags: none, or with rg_id "RG:Z:<rg_id>" on every record (rg_id: 1..255 bytes of [ -~]).
+//   Tags out of the header line (bfq_ubam_tag_opts; off unless asked for), modelled on `samtools import -T`; parity with
+//     htslib is not pinned.  Behind the name the header line -- all of it, CR before LF stripped -- is cut at tabs.  Where a
+//     space ended the name, the bytes up to the first tab are a comment and dropped.  A field [A-Za-z][A-Za-z0-9]:[AiZH]:value
+//     becomes a tag of the record, in line order, between QUAL and the RG tag of rg_id, when no list is given (n_tags 0) or
+//     its key is in the list (at most 32 keys, each [A-Za-z][A-Za-z0-9]):
+//       A  exactly one byte of [ -~]                                      stored A, 4 bytes
+//       i  an optional '-' and 1..10 digits, within [-2^31, 2^32 - 1]     stored at htslib's smallest width: 0..255 C, ..65535
+//          S, else I; -128.. c, -32768.. s, else i ("-0" is 0): 4, 5 or 7 bytes
+//       Z  bytes of [ -~] (may be none)                                   stored Z, 4 + n bytes
+//       H  an even number of hex digits (may be none)                     stored H, 4 + n bytes
+//     Every other field is dropped and counted (fields_dropped), never refused: types f and B, an integer out of range or
+//     above 10 digits, "+5", an empty i, a malformed key, an empty field, a key not in the list, a Z value with a byte outside
+//     [ -~] (a NUL in it would end the value early) or above 2^20 bytes, what would take a record's tags above 2^23 bytes;
+//     and, with rg_id set, an RG field: the constant RG tag comes last, as without tags.  comments_dropped then counts the
+//     reads of which some byte behind the name did not become a tag: a comment, or a dropped field.
+//     No field is longer stored than written ("\tXX:A:c" 7 of text, 4 stored; "\tXX:i:0" 7 and 4, 256 9 and 5, 65536 11 and
+//     7, -1 8 and 4, -129 10 and 5, -32769 12 and 7; Z / H 6 + n and 4 + n): the stream's bound of bfq_ubam.hip holds.
+//     Identity: BAM -> text (every tag, bfq_bam.h) -> BAM (tags on, header_text the original's) gives the inflated stream
+//     byte for byte for uBAM records of flags 4 / 77 / 141 with qualities <= 93 (as without tags) whose tags are of types A /
+//     Z / H or integers stored at their smallest width and whose values are printable.  Text -> BAM -> text is one for
+//     header lines without a comment whose fields are all well-formed (an integer without leading zeros or "-0").
 //   Header: "BAM\1", l_text, the text, n_ref 0.  header_text given: written as it is (the caller's to make valid); NULL:
 //     "@HD\tVN:1.6\tSO:unsorted\n" and, with rg_id, "@RG\tID:<rg_id>\n".
 //   Sizes: a record is 36 + (l_name + 1) + ceil(l_seq / 2) + l_seq bytes, + 4 + strlen(rg_id): the stream's length is
@@ -40,6 +61,8 @@
 #include "bfq_bam_patch.h"
 
 #define BFQ_UBAM_MAX_NAME 254u
+#define BFQ_UBAM_MAX_FIELD (1u << 20)              // bytes of a Z / H value
+#define BFQ_UBAM_MAX_TAGS (1u << 23)               // bytes of a record's tags out of its header line
 #define BFQ_UBAM_PIECE 65280ull                     // bytes of stream per BGZF member (bfq_deflate.h's BFQ_DEFL_PIECE)
 
 enum {
@@ -96,7 +119,11 @@ struct bfq_ubam_cnt { u64 named, comments, unknown, pad; };
 // How the nl lanes of a record agree: the host's one lane with itself.  (The device's wave64: k_ubam.hip.)
 struct bfq_ubam_alone {
     static BFQ_HD u32 first(bool v) { return v ? 0u : 1u; }        // the lowest lane whose v holds; nl: none
+    static BFQ_HD bool any(bool v) { return v; }
 };
+// the tag selection of a call (on == 0: tags off; dropRG: rg_id is set) and what the sizing pass counts
+struct bfq_ubam_tagsel { u32 on, n, dropRG, pad; u8 tag[32][2]; };
+struct bfq_ubam_tcnt { u64 written, dropped, bytes, pad; };
 
 // unaligned 8- and 4-byte accesses (the device takes them as they are; the host through memcpy)
 BFQ_HD u64 bfq_ubam_ld64(const u8 *p) { u64 v; __builtin_memcpy(&v, p, 8); return v; }
@@ -162,10 +189,88 @@ BFQ_HD u32 bfq_ubam_name(const u8 *t, u64 s0, u64 e0, u32 k, u32 mateSuffix, u64
     return BFQ_UBAM_OK;
 }
 
+// ---------------------------------------------------------------- tags out of the header line
+// where the field that starts at t[fs] ends: the first tab at or behind fs, or e0.  The nl lanes look at a byte each.
+template <class W> BFQ_HD u64 bfq_ubam_field_end(const u8 *t, u64 fs, u64 e0, u32 lane, u32 nl)
+{
+    for (u64 base = fs;; base += nl) {
+        const u64 q = base + lane;
+        const u32 f = W::first(q >= e0 || t[q] == '\t');
+        if (f < nl) return base + f;
+    }
+}
+// One field: type 0: dropped; else the tag's key, its stored type, its bytes in the record (stored), where its value
+// stands in the text (val, vlen) and an integer's value (num, two's complement).
+struct bfq_ubam_fld { u32 k0, k1, type, stored, vlen, num; u64 val; };
+// The field t[fs, fe), by nl lanes that all take the same path: they share the bytes of a Z / H value; everything else is
+// the same few loads in every lane.
+template <class W> BFQ_HD void bfq_ubam_field(const u8 *t, u64 fs, u64 fe, const bfq_ubam_tagsel &G, u32 lane, u32 nl, bfq_ubam_fld *F)
+{
+    F->type = 0; F->stored = 0; F->vlen = 0; F->num = 0; F->val = fs;
+    if (fe - fs < 5) return;
+    const u32 k0 = t[fs], k1 = t[fs + 1], ty = t[fs + 3];
+    if (!bfq_bam_key_ok(k0, k1) || t[fs + 2] != ':' || t[fs + 4] != ':') return;
+    if (G.dropRG && k0 == 'R' && k1 == 'G') return;
+    if (G.n) {
+        bool in = false;
+        for (u32 j = 0; j < G.n; j++) in = in || (G.tag[j][0] == k0 && G.tag[j][1] == k1);
+        if (!in) return;
+    }
+    const u64 v = fs + 5, vl = fe - v;
+    F->k0 = k0; F->k1 = k1; F->val = v;
+    if (ty == 'A') {
+        if (vl != 1 || t[v] < 0x20 || t[v] > 0x7e) return;
+        F->type = 'A'; F->stored = 4;
+    } else if (ty == 'i') {
+        const u32 neg = vl && t[v] == '-' ? 1u : 0u;
+        if (vl < 1 + neg || vl > 10 + neg) return;
+        u64 a = 0;
+        for (u64 j = neg; j < vl; j++) {
+            const u32 d = (u32)t[v + j] - '0';
+            if (d > 9) return;
+            a = a * 10 + d;
+        }
+        if (a > (neg ? 2147483648ull : 4294967295ull)) return;
+        u32 w;
+        if (!neg || !a) { F->type = a <= 255 ? 'C' : a <= 65535 ? 'S' : 'I'; w = a <= 255 ? 1 : a <= 65535 ? 2 : 4; F->num = (u32)a; }
+        else { F->type = a <= 128 ? 'c' : a <= 32768 ? 's' : 'i'; w = a <= 128 ? 1 : a <= 32768 ? 2 : 4; F->num = 0u - (u32)a; }
+        F->stored = 3 + w;
+    } else if (ty == 'Z' || ty == 'H') {
+        if (vl > BFQ_UBAM_MAX_FIELD || (ty == 'H' && (vl & 1))) return;
+        bool bad = false;
+        for (u64 j = lane; j < vl; j += nl) {
+            const u32 ch = t[v + j];
+            bad = bad || (ty == 'Z' ? ch < 0x20u || ch > 0x7eu : !(ch - '0' < 10u || (ch | 32u) - 'a' < 6u));
+        }
+        if (W::any(bad)) return;
+        F->type = ty; F->vlen = (u32)vl; F->stored = 4 + (u32)vl;
+    }
+}
+// The fields of the header line t[., e0) behind the name, which ends at p, by nl lanes.  each(F, at): called for every
+// field that becomes a tag, at byte `at` of the record's tags.  Returns the tags' bytes; *dropped: the fields that did not
+// become one; *junk: some byte behind the name did not become a tag.
+template <class W, class Each> BFQ_HD u32 bfq_ubam_fields(const u8 *t, u64 p, u64 e0, const bfq_ubam_tagsel &G, u32 lane, u32 nl, u32 *dropped, u32 *junk, Each &&each)
+{
+    u32 bytes = 0;
+    *dropped = 0; *junk = 0;
+    if (p < e0 && t[p] == ' ') { *junk = 1; p = bfq_ubam_field_end<W>(t, p, e0, lane, nl); }
+    while (p < e0) {                                                // t[p] is a tab
+        const u64 fs = p + 1, fe = bfq_ubam_field_end<W>(t, fs, e0, lane, nl);
+        bfq_ubam_fld F;
+        bfq_ubam_field<W>(t, fs, fe, G, lane, nl, &F);
+        if (F.type && bytes + F.stored <= BFQ_UBAM_MAX_TAGS) { each(F, bytes); bytes += F.stored; }
+        else { (*dropped)++; *junk = 1; }
+        p = fe;
+    }
+    return bytes;
+}
+
 // The sizing pass of read i of text k, by one lane: 0 and *size (the record's bytes, block_size included), or why the read
 // is refused.  C: this lane's counts (named, comments).  Reads the header line's first 256 bytes, the mate's with
-// pairedCheck, the first byte of the third line and the quality line; writes nothing.
-BFQ_HD u32 bfq_ubam_size_read(const bfq_ubam_job &J, u32 k, u64 i, u32 *size, bfq_ubam_cnt *C)
+// pairedCheck, the first byte of the third line and the quality line; writes nothing.  TAGS: it walks the whole header
+// line, validates every field and adds the tags' stored bytes to the size (T: this lane's tag counts).
+template <bool TAGS = false>
+BFQ_HD u32 bfq_ubam_size_read(const bfq_ubam_job &J, u32 k, u64 i, u32 *size, bfq_ubam_cnt *C, const bfq_ubam_tagsel *G = nullptr, bfq_ubam_tcnt *T = nullptr)
 {
     const u8 *t = J.T.text[k];
     const u64 *le = J.T.lineEnd[k];
@@ -199,8 +304,16 @@ BFQ_HD u32 bfq_ubam_size_read(const bfq_ubam_job &J, u32 k, u64 i, u32 *size, bf
     for (; p < e3; p++) bad |= ((u32)t[p] - 33u > 93u) ? 1u : 0u;
     if (bad) return BFQ_UBAM_E_QUAL;
     if (!nl) { nl = bfq_ubam_digits(bfq_ubam_index(J, k, i)); C->named++; }
+    u32 tagBytes = 0;
+    if constexpr (TAGS) {
+        u64 p = s0 + 1;
+        while (p < e0 && t[p] != ' ' && t[p] != '\t') p++;          // (the name's end: within 255 bytes, or the read was refused)
+        u32 dropped = 0, written = 0;
+        tagBytes = bfq_ubam_fields<bfq_ubam_alone>(t, p, e0, *G, 0, 1, &dropped, &comment, [&](const bfq_ubam_fld &, u32) { written++; });
+        T->written += written; T->dropped += dropped; T->bytes += tagBytes;
+    }
     C->comments += comment;
-    *size = (u32)(36u + nl + 1u + (u32)((L + 1) / 2) + (u32)L + J.tagLen);
+    *size = (u32)(36u + nl + 1u + (u32)((L + 1) / 2) + (u32)L + tagBytes + J.tagLen);
     return BFQ_UBAM_OK;
 }
 
@@ -215,7 +328,10 @@ BFQ_HD u32 bfq_ubam_fixed(u32 j, u32 size, u32 nameLen, u32 flag, u32 lseq)
 // bytes of SEQ -- two bases, neighbouring bytes of the text -- and whole bytes of QUAL, four and eight at a time where the
 // destination is aligned (the text is read unaligned), byte by byte in front of and behind that; the tag's bytes last.  No
 // two lanes write one byte, no lane walks a read, and every byte of the record is written.  *unknown: this lane's count.
-template <class W> BFQ_HD void bfq_ubam_write_rec(u8 *out, u64 o, u32 size, const bfq_ubam_job &J, u32 k, u64 i, u32 lane, u32 nl, u64 *unknown)
+// TAGS: the fields of the header line that the sizing pass took stand between QUAL and that tag: the lanes share a Z / H
+// value's bytes; a tag's three leading bytes, its NUL and the <= 4 bytes of an integer are lane 0's.
+template <class W, bool TAGS = false>
+BFQ_HD void bfq_ubam_write_rec(u8 *out, u64 o, u32 size, const bfq_ubam_job &J, u32 k, u64 i, u32 lane, u32 nl, u64 *unknown, const bfq_ubam_tagsel *G = nullptr)
 {
     const u8 *t = J.T.text[k];
     const u64 *le = J.T.lineEnd[k];
@@ -233,6 +349,7 @@ template <class W> BFQ_HD void bfq_ubam_write_rec(u8 *out, u64 o, u32 size, cons
         const u32 f = W::first(stop);
         if (f < nl) { n = base + f; break; }
     }
+    const u64 nameEnd = b + n;
     if (J.mateSuffix && k && n > 2 && t[b + n - 2] == '/' && t[b + n - 1] == (u8)('0' + k)) n -= 2;
     const u64 number = bfq_ubam_index(J, k, i);
     const u32 nameLen = n ? n : bfq_ubam_digits(number);
@@ -285,6 +402,23 @@ template <class W> BFQ_HD void bfq_ubam_write_rec(u8 *out, u64 o, u32 size, cons
     for (u32 w = lane; w < qw; w += nl) bfq_ubam_st64(qual + qh + 8 * w, bfq_ubam_ld64(t + s3 + qh + 8 * (u64)w) - 0x2121212121212121ull);   // (every byte >= 33: no borrow)
     for (u32 j = qt + lane; j < L; j += nl) qual[j] = (u8)(t[s3 + j] - 33);
     u8 *tag = qual + L;
+    if constexpr (TAGS) {
+        u32 dropped, junk;
+        u8 *const first = tag;
+        tag += bfq_ubam_fields<W>(t, nameEnd, e0, *G, lane, nl, &dropped, &junk, [&](const bfq_ubam_fld &F, u32 at) {
+            u8 *d = first + at;
+            const bool str = F.type == 'Z' || F.type == 'H';
+            if (str)
+                for (u32 j = lane; j < F.vlen; j += nl) d[3 + j] = t[F.val + j];
+            if (lane == 0) {
+                d[0] = (u8)F.k0; d[1] = (u8)F.k1; d[2] = (u8)F.type;
+                if (str) d[3 + F.vlen] = 0;
+                else if (F.type == 'A') d[3] = t[F.val];
+                else
+                    for (u32 j = 0; j + 3 < F.stored; j++) d[3 + j] = (u8)(F.num >> (8 * j));
+            }
+        });
+    }
     for (u32 j = lane; j < J.tagLen; j += nl) tag[j] = J.tag[j];
 }
 
@@ -303,6 +437,22 @@ inline bool bfq_ubam_resolve(const bfq_ubam_opts *in, bfq_ubam_opts *O, bfq_ubam
     }
     if (O->level > 1) { E->kind = BFQ_UBAM_E_LEVEL; return false; }
     if (O->header_len >= (1ull << 31) || (!O->header_text && O->header_len)) { E->kind = BFQ_UBAM_E_HEADER; return false; }
+    return true;
+}
+// the tag selection of a call: off unless in->reserved holds BFQ_UBAM_OPTS_TAGS; false: refused (*why)
+inline bool bfq_ubam_tags_resolve(const bfq_ubam_opts *in, bfq_ubam_tagsel *G, bfq_ubam_tag_stats **stats, const char **why)
+{
+    memset(G, 0, sizeof *G);
+    *stats = nullptr; *why = nullptr;
+    if (!in || in->reserved != BFQ_UBAM_OPTS_TAGS) return true;
+    const bfq_ubam_tag_opts *X = (const bfq_ubam_tag_opts *)in;
+    if (X->n_tags > 32) { *why = "FASTQ to BAM: tags: more than 32 tags"; return false; }
+    for (u32 j = 0; j < X->n_tags; j++) {
+        if (!bfq_bam_key_ok(X->tag[j][0], X->tag[j][1])) { *why = "FASTQ to BAM: tags: a tag that is not [A-Za-z][A-Za-z0-9]"; return false; }
+        G->tag[j][0] = X->tag[j][0]; G->tag[j][1] = X->tag[j][1];
+    }
+    G->on = 1; G->n = X->n_tags; G->dropRG = in->rg_id ? 1u : 0u;
+    *stats = X->stats;
     return true;
 }
 // the stream's header and the tag of every record
@@ -364,8 +514,10 @@ inline void bfq_ubam_totals(const bfq_ubam_job &J, u64 rawLen, const bfq_ubam_cn
 // out[0, cap): where the stream goes (measure: not touched).  Returns 0; 2 = refused (*X); 3 = cap below the length
 // (S->raw_len: the length).  Nothing is written unless 0 is returned.
 inline int bfq_ubam_host_form(const u8 *const text[3], const u64 textLen[3], const bfq_ubam_opts &O, u8 *out, u64 cap, bool measure, bfq_ubam_stats *S,
-                              bfq_ubam_err *X)
+                              bfq_ubam_err *X, const bfq_ubam_tagsel *G = nullptr, bfq_ubam_tag_stats *TS = nullptr)
 {
+    const bool tags = G && G->on;
+    bfq_ubam_tcnt TC{};
     *S = bfq_ubam_stats{};
     *X = bfq_ubam_err{};
     bool present[3];
@@ -396,13 +548,14 @@ inline int bfq_ubam_host_form(const u8 *const text[3], const u64 textLen[3], con
         u32 k, size = 0;
         u64 i;
         bfq_ubam_where(J, r, &k, &i);
-        const u32 why = bfq_ubam_size_read(J, k, i, &size, &C);
+        const u32 why = tags ? bfq_ubam_size_read<true>(J, k, i, &size, &C, G, &TC) : bfq_ubam_size_read(J, k, i, &size, &C);
         if (why) { bfq_ubam_read_err(J, r, why, X); return 2; }
         off[r] = at;
         at += size;
     }
     off[nrec] = at;
     bfq_ubam_totals(J, at, C, S);
+    if (tags && TS) { TS->tags_written = TC.written; TS->fields_dropped = TC.dropped; TS->tag_bytes = TC.bytes; }
     if (measure) return 0;
     if (cap < at) return 3;
     memcpy(out, hdr.data(), hdr.size());
@@ -410,7 +563,8 @@ inline int bfq_ubam_host_form(const u8 *const text[3], const u64 textLen[3], con
         u32 k;
         u64 i;
         bfq_ubam_where(J, r, &k, &i);
-        bfq_ubam_write_rec<bfq_ubam_alone>(out, off[r], (u32)(off[r + 1] - off[r]), J, k, i, 0, 1, &C.unknown);
+        if (tags) bfq_ubam_write_rec<bfq_ubam_alone, true>(out, off[r], (u32)(off[r + 1] - off[r]), J, k, i, 0, 1, &C.unknown, G);
+        else bfq_ubam_write_rec<bfq_ubam_alone>(out, off[r], (u32)(off[r + 1] - off[r]), J, k, i, 0, 1, &C.unknown);
     }
     S->unknown_bases = C.unknown;
     return 0;

@@ -8,7 +8,8 @@
 //   4  bfq_fastq_to_bam / _fd / bfq_fastq_restore_bam_fd: the stream deflated where it lies (bfq_deflate_core): it never
 //      crosses to the host uncompressed
 //   arena   8 bytes per text line (and 12 per 4 KiB of text while they are indexed), 12 bytes per record, the stream -- before
-//           the sizing pass bounded by the texts' bytes + 53 + the tag per read --, the deflate batch; all reserved at once.
+//           the sizing pass bounded by the texts' bytes + 53 + the tag per read (with tags out of the header line too: no
+//           field is longer stored than written, bfq_ubam.h goes through the types) --, the deflate batch; all reserved at once.
 //           Uploaded texts lie in the context's text buffer, beside the arena, like the text of every FASTQ entry point.
 // bfq_fastq_to_bam_host is the host form of bfq_ubam.h, for tests and as the statement of the algorithm: no entry point
 // here falls back to it.
@@ -24,8 +25,9 @@
 
 static_assert(sizeof(bfq_ubam_stats) == 72 && sizeof(bfq_ubam_opts) == 40 && BFQ_UBAM_PIECE == BFQ_DEFL_PIECE, "the C-ABI's structures; the member size");
 
-void bfq_ubam_launch_size(bfq_ctx *c, const bfq_ubam_job &J, u64 nrec, u32 *d_sizes, u64 *d_firstBad, bfq_ubam_cnt *d_cnt);                   // k_ubam.hip
-void bfq_ubam_launch_write(bfq_ctx *c, const bfq_ubam_job &J, u64 nrec, const u64 *d_off, u8 *d_out, u64 rawLen, bfq_ubam_cnt *d_cnt);
+void bfq_ubam_launch_size(bfq_ctx *c, const bfq_ubam_job &J, u64 nrec, u32 *d_sizes, u64 *d_firstBad, bfq_ubam_cnt *d_cnt, const bfq_ubam_tagsel &G,
+                          bfq_ubam_tcnt *d_tcnt);                                                                                           // k_ubam.hip
+void bfq_ubam_launch_write(bfq_ctx *c, const bfq_ubam_job &J, u64 nrec, const u64 *d_off, u8 *d_out, u64 rawLen, bfq_ubam_cnt *d_cnt, const bfq_ubam_tagsel &G);
 
 #define UBAM_NL_CHUNK 4096u                                        // (k_fastq.hip's: bfq_line_index takes 12 bytes per chunk)
 #define UBAM_NONE (~0ull)
@@ -37,6 +39,16 @@ static bfq_ubam_opts ubam_opts(const bfq_ubam_opts *in)
     bfq_ubam_err X;
     if (!bfq_ubam_resolve(in, &O, &X)) ubam_refuse(X);
     return O;
+}
+
+// the tag selection of a call (off without the extension); *stats: where its counts go (zeroed here: a refused call leaves them 0)
+static bfq_ubam_tagsel ubam_tags(const bfq_ubam_opts *in, bfq_ubam_tag_stats **stats)
+{
+    bfq_ubam_tagsel G;
+    const char *why = nullptr;
+    if (!bfq_ubam_tags_resolve(in, &G, stats, &why)) throw BfqError{BFQ_E_ARG, why};
+    if (*stats) **stats = bfq_ubam_tag_stats{};
+    return G;
 }
 
 extern "C" void bfq_ubam_default_opts(bfq_ubam_opts *o) { if (o) bfq_ubam_defaults(o); }
@@ -53,11 +65,14 @@ extern "C" int bfq_fastq_to_bam_host(const uint8_t *const text[3], const uint64_
     try {
         if (!text || !text_len || !raw_len || (!out_raw && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_ubam_opts O = ubam_opts(opts);
+        bfq_ubam_tag_stats *tagStats = nullptr, TS{};
+        const bfq_ubam_tagsel G = ubam_tags(opts, &tagStats);
         const u64 tl[3] = {text[0] ? text_len[0] : 0, text[1] ? text_len[1] : 0, text[2] ? text_len[2] : 0};
         bfq_ubam_stats S;
         bfq_ubam_err X;
-        const int r = bfq_ubam_host_form(text, tl, O, out_raw, cap, false, &S, &X);
+        const int r = bfq_ubam_host_form(text, tl, O, out_raw, cap, false, &S, &X, &G, &TS);
         if (r == 2) ubam_refuse(X);
+        if (tagStats) *tagStats = TS;
         *raw_len = S.raw_len;
         if (r == 3) throw BfqError{BFQ_E_ARG, "output buffer too small for the stream"};
         if (stats) *stats = S;
@@ -74,7 +89,7 @@ extern "C" int bfq_fastq_to_bam_host(const uint8_t *const text[3], const uint64_
 // the texts of a call: on the host (h) or on the device (d); neither: absent
 struct UbamTexts { const u8 *h[3] = {nullptr, nullptr, nullptr}, *d[3] = {nullptr, nullptr, nullptr}; u64 len[3] = {0, 0, 0}; };
 // what steps 1-3 leave: the stream in the arena and the counts
-struct UbamStream { u8 *d_s = nullptr; u64 raw = 0; bfq_ubam_stats S{}; };
+struct UbamStream { u8 *d_s = nullptr; u64 raw = 0; bfq_ubam_stats S{}; bfq_ubam_tag_stats T{}; };
 
 // arena bytes of steps 1-3 (behind the counting of the lines) for texts of `bytes` bytes and at most `lines` lines in all,
 // of which `texts` are present; + extra(bound of the stream)
@@ -88,7 +103,7 @@ static size_t ubam_need(u64 bytes, u64 lines, u32 texts, size_t hdrLen, size_t t
 
 // Steps 2-3 on texts that stand on the device at 16-byte aligned addresses, in an arena that holds ubam_need() bytes above
 // its top.  sized(raw) runs once the stream's length is known and before anything is written: it throws for a short capacity.
-static void ubam_records(bfq_ctx *c, const u8 *const d_t[3], const u64 len[3], const bool present[3], const bfq_ubam_opts &O, bool measure,
+static void ubam_records(bfq_ctx *c, const u8 *const d_t[3], const u64 len[3], const bool present[3], const bfq_ubam_opts &O, const bfq_ubam_tagsel &G, bool measure,
                          const std::function<void(u64)> &sized, UbamStream *out)
 {
     bfq_ubam_err R;
@@ -110,13 +125,16 @@ static void ubam_records(bfq_ctx *c, const u8 *const d_t[3], const u64 len[3], c
     u32 *d_sizes = c->alloc<u32>(nrec + 1);
     u64 *d_off = c->alloc<u64>(nrec + 2);
     u64 *d_bad = c->alloc<u64>(1);
-    bfq_ubam_cnt *d_cnt = c->alloc<bfq_ubam_cnt>(1);
+    bfq_ubam_cnt *d_cnt = c->alloc<bfq_ubam_cnt>(2);                // (the tag counts behind the counts: both are 32 bytes)
+    bfq_ubam_tcnt *d_tcnt = (bfq_ubam_tcnt *)(d_cnt + 1);
     HIP_CHECK(hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
-    HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(bfq_ubam_cnt), c->stream));
-    bfq_ubam_launch_size(c, J, nrec, d_sizes, d_bad, d_cnt);
+    HIP_CHECK(hipMemsetAsync(d_cnt, 0, 2 * sizeof(bfq_ubam_cnt), c->stream));
+    bfq_ubam_launch_size(c, J, nrec, d_sizes, d_bad, d_cnt, G, d_tcnt);
     bfq_exscan_u32(c, d_sizes, d_off, nrec, d_off + nrec);
     u64 firstBad = UBAM_NONE, total = 0;
     bfq_ubam_cnt C{};
+    bfq_ubam_tcnt TC{};
+    if (G.on) HIP_CHECK(hipMemcpyAsync(&TC, d_tcnt, sizeof TC, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipMemcpyAsync(&firstBad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipMemcpyAsync(&total, d_off + nrec, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipMemcpyAsync(&C, d_cnt, sizeof C, hipMemcpyDeviceToHost, c->stream));
@@ -128,12 +146,13 @@ static void ubam_records(bfq_ctx *c, const u8 *const d_t[3], const u64 len[3], c
     }
     const u64 raw = hdr.size() + total;
     bfq_ubam_totals(J, raw, C, &out->S);
+    out->T.tags_written = TC.written; out->T.fields_dropped = TC.dropped; out->T.tag_bytes = TC.bytes;
     out->raw = raw;
     sized(raw);
     if (measure) { c->profCollect(); return; }
     u8 *d_s = c->alloc<u8>(raw + 64);
     bfq_upload(c, d_s, hdr.data(), hdr.size());
-    bfq_ubam_launch_write(c, J, nrec, d_off, d_s + hdr.size(), raw, d_cnt);
+    bfq_ubam_launch_write(c, J, nrec, d_off, d_s + hdr.size(), raw, d_cnt, G);
     HIP_CHECK(hipMemcpyAsync(&C, d_cnt, sizeof C, hipMemcpyDeviceToHost, c->stream));
     c->sync();                                                      // (hdr and tag live till here)
     c->profCollect();
@@ -142,7 +161,7 @@ static void ubam_records(bfq_ctx *c, const u8 *const d_t[3], const u64 len[3], c
 }
 
 // Steps 1-3.  extra(bound): arena bytes the caller needs behind them for a stream of at most that length.
-static void ubam_core(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts &O, bool measure, const std::function<size_t(u64)> &extra,
+static void ubam_core(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts &O, const bfq_ubam_tagsel &G, bool measure, const std::function<size_t(u64)> &extra,
                       const std::function<void(u64)> &sized, UbamStream *out)
 {
     bfq_ubam_err R;
@@ -191,7 +210,7 @@ static void ubam_core(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts &O, bo
     bfq_phase("alloc");
     c->reserve(need + (measure ? 0 : extra(bound)) + (1u << 20));
     bfq_phase("gpu");
-    ubam_records(c, d_t, X.len, present, O, measure, sized, out);
+    ubam_records(c, d_t, X.len, present, O, G, measure, sized, out);
 }
 
 extern "C" int bfq_fastq_to_bam_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint64_t *raw_len,
@@ -203,10 +222,13 @@ extern "C" int bfq_fastq_to_bam_measure(bfq_ctx *c, const uint8_t *const h_text[
     return guarded(c, [&] {
         if (!h_text || !text_len || !raw_len) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_ubam_opts O = ubam_opts(opts);
+        bfq_ubam_tag_stats *tagStats = nullptr;
+        const bfq_ubam_tagsel G = ubam_tags(opts, &tagStats);
         UbamTexts X;
         for (int k = 0; k < 3; k++) { X.h[k] = h_text[k]; X.len[k] = h_text[k] ? text_len[k] : 0; }
         UbamStream U;
-        ubam_core(c, X, O, true, [](u64) { return (size_t)0; }, [](u64) {}, &U);
+        ubam_core(c, X, O, G, true, [](u64) { return (size_t)0; }, [](u64) {}, &U);
+        if (tagStats) *tagStats = U.T;
         *raw_len = U.raw;
         if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = U.S.written[k];
         if (stats) *stats = U.S;
@@ -221,10 +243,12 @@ extern "C" int bfq_fastq_to_bam_device(bfq_ctx *c, const uint8_t *const d_text[3
     return guarded(c, [&] {
         if (!d_text || !text_len || !raw_len || (!d_out_raw && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_ubam_opts O = ubam_opts(opts);
+        bfq_ubam_tag_stats *tagStats = nullptr;
+        const bfq_ubam_tagsel G = ubam_tags(opts, &tagStats);
         UbamTexts X;
         for (int k = 0; k < 3; k++) { X.d[k] = d_text[k]; X.len[k] = d_text[k] ? text_len[k] : 0; }
         UbamStream U;
-        ubam_core(c, X, O, false, [](u64) { return (size_t)0; }, [&](u64 raw) {
+        ubam_core(c, X, O, G, false, [](u64) { return (size_t)0; }, [&](u64 raw) {
             if (cap >= raw) return;
             *raw_len = raw;
             c->profCollect();
@@ -235,6 +259,7 @@ extern "C" int bfq_fastq_to_bam_device(bfq_ctx *c, const uint8_t *const d_text[3
         c->sync();
         *raw_len = U.raw;
         if (stats) *stats = U.S;
+        if (tagStats) *tagStats = U.T;
     });
 }
 
@@ -242,8 +267,10 @@ extern "C" int bfq_fastq_to_bam_device(bfq_ctx *c, const uint8_t *const d_text[3
 static void ubam_compressed(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts *opts, HostRef dst, u64 cap, uint64_t *out_len, bfq_ubam_stats *stats)
 {
     const bfq_ubam_opts O = ubam_opts(opts);
+    bfq_ubam_tag_stats *tagStats = nullptr;
+    const bfq_ubam_tagsel G = ubam_tags(opts, &tagStats);
     UbamStream U;
-    ubam_core(c, X, O, false, [&](u64 bound) { return bfq_deflate_need(c, bound, false, 0) + 4096; }, [&](u64 raw) {
+    ubam_core(c, X, O, G, false, [&](u64 bound) { return bfq_deflate_need(c, bound, false, 0) + 4096; }, [&](u64 raw) {
         if (cap >= bfq_defl_bound(raw)) return;
         *out_len = bfq_defl_bound(raw);
         c->profCollect();
@@ -251,6 +278,7 @@ static void ubam_compressed(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts 
     }, &U);
     *out_len = bfq_deflate_core(c, U.d_s, HostRef{}, U.raw, (int)O.level, dst, true, 0);
     if (stats) *stats = U.S;
+    if (tagStats) *tagStats = U.T;
 }
 
 extern "C" int bfq_fastq_to_bam(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint8_t *h_out, uint64_t cap,
@@ -306,6 +334,8 @@ extern "C" int bfq_fastq_to_bam_fd(bfq_ctx *c, const int text_fd[3], const bfq_u
 size_t bfq_ubam_held_need(bfq_ctx *c, u64 bound, const bfq_ubam_opts *opts)
 {
     const bfq_ubam_opts O = ubam_opts(opts);
+    bfq_ubam_tag_stats *tagStats = nullptr;
+    ubam_tags(opts, &tagStats);                                     // (a tag list that is refused: here, before the restore begins)
     u64 rawBound = 0;
     const size_t need = ubam_need(bound, 4 * (bound / 6 + 1), 1, bfq_ubam_header(O).size(), bfq_ubam_tag(O).size(), true, &rawBound);
     return need + bfq_deflate_need(c, rawBound, false, 0) + 4096;
@@ -316,9 +346,12 @@ u64 bfq_ubam_held(bfq_ctx *c, const u8 *d_text, u64 len, const bfq_ubam_opts *op
     const u8 *d_t[3] = {d_text, nullptr, nullptr};
     const u64 lens[3] = {len, 0, 0};
     const bool present[3] = {true, false, false};
+    bfq_ubam_tag_stats *tagStats = nullptr;
+    const bfq_ubam_tagsel G = ubam_tags(opts, &tagStats);
     UbamStream U;
-    ubam_records(c, d_t, lens, present, O, false, [](u64) {}, &U);
+    ubam_records(c, d_t, lens, present, O, G, false, [](u64) {}, &U);
     const u64 zl = bfq_deflate_core(c, U.d_s, HostRef{}, U.raw, (int)O.level, dst, true, 0);
     if (stats) *stats = U.S;
+    if (tagStats) *tagStats = U.T;
     return zl;
 }

@@ -104,3 +104,20 @@ struct OutFile {
     }
     ~OutFile() { if (fd >= 0) ::close(fd); }
 };
+
+// A tag selection of the command line ("*": every tag; "BC,RX": those) into the n_tags / tag[][] of bfq_bam_tag_opts and
+// bfq_ubam_tag_opts.  false: not '*' and not a comma-separated list of at most 32 two-byte tags (what a tag may be the
+// library checks).
+static inline bool parse_tag_list(const char *arg, uint32_t *n, uint8_t tag[32][2])
+{
+    *n = 0;
+    if (!strcmp(arg, "*")) return true;
+    for (const char *p = arg;;) {
+        if (*n == 32 || !p[0] || !p[1] || p[0] == ',' || p[1] == ',') return false;
+        tag[*n][0] = (uint8_t)p[0]; tag[*n][1] = (uint8_t)p[1];
+        (*n)++;
+        if (!p[2]) return true;
+        if (p[2] != ',') return false;
+        p += 3;
+    }
+}

@@ -1,6 +1,6 @@
 // restore_main.cpp -- the way back from the compressed streams to a FASTQ file (not a tool of the reference, which leaves
 // this to `7z x` / `bsc d` + `paste`):
-//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z | -b] -o OUT.fq [-V]
+//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z | -b [-a LIST|'*']] -o OUT.fq [-V]
 // The inputs are what `bsc e`, bfq_fastq_job.compress_streams = 1 / 2 / 3 and parallel.py --compress write
 // (include/bfqzip_hip.h, bfq_fastq_restore_fd).  -P PERM: the BFQPERM1 file `bfq_reorder -P` / `parallel.py --keep-order`
 // wrote for the run: the records come back in the order of the original file (bfq_fastq_restore_ordered_fd).
@@ -11,7 +11,8 @@
 // original order draw on all groups at once.  -z: OUT.fq is written as BGZF (.fq.gz: bfq_fastq_restore_bgzf_fd, the text is
 // deflated on the device and never crosses to the host), with and without -P; not with -g / -G.  -b: the output is written as an
 // unaligned BAM instead (OUT.bam: bfq_fastq_restore_bam_fd, the restored text becomes unpaired records on the device and those
-// are deflated there), with and without -P; not with -z, -g / -G.  Exit status 0 on success; 1 with the library's message
+// are deflated there), with and without -P; not with -z, -g / -G; with -a LIST|'*' the fields XX:T:value of the restored header
+// lines become aux tags of the records (bfq_ubam_tag_opts, as bfq_bam -w -a).  Exit status 0 on success; 1 with the library's message
 // otherwise, and then OUT.fq is left empty.
 #include <unistd.h>
 #include <sys/mman.h>
@@ -20,7 +21,7 @@
 
 static int usage(const char *argv0)
 {
-    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z | -b] -o OUT.fq [-V]\n"
+    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z | -b [-a LIST|'*']] -o OUT.fq [-V]\n"
                     "  -d <arg>  container(s) of the DNA stream (OUT.fq.dna; BFQDNAC1 / BFQRANS2 members, or one BFQEBWT1) (REQUIRED)\n"
                     "  -q <arg>  container(s) of the quality stream (OUT.fq.qs) (REQUIRED)\n"
                     "  -H <arg>  container(s) of the header stream (OUT.h); without it every header line is \"@\"\n"
@@ -30,6 +31,7 @@ static int usage(const char *argv0)
                     "  -l        print the plan of the groups and exit (no GPU, no output file; -o not needed)\n"
                     "  -z        write the output as BGZF (OUT.fq.gz), deflated on the GPU; not with -g / -G\n"
                     "  -b        write the output as an unaligned BAM (OUT.bam), records made and deflated on the GPU; not with -z, -g / -G\n"
+                    "  -a <arg>  with -b: the fields XX:T:value of the header lines become aux tags: '*' = every field, or a list (BC,RX)\n"
                     "  -o <arg>  output FASTQ (REQUIRED)\n"
                     "  -V        phase timeline on stderr\n", argv0);
     return 1;
@@ -70,10 +72,12 @@ int main(int argc, char **argv)
 {
     bfq_phase("start");
     std::string dna, qs, hdr, perm, output;
-    bool grouped = false, list = false, bgzf = false, ubam = false;
+    bool grouped = false, list = false, bgzf = false, ubam = false, tags = false, verbose = false;
+    bfq_ubam_tag_opts X = {};
+    bfq_ubam_tag_stats TS = {};
     uint64_t first = 0, count = ~0ull;
     int opt;
-    while ((opt = getopt(argc, argv, "d:q:H:P:o:gG:lzbVh")) != -1) {
+    while ((opt = getopt(argc, argv, "d:q:H:P:o:gG:lzba:Vh")) != -1) {
         switch (opt) {
         case 'd': dna = optarg; break;
         case 'q': qs = optarg; break;
@@ -92,7 +96,10 @@ int main(int argc, char **argv)
         case 'l': list = true; break;
         case 'z': bgzf = true; break;
         case 'b': ubam = true; break;
-        case 'V': bfq_phase_enable(1); break;
+        case 'a':
+            if (!parse_tag_list(optarg, &X.n_tags, X.tag)) { fprintf(stderr, "bfq_restore: -a: '*', or at most 32 two-byte tags separated by commas\n"); return usage(argv[0]); }
+            tags = true; break;
+        case 'V': bfq_phase_enable(1); verbose = true; break;
         default: return usage(argv[0]);
         }
     }
@@ -111,6 +118,8 @@ int main(int argc, char **argv)
         fprintf(stderr, "bfq_restore: -b does not go with -z (a BAM file is BGZF already) or with -g / -G (the grouped restore writes plain text)\n");
         return usage(argv[0]);
     }
+    if (tags && !ubam) { fprintf(stderr, "bfq_restore: -a needs -b: tags are written into a BAM\n"); return usage(argv[0]); }
+    if (tags) { bfq_ubam_default_opts(&X.o); X.o.reserved = BFQ_UBAM_OPTS_TAGS; X.stats = &TS; }
     InFile fd, fq, fh, fp;
     if (!fd.open(dna) || !fq.open(qs) || (!hdr.empty() && !fh.open(hdr)) || (!perm.empty() && !fp.open(perm))) { fprintf(stderr, "bfq_restore: cannot read the inputs\n"); return 1; }
     if (list) return list_groups(fd, fq, hdr.empty() ? nullptr : &fh);
@@ -145,8 +154,8 @@ int main(int argc, char **argv)
     if (!c) return 1;
     uint64_t outLen = 0, reads = 0, rawLen = 0;
     bfq_ubam_stats US = {};
-    const int rc = ubam ? bfq_fastq_restore_bam_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd, fp.size, nullptr,
-                                                   outText.fd, &outLen, &US)
+    const int rc = ubam ? bfq_fastq_restore_bam_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd, fp.size,
+                                                   tags ? &X.o : nullptr, outText.fd, &outLen, &US)
                    : bgzf ? bfq_fastq_restore_bgzf_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd, fp.size, 1,
                                                     outText.fd, &outLen, &rawLen, &reads)
                    : grouped ? bfq_fastq_restore_grouped_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, first, count, outText.fd, &outLen, &reads)
@@ -164,6 +173,9 @@ int main(int argc, char **argv)
     bfq_destroy(c);
     if (!closed) { perror("bfq_restore"); return 1; }
     bfq_phase_report("bfq_restore");
+    if (tags && verbose)
+        fprintf(stderr, "bfq_restore: tags: %llu written, %llu fields dropped, %llu bytes of stream\n", (unsigned long long)TS.tags_written,
+                (unsigned long long)TS.fields_dropped, (unsigned long long)TS.tag_bytes);
     if (ubam) printf("%llu records, %llu bytes of stream -> %llu bytes\n", (unsigned long long)US.records, (unsigned long long)US.raw_len, (unsigned long long)outLen);
     else if (bgzf) printf("%llu reads, %llu bytes -> %llu bytes\n", (unsigned long long)reads, (unsigned long long)rawLen, (unsigned long long)outLen);
     else printf("%llu reads, %llu bytes\n", (unsigned long long)reads, (unsigned long long)outLen);

@@ -231,11 +231,12 @@ def bam_names(path, out, split):
     return [os.path.join(d, root + tag + ".fastq") for tag in (("_1", "_2") if split else ("",))]
 
 
-def convert_bam_inputs(eng, comm, inputs, out="", paired=False, log=None):
+def convert_bam_inputs(eng, comm, inputs, out="", paired=False, log=None, tags=None):
     """--bam: an input for which api.bam_probe holds is converted to FASTQ text on the GPU (eng.bam_to_fastq_files) by rank 0
     before the line index is built, as inflate_inputs does for .gz, and the run goes on with that file: returns (the new
     input list, the files written).  With -p and a single BAM input the file is split by its READ1 / READ2 flags, with the
-    pairing check (records that are neither are left out), and the run goes on as a two-file paired run."""
+    pairing check (records that are neither are left out), and the run goes on as a two-file paired run.  tags (--bam-tags):
+    the aux tags written behind the names (api.bam_opts)."""
     from . import api
     new, tmp = [], []
     for p in inputs:
@@ -247,9 +248,10 @@ def convert_bam_inputs(eng, comm, inputs, out="", paired=False, log=None):
         split = paired and len(inputs) == 1
         q = bam_names(p, out, split)
         if comm.rank == 0:                                          # (a damaged or unpaired file: the library's message)
-            n, reads, st = eng.bam_to_fastq_files(p, (None, q[0], q[1]) if split else (q[0], None, None), split=int(split), paired_check=int(split))
+            n, reads, st = eng.bam_to_fastq_files(p, (None, q[0], q[1]) if split else (q[0], None, None), split=int(split), paired_check=int(split),
+                                                      **(dict(tags=tags) if tags else {}))
             if log:
-                log(f"bam: {p} -> {q}, {reads} reads, {st}")
+                log(f"bam: {p} -> {q}, {reads} reads, {st}" + (f", {st.tags}" if tags else ""))
         new += q
         tmp += q
     if tmp:
@@ -714,8 +716,25 @@ def main(argv=None):
                     help="with a merged FASTQ output: after the run the output text becomes an unaligned BAM on the GPU of rank 0 "
                          "and goes to PATH (with -p both merged texts become one paired uBAM, the names compared with -H); "
                          "not with --bam-out, --restore, --streams-only or --compress")
+    ap.add_argument("--bam-tags", default="", metavar="LIST",
+                    help="aux tags through the FASTQ header lines: '*' = every tag, or a list (BC,RX).  With --bam the selected tags of "
+                         "a record are written behind its name as <tab>XX:T:value; with --ubam-out the fields XX:T:value of the header "
+                         "lines become tags of the records; needs kept headers (-H or --m3); --bam-out keeps the input's tags as they are")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.bam_tags:
+        why = None
+        try:
+            api._tag_list(a.bam_tags, "--bam-tags")
+        except ValueError as e:
+            why = str(e)
+        if not why and not (a.headers or a.m3):
+            why = "--bam-tags needs kept headers (-H or --m3): a run without them writes \"@\" alone and the tags would be lost"
+        elif not why and not (a.bam or a.ubam_out):
+            why = "--bam-tags applies to a --bam input and to --ubam-out: one of them"
+        if why:
+            print("=== ERROR ===\n" + why, file=sys.stderr)
+            return 1
     if a.ubam_out:
         why = None
         if a.bam_out:
@@ -788,7 +807,7 @@ def main(argv=None):
         return 0
     converted, bam_src = [], a.input[0]
     if a.bam:
-        a.input, converted = convert_bam_inputs(eng, comm, a.input, a.out, paired=a.paired, log=log)
+        a.input, converted = convert_bam_inputs(eng, comm, a.input, a.out, paired=a.paired, log=log, tags=a.bam_tags or None)
         if a.paired and len(a.input) != 2:
             print("=== ERROR ===\npaired end mode", file=sys.stderr)
             return 1
@@ -839,9 +858,10 @@ def main(argv=None):
         if comm.rank == 0:
             fq = [n["fastq"] for n in names]
             try:
-                n, st = eng.fastq_to_bam_files((None, fq[0], fq[1]) if a.paired else (fq[0],), a.ubam_out, paired_check=int(a.paired and a.headers))
+                n, st = eng.fastq_to_bam_files((None, fq[0], fq[1]) if a.paired else (fq[0],), a.ubam_out, paired_check=int(a.paired and a.headers),
+                                                   **(dict(tags=a.bam_tags) if a.bam_tags else {}))
                 if log:
-                    log(f"ubam-out: {' '.join(fq)} -> {a.ubam_out}, {n} bytes, {st}")
+                    log(f"ubam-out: {' '.join(fq)} -> {a.ubam_out}, {n} bytes, {st}" + (f", {st.tags}" if a.bam_tags else ""))
             except api.BfqError as e:                                # (a refusal: the library's message; every rank leaves with it)
                 failed = e
                 print(f"=== ERROR ===\n--ubam-out: {e}", file=sys.stderr)

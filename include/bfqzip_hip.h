@@ -755,6 +755,21 @@ typedef struct bfq_bam_opts { uint32_t exclude_flags, mate_suffix, default_qual,
 typedef struct bfq_bam_stats {
     uint64_t records, written[3], skipped, reversed, no_qual, clamped_quals, n_ref, header_bytes, pieces, walkers, dead, repaired, rounds;
 } bfq_bam_stats;
+/* Aux tags into the header line -- this project's definition, modelled on `samtools fastq -T` (csrc/bfq_bam.h states it in
+ * full).  opts->reserved == BFQ_BAM_OPTS_TAGS: opts points to a bfq_bam_tag_opts, read by bfq_bam_measure, bfq_bam_to_fastq,
+ * _device, _fd and _host (bfq_bam_patch* ignores it; any other value of reserved is ignored as before).  Behind the name and
+ * its suffix every selected tag of a kept record is written as \tXX:T:value, in the record's order: A as XX:A:c, c C s S i I
+ * as XX:i:<decimal>, Z and H as XX:Z: / XX:H:<bytes>.  n_tags 0: every tag; else the tags of tag[0, n_tags) (at most 32,
+ * each [A-Za-z][A-Za-z0-9], else BFQ_E_ARG before any work).  A selected tag of type f or B, one whose Z / H value or A
+ * character holds a byte outside [0x20, 0x7e], and one whose key is not [A-Za-z][A-Za-z0-9] is left out and counted
+ * (tags_dropped) -- with strict refused, nothing written: "BAM tags: record <i> at byte <off>: tag <XX> of type <T> cannot
+ * be carried".  The tag area of every kept record must parse (a known type, every value inside the block, a NUL for every
+ * Z / H), else "damaged BAM input: record <i> at byte <off>: malformed tag area".  *stats (may be NULL): tags_written,
+ * tags_dropped, tag_bytes (the bytes of text the tags took).  With tags the host and file forms reserve 5/2 of the stream
+ * for the texts. */
+#define BFQ_BAM_OPTS_TAGS 0x31474154u
+typedef struct bfq_bam_tag_stats { uint64_t tags_written, tags_dropped, tag_bytes; } bfq_bam_tag_stats;
+typedef struct bfq_bam_tag_opts { bfq_bam_opts o; uint32_t n_tags, strict; uint8_t tag[32][2]; bfq_bam_tag_stats *stats; } bfq_bam_tag_opts;
 void bfq_bam_default_opts(bfq_bam_opts *o);
 int bfq_bam_probe(const uint8_t *h, uint64_t len);
 int bfq_bam_measure(bfq_ctx *c, const uint8_t *h_in, uint64_t len, const bfq_bam_opts *opts, uint64_t out_len[3], uint64_t n_reads[3],
@@ -876,6 +891,21 @@ typedef struct bfq_ubam_opts {
     const char *rg_id;
 } bfq_ubam_opts;
 typedef struct bfq_ubam_stats { uint64_t records, written[3], named, comments_dropped, unknown_bases, raw_len, members; } bfq_ubam_stats;
+/* Aux tags out of the header line -- this project's definition, modelled on `samtools import -T` (csrc/bfq_ubam.h states it
+ * in full).  opts->reserved == BFQ_UBAM_OPTS_TAGS: opts points to a bfq_ubam_tag_opts, read by every entry point that takes
+ * a bfq_ubam_opts (any other value of reserved is ignored as before).  Behind the name the header line is cut at tabs (a
+ * name ended by a space: the bytes up to the first tab are a comment and dropped).  A field [A-Za-z][A-Za-z0-9]:[AiZH]:value
+ * -- A: one byte of [ -~]; i: an optional '-' and 1..10 digits within [-2^31, 2^32 - 1], stored at the smallest width (C S I
+ * / c s i); Z: bytes of [ -~]; H: an even number of hex digits -- becomes a tag of the record, in line order, between QUAL and
+ * the RG tag of rg_id, when n_tags is 0 or it is one of tag[0, n_tags) (at most 32, each [A-Za-z][A-Za-z0-9], else BFQ_E_ARG
+ * before any work).  Every other field is dropped and counted (fields_dropped), never refused; so is an RG field when rg_id
+ * is set.  comments_dropped then counts the reads of which some byte behind the name did not become a tag.  *stats (may be
+ * NULL): tags_written, fields_dropped, tag_bytes (the bytes of stream the tags took).  BAM -> text (every tag) -> BAM (tags
+ * on, header_text the original's) gives the stream back byte for byte for uBAM records of flags 4 / 77 / 141 with qualities
+ * <= 93 whose tags are of types A / Z / H or integers at their smallest width, with printable values. */
+#define BFQ_UBAM_OPTS_TAGS 0x32474154u
+typedef struct bfq_ubam_tag_stats { uint64_t tags_written, fields_dropped, tag_bytes; } bfq_ubam_tag_stats;
+typedef struct bfq_ubam_tag_opts { bfq_ubam_opts o; uint32_t n_tags, pad; uint8_t tag[32][2]; bfq_ubam_tag_stats *stats; } bfq_ubam_tag_opts;
 void bfq_ubam_default_opts(bfq_ubam_opts *o);
 int bfq_fastq_to_bam_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint64_t *raw_len,
                              uint64_t n_reads[3], bfq_ubam_stats *stats);
