@@ -1350,6 +1350,10 @@ class Engine:
         return int(self.L.bfq_stream_bound(n))
 
     # ---- profiling
+    def refine_form(self):
+        """The refinement's chunk kernel in use: 1 = text words by two loads side by side, 0 = BFQ_REFINE_PIPE=0 (as set_params() read it)."""
+        return int(self.L.bfq_refine_form(self.h))
+
     def prof_reset(self):
         self.L.bfq_prof_reset(self.h)
 

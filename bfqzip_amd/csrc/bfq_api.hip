@@ -310,6 +310,7 @@ extern "C" int bfq_radix_geometry(uint64_t n_rows, uint64_t *tile_rows, uint64_t
     if (block_rows) *block_rows = bfq_radix_block_elems(n_rows);
     return BFQ_OK;
 }
+extern "C" int bfq_refine_form(bfq_ctx *c) { return c ? (c->env.refinePipe ? 1 : 0) : BFQ_E_ARG; }
 extern "C" int bfq_prof_get(bfq_ctx *c, int idx, char *name, int cap, double *ms, uint64_t *launches, double *bytes)
 {
     if (!c || idx < 0 || idx >= K_NUM) return BFQ_E_ARG;

@@ -61,6 +61,7 @@ BfqEnv bfq_env_read()
         e.posBins = geti("BFQ_POSBINS", 1) != 0;
         e.posBinWc = geti("BFQ_POSBIN_WC", 1) != 0;
         e.fuseKeys = geti("BFQ_FUSEKEYS", 1) != 0;
+        e.refinePipe = geti("BFQ_REFINE_PIPE", 1) != 0;
         e.ioThreads = geti("BFQ_IO_THREADS", 0);
         e.prefaultThreads = geti("BFQ_PREFAULT_THREADS", -1);
         e.hugeCap = getu("BFQ_HUGE_CAP", 0);

@@ -23,6 +23,7 @@ struct BfqEnv {
     bool posBins = true;            // BFQ_POSBINS=0: the device-resident fused path inverts by LF walks again (A/B runs)
     bool posBinWc = true;           // BFQ_POSBIN_WC=0: the position bins write per-tile runs at the bin's cursor again, not whole 64-byte chunks (A/B runs)
     bool fuseKeys = true;           // BFQ_FUSEKEYS=0: step 1 in one piece writes the sort records with k_build_keys and streams all five passes again (A/B runs)
+    bool refinePipe = true;         // BFQ_REFINE_PIPE=0: the refinement's chunk kernel loads a round's third text word behind the first two again (k_refine_chunk_seq; A/B runs)
     int ioThreads = 0;              // BFQ_IO_THREADS: staging workers (0: by core count)
     int prefaultThreads = -1;       // BFQ_PREFAULT_THREADS: helpers that fault in output mappings (-1: by core count)
     unsigned long long hugeCap = 0; // BFQ_HUGE_CAP: slot budget of the huge-segment rounds (test knob)

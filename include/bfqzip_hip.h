@@ -971,6 +971,9 @@ int  bfq_posbin_geometry(uint64_t n_rows, uint64_t *window, int *bin_shift);
 /* introspection: how the suffix sort cuts n_rows rows -- the rows of a scatter tile and of a radix block (a whole number of
  * tiles, which one workgroup runs through one after the other; fewer tiles for smaller collections). */
 int  bfq_radix_geometry(uint64_t n_rows, uint64_t *tile_rows, uint64_t *block_rows);
+/* introspection: which form of the refinement's chunk kernel the context launches, as bfq_create() / bfq_set_params() read it
+ * from BFQ_REFINE_PIPE: 1 (default) = a round's text words by two loads side by side, 0 = the third word behind the first two. */
+int  bfq_refine_form(bfq_ctx *c);
 int  bfq_prof_get(bfq_ctx *c, int idx, char *name, int name_cap, double *total_ms,
                   uint64_t *launches, double *alg_bytes_total);
 /* per-launch durations (ms, launch order, since the last reset) of ONE kernel chosen by its bfq_prof_get index (-1: none):
