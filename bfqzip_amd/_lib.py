@@ -43,6 +43,9 @@ SYMBOLS = [
     "bfq_bam_patch_host", "bfq_bam_patch_device", "bfq_bam_patch", "bfq_bam_patch_fd",
     "bfq_ubam_default_opts", "bfq_fastq_to_bam_measure", "bfq_fastq_to_bam_host", "bfq_ubam_host_error", "bfq_fastq_to_bam_device", "bfq_fastq_to_bam",
     "bfq_fastq_to_bam_fd", "bfq_fastq_restore_bam_fd",
+    "bfq_pairs_default_opts", "bfq_pairs_host_error",
+    "bfq_fastq_deinterleave_measure", "bfq_fastq_deinterleave", "bfq_fastq_deinterleave_device", "bfq_fastq_deinterleave_fd", "bfq_fastq_deinterleave_host",
+    "bfq_fastq_interleave_measure", "bfq_fastq_interleave", "bfq_fastq_interleave_device", "bfq_fastq_interleave_fd", "bfq_fastq_interleave_host",
     "bfq_workspace_bytes", "bfq_workspace_read", "bfq_version",
 ]
 
@@ -188,6 +191,22 @@ UBAM_OPTS_TAGS = 0x32474154                                        # BFQ_UBAM_OP
 class UbamTagOpts(C.Structure):
     """bfq_ubam_tag_opts: o (a UbamOpts whose reserved holds UBAM_OPTS_TAGS), n_tags (0: every field), pad, tag[32][2], stats"""
     _fields_ = [("o", UbamOpts), ("n_tags", C.c_uint32), ("pad", C.c_uint32), ("tag", (C.c_uint8 * 2) * 32), ("stats", C.POINTER(UbamTagStats))]
+
+
+class PairsOpts(C.Structure):
+    """bfq_pairs_opts: check_names, mate_suffix, orphans, reserved (must be 0)"""
+    _fields_ = [(k, C.c_uint32) for k in ("check_names", "mate_suffix", "orphans", "reserved")]
+
+
+class PairsStats(C.Structure):
+    """bfq_pairs_stats: records, pairs, singles, out_len[3]"""
+    _fields_ = [(k, C.c_uint64) for k in ("records", "pairs", "singles")] + [("out_len", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {k: [int(v) for v in self.out_len] if k == "out_len" else int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "PairsStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
 
 
 CMP_SYMS = 6
@@ -397,6 +416,21 @@ def lib():
         L.bfq_fastq_to_bam.argtypes = [vp, C.POINTER(vp), a3, puo, vp, u64, pu64, pus]
         L.bfq_fastq_to_bam_fd.argtypes = [vp, i3, puo, C.c_int, pu64, pus]
         L.bfq_fastq_restore_bam_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, puo, C.c_int, pu64, pus]
+        ppo, pps2 = C.POINTER(PairsOpts), C.POINTER(PairsStats)
+        L.bfq_pairs_default_opts.restype = None
+        L.bfq_pairs_default_opts.argtypes = [ppo]
+        L.bfq_pairs_host_error.restype = C.c_char_p
+        L.bfq_pairs_host_error.argtypes = []
+        L.bfq_fastq_deinterleave_measure.argtypes = [vp, vp, u64, ppo, a3, a3, pps2]
+        L.bfq_fastq_deinterleave.argtypes = [vp, vp, u64, ppo, C.POINTER(vp), a3, a3, a3, pps2]
+        L.bfq_fastq_deinterleave_device.argtypes = [vp, vp, u64, ppo, C.POINTER(vp), a3, a3, a3, pps2]
+        L.bfq_fastq_deinterleave_fd.argtypes = [vp, C.c_int, u64, ppo, i3, a3, a3, pps2]
+        L.bfq_fastq_deinterleave_host.argtypes = [vp, u64, ppo, C.POINTER(vp), a3, a3, a3, pps2]
+        L.bfq_fastq_interleave_measure.argtypes = [vp, C.POINTER(vp), a3, ppo, pu64, a3, pps2]
+        L.bfq_fastq_interleave.argtypes = [vp, C.POINTER(vp), a3, ppo, vp, u64, pu64, pps2]
+        L.bfq_fastq_interleave_device.argtypes = [vp, C.POINTER(vp), a3, ppo, vp, u64, pu64, pps2]
+        L.bfq_fastq_interleave_fd.argtypes = [vp, i3, ppo, C.c_int, pu64, pps2]
+        L.bfq_fastq_interleave_host.argtypes = [C.POINTER(vp), a3, ppo, vp, u64, pu64, pps2]
         L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_radix_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(u64)]

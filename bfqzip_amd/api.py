@@ -431,6 +431,64 @@ def fastq_to_bam_host(texts, out=None, **opts):
     return out[:int(rl.value)], st
 
 
+def pairs_opts(check_names=1, mate_suffix=1, orphans=0, reserved=0):
+    """bfq_pairs_opts (include/bfqzip_hip.h); the defaults are bfq_pairs_default_opts'.  check_names: the keys of the two mates
+    of every pair are compared; mate_suffix: a trailing /1 or /2 is no part of the key; orphans: the split pairs the records
+    of every run of equal keys and sends what is left over to output 0; reserved must be 0."""
+    o = _lib.PairsOpts()
+    o.check_names, o.mate_suffix, o.orphans, o.reserved = int(check_names), int(mate_suffix), int(orphans), int(reserved)
+    return o
+
+
+def _pairs_raise(rc, msg, needed):
+    e = BfqError(rc, msg)
+    e.needed = [int(v) for v in needed] if hasattr(needed, "__len__") else int(needed)   # the lengths needed, when a buffer was too small; else 0
+    raise e
+
+
+def fastq_deinterleave_host(text, outs=None, **opts):
+    """(texts[3], stats) of an interleaved FASTQ text split by the host form (bfq_fastq_deinterleave_host: the steps of
+    csrc/bfq_pairs.h by one thread, no GPU): the statement of the algorithm -- Engine.fastq_deinterleave gives the same bytes,
+    stats and messages.  texts[1] / texts[2]: the mates; texts[0]: the singletons of orphans=1.  opts: pairs_opts().  `outs`:
+    three uint8 arrays to fill; one that is too small raises BfqError with .needed = the three lengths, nothing written.
+    stats.n_reads: the reads per output."""
+    text = _u8(text)
+    L = _lib.lib()
+    O, st = pairs_opts(**opts), _lib.PairsStats()
+    ol, nr = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+    src = _ptr(text) if len(text) else None
+    if outs is None:
+        rc = L.bfq_fastq_deinterleave_host(src, len(text), C.byref(O), None, None, ol, nr, C.byref(st))
+        if rc != 0:
+            _pairs_raise(rc, L.bfq_pairs_host_error().decode(), ol)
+        outs = [np.empty(int(v), np.uint8) for v in ol]
+    ptrs, caps = _bam_outs(outs)
+    rc = L.bfq_fastq_deinterleave_host(src, len(text), C.byref(O), ptrs, caps, ol, nr, C.byref(st))
+    if rc != 0:
+        _pairs_raise(rc, L.bfq_pairs_host_error().decode(), ol)
+    st.n_reads = [int(v) for v in nr]
+    return [o[:int(n)] for o, n in zip(outs, ol)], st
+
+
+def fastq_interleave_host(texts, out=None, **opts):
+    """(the interleaved text, stats) of the mates texts[1] and texts[2] (and the reads of an optional texts[0] behind the
+    pairs; None: absent) by the host form (bfq_fastq_interleave_host, no GPU): Engine.fastq_interleave gives the same bytes,
+    stats and messages.  opts: pairs_opts().  `out`: a uint8 array to fill; one that is too small raises BfqError with
+    .needed = the length, nothing written."""
+    L = _lib.lib()
+    keep, ptrs, lens = _bam_texts(texts)
+    O, st, ol = pairs_opts(**opts), _lib.PairsStats(), C.c_uint64(0)
+    if out is None:
+        rc = L.bfq_fastq_interleave_host(ptrs, lens, C.byref(O), None, 0, C.byref(ol), C.byref(st))
+        if rc != 0:
+            _pairs_raise(rc, L.bfq_pairs_host_error().decode(), 0)
+        out = np.empty(int(ol.value), np.uint8)
+    rc = L.bfq_fastq_interleave_host(ptrs, lens, C.byref(O), _ptr(out) if len(out) else None, len(out), C.byref(ol), C.byref(st))
+    if rc != 0:
+        _pairs_raise(rc, L.bfq_pairs_host_error().decode(), ol.value)
+    return out[:int(ol.value)], st
+
+
 def text_len(a):
     """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
     a = _u8(a)
@@ -453,6 +511,8 @@ class HostText:
     bam_to_fastq_host = staticmethod(bam_to_fastq_host)
     bam_patch_host = staticmethod(bam_patch_host)
     fastq_to_bam_host = staticmethod(fastq_to_bam_host)
+    fastq_deinterleave_host = staticmethod(fastq_deinterleave_host)
+    fastq_interleave_host = staticmethod(fastq_interleave_host)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -1039,6 +1099,109 @@ class Engine:
             rc = self.L.bfq_fastq_to_bam_fd(self.h, (C.c_int * 3)(*fds[0:3]), C.byref(O), fds[3], C.byref(ol), C.byref(st))
             if rc != 0:
                 _ubam_raise(rc, self.L.bfq_last_error(self.h).decode(), ol.value)
+            return int(ol.value), st
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+    # ---- interleaved paired FASTQ (bfq_fastq_deinterleave* / bfq_fastq_interleave*, csrc/bfq_pairs.h)
+    def _pairs_ck(self, rc, needed):
+        if rc != 0:
+            _pairs_raise(rc, self.L.bfq_last_error(self.h).decode(), needed)
+
+    def fastq_deinterleave_measure(self, text, **opts):
+        """bfq_fastq_deinterleave_measure: (the three text lengths, the three read counts, stats) of an interleaved FASTQ
+        text; nothing is written.  An improperly paired text raises BfqError with the library's message."""
+        text = _u8(text)
+        O, st, ol, nr = pairs_opts(**opts), _lib.PairsStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        self._pairs_ck(self.L.bfq_fastq_deinterleave_measure(self.h, _ptr(text) if len(text) else None, len(text), C.byref(O), ol, nr, C.byref(st)), ol)
+        return [int(v) for v in ol], [int(v) for v in nr], st
+
+    def fastq_deinterleave(self, text, outs=None, **opts):
+        """(texts[3], stats): an interleaved paired FASTQ text (plain, not compressed) split on the GPU (bfq_fastq_deinterleave)
+        into the mates texts[1] and texts[2]; with orphans=1 the singletons go to texts[0].  Records move byte for byte.
+        opts: pairs_opts() (check_names, mate_suffix, orphans).  `outs`: three uint8 arrays to fill; without them the text is
+        measured first.  A buffer below its text raises BfqError with .needed = the three lengths and nothing is written; an
+        improperly paired text raises BfqError ("interleaved FASTQ: pair <k> (records <2k> and <2k+1>): the names differ",
+        "interleaved FASTQ: <N> records, an odd number").  stats.n_reads: the reads per output."""
+        text = _u8(text)
+        if outs is None:
+            outs = [np.empty(v, np.uint8) for v in self.fastq_deinterleave_measure(text, **opts)[0]]
+        O, st, ol, nr = pairs_opts(**opts), _lib.PairsStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        ptrs, caps = _bam_outs(outs)
+        self._pairs_ck(self.L.bfq_fastq_deinterleave(self.h, _ptr(text) if len(text) else None, len(text), C.byref(O), ptrs, caps, ol, nr, C.byref(st)), ol)
+        st.n_reads = [int(v) for v in nr]
+        return [o[:int(n)] for o, n in zip(outs, ol)], st
+
+    def fastq_deinterleave_device(self, d_text, n, d_outs, caps, **opts):
+        """bfq_fastq_deinterleave_device: the text of n bytes at the device address d_text, the three texts at the device
+        addresses d_outs (caps bytes each; None / 0 with cap 0: none); returns (lengths, read counts, stats)."""
+        O, st, ol, nr = pairs_opts(**opts), _lib.PairsStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        ptrs, cp = (C.c_void_p * 3)(*[int(p) if p else None for p in d_outs]), (C.c_uint64 * 3)(*[int(v) for v in caps])
+        self._pairs_ck(self.L.bfq_fastq_deinterleave_device(self.h, C.c_void_p(d_text), int(n), C.byref(O), ptrs, cp, ol, nr, C.byref(st)), ol)
+        return [int(v) for v in ol], [int(v) for v in nr], st
+
+    def fastq_deinterleave_files(self, src, dsts, **opts):
+        """bfq_fastq_deinterleave_fd on named files: dsts = the paths of outputs 0 (singletons), 1, 2 (None: not written).
+        The outputs are left empty on a refusal.  Returns (lengths, read counts, stats)."""
+        import os
+        fds = []
+        try:
+            fds.append(os.open(src, os.O_RDONLY))
+            for d in dsts:
+                fds.append(os.open(d, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) if d is not None else -1)
+            O, st, ol, nr = pairs_opts(**opts), _lib.PairsStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+            self._pairs_ck(self.L.bfq_fastq_deinterleave_fd(self.h, fds[0], os.fstat(fds[0]).st_size, C.byref(O), (C.c_int * 3)(*fds[1:4]), ol, nr, C.byref(st)), ol)
+            return [int(v) for v in ol], [int(v) for v in nr], st
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+    def fastq_interleave_measure(self, texts, **opts):
+        """bfq_fastq_interleave_measure: (the interleaved text's length, the read counts of the three texts, stats); nothing
+        is written."""
+        keep, ptrs, lens = _bam_texts(texts)
+        O, st, ol, nr = pairs_opts(**opts), _lib.PairsStats(), C.c_uint64(0), (C.c_uint64 * 3)()
+        self._pairs_ck(self.L.bfq_fastq_interleave_measure(self.h, ptrs, lens, C.byref(O), C.byref(ol), nr, C.byref(st)), 0)
+        return int(ol.value), [int(v) for v in nr], st
+
+    def fastq_interleave(self, texts, out=None, **opts):
+        """(the interleaved text, stats): the mates texts[1] and texts[2] merged on the GPU (bfq_fastq_interleave) into one
+        text with the mates alternating, the reads of an optional texts[0] behind the pairs (None: absent).  opts:
+        pairs_opts() (check_names, mate_suffix).  `out`: a uint8 array to fill (the sum of the texts' lengths, + 1 for each
+        that lacks its final newline); one that is too small raises BfqError with .needed = the length, nothing written.
+        Refusals raise BfqError ("FASTQ interleave: text 1 holds <n> reads, text 2 holds <m>", "FASTQ interleave: pair <k>:
+        the names differ")."""
+        keep, ptrs, lens = _bam_texts(texts)
+        if out is None:
+            out = np.empty(sum(len(t) + 1 for t in keep if t is not None), np.uint8)
+        O, st, ol = pairs_opts(**opts), _lib.PairsStats(), C.c_uint64(0)
+        self._pairs_ck(self.L.bfq_fastq_interleave(self.h, ptrs, lens, C.byref(O), _ptr(out) if len(out) else None, len(out), C.byref(ol), C.byref(st)), ol.value)
+        return out[:int(ol.value)], st
+
+    def fastq_interleave_device(self, d_texts, text_lens, d_out, cap, **opts):
+        """bfq_fastq_interleave_device: the texts at the device addresses d_texts (None / 0: absent), the interleaved text at
+        the device address d_out (cap bytes); returns (its length, stats)."""
+        ptrs = (C.c_void_p * 3)(*[int(p) if p else None for p in d_texts])
+        lens = (C.c_uint64 * 3)(*[int(v) for v in text_lens])
+        O, st, ol = pairs_opts(**opts), _lib.PairsStats(), C.c_uint64(0)
+        self._pairs_ck(self.L.bfq_fastq_interleave_device(self.h, ptrs, lens, C.byref(O), C.c_void_p(d_out), int(cap), C.byref(ol), C.byref(st)), ol.value)
+        return int(ol.value), st
+
+    def fastq_interleave_files(self, texts, dst, **opts):
+        """bfq_fastq_interleave_fd on named files: the FASTQ files texts[k] (None: absent) as the interleaved file dst (left
+        empty on a refusal).  Returns (the length of dst, stats)."""
+        import os
+        texts = list(texts) + [None] * (3 - len(texts))
+        fds = []
+        try:
+            for t in texts[:3]:
+                fds.append(os.open(t, os.O_RDONLY) if t is not None else -1)
+            fds.append(os.open(dst, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            O, st, ol = pairs_opts(**opts), _lib.PairsStats(), C.c_uint64(0)
+            self._pairs_ck(self.L.bfq_fastq_interleave_fd(self.h, (C.c_int * 3)(*fds[0:3]), C.byref(O), fds[3], C.byref(ol), C.byref(st)), ol.value)
             return int(ol.value), st
         finally:
             for fd in fds:

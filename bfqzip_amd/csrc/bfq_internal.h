@@ -30,7 +30,7 @@ enum BfqKernel {
     K_REFINE_WAVE, K_REFINE_BIG, K_EMIT, K_RANK_BUILD, K_RANK_FINAL, K_LCP_FLAGS, K_CLUSTER,
     K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER,
     K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_POSBIN_L1, K_POSBIN_L2, K_POSBIN_APPLY, K_POSBIN_CHECK,
-    K_CMP_CHECK, K_CMP_COMPARE, K_CMP_EMIT, K_BGZF, K_DEFLATE, K_UBAM_SIZE, K_UBAM_WRITE, K_NUM
+    K_CMP_CHECK, K_CMP_COMPARE, K_CMP_EMIT, K_BGZF, K_DEFLATE, K_UBAM_SIZE, K_UBAM_WRITE, K_PAIRS_CMP, K_PAIRS_MOVE, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -492,6 +492,17 @@ void bfq_reorder_gather(bfq_ctx *c, const RoText &t, const u64 *perm, const u64 
 void bfq_perm_pack(bfq_ctx *c, const u64 *perm, u64 N, u64 *d_words);                            // d_words: bfq_perm_words() of them
 u64 bfq_perm_unpack_invert(bfq_ctx *c, const u64 *d_words, u64 N, u64 *perm, u64 *inv);         // the first offending position, ~0: none; synchronises
 void bfq_reorder_sizes(bfq_ctx *c, const u64 *order, const RoText *mates, int nmates, u64 N, u64 *const *sizes);   // sizes[p][j] = size of record order[j]
+
+// interleaved paired FASTQ (k_pairs.hip; bfq_pairs.hip drives them; the definition: bfq_pairs.h).  A text of the call: its bytes,
+// its record index, its length (with its final LF) and its records.
+struct PrText { const u8 *buf; const FqRec *rec; u64 len, N; };
+void bfq_pairs_compare(bfq_ctx *c, const PrText &a, const PrText *b, u64 P, u32 suffix, u64 *d_firstBad);   // *d_firstBad preset to all-ones
+void bfq_pairs_run_starts(bfq_ctx *c, const PrText &a, u32 suffix, u64 *start);
+void bfq_pairs_roles(bfq_ctx *c, const PrText &a, const u64 *start, u8 *role, u64 *const sz[3], u64 *d_cnt);   // d_cnt[0, 2) zeroed: singles, pairs
+void bfq_pairs_pair_sizes(bfq_ctx *c, const PrText &a, u64 P, u64 *sz);
+void bfq_pairs_split(bfq_ctx *c, const PrText &a, const u64 *off1, u8 *o1, u8 *o2);
+void bfq_pairs_split_roles(bfq_ctx *c, const PrText &a, const u8 *role, const u64 *const off[3], u8 *const o[3]);
+void bfq_pairs_merge(bfq_ctx *c, const PrText &a, const PrText &b, u8 *out);
 
 // two FASTQ texts compared where they lie (k_compare.hip; bfq_compare.hip drives them).  inv == nullptr: read i of A pairs with
 // read i of B, else with read inv[i].  d_rep: a zeroed report on the device whose first_changed_read is all-ones.

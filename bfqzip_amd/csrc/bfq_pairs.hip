@@ -1,0 +1,516 @@
+// bfq_pairs.hip -- interleaved paired FASTQ (include/bfqzip_hip.h, bfq_fastq_deinterleave* / bfq_fastq_interleave*): the host
+// side of splitting one text with alternating mates and of merging two texts of mates.  The definition and the host forms
+// are bfq_pairs.h's; the kernels are k_pairs.hip's.  One call:
+//   1  every text looked at (1f 8b, its last byte), uploaded into the context's text buffer -- or taken where it lies on the
+//      device --, its lines counted there, the arena reserved from the counts, the texts indexed (bfq_fastq_index: the line
+//      index and record parser of every FASTQ entry point, and its refusals)
+//   2  the checks -- the record counts, the keys of the pairs -- and the sizes: exact output lengths, and the capacities
+//      checked against them.  Up to here nothing of the caller's has been touched
+//   3  the move, one copy of every record: into the caller's device buffers, or into the arena and from there through
+//      bfq_download (host buffers) or the background writers (files)
+//   arena   per text 8 bytes per line (and 12 per 4 KiB while they are indexed) and 44 per record; 16 bytes per pair (orphan
+//           mode: 57 per record) of sizes and offsets; the outputs unless they are the caller's device buffers
+// The *_host forms run bfq_pairs.h by one thread, for tests and as the statement of the algorithm: no entry point here falls
+// back to them.
+#include <string.h>
+#include <stdio.h>
+#include <sys/stat.h>
+#include <algorithm>
+#include <functional>
+#include "bfq_internal.h"
+#include "bfq_pairs.h"
+
+static_assert(sizeof(bfq_pairs_opts) == 16 && sizeof(bfq_pairs_stats) == 48, "the C-ABI's structures");
+
+#define PR_NL_CHUNK 4096u                                          // (k_fastq.hip's: bfq_line_index takes 12 bytes per chunk)
+
+static void pr_refuse(const bfq_pairs_err &X) { throw BfqError{bfq_pairs_code(X), bfq_pairs_message(X)}; }
+static bfq_pairs_opts pr_opts(const bfq_pairs_opts *in)
+{
+    bfq_pairs_opts O;
+    bfq_pairs_err X;
+    if (!bfq_pairs_resolve(in, &O, &X)) pr_refuse(X);
+    return O;
+}
+
+extern "C" void bfq_pairs_default_opts(bfq_pairs_opts *o) { if (o) bfq_pairs_defaults(o); }
+
+static thread_local std::string g_pairsHostErr;
+extern "C" const char *bfq_pairs_host_error(void) { return g_pairsHostErr.c_str(); }
+
+template <class F> static int pr_host_guarded(F body)
+{
+    g_pairsHostErr.clear();
+    try {
+        body();
+        return BFQ_OK;
+    } catch (const BfqError &e) {
+        g_pairsHostErr = e.msg;
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        g_pairsHostErr = "host out of memory";
+        return BFQ_E_NOMEM;
+    }
+}
+
+extern "C" int bfq_fastq_deinterleave_host(const uint8_t *text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const h_out[3], const uint64_t cap[3],
+                                           uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats)
+{
+    if (out_len) out_len[0] = out_len[1] = out_len[2] = 0;
+    if (n_reads) n_reads[0] = n_reads[1] = n_reads[2] = 0;
+    if (stats) *stats = bfq_pairs_stats{};
+    return pr_host_guarded([&] {
+        if (!out_len || (!text && len)) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_pairs_opts O = pr_opts(opts);
+        const bool measure = !h_out && !cap;
+        if (!measure && (!h_out || !cap)) throw BfqError{BFQ_E_ARG, "null argument"};
+        if (!measure)
+            for (int k = 0; k < 3; k++)
+                if (!h_out[k] && cap[k]) throw BfqError{BFQ_E_ARG, "null argument"};
+        bfq_pairs_stats S;
+        bfq_pairs_err X;
+        u64 nr[3];
+        const int r = bfq_pairs_split_host(text, len, O, h_out, cap, measure, &S, nr, &X);
+        if (r == 2) pr_refuse(X);
+        for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
+        if (r == 3) { X.kind = BFQ_PAIRS_E_CAP; pr_refuse(X); }
+        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+        if (stats) *stats = S;
+    });
+}
+
+extern "C" int bfq_fastq_interleave_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts, uint8_t *out, uint64_t cap,
+                                         uint64_t *out_len, bfq_pairs_stats *stats)
+{
+    if (out_len) *out_len = 0;
+    if (stats) *stats = bfq_pairs_stats{};
+    return pr_host_guarded([&] {
+        if (!text || !text_len || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_pairs_opts O = pr_opts(opts);
+        const bool measure = !out && !cap;
+        bfq_pairs_stats S;
+        bfq_pairs_err X;
+        u64 nr[3];
+        const int r = bfq_pairs_merge_host(text, text_len, O, out, cap, measure, &S, nr, &X);
+        if (r == 2) pr_refuse(X);
+        *out_len = S.out_len[0];
+        if (r == 3) { X.kind = BFQ_PAIRS_E_CAP; X.merge = 1; pr_refuse(X); }
+        if (stats) *stats = S;
+    });
+}
+
+// ---------------------------------------------------------------- the texts of a call
+// a text: host memory or an open file (ref), or device memory (d); neither: absent
+struct PrSrc {
+    HostRef ref; const u8 *d = nullptr; u64 len = 0;
+    bool present() const { return d || !ref.null(); }
+};
+
+static void pr_peek(bfq_ctx *c, const PrSrc &s, u64 off, u8 *dst, size_t n)
+{
+    if (s.d) { HIP_CHECK(hipMemcpyAsync(dst, s.d + off, n, hipMemcpyDeviceToHost, c->stream)); c->sync(); }
+    else if (s.ref.ptr) memcpy(dst, (const u8 *)s.ref.ptr + off, n);
+    else if (pread(s.ref.fd, dst, n, (off_t)(s.ref.off + off)) != (ssize_t)n) throw BfqError{BFQ_E_IO, "cannot read the input file"};
+}
+
+static void pr_nomem(bfq_ctx *c, size_t need)
+{
+    char b[240];
+    snprintf(b, sizeof b, "splitting or merging the mates needs %.2f GiB of device memory (text + outputs + index), above the cap of %.2f GiB "
+                          "(bfq_params.ws_cap_mib / BFQ_WS_CAP)", need / 1073741824.0, c->wsLimit() / 1073741824.0);
+    throw BfqError{BFQ_E_NOMEM, b};
+}
+
+// Step 1 for the texts src[0, 3) (merge: the refusal names the text): t[k] = text k on the device with its index (an absent
+// or empty text: no records).  orphans / arenaOut: what steps 2 and 3 take from the arena beside the index.
+static void pr_stage(bfq_ctx *c, const PrSrc src[3], u32 merge, bool orphans, bool arenaOut, PrText t[3])
+{
+    u64 tl[3] = {0, 0, 0};
+    bool moved[3] = {false, false, false};
+    size_t bufNeed = 0;
+    for (u32 k = 0; k < 3; k++) {
+        t[k] = PrText{nullptr, nullptr, 0, 0};
+        if (!src[k].present() || !src[k].len) continue;
+        u8 first[2] = {0, 0};
+        if (src[k].len >= 2) pr_peek(c, src[k], 0, first, 2);
+        bfq_pairs_err X;
+        if (!bfq_pairs_gzip_ok(first, src[k].len, merge, k, &X)) pr_refuse(X);
+    }
+    for (u32 k = 0; k < 3; k++) {
+        if (!src[k].present() || !src[k].len) continue;
+        u8 last = 10;
+        pr_peek(c, src[k], src[k].len - 1, &last, 1);
+        tl[k] = src[k].len + (last == 10 ? 0 : 1);
+        // a device text stays where it lies unless its address is no multiple of 16 (the line kernels read 16 aligned bytes at
+        // a time) or it lacks its final LF (which it gets in the copy)
+        moved[k] = !src[k].d || ((uintptr_t)src[k].d & 15u) || tl[k] != src[k].len;
+        if (moved[k]) bufNeed += ((size_t)tl[k] + 64 + 255) & ~(size_t)255;
+    }
+    const u64 bytes = tl[0] + tl[1] + tl[2], maxLen = std::max(tl[0], std::max(tl[1], tl[2]));
+    const size_t outBytes = arenaOut ? (size_t)bytes + 3 * 4096 : 0;
+    if (c->wsLimit() && bufNeed + outBytes > c->wsLimit()) pr_nomem(c, bufNeed + outBytes);
+    bfq_phase("alloc");
+    u8 *buf = bufNeed ? c->textBuf(bufNeed) : nullptr;
+    if (bufNeed) bfq_phase("read_h2d");
+    for (u32 k = 0; k < 3; k++) {
+        if (!tl[k]) continue;
+        t[k].buf = src[k].d; t[k].len = tl[k];
+        if (!moved[k]) continue;
+        if (src[k].d) HIP_CHECK(hipMemcpyAsync(buf, src[k].d, (size_t)src[k].len, hipMemcpyDeviceToDevice, c->stream));
+        else bfq_upload(c, buf, src[k].ref, src[k].len);
+        if (tl[k] > src[k].len) HIP_CHECK(hipMemsetAsync(buf + src[k].len, '\n', 1, c->stream));
+        t[k].buf = buf;
+        buf += ((size_t)tl[k] + 64 + 255) & ~(size_t)255;
+    }
+    bfq_phase("alloc");
+    c->reserve(12 * (size_t)(maxLen / PR_NL_CHUNK + 2) + 8192 + (1u << 20));
+    bfq_phase("gpu");
+    u64 lines[3] = {0, 0, 0}, nb = 0;
+    size_t need = outBytes + (4u << 20);
+    for (u32 k = 0; k < 3; k++) {
+        if (!tl[k]) continue;
+        lines[k] = bfq_fastq_count_lines(c, t[k].buf, tl[k]);
+        const u64 n = lines[k] / 4 + 2;
+        nb += n;
+        need += 8 * (size_t)(lines[k] + 64) + 12 * (size_t)(tl[k] / PR_NL_CHUNK + 2) + 8192 + 44 * (size_t)(n + 64) + 32 * (size_t)(n / 4096 + 2);
+    }
+    need += (orphans ? 57 : 8) * (size_t)(nb + 64) + 64 * (size_t)(nb / 4096 + 2);
+    if (c->wsLimit() && bufNeed + need > c->wsLimit()) pr_nomem(c, bufNeed + need);
+    bfq_phase("alloc");
+    c->reserve(need);
+    bfq_phase("gpu");
+    c->zeroCounters();
+    for (u32 k = 0; k < 3; k++) {
+        if (!tl[k]) continue;
+        DevFastq fq;
+        bfq_fastq_index(c, t[k].buf, tl[k], &fq);
+        t[k].rec = (const FqRec *)fq.rec; t[k].N = fq.N;
+    }
+}
+
+// what becomes of the outputs: sized(len) runs once the lengths are exact and before anything is written (it throws for a
+// short capacity, and opens files); d_dst[k]: the caller's device buffer, nullptr: the arena and then put()
+struct PrSink {
+    std::function<void(const u64 *)> sized;
+    u8 *d_dst[3] = {nullptr, nullptr, nullptr};
+    bool device = false;
+    std::function<void(int, const u8 *, u64)> put;
+};
+
+static u64 pr_first_bad(bfq_ctx *c, const PrText &a, const PrText *b, u64 P, u32 suffix)
+{
+    u64 *d_bad = c->alloc<u64>(1);
+    HIP_CHECK(hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    bfq_pairs_compare(c, a, b, P, suffix, d_bad);
+    u64 bad = BFQ_PAIRS_NONE;
+    HIP_CHECK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    return bad;
+}
+
+static void split_core(bfq_ctx *c, const PrSrc &in, const bfq_pairs_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_pairs_stats *S)
+{
+    const PrSrc src[3] = {in, PrSrc{}, PrSrc{}};
+    PrText t3[3];
+    pr_stage(c, src, 0, O.orphans != 0, !measure && !sink.device, t3);
+    const PrText &t = t3[0];
+    const u64 N = t.N;
+    bfq_pairs_err X;
+    u64 lens[3] = {0, 0, 0};
+    const u64 *off[3] = {nullptr, nullptr, nullptr};
+    const u8 *role = nullptr;
+    if (!O.orphans) {
+        if (N & 1) { c->profCollect(); X.kind = BFQ_PAIRS_E_ODD; X.n = N; pr_refuse(X); }
+        const u64 P = N / 2;
+        if (O.check_names) {
+            const u64 bad = pr_first_bad(c, t, nullptr, P, O.mate_suffix);
+            if (bad != BFQ_PAIRS_NONE) { c->profCollect(); X.kind = BFQ_PAIRS_E_NAMES; X.n = bad; pr_refuse(X); }
+        }
+        u64 *sz = c->alloc<u64>(P + 1), *off1 = c->alloc<u64>(P + 2);
+        bfq_pairs_pair_sizes(c, t, P, sz);
+        bfq_exscan_u64(c, sz, off1, P, off1 + P);
+        HIP_CHECK(hipMemcpyAsync(&lens[1], off1 + P, 8, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        lens[2] = t.len - lens[1];
+        nReads[0] = 0; nReads[1] = nReads[2] = P;
+        off[1] = off1;
+    } else {
+        u64 *start = c->alloc<u64>(N + 1), *sz[3], *o[3], *d_cnt = c->alloc<u64>(2), cnt[2] = {0, 0};
+        u8 *r = c->alloc<u8>(N + 1);
+        for (int k = 0; k < 3; k++) { sz[k] = c->alloc<u64>(N + 1); o[k] = c->alloc<u64>(N + 2); }
+        HIP_CHECK(hipMemsetAsync(d_cnt, 0, 16, c->stream));
+        bfq_pairs_run_starts(c, t, O.mate_suffix, start);
+        bfq_pairs_roles(c, t, start, r, sz, d_cnt);
+        for (int k = 0; k < 3; k++) {
+            bfq_exscan_u64(c, sz[k], o[k], N, o[k] + N);
+            HIP_CHECK(hipMemcpyAsync(&lens[k], o[k] + N, 8, hipMemcpyDeviceToHost, c->stream));
+            off[k] = o[k];
+        }
+        HIP_CHECK(hipMemcpyAsync(cnt, d_cnt, 16, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        nReads[0] = cnt[0]; nReads[1] = nReads[2] = cnt[1];
+        role = r;
+    }
+    *S = bfq_pairs_stats{};
+    S->records = N; S->pairs = nReads[1]; S->singles = nReads[0];
+    for (int k = 0; k < 3; k++) S->out_len[k] = lens[k];
+    sink.sized(lens);
+    if (measure) { c->profCollect(); return; }
+    u8 *dst[3];
+    for (int k = 0; k < 3; k++) dst[k] = sink.device ? sink.d_dst[k] : c->alloc<u8>(lens[k] + 64);
+    if (role) bfq_pairs_split_roles(c, t, role, off, dst);
+    else bfq_pairs_split(c, t, off[1], dst[1], dst[2]);
+    if (!sink.device)
+        for (int k = 0; k < 3; k++)
+            if (lens[k]) sink.put(k, dst[k], lens[k]);
+    c->sync();
+    c->profCollect();
+}
+
+static void merge_core(bfq_ctx *c, const PrSrc src[3], const bfq_pairs_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_pairs_stats *S)
+{
+    PrText t[3];
+    pr_stage(c, src, 1, false, !measure && !sink.device, t);
+    bfq_pairs_err X;
+    X.merge = 1;
+    if (t[1].N != t[2].N) { c->profCollect(); X.kind = BFQ_PAIRS_E_COUNTS; X.n = t[1].N; X.m = t[2].N; pr_refuse(X); }
+    const u64 P = t[1].N;
+    if (O.check_names) {
+        const u64 bad = pr_first_bad(c, t[1], &t[2], P, O.mate_suffix);
+        if (bad != BFQ_PAIRS_NONE) { c->profCollect(); X.kind = BFQ_PAIRS_E_NAMES; X.n = bad; pr_refuse(X); }
+    }
+    const u64 total = t[0].len + t[1].len + t[2].len;
+    *S = bfq_pairs_stats{};
+    S->records = 2 * P + t[0].N; S->pairs = P; S->singles = t[0].N; S->out_len[0] = total;
+    nReads[0] = t[0].N; nReads[1] = nReads[2] = P;
+    sink.sized(&total);
+    if (measure) { c->profCollect(); return; }
+    u8 *dst = sink.device ? sink.d_dst[0] : c->alloc<u8>(total + 64);
+    bfq_pairs_merge(c, t[1], t[2], dst);
+    if (t[0].len) HIP_CHECK(hipMemcpyAsync(dst + t[1].len + t[2].len, t[0].buf, (size_t)t[0].len, hipMemcpyDeviceToDevice, c->stream));
+    if (!sink.device && total) sink.put(0, dst, total);
+    c->sync();
+    c->profCollect();
+}
+
+// ---------------------------------------------------------------- the split's entry points
+static void pr_zero3(uint64_t *a) { if (a) a[0] = a[1] = a[2] = 0; }
+// the capacities against the lengths: a short one leaves out_len[] = the lengths needed
+static void pr_check_caps(bfq_ctx *c, const uint64_t *cap, const u64 *lens, int n, uint64_t *out_len, u32 merge)
+{
+    bool ok = true;
+    for (int k = 0; k < n; k++) ok = ok && cap[k] >= lens[k];
+    if (ok) return;
+    for (int k = 0; k < n; k++) out_len[k] = lens[k];
+    c->profCollect();
+    bfq_pairs_err X;
+    X.kind = BFQ_PAIRS_E_CAP; X.merge = merge;
+    pr_refuse(X);
+}
+
+static int pr_split_mem(bfq_ctx *c, PrSrc in, const bfq_pairs_opts *opts, uint8_t *const *out, const uint64_t *cap, bool device, bool measure,
+                        uint64_t *out_len, uint64_t *n_reads, bfq_pairs_stats *stats)
+{
+    pr_zero3(out_len); pr_zero3(n_reads);
+    if (stats) *stats = bfq_pairs_stats{};
+    return guarded(c, [&] {
+        if (!out_len || (!in.present() && in.len) || (!measure && (!out || !cap))) throw BfqError{BFQ_E_ARG, "null argument"};
+        if (!measure)
+            for (int k = 0; k < 3; k++)
+                if (!out[k] && cap[k]) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_pairs_opts O = pr_opts(opts);
+        PrSink sink;
+        sink.device = device;
+        sink.sized = [&](const u64 *lens) { if (!measure) pr_check_caps(c, cap, lens, 3, out_len, 0); };
+        if (!measure && device) for (int k = 0; k < 3; k++) sink.d_dst[k] = out[k];
+        sink.put = [&](int k, const u8 *d_text, u64 len) {
+            bfq_phase("d2h_write");
+            bfq_download(c, out[k], d_text, len);
+            bfq_phase("gpu");
+        };
+        u64 nr[3] = {0, 0, 0};
+        bfq_pairs_stats S;
+        split_core(c, in, O, measure, sink, nr, &S);
+        for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
+        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+        if (stats) *stats = S;
+    });
+}
+
+extern "C" int bfq_fastq_deinterleave_measure(bfq_ctx *c, const uint8_t *h_text, uint64_t len, const bfq_pairs_opts *opts, uint64_t out_len[3],
+                                              uint64_t n_reads[3], bfq_pairs_stats *stats)
+{
+    PrSrc in;
+    in.ref = HostRef::mem(h_text); in.len = len;
+    return pr_split_mem(c, in, opts, nullptr, nullptr, false, true, out_len, n_reads, stats);
+}
+extern "C" int bfq_fastq_deinterleave(bfq_ctx *c, const uint8_t *h_text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const h_out[3],
+                                      const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats)
+{
+    PrSrc in;
+    in.ref = HostRef::mem(h_text); in.len = len;
+    return pr_split_mem(c, in, opts, h_out, cap, false, false, out_len, n_reads, stats);
+}
+extern "C" int bfq_fastq_deinterleave_device(bfq_ctx *c, const uint8_t *d_text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const d_out[3],
+                                             const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats)
+{
+    PrSrc in;
+    in.d = d_text; in.len = len;
+    return pr_split_mem(c, in, opts, d_out, cap, true, false, out_len, n_reads, stats);
+}
+
+// the output files of a call: opened once the lengths are known, left empty when the call fails
+struct PrFiles {
+    OutFile of[3];
+    int fd[3] = {-1, -1, -1};
+    bool open = false;
+    void start(const u64 *lens, int n)
+    {
+        for (int k = 0; k < n; k++)
+            if (fd[k] >= 0) of[k].open(fd[k], lens[k] + 4096, lens[k]);
+        open = true;
+    }
+    bool finish(const uint64_t *lens, int n)
+    {
+        bool ok = true;
+        for (int k = 0; k < n; k++)
+            if (fd[k] >= 0) ok = of[k].close(lens[k]) && ok;
+        open = false;
+        return ok;
+    }
+    void fail(bfq_ctx *c, int n)
+    {
+        if (open) { try { bfq_write_wait(c); } catch (...) {} }
+        for (int k = 0; k < n; k++) {
+            if (fd[k] < 0) continue;
+            if (open) of[k].close(0);
+            else if (ftruncate(fd[k], 0) != 0) {}
+        }
+        open = false;
+    }
+};
+
+extern "C" int bfq_fastq_deinterleave_fd(bfq_ctx *c, int in_fd, uint64_t len, const bfq_pairs_opts *opts, const int out_fd[3], uint64_t out_len[3],
+                                         uint64_t n_reads[3], bfq_pairs_stats *stats)
+{
+    pr_zero3(out_len); pr_zero3(n_reads);
+    if (stats) *stats = bfq_pairs_stats{};
+    return guarded(c, [&] {
+        if (!out_len || !out_fd) throw BfqError{BFQ_E_ARG, "null argument"};
+        if (in_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
+        PrFiles F;
+        for (int k = 0; k < 3; k++) F.fd[k] = out_fd[k];
+        try {
+            const bfq_pairs_opts O = pr_opts(opts);
+            PrSrc in;
+            in.ref = HostRef::file(in_fd); in.len = len;
+            PrSink sink;
+            sink.sized = [&](const u64 *lens) {
+                F.start(lens, 3);
+                c->call.writeHint = (size_t)(lens[0] + lens[1] + lens[2]);
+            };
+            sink.put = [&](int k, const u8 *d_text, u64 n) { if (F.fd[k] >= 0) bfq_write_async(c, F.of[k].at(0), d_text, n); };
+            u64 nr[3] = {0, 0, 0};
+            bfq_pairs_stats S;
+            split_core(c, in, O, false, sink, nr, &S);
+            bfq_phase("d2h_write");
+            bfq_write_wait(c);
+            if (!F.finish(S.out_len, 3)) throw BfqError{BFQ_E_IO, "cannot size the output files"};
+            for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
+            if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+            if (stats) *stats = S;
+        } catch (...) {
+            F.fail(c, 3);
+            throw;
+        }
+    });
+}
+
+// ---------------------------------------------------------------- the merge's entry points
+static int pr_merge_mem(bfq_ctx *c, const uint8_t *const *text, const uint64_t *text_len, const bfq_pairs_opts *opts, uint8_t *out, uint64_t cap, bool device,
+                        bool measure, uint64_t *out_len, uint64_t *n_reads, bfq_pairs_stats *stats)
+{
+    if (out_len) *out_len = 0;
+    pr_zero3(n_reads);
+    if (stats) *stats = bfq_pairs_stats{};
+    return guarded(c, [&] {
+        if (!text || !text_len || !out_len || (!measure && !out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_pairs_opts O = pr_opts(opts);
+        PrSrc src[3];
+        for (int k = 0; k < 3; k++) {
+            if (!text[k]) continue;
+            if (device) src[k].d = text[k]; else src[k].ref = HostRef::mem(text[k]);
+            src[k].len = text_len[k];
+        }
+        PrSink sink;
+        sink.device = device;
+        sink.sized = [&](const u64 *total) { if (!measure) pr_check_caps(c, &cap, total, 1, out_len, 1); };
+        sink.d_dst[0] = device ? out : nullptr;
+        sink.put = [&](int, const u8 *d_text, u64 len) {
+            bfq_phase("d2h_write");
+            bfq_download(c, out, d_text, len);
+            bfq_phase("gpu");
+        };
+        u64 nr[3] = {0, 0, 0};
+        bfq_pairs_stats S;
+        merge_core(c, src, O, measure, sink, nr, &S);
+        *out_len = S.out_len[0];
+        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+        if (stats) *stats = S;
+    });
+}
+
+extern "C" int bfq_fastq_interleave_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts,
+                                            uint64_t *out_len, uint64_t n_reads[3], bfq_pairs_stats *stats)
+{
+    return pr_merge_mem(c, h_text, text_len, opts, nullptr, 0, false, true, out_len, n_reads, stats);
+}
+extern "C" int bfq_fastq_interleave(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts, uint8_t *h_out,
+                                    uint64_t cap, uint64_t *out_len, bfq_pairs_stats *stats)
+{
+    return pr_merge_mem(c, h_text, text_len, opts, h_out, cap, false, false, out_len, nullptr, stats);
+}
+extern "C" int bfq_fastq_interleave_device(bfq_ctx *c, const uint8_t *const d_text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts, uint8_t *d_out,
+                                           uint64_t cap, uint64_t *out_len, bfq_pairs_stats *stats)
+{
+    return pr_merge_mem(c, d_text, text_len, opts, d_out, cap, true, false, out_len, nullptr, stats);
+}
+
+extern "C" int bfq_fastq_interleave_fd(bfq_ctx *c, const int text_fd[3], const bfq_pairs_opts *opts, int out_fd, uint64_t *out_len, bfq_pairs_stats *stats)
+{
+    if (out_len) *out_len = 0;
+    if (stats) *stats = bfq_pairs_stats{};
+    return guarded(c, [&] {
+        if (!out_len || !text_fd) throw BfqError{BFQ_E_ARG, "null argument"};
+        if (out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
+        PrFiles F;
+        F.fd[0] = out_fd;
+        try {
+            const bfq_pairs_opts O = pr_opts(opts);
+            PrSrc src[3];
+            for (int k = 0; k < 3; k++) {
+                if (text_fd[k] < 0) continue;
+                struct stat st;
+                if (fstat(text_fd[k], &st) != 0) throw BfqError{BFQ_E_IO, std::string("cannot stat a text file: ") + strerror(errno)};
+                src[k].ref = HostRef::file(text_fd[k]); src[k].len = (u64)st.st_size;
+            }
+            PrSink sink;
+            sink.sized = [&](const u64 *total) {
+                F.start(total, 1);
+                c->call.writeHint = (size_t)*total;
+            };
+            sink.put = [&](int, const u8 *d_text, u64 n) { bfq_write_async(c, F.of[0].at(0), d_text, n); };
+            u64 nr[3] = {0, 0, 0};
+            bfq_pairs_stats S;
+            merge_core(c, src, O, false, sink, nr, &S);
+            bfq_phase("d2h_write");
+            bfq_write_wait(c);
+            if (!F.finish(S.out_len, 1)) throw BfqError{BFQ_E_IO, "cannot size the output file"};
+            *out_len = S.out_len[0];
+            if (stats) *stats = S;
+        } catch (...) {
+            F.fail(c, 1);
+            throw;
+        }
+    });
+}

@@ -259,6 +259,47 @@ def convert_bam_inputs(eng, comm, inputs, out="", paired=False, log=None, tags=N
     return new, tmp
 
 
+def split_interleaved_input(eng, comm, inputs, out="", log=None):
+    """--interleaved: the one input -- a FASTQ file with the mates alternating -- is split on the GPU into <name>_1.fastq and
+    <name>_2.fastq beside the outputs (bam_names, as the one paired BAM of --bam -p) by rank 0, in strict mode with the name
+    check (eng.fastq_deinterleave_files), and the run goes on as a two-file paired run: returns (the new input list, the
+    files written, None) -- or, for a file that is not properly paired, (the old list, the files written, the library's
+    message) on every rank, before any block runs."""
+    from . import api
+    q = bam_names(inputs[0], out, True)
+    why = None
+    if comm.rank == 0:
+        try:
+            n, reads, st = eng.fastq_deinterleave_files(inputs[0], (None, q[0], q[1]), check_names=1, orphans=0)
+            if log:
+                log(f"interleaved: {inputs[0]} -> {q}, {reads[1]} pairs, {st}")
+        except api.BfqError as e:
+            why = str(e)
+    if comm.all_gather_i64([1 if why else 0])[0, 0]:
+        return list(inputs), q, why or "the interleaved input was refused on rank 0"
+    comm.barrier()
+    return q, q, None
+
+
+def merge_interleaved_output(eng, comm, outputs, path, check_names, log=None):
+    """--interleaved-out: after the run rank 0 merges the two merged output texts into one file with the mates alternating
+    (eng.fastq_interleave_files), the names compared when the run kept them.  Returns None, or the library's message on every
+    rank."""
+    from . import api
+    comm.barrier()
+    why = None
+    if comm.rank == 0:
+        try:
+            n, st = eng.fastq_interleave_files((None, outputs[0], outputs[1]), path, check_names=int(check_names))
+            if log:
+                log(f"interleaved-out: {' '.join(outputs)} -> {path}, {n} bytes, {st}")
+        except api.BfqError as e:
+            why = str(e)
+    if comm.all_gather_i64([1 if why else 0])[0, 0]:
+        return why or "the merge was refused on rank 0"
+    return None
+
+
 def reordered_names(inputs, mode):
     """Where --reorder puts its intermediate files: <root>.reordered<ext> (mode 2, BFQzip_parallel.py:398) or
     <root>.random<ext> (mode 1, :421) beside every input."""
@@ -720,8 +761,37 @@ def main(argv=None):
                     help="aux tags through the FASTQ header lines: '*' = every tag, or a list (BC,RX).  With --bam the selected tags of "
                          "a record are written behind its name as <tab>XX:T:value; with --ubam-out the fields XX:T:value of the header "
                          "lines become tags of the records; needs kept headers (-H or --m3); --bam-out keeps the input's tags as they are")
+    ap.add_argument("--interleaved", action="store_true",
+                    help="the one input is a FASTQ file with the mates alternating (bwa mem -p, fastp --interleaved_in): it is split on the "
+                         "GPU into <name>_1.fastq / <name>_2.fastq beside the outputs first, with the name check (--keep-inflated keeps "
+                         "them), and the run goes on as -p on those; a file that is not properly paired ends the run")
+    ap.add_argument("--interleaved-out", default="", metavar="PATH",
+                    help="with -p and a merged FASTQ output: after the run the two output texts are merged on the GPU of rank 0 into one "
+                         "file with the mates alternating at PATH (the names compared with -H or --m3); not with --restore, "
+                         "--streams-only or --compress")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.interleaved:
+        why = None
+        if len(a.input) != 1 or a.restore:
+            why = "--interleaved takes exactly one input, a FASTQ file with the mates alternating"
+        elif a.bam:
+            why = "--interleaved reads FASTQ text: one paired BAM input goes through --bam -p"
+        if why:
+            print("=== ERROR ===\n" + why, file=sys.stderr)
+            return 1
+        a.paired = True
+    if a.interleaved_out:
+        why = None
+        if not a.paired:
+            why = "--interleaved-out merges the two outputs of a paired run: it needs -p (or --interleaved)"
+        elif a.restore:
+            why = "--interleaved-out follows a run: not with --restore"
+        elif ((a.m2 or a.m3) and a.streams_only) or (a.compress and not a.m0):
+            why = "--interleaved-out merges the merged FASTQ texts: not with --streams-only or --compress"
+        if why:
+            print("=== ERROR ===\n" + why, file=sys.stderr)
+            return 1
     if a.bam_tags:
         why = None
         try:
@@ -767,7 +837,7 @@ def main(argv=None):
     if a.restore and (len(a.input) not in (2, 3) or not a.out):
         print("=== ERROR ===\n--restore DNA.bsc QS.bsc [HDR.bsc] -o OUT.fq", file=sys.stderr)
         return 1
-    if a.paired and len(a.input) != 2 and not (a.bam and len(a.input) == 1):
+    if a.paired and len(a.input) != 2 and not ((a.bam or a.interleaved) and len(a.input) == 1):
         print("=== ERROR ===\npaired end mode", file=sys.stderr)
         return 1
     if a.m3:
@@ -813,6 +883,19 @@ def main(argv=None):
             return 1
     a.input, inflated = inflate_inputs(eng, comm, a.input, a.out, log=log, gunzip=a.gunzip)
     inflated = converted + inflated
+    if a.interleaved:
+        a.input, mates, why = split_interleaved_input(eng, comm, a.input, a.out, log=log)
+        inflated += mates
+        if why:                                                      # (not properly paired: the library's message; every rank leaves with it)
+            if comm.rank == 0:
+                print(f"=== ERROR ===\n--interleaved: {why}", file=sys.stderr)
+                for q in inflated:
+                    if os.path.exists(q) and not a.keep_inflated:
+                        os.remove(q)
+            eng.close()
+            if dist:
+                dist.destroy_process_group()
+            return 1
     perm_path = reordered_names(a.input[:1], a.reorder)[0] + ".perm" if (a.keep_order and a.reorder) else None
     keep = dict(perm_path=perm_path) if perm_path else {}
     original = list(a.input)
@@ -866,6 +949,15 @@ def main(argv=None):
                 failed = e
                 print(f"=== ERROR ===\n--ubam-out: {e}", file=sys.stderr)
         if comm.all_gather_i64([1 if failed else 0])[0, 0]:
+            eng.close()
+            if dist:
+                dist.destroy_process_group()
+            return 1
+    if a.interleaved_out:                                            # (after the order is restored: the outputs are what the user keeps)
+        why = merge_interleaved_output(eng, comm, [n["fastq"] for n in names], a.interleaved_out, a.headers, log=log)
+        if why:
+            if comm.rank == 0:
+                print(f"=== ERROR ===\n--interleaved-out: {why}", file=sys.stderr)
             eng.close()
             if dist:
                 dist.destroy_process_group()

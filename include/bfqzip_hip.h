@@ -919,6 +919,70 @@ int bfq_fastq_to_bam(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t 
 int bfq_fastq_to_bam_fd(bfq_ctx *c, const int text_fd[3], const bfq_ubam_opts *opts, int out_fd, uint64_t *out_len, bfq_ubam_stats *stats);
 int bfq_fastq_restore_bam_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len, int perm_fd,
                              uint64_t permz_len, const bfq_ubam_opts *opts, int out_fd, uint64_t *out_len, bfq_ubam_stats *stats);
+/* ---- interleaved paired FASTQ: one text with the mates alternating <-> the two texts of mates (k_pairs.hip; the definition
+ * in full, the key rule, the messages and the host forms: csrc/bfq_pairs.h).  What `bwa mem -p`, fastp --interleaved_in and
+ * `samtools fastq` without -1 -2 read and write.  Records move verbatim: a record is its four lines byte for byte (header
+ * comment, '+' line and CRs included); a text whose last line lacks its LF gets one.
+ *   The text: plain FASTQ, parsed by the line index and record parser of bfq_fastq_reorder; malformed text keeps the words
+ *     of bfq_fastq_run ("FASTQ: number of lines is not a multiple of 4", "FASTQ: len(DNA) != len(QS) in a record",
+ *     BFQ_E_TOO_LONG "read longer than BFQ_MAX_READ_LEN").  A text that begins with 1f 8b: BFQ_E_ARG, "... inflate the text
+ *     first" (bfq_bgzf_inflate*, bfq_gzip_inflate*): these calls take no compressed parts.
+ *   Key of a record: the bytes behind '@' up to the first blank, tab, CR or line end; with mate_suffix a trailing "/1" or "/2"
+ *     is removed -- either one, at either position, where at least one byte remains (laxer than bfq_fastq_to_bam, which
+ *     removes only the matching suffix: in orphan mode a record's role is not known before the pairing).  Keys compare in
+ *     full at any length; two empty keys ("@" alone) are equal.
+ *   opts (NULL: the defaults): check_names 1, mate_suffix 1, orphans 0; reserved != 0: BFQ_E_ARG.
+ *   bfq_fastq_deinterleave* : one text -> out[3]: 0 singletons, 1 and 2 the mates.
+ *     orphans 0: an odd record count N: BFQ_E_ARG "interleaved FASTQ: <N> records, an odd number".  Record 2k to output 1,
+ *       record 2k + 1 to output 2, output 0 empty.  check_names: "interleaved FASTQ: pair <k> (records <2k> and <2k+1>): the
+ *       names differ", the first offending pair of the file (compared on the device, one atomicMin).
+ *     orphans 1: the file is cut into maximal runs of consecutive records with equal keys; in a run that starts at record s
+ *       with r records, s + 2j and s + 2j + 1 are a pair for 2j + 1 < r (outputs 1 and 2); with r odd the run's last record
+ *       goes to output 0, in file order.  Nothing is refused for pairing; check_names is implied.  The run start of every
+ *       record is an inclusive max-scan over the whole file.
+ *   bfq_fastq_interleave* : text[3] -> one text: record k of text[1], record k of text[2], for every k, then the records of
+ *     an optional text[0] (a NULL text, or text_fd < 0, holds no reads).  "FASTQ interleave: text 1 holds <n> reads, text 2
+ *     holds <m>"; check_names: "FASTQ interleave: pair <k>: the names differ".
+ *   Every refusal is BFQ_E_ARG but the too-long read, writes nothing in every form -- sizes and checks are finished before
+ *   the first byte moves; the device forms write straight into the caller's buffers after them -- and leaves the context
+ *   usable.  Output lengths are exact before anything is written.
+ *       _measure : host text(s) in; out_len, n_reads[3] (reads per output; of the merge: per input text) and *stats; nothing
+ *                  is written.
+ *       plain    : host buffers.  A cap[k] below the measured length: BFQ_E_ARG, nothing written, out_len[] = the lengths
+ *                  needed (every other failure leaves them 0).
+ *       _device  : device buffers in and out; the text never exists on the host.  cap as above.
+ *       _fd      : open files; an out_fd[k] < 0 is not written; output files are sized to their text (0 on a failure).
+ *       _host    : one thread, no context, no GPU: the same bytes, stats and messages.  States the algorithm and is what the
+ *                  tests compare with; NO entry point falls back to it.  Message: bfq_pairs_host_error() (of the calling
+ *                  thread's last call).
+ *   Device memory: the input text(s) (in the context's text buffer when uploaded, or when a device text lies at an address
+ *   that is no multiple of 16 or lacks its final LF), and in the workspace, reserved once: 8 bytes per line and 44 per
+ *   record of index, 16 per pair (orphans: 57 per record) of sizes and offsets, and -- host and file forms -- the outputs.
+ *   Above ws_cap_mib: BFQ_E_NOMEM with the size in the message.
+ *   stats (may be NULL): records, pairs, singles, out_len[3] (of the merge: out_len[0] = the interleaved text's length). */
+typedef struct bfq_pairs_opts  { uint32_t check_names, mate_suffix, orphans, reserved; } bfq_pairs_opts;
+typedef struct bfq_pairs_stats { uint64_t records, pairs, singles, out_len[3]; } bfq_pairs_stats;
+void bfq_pairs_default_opts(bfq_pairs_opts *o);
+int bfq_fastq_deinterleave_measure(bfq_ctx *c, const uint8_t *h_text, uint64_t len, const bfq_pairs_opts *opts, uint64_t out_len[3], uint64_t n_reads[3],
+                                   bfq_pairs_stats *stats);
+int bfq_fastq_deinterleave(bfq_ctx *c, const uint8_t *h_text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const h_out[3], const uint64_t cap[3],
+                           uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats);
+int bfq_fastq_deinterleave_device(bfq_ctx *c, const uint8_t *d_text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const d_out[3], const uint64_t cap[3],
+                                  uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats);
+int bfq_fastq_deinterleave_fd(bfq_ctx *c, int in_fd, uint64_t len, const bfq_pairs_opts *opts, const int out_fd[3], uint64_t out_len[3],
+                              uint64_t n_reads[3], bfq_pairs_stats *stats);
+int bfq_fastq_deinterleave_host(const uint8_t *text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const h_out[3], const uint64_t cap[3],
+                                uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats);
+int bfq_fastq_interleave_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts, uint64_t *out_len,
+                                 uint64_t n_reads[3], bfq_pairs_stats *stats);
+int bfq_fastq_interleave(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts, uint8_t *h_out, uint64_t cap,
+                         uint64_t *out_len, bfq_pairs_stats *stats);
+int bfq_fastq_interleave_device(bfq_ctx *c, const uint8_t *const d_text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts, uint8_t *d_out,
+                                uint64_t cap, uint64_t *out_len, bfq_pairs_stats *stats);
+int bfq_fastq_interleave_fd(bfq_ctx *c, const int text_fd[3], const bfq_pairs_opts *opts, int out_fd, uint64_t *out_len, bfq_pairs_stats *stats);
+int bfq_fastq_interleave_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts, uint8_t *out, uint64_t cap,
+                              uint64_t *out_len, bfq_pairs_stats *stats);
+const char *bfq_pairs_host_error(void);
 /* ---- bgzip-compressed output: BGZF members deflated on the device (k_deflate.hip; the format and every bound:
  * csrc/bfq_deflate.h).  A text of len bytes is cut at multiples of 65 280 bytes (htslib's member size; the cut depends on
  * nothing else); every piece becomes one BGZF member -- htslib's 18-byte header, a raw deflate payload, CRC32 and ISIZE --
