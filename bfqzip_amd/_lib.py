@@ -46,6 +46,7 @@ SYMBOLS = [
     "bfq_pairs_default_opts", "bfq_pairs_host_error",
     "bfq_fastq_deinterleave_measure", "bfq_fastq_deinterleave", "bfq_fastq_deinterleave_device", "bfq_fastq_deinterleave_fd", "bfq_fastq_deinterleave_host",
     "bfq_fastq_interleave_measure", "bfq_fastq_interleave", "bfq_fastq_interleave_device", "bfq_fastq_interleave_fd", "bfq_fastq_interleave_host",
+    "bfq_repair_default_opts", "bfq_fastq_repair_measure", "bfq_fastq_repair", "bfq_fastq_repair_device", "bfq_fastq_repair_fd", "bfq_fastq_repair_host",
     "bfq_workspace_bytes", "bfq_workspace_read", "bfq_version",
 ]
 
@@ -207,6 +208,23 @@ class PairsStats(C.Structure):
 
     def __repr__(self):
         return "PairsStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
+
+
+class RepairOpts(C.Structure):
+    """bfq_repair_opts: mate_suffix, hash_bits (1..40), seed, reserved[2] (must be 0)"""
+    _fields_ = [("mate_suffix", C.c_uint32), ("hash_bits", C.c_uint32), ("seed", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+class RepairStats(C.Structure):
+    """bfq_repair_stats: records, pairs, singles, out_len[3], n_in[3], dup_groups, mixed_runs, max_run"""
+    _fields_ = ([(k, C.c_uint64) for k in ("records", "pairs", "singles")] + [("out_len", C.c_uint64 * 3), ("n_in", C.c_uint64 * 3)] +
+                [(k, C.c_uint64) for k in ("dup_groups", "mixed_runs", "max_run")])
+
+    def as_dict(self):
+        return {k: [int(v) for v in getattr(self, k)] if k in ("out_len", "n_in") else int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "RepairStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
 
 
 CMP_SYMS = 6
@@ -431,6 +449,14 @@ def lib():
         L.bfq_fastq_interleave_device.argtypes = [vp, C.POINTER(vp), a3, ppo, vp, u64, pu64, pps2]
         L.bfq_fastq_interleave_fd.argtypes = [vp, i3, ppo, C.c_int, pu64, pps2]
         L.bfq_fastq_interleave_host.argtypes = [C.POINTER(vp), a3, ppo, vp, u64, pu64, pps2]
+        pro, prs = C.POINTER(RepairOpts), C.POINTER(RepairStats)
+        L.bfq_repair_default_opts.restype = None
+        L.bfq_repair_default_opts.argtypes = [pro]
+        L.bfq_fastq_repair_measure.argtypes = [vp, C.POINTER(vp), a3, pro, a3, a3, prs]
+        L.bfq_fastq_repair.argtypes = [vp, C.POINTER(vp), a3, pro, C.POINTER(vp), a3, a3, a3, prs]
+        L.bfq_fastq_repair_device.argtypes = [vp, C.POINTER(vp), a3, pro, C.POINTER(vp), a3, a3, a3, prs]
+        L.bfq_fastq_repair_fd.argtypes = [vp, i3, pro, i3, a3, a3, prs]
+        L.bfq_fastq_repair_host.argtypes = [C.POINTER(vp), a3, pro, C.POINTER(vp), a3, a3, a3, prs]
         L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_radix_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(u64)]

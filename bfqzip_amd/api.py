@@ -489,6 +489,40 @@ def fastq_interleave_host(texts, out=None, **opts):
     return out[:int(ol.value)], st
 
 
+def repair_opts(mate_suffix=1, hash_bits=40, seed=0, reserved=(0, 0)):
+    """bfq_repair_opts (include/bfqzip_hip.h); the defaults are bfq_repair_default_opts'.  mate_suffix: a trailing /1 or /2 is no
+    part of the key (and, in text 0, says which mate a record is); hash_bits (1..40): the bits of the name hash the records
+    are sorted by -- small values are a test knob, the outputs do not depend on it, nor on seed; reserved must be 0."""
+    o = _lib.RepairOpts()
+    o.mate_suffix, o.hash_bits, o.seed = int(mate_suffix), int(hash_bits), int(seed)
+    o.reserved[0], o.reserved[1] = (int(reserved), 0) if not hasattr(reserved, "__len__") else (int(reserved[0]), int(reserved[1]))
+    return o
+
+
+def fastq_repair_host(texts, outs=None, **opts):
+    """(texts[3], stats) of the texts (texts[1] and texts[2]: mate files; texts[0]: a mixed file; None: absent) with the mates
+    matched by name by the host form (bfq_fastq_repair_host: the steps of csrc/bfq_pairs.h by one thread, no GPU): the
+    statement of the algorithm -- Engine.fastq_repair gives the same bytes, stats and messages.  Result texts[1] / texts[2]:
+    the mates, pair k at place k of both; texts[0]: the singletons.  opts: repair_opts().  `outs`: three uint8 arrays to fill;
+    one that is too small raises BfqError with .needed = the three lengths, nothing written.  stats.n_reads: the reads per
+    output."""
+    L = _lib.lib()
+    keep, ptrs, lens = _bam_texts(texts)
+    O, st = repair_opts(**opts), _lib.RepairStats()
+    ol, nr = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+    if outs is None:
+        rc = L.bfq_fastq_repair_host(ptrs, lens, C.byref(O), None, None, ol, nr, C.byref(st))
+        if rc != 0:
+            _pairs_raise(rc, L.bfq_pairs_host_error().decode(), ol)
+        outs = [np.empty(int(v), np.uint8) for v in ol]
+    optrs, caps = _bam_outs(outs)
+    rc = L.bfq_fastq_repair_host(ptrs, lens, C.byref(O), optrs, caps, ol, nr, C.byref(st))
+    if rc != 0:
+        _pairs_raise(rc, L.bfq_pairs_host_error().decode(), ol)
+    st.n_reads = [int(v) for v in nr]
+    return [o[:int(n)] for o, n in zip(outs, ol)], st
+
+
 def text_len(a):
     """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
     a = _u8(a)
@@ -513,6 +547,7 @@ class HostText:
     fastq_to_bam_host = staticmethod(fastq_to_bam_host)
     fastq_deinterleave_host = staticmethod(fastq_deinterleave_host)
     fastq_interleave_host = staticmethod(fastq_interleave_host)
+    fastq_repair_host = staticmethod(fastq_repair_host)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -1203,6 +1238,64 @@ class Engine:
             O, st, ol = pairs_opts(**opts), _lib.PairsStats(), C.c_uint64(0)
             self._pairs_ck(self.L.bfq_fastq_interleave_fd(self.h, (C.c_int * 3)(*fds[0:3]), C.byref(O), fds[3], C.byref(ol), C.byref(st)), ol.value)
             return int(ol.value), st
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+    # ---- repair paired FASTQ: the mates matched by name across the texts (bfq_fastq_repair*, csrc/bfq_pairs.h)
+    def fastq_repair_measure(self, texts, **opts):
+        """bfq_fastq_repair_measure: (the three text lengths, the three read counts, stats) of the repair of texts (see
+        fastq_repair); nothing is written."""
+        keep, ptrs, lens = _bam_texts(texts)
+        O, st, ol, nr = repair_opts(**opts), _lib.RepairStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        self._pairs_ck(self.L.bfq_fastq_repair_measure(self.h, ptrs, lens, C.byref(O), ol, nr, C.byref(st)), ol)
+        return [int(v) for v in ol], [int(v) for v in nr], st
+
+    def fastq_repair(self, texts, outs=None, **opts):
+        """(texts[3], stats): the mates of paired FASTQ matched by name on the GPU (bfq_fastq_repair), wherever they stand.
+        texts[1] and texts[2]: mate files (each may have lost reads of its own, in any order); texts[0]: a mixed file (its
+        /1 and /2 suffixes say which mate a record is; without them equal names are paired two by two); None: absent.  Result
+        texts[1] and texts[2]: the mates, pair k at place k of both, in the order of the first mates in the input; texts[0]:
+        the singletons in input order.  Records move byte for byte.  opts: repair_opts() (mate_suffix; hash_bits and seed
+        never show in the outputs).  `outs`: three uint8 arrays to fill; without them the texts are measured first.  A
+        buffer below its text raises BfqError with .needed = the three lengths and nothing is written.  More than 1024
+        records of one name: BfqError ("FASTQ repair: more than 1024 records share a name or a name hash ...").
+        stats.n_reads: the reads per output."""
+        if outs is None:
+            outs = [np.empty(v, np.uint8) for v in self.fastq_repair_measure(texts, **opts)[0]]
+        keep, ptrs, lens = _bam_texts(texts)
+        O, st, ol, nr = repair_opts(**opts), _lib.RepairStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        optrs, caps = _bam_outs(outs)
+        self._pairs_ck(self.L.bfq_fastq_repair(self.h, ptrs, lens, C.byref(O), optrs, caps, ol, nr, C.byref(st)), ol)
+        st.n_reads = [int(v) for v in nr]
+        return [o[:int(n)] for o, n in zip(outs, ol)], st
+
+    def fastq_repair_device(self, d_texts, text_lens, d_outs, caps, **opts):
+        """bfq_fastq_repair_device: the texts at the device addresses d_texts (None / 0: absent), the three texts at the
+        device addresses d_outs (caps bytes each; None / 0 with cap 0: none); returns (lengths, read counts, stats)."""
+        ptrs = (C.c_void_p * 3)(*[int(p) if p else None for p in d_texts])
+        lens = (C.c_uint64 * 3)(*[int(v) for v in text_lens])
+        optrs, cp = (C.c_void_p * 3)(*[int(p) if p else None for p in d_outs]), (C.c_uint64 * 3)(*[int(v) for v in caps])
+        O, st, ol, nr = repair_opts(**opts), _lib.RepairStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+        self._pairs_ck(self.L.bfq_fastq_repair_device(self.h, ptrs, lens, C.byref(O), optrs, cp, ol, nr, C.byref(st)), ol)
+        return [int(v) for v in ol], [int(v) for v in nr], st
+
+    def fastq_repair_files(self, texts, dsts, **opts):
+        """bfq_fastq_repair_fd on named files: the FASTQ files texts[k] (None: absent), dsts = the paths of outputs 0
+        (singletons), 1, 2 (None: not written).  The outputs are left empty on a refusal.  Returns (lengths, read counts,
+        stats)."""
+        import os
+        texts = list(texts) + [None] * (3 - len(texts))
+        fds = []
+        try:
+            for t in texts[:3]:
+                fds.append(os.open(t, os.O_RDONLY) if t is not None else -1)
+            for d in dsts:
+                fds.append(os.open(d, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) if d is not None else -1)
+            O, st, ol, nr = repair_opts(**opts), _lib.RepairStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+            self._pairs_ck(self.L.bfq_fastq_repair_fd(self.h, (C.c_int * 3)(*fds[0:3]), C.byref(O), (C.c_int * 3)(*fds[3:6]), ol, nr, C.byref(st)), ol)
+            return [int(v) for v in ol], [int(v) for v in nr], st
         finally:
             for fd in fds:
                 if fd >= 0:

@@ -503,6 +503,13 @@ void bfq_pairs_pair_sizes(bfq_ctx *c, const PrText &a, u64 P, u64 *sz);
 void bfq_pairs_split(bfq_ctx *c, const PrText &a, const u64 *off1, u8 *o1, u8 *o2);
 void bfq_pairs_split_roles(bfq_ctx *c, const PrText &a, const u8 *role, const u64 *const off[3], u8 *const o[3]);
 void bfq_pairs_merge(bfq_ctx *c, const PrText &a, const PrText &b, u8 *out);
+// ... the repair (k_pairs.hip, its last section).  t[3]: the texts of the call, N: their records, numbered 1, 2, 0.
+void bfq_repair_sort(bfq_ctx *c, const PrText t[3], u64 N, const bfq_repair_opts &O, u64 *h, u8 *hint, SortRec a, SortRec b, u64 *sg, u64 *sh, u64 *start,
+                     u64 *d_stat);   // d_stat[0, 2): the longest run, the smallest global number in a run that is too long (~0: none)
+void bfq_repair_group(bfq_ctx *c, const PrText t[3], u64 N, u32 suffix, const u64 *start, const u64 *sg, const u64 *sh, u8 *role, u64 *anchor, u8 *f1, u8 *f0,
+                      u64 *d_cnt);   // d_cnt[0, 2) zeroed: dup_groups, mixed_runs
+void bfq_repair_place(bfq_ctx *c, const PrText t[3], u64 N, const u8 *role, const u64 *anchor, const u64 *rank1, const u64 *rank0, u64 *slot, u64 *const sz[3]);
+void bfq_repair_move(bfq_ctx *c, const PrText t[3], u64 N, const u8 *role, const u64 *slot, const u64 *const off[3], u8 *const o[3]);
 
 // two FASTQ texts compared where they lie (k_compare.hip; bfq_compare.hip drives them).  inv == nullptr: read i of A pairs with
 // read i of B, else with read inv[i].  d_rep: a zeroed report on the device whose first_changed_read is all-ones.

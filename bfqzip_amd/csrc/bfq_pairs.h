@@ -26,16 +26,32 @@
 //     Output: record k of text 1, record k of text 2, for every k, then the records of text 0.  An absent text holds no
 //     reads.  Different read counts: "FASTQ interleave: text 1 holds <n> reads, text 2 holds <m>".  With check_names:
 //     "FASTQ interleave: pair <k>: the names differ", the first one.
+//   Repair (bfq_fastq_repair*): the mates are matched by name wherever they stand.  text[1], text[2] and text[0] as in the
+//     merge; the global number g of a record counts the records of text 1, then those of text 2, then those of text 0.
+//     Hint of a record: 1 from text 1, 2 from text 2; from text 0, with mate_suffix, 1 where the key lost a "/1", 2 where it
+//     lost a "/2"; else 0 (none).  A group is all records of the call with equal keys, split in global order into the lists
+//     L1, L2 and L0 by hint.  Pairs: (L1[k], L2[k]) for k < min(|L1|, |L2|), then (L0[2j], L0[2j + 1]) for 2j + 1 < |L0|;
+//     the first of a pair goes to output 1, the second to output 2, every other record of the group to output 0.  Pairs
+//     come in increasing global number of their output-1 record (a repaired R1 keeps R1's order), singletons in increasing
+//     global number.  The outputs are a function of the texts and mate_suffix alone.
+//     How: the records are sorted by the top hash_bits bits of a 64-bit hash of the key (bfq_repair_hash, below; stable, so a
+//     run of equal sort keys is in global order), a run is cut into groups by the full hash and then the key's bytes.  A run of
+//     more than BFQ_REPAIR_RUN_MAX records is refused, "FASTQ repair: more than 1024 records share a name or a name hash (the
+//     first: record <i> of text <k>): names do not identify the mates": <i> is the smallest global number in such a run,
+//     given relative to its text.  This bounds every loop of the grouping and refuses a file of "@"-only headers.
+//     Statistics: dup_groups = groups of more than two records, mixed_runs = runs that hold more than one name, max_run = the
+//     longest run; the last two depend on hash_bits and the seed, nothing else does.
 //   All refusals but the too-long read are BFQ_E_ARG.  In every form a refusal writes nothing: sizes and checks are finished
 //   before the first byte moves, and the output lengths are exact before anything is written.
-// Out of scope: adding or rewriting "/1" "/2"; repairing files whose mates are not adjacent (collate by name first); BGZF
-// parts inside these calls (the front-ends inflate with bfq_bgzf_inflate* / bfq_gzip_inflate*); interleaved output straight
-// from bfq_restore.
+// Out of scope: adding or rewriting "/1" "/2"; BGZF parts inside these calls (the front-ends inflate with bfq_bgzf_inflate* /
+// bfq_gzip_inflate*); repair inside bfq_bam itself; interleaved output straight from bfq_restore.
 #pragma once
 #include "bfq_common.h"
+#include "bfq_reorder.h"                            // bfq_fmix64
 #include "../../include/bfqzip_hip.h"
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -49,22 +65,30 @@ enum {
     BFQ_PAIRS_E_ODD,         // strict split: an odd record count
     BFQ_PAIRS_E_COUNTS,      // merge: the mates' read counts differ
     BFQ_PAIRS_E_NAMES,       // the keys of a pair differ
-    BFQ_PAIRS_E_CAP          // an output below its text
+    BFQ_PAIRS_E_CAP,         // an output below its text
+    BFQ_PAIRS_E_HASH_BITS,   // repair: bfq_repair_opts.hash_bits outside 1..40
+    BFQ_PAIRS_E_RUN          // repair: more than BFQ_REPAIR_RUN_MAX records in a run of equal sort keys
 };
+#define BFQ_REPAIR_RUN_MAX 1024u
 #define BFQ_PAIRS_NONE (~0ull)
-// what is refused: merge (or split), text k, the two numbers the message names
+// what is refused: merge = 1 (0: the split, 2: the repair), text k, the two numbers the message names
 struct bfq_pairs_err { u32 kind = 0, merge = 0, k = 0, pad = 0; u64 n = 0, m = 0; };
 inline int bfq_pairs_code(const bfq_pairs_err &E) { return E.kind == BFQ_PAIRS_E_TOO_LONG ? BFQ_E_TOO_LONG : BFQ_E_ARG; }
 inline std::string bfq_pairs_message(const bfq_pairs_err &E)
 {
     char b[320];
     switch (E.kind) {
-    case BFQ_PAIRS_E_RESERVED: return "bfq_pairs_opts.reserved: must be 0";
+    case BFQ_PAIRS_E_RESERVED: return E.merge == 2 ? "bfq_repair_opts.reserved: must be 0" : "bfq_pairs_opts.reserved: must be 0";
+    case BFQ_PAIRS_E_HASH_BITS: return "bfq_repair_opts.hash_bits: must be 1..40";
+    case BFQ_PAIRS_E_RUN:
+        snprintf(b, sizeof b, "FASTQ repair: more than %u records share a name or a name hash (the first: record %llu of text %u): names do not identify the mates",
+                 BFQ_REPAIR_RUN_MAX, E.n, E.k);
+        return b;
     case BFQ_PAIRS_E_LINES: return "FASTQ: number of lines is not a multiple of 4";
     case BFQ_PAIRS_E_FASTQ: return "FASTQ: len(DNA) != len(QS) in a record";
     case BFQ_PAIRS_E_TOO_LONG: return "read longer than BFQ_MAX_READ_LEN";
     case BFQ_PAIRS_E_GZIP:
-        if (E.merge) snprintf(b, sizeof b, "FASTQ interleave: text %u is compressed (it begins with 1f 8b): inflate the text first", E.k);
+        if (E.merge) snprintf(b, sizeof b, "FASTQ %s: text %u is compressed (it begins with 1f 8b): inflate the text first", E.merge == 2 ? "repair" : "interleave", E.k);
         else snprintf(b, sizeof b, "interleaved FASTQ: the text is compressed (it begins with 1f 8b): inflate the text first");
         return b;
     case BFQ_PAIRS_E_ODD: snprintf(b, sizeof b, "interleaved FASTQ: %llu records, an odd number", E.n); return b;
@@ -73,7 +97,7 @@ inline std::string bfq_pairs_message(const bfq_pairs_err &E)
         if (E.merge) snprintf(b, sizeof b, "FASTQ interleave: pair %llu: the names differ", E.n);
         else snprintf(b, sizeof b, "interleaved FASTQ: pair %llu (records %llu and %llu): the names differ", E.n, 2 * E.n, 2 * E.n + 1);
         return b;
-    case BFQ_PAIRS_E_CAP: return E.merge ? "output buffer smaller than the interleaved text" : "output buffer smaller than the text it receives";
+    case BFQ_PAIRS_E_CAP: return E.merge == 1 ? "output buffer smaller than the interleaved text" : "output buffer smaller than the text it receives";
     default: return "ok";
     }
 }
@@ -103,6 +127,50 @@ BFQ_HD bool bfq_pairs_same(const u8 *ta, u64 sa, u64 na, const u8 *tb, u64 sb, u
 }
 // Orphan mode: the output of record i whose run starts at record `start`; last: i is its run's last record.
 BFQ_HD u32 bfq_pairs_role(u64 i, u64 start, bool last) { return ((i - start) & 1u) ? 2u : last ? 0u : 1u; }
+
+// ---- repair: the hash of a key, the hint of a record, the role of a record in its group
+// The key's bytes in 8-byte little-endian chunks w_j, the last one zero-padded: acc = sum_j fmix64(w_j + C * (j + 1)) mod 2^64,
+// h = fmix64(acc ^ fmix64(L ^ seed)) with L the key's length.  The sum is commutative on purpose: lanes that share a record
+// each take chunks and reduce.  Keys that differ only by trailing zero bytes have equal chunks and differ through L.
+#define BFQ_REPAIR_GOLD 0x9E3779B97F4A7C15ull
+BFQ_HD u64 bfq_repair_word(const u8 *p, u64 n)           // the first n <= 8 bytes at p, little-endian, zero-padded
+{
+    u64 w = 0;
+    for (u64 b = 0; b < n; b++) w |= (u64)p[b] << (8 * b);
+    return w;
+}
+BFQ_HD u64 bfq_repair_chunk(u64 w, u64 j) { return bfq_fmix64(w + BFQ_REPAIR_GOLD * (j + 1)); }
+BFQ_HD u64 bfq_repair_finish(u64 acc, u64 L, u64 seed) { return bfq_fmix64(acc ^ bfq_fmix64(L ^ seed)); }
+BFQ_HD u64 bfq_repair_hash(const u8 *key, u64 L, u64 seed)
+{
+    u64 acc = 0;
+    for (u64 j = 0; 8 * j < L; j++) acc += bfq_repair_chunk(bfq_repair_word(key + 8 * j, L - 8 * j < 8 ? L - 8 * j : 8), j);
+    return bfq_repair_finish(acc, L, seed);
+}
+BFQ_HD u64 bfq_repair_sort_key(u64 h, u32 hashBits) { return h >> (64 - hashBits); }
+// The hint of a record of text `src` whose header line is t[s, s + n) and whose key (bfq_pairs_key) is t[ks, ks + kl): behind a
+// key that lost its suffix stands the '/', behind any other a blank, a tab, a CR or the line's end.
+BFQ_HD u32 bfq_repair_hint(const u8 *t, u64 s, u64 n, u32 src, u64 ks, u64 kl)
+{
+    if (src) return src;
+    return ks + kl < s + n && t[ks + kl] == '/' ? (t[ks + kl + 1] == '1' ? 1u : 2u) : 0u;
+}
+// The role of a record with hint `hint` that has before[] records of its group in front of it, by hint, in a group of
+// total[]: 0, 1 or 2 = its output.  *mate: for a pair member the index, in its list, of the group's record that is the
+// pair's output-1 record (list L1 for hints 1 and 2, list L0 for hint 0) -- for an output-1 record its own.
+BFQ_HD u32 bfq_repair_role(u32 hint, const u32 before[3], const u32 total[3], u32 *mate)
+{
+    const u32 p12 = total[1] < total[2] ? total[1] : total[2];
+    *mate = 0;
+    if (hint) {
+        if (before[hint] >= p12) return 0;
+        *mate = before[hint];
+        return hint;
+    }
+    if ((before[0] | 1u) >= total[0]) return 0;            // the last of an odd list
+    *mate = before[0] & ~1u;
+    return (before[0] & 1u) ? 2u : 1u;
+}
 
 // ---------------------------------------------------------------- host side
 inline void bfq_pairs_defaults(bfq_pairs_opts *o) { o->check_names = 1; o->mate_suffix = 1; o->orphans = 0; o->reserved = 0; }
@@ -242,5 +310,133 @@ inline int bfq_pairs_merge_host(const u8 *const text[3], const uint64_t textLen[
         at += bfq_pairs_put(out + at, text[2], len[2], I[2], k);
     }
     for (u64 i = 0; i < I[0].N; i++) at += bfq_pairs_put(out + at, text[0], len[0], I[0], i);
+    return 0;
+}
+
+// ---------------------------------------------------------------- repair
+inline void bfq_repair_defaults(bfq_repair_opts *o) { o->mate_suffix = 1; o->hash_bits = 40; o->seed = 0; o->reserved[0] = o->reserved[1] = 0; }
+inline bool bfq_repair_resolve(const bfq_repair_opts *in, bfq_repair_opts *O, bfq_pairs_err *E)
+{
+    bfq_repair_defaults(O);
+    if (in) *O = *in;
+    E->merge = 2;
+    if (O->reserved[0] || O->reserved[1]) { E->kind = BFQ_PAIRS_E_RESERVED; return false; }
+    if (O->hash_bits < 1 || O->hash_bits > 40) { E->kind = BFQ_PAIRS_E_HASH_BITS; return false; }
+    return true;
+}
+// the text a global record number lies in (the order of the numbering: 1, 2, 0) and its number there
+inline u32 bfq_repair_text_of(u64 g, const u64 n[3], u64 *i)
+{
+    if (g < n[1]) { *i = g; return 1; }
+    if (g < n[1] + n[2]) { *i = g - n[1]; return 2; }
+    *i = g - n[1] - n[2];
+    return 0;
+}
+
+// The host form of the repair: the steps of the kernels by one thread.  out[k] of cap[k] bytes (measure: not touched).  Returns
+// 0; 2 = refused (*X); 3 = a cap below its length (S->out_len: the lengths).  Nothing is written unless 0 is returned.
+inline int bfq_pairs_repair_host(const u8 *const text[3], const uint64_t textLen[3], const bfq_repair_opts &O, u8 *const out[3], const uint64_t cap[3],
+                                 bool measure, bfq_repair_stats *S, u64 nReads[3], bfq_pairs_err *X)
+{
+    *S = bfq_repair_stats{};
+    *X = bfq_pairs_err{};
+    X->merge = 2;
+    nReads[0] = nReads[1] = nReads[2] = 0;
+    u64 len[3];
+    for (u32 k = 0; k < 3; k++) {
+        len[k] = text[k] ? textLen[k] : 0;
+        if (!bfq_pairs_gzip_ok(text[k], len[k], 2, k, X)) return 2;
+    }
+    bfq_pairs_index I[3];
+    for (u32 k = 0; k < 3; k++)
+        if (!bfq_pairs_parse(text[k], len[k], &I[k], X)) return 2;
+    const u64 n[3] = {I[0].N, I[1].N, I[2].N}, N = n[0] + n[1] + n[2];
+    // step 1: key, hint and hash of every record, in global order
+    struct Rec { u64 h, ks, kl, size; u32 src, hint; u64 i; };
+    std::vector<Rec> R(N);
+    std::vector<u64> order(N);
+    for (u64 g = 0; g < N; g++) {
+        Rec &r = R[g];
+        r.src = bfq_repair_text_of(g, n, &r.i);
+        const u8 *t = text[r.src];
+        const bfq_pairs_index &J = I[r.src];
+        bfq_pairs_key(t, J.hs[r.i], J.hl[r.i], O.mate_suffix, &r.ks, &r.kl);
+        r.hint = bfq_repair_hint(t, J.hs[r.i], J.hl[r.i], r.src, r.ks, r.kl);
+        r.h = bfq_repair_hash(t + r.ks, r.kl, O.seed);
+        r.size = J.hs[r.i + 1] - J.hs[r.i];
+        order[g] = g;
+    }
+    // step 2: the stable sort on the sort key
+    std::stable_sort(order.begin(), order.end(), [&](u64 a, u64 b) { return bfq_repair_sort_key(R[a].h, O.hash_bits) < bfq_repair_sort_key(R[b].h, O.hash_bits); });
+    // step 3: the runs; their lengths are checked before any of them is walked
+    std::vector<u64> start(N + 1);
+    u64 firstBad = BFQ_PAIRS_NONE;
+    for (u64 p = 0, run = 0; p < N; p++) {
+        if (p == 0 || bfq_repair_sort_key(R[order[p - 1]].h, O.hash_bits) != bfq_repair_sort_key(R[order[p]].h, O.hash_bits)) run = p;
+        start[p] = run;
+    }
+    start[N] = N;
+    for (u64 p = 0; p < N; p++) {
+        if (start[p + 1] != p + 1) continue;                    // p ends a run
+        const u64 r = p + 1 - start[p];
+        if (r > S->max_run) S->max_run = r;
+        if (r > BFQ_REPAIR_RUN_MAX && order[start[p]] < firstBad) firstBad = order[start[p]];
+    }
+    if (firstBad != BFQ_PAIRS_NONE) {
+        X->kind = BFQ_PAIRS_E_RUN;
+        X->k = bfq_repair_text_of(firstBad, n, &X->n);
+        *S = bfq_repair_stats{};
+        return 2;
+    }
+    auto same = [&](const Rec &a, const Rec &b) { return a.h == b.h && a.kl == b.kl && !memcmp(text[a.src] + a.ks, text[b.src] + b.ks, (size_t)a.kl); };
+    std::vector<u8> role(N);
+    std::vector<u64> anchor(N);
+    for (u64 p = 0; p < N; p++) {
+        const Rec &me = R[order[p]];
+        u64 e = start[p];
+        u32 before[3] = {0, 0, 0}, total[3] = {0, 0, 0};
+        bool mixed = false;
+        for (; e < N && start[e] == start[p]; e++) {
+            const Rec &o = R[order[e]];
+            if (!same(me, o)) { mixed = true; continue; }
+            total[o.hint]++;
+            if (e < p) before[o.hint]++;
+        }
+        u32 mate = 0;
+        const u32 r = bfq_repair_role(me.hint, before, total, &mate);
+        role[order[p]] = (u8)r;
+        if (r) {                                                // the anchor: the mate-th record of list L1 (hint 0: L0) of the group
+            const u32 list = me.hint ? 1u : 0u;
+            u32 seen = 0;
+            for (u64 q = start[p]; q < e; q++) {
+                const Rec &o = R[order[q]];
+                if (o.hint != list || !same(me, o)) continue;
+                if (seen++ == mate) { anchor[order[p]] = order[q]; break; }
+            }
+        }
+        if (p == start[p] && mixed) S->mixed_runs++;
+        if (before[0] + before[1] + before[2] == 0 && total[0] + total[1] + total[2] > 2) S->dup_groups++;
+    }
+    // step 4: ranks in global order, sizes, offsets
+    std::vector<u64> rank1(N), rank0(N), off[3];
+    u64 P = 0, Z = 0;
+    for (u64 g = 0; g < N; g++) { rank1[g] = P; rank0[g] = Z; P += role[g] == 1; Z += role[g] == 0; }
+    off[0].assign(Z + 1, 0); off[1].assign(P + 1, 0); off[2].assign(P + 1, 0);
+    std::vector<u64> slot(N);
+    for (u64 g = 0; g < N; g++) {
+        slot[g] = role[g] ? rank1[anchor[g]] : rank0[g];
+        off[role[g]][slot[g]] = R[g].size;
+    }
+    u64 at[3] = {0, 0, 0};
+    for (int k = 0; k < 3; k++)
+        for (u64 j = 0; j < off[k].size(); j++) { const u64 s = off[k][j]; off[k][j] = at[k]; at[k] += s; }
+    S->records = N; S->pairs = P; S->singles = Z;
+    for (int k = 0; k < 3; k++) { S->out_len[k] = at[k]; S->n_in[k] = n[k]; }
+    nReads[0] = Z; nReads[1] = nReads[2] = P;
+    if (measure) return 0;
+    for (int k = 0; k < 3; k++)
+        if (cap[k] < at[k]) return 3;
+    // step 5: every record moved once
+    for (u64 g = 0; g < N; g++) bfq_pairs_put(out[role[g]] + off[role[g]][slot[g]], text[R[g].src], len[R[g].src], I[R[g].src], R[g].i);
     return 0;
 }

@@ -9,7 +9,9 @@
 //   3  the move, one copy of every record: into the caller's device buffers, or into the arena and from there through
 //      bfq_download (host buffers) or the background writers (files)
 //   arena   per text 8 bytes per line (and 12 per 4 KiB while they are indexed) and 44 per record; 16 bytes per pair (orphan
-//           mode: 57 per record) of sizes and offsets; the outputs unless they are the caller's device buffers
+//           mode: 57 per record; repair: 83 per record) of sizes and offsets; the outputs unless they are the caller's device
+//           buffers
+// The repair (bfq_fastq_repair*) stages its three texts the same way; its step 2 is hash, sort, group and place (k_pairs.hip).
 // The *_host forms run bfq_pairs.h by one thread, for tests and as the statement of the algorithm: no entry point here falls
 // back to them.
 #include <string.h>
@@ -20,7 +22,7 @@
 #include "bfq_internal.h"
 #include "bfq_pairs.h"
 
-static_assert(sizeof(bfq_pairs_opts) == 16 && sizeof(bfq_pairs_stats) == 48, "the C-ABI's structures");
+static_assert(sizeof(bfq_pairs_opts) == 16 && sizeof(bfq_pairs_stats) == 48 && sizeof(bfq_repair_opts) == 24 && sizeof(bfq_repair_stats) == 96, "the C-ABI's structures");
 
 #define PR_NL_CHUNK 4096u                                          // (k_fastq.hip's: bfq_line_index takes 12 bytes per chunk)
 
@@ -122,8 +124,9 @@ static void pr_nomem(bfq_ctx *c, size_t need)
 }
 
 // Step 1 for the texts src[0, 3) (merge: the refusal names the text): t[k] = text k on the device with its index (an absent
-// or empty text: no records).  orphans / arenaOut: what steps 2 and 3 take from the arena beside the index.
-static void pr_stage(bfq_ctx *c, const PrSrc src[3], u32 merge, bool orphans, bool arenaOut, PrText t[3])
+// or empty text: no records; merge = 2: the repair).  perRec / arenaOut: what steps 2 and 3 take from the arena beside the
+// index, in bytes per record, and whether the outputs lie there.
+static void pr_stage(bfq_ctx *c, const PrSrc src[3], u32 merge, size_t perRec, bool arenaOut, PrText t[3])
 {
     u64 tl[3] = {0, 0, 0};
     bool moved[3] = {false, false, false};
@@ -174,7 +177,7 @@ static void pr_stage(bfq_ctx *c, const PrSrc src[3], u32 merge, bool orphans, bo
         nb += n;
         need += 8 * (size_t)(lines[k] + 64) + 12 * (size_t)(tl[k] / PR_NL_CHUNK + 2) + 8192 + 44 * (size_t)(n + 64) + 32 * (size_t)(n / 4096 + 2);
     }
-    need += (orphans ? 57 : 8) * (size_t)(nb + 64) + 64 * (size_t)(nb / 4096 + 2);
+    need += perRec * (size_t)(nb + 64) + 64 * (size_t)(nb / 4096 + 2);
     if (c->wsLimit() && bufNeed + need > c->wsLimit()) pr_nomem(c, bufNeed + need);
     bfq_phase("alloc");
     c->reserve(need);
@@ -212,7 +215,7 @@ static void split_core(bfq_ctx *c, const PrSrc &in, const bfq_pairs_opts &O, boo
 {
     const PrSrc src[3] = {in, PrSrc{}, PrSrc{}};
     PrText t3[3];
-    pr_stage(c, src, 0, O.orphans != 0, !measure && !sink.device, t3);
+    pr_stage(c, src, 0, O.orphans ? 57 : 8, !measure && !sink.device, t3);
     const PrText &t = t3[0];
     const u64 N = t.N;
     bfq_pairs_err X;
@@ -270,7 +273,7 @@ static void split_core(bfq_ctx *c, const PrSrc &in, const bfq_pairs_opts &O, boo
 static void merge_core(bfq_ctx *c, const PrSrc src[3], const bfq_pairs_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_pairs_stats *S)
 {
     PrText t[3];
-    pr_stage(c, src, 1, false, !measure && !sink.device, t);
+    pr_stage(c, src, 1, 8, !measure && !sink.device, t);
     bfq_pairs_err X;
     X.merge = 1;
     if (t[1].N != t[2].N) { c->profCollect(); X.kind = BFQ_PAIRS_E_COUNTS; X.n = t[1].N; X.m = t[2].N; pr_refuse(X); }
@@ -512,5 +515,194 @@ extern "C" int bfq_fastq_interleave_fd(bfq_ctx *c, const int text_fd[3], const b
             F.fail(c, 1);
             throw;
         }
+    });
+}
+
+// ---------------------------------------------------------------- the repair
+// arena bytes per record beside the index: role, two role flags and anchor (11) stay; under them first the hashes, hints, two
+// sort records, the sorted (g, hint) and h words and the run starts (57, + at most 1 of radix counts), then, in the same
+// space, two ranks, the slot, three sizes and three offsets (72): 83 at the peak
+#define RP_PER_REC 88u
+
+extern "C" void bfq_repair_default_opts(bfq_repair_opts *o) { if (o) bfq_repair_defaults(o); }
+
+static bfq_repair_opts rp_opts(const bfq_repair_opts *in)
+{
+    bfq_repair_opts O;
+    bfq_pairs_err X;
+    if (!bfq_repair_resolve(in, &O, &X)) pr_refuse(X);
+    return O;
+}
+
+static void repair_core(bfq_ctx *c, const PrSrc src[3], const bfq_repair_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_repair_stats *S)
+{
+    PrText t[3];
+    pr_stage(c, src, 2, RP_PER_REC, !measure && !sink.device, t);
+    const u64 N = t[0].N + t[1].N + t[2].N;
+    u8 *role = c->alloc<u8>(N + 1), *f1 = c->alloc<u8>(N + 1), *f0 = c->alloc<u8>(N + 1);
+    u64 *anchor = c->alloc<u64>(N + 1), *d_stat = c->alloc<u64>(9);   // d_stat: longest run, first bad record, dup_groups, mixed_runs, P, Z, three lengths
+    u64 stat[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    {
+        const size_t m = c->mark();
+        u64 *h = c->alloc<u64>(N + 1), *sg = c->alloc<u64>(N + 1), *sh = c->alloc<u64>(N + 1), *start = c->alloc<u64>(N + 1);
+        u8 *hint = c->alloc<u8>(N + 1);
+        SortRec a{c->alloc<u32>(N + 4), c->alloc<u64>(N + 4)}, b{c->alloc<u32>(N + 4), c->alloc<u64>(N + 4)};
+        bfq_repair_sort(c, t, N, O, h, hint, a, b, sg, sh, start, d_stat);
+        HIP_CHECK(hipMemcpyAsync(stat, d_stat, 16, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        if (stat[1] != BFQ_PAIRS_NONE) {                          // a run too long to walk: refused before anything walks it
+            c->profCollect();
+            bfq_pairs_err X;
+            const u64 n[3] = {t[0].N, t[1].N, t[2].N};
+            X.kind = BFQ_PAIRS_E_RUN; X.merge = 2;
+            X.k = bfq_repair_text_of(stat[1], n, &X.n);
+            pr_refuse(X);
+        }
+        HIP_CHECK(hipMemsetAsync(d_stat + 2, 0, 16, c->stream));
+        bfq_repair_group(c, t, N, O.mate_suffix, start, sg, sh, role, anchor, f1, f0, d_stat + 2);
+        c->release(m);   // stream-ordered, as in k_scan.hip
+    }
+    u64 *rank1 = c->alloc<u64>(N + 2), *rank0 = c->alloc<u64>(N + 2), *slot = c->alloc<u64>(N + 1), *sz[3], *o[3];
+    for (int k = 0; k < 3; k++) { sz[k] = c->alloc<u64>(N + 1); o[k] = c->alloc<u64>(N + 2); }
+    bfq_exscan_u8(c, f1, rank1, N, d_stat + 4);
+    bfq_exscan_u8(c, f0, rank0, N, d_stat + 5);
+    HIP_CHECK(hipMemcpyAsync(stat + 2, d_stat + 2, 32, hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    const u64 P = stat[4], Z = stat[5], cnt[3] = {Z, P, P};
+    bfq_repair_place(c, t, N, role, anchor, rank1, rank0, slot, sz);
+    for (int k = 0; k < 3; k++) bfq_exscan_u64(c, sz[k], o[k], cnt[k], d_stat + 6 + k);
+    HIP_CHECK(hipMemcpyAsync(stat + 6, d_stat + 6, 24, hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    const u64 lens[3] = {stat[6], stat[7], stat[8]};
+    *S = bfq_repair_stats{};
+    S->records = N; S->pairs = P; S->singles = Z; S->dup_groups = stat[2]; S->mixed_runs = stat[3]; S->max_run = stat[0];
+    for (int k = 0; k < 3; k++) { S->out_len[k] = lens[k]; S->n_in[k] = t[k].N; }
+    nReads[0] = Z; nReads[1] = nReads[2] = P;
+    sink.sized(lens);
+    if (measure) { c->profCollect(); return; }
+    u8 *dst[3];
+    for (int k = 0; k < 3; k++) dst[k] = sink.device ? sink.d_dst[k] : c->alloc<u8>(lens[k] + 64);
+    const u64 *const off[3] = {o[0], o[1], o[2]};
+    bfq_repair_move(c, t, N, role, slot, off, dst);
+    if (!sink.device)
+        for (int k = 0; k < 3; k++)
+            if (lens[k]) sink.put(k, dst[k], lens[k]);
+    c->sync();
+    c->profCollect();
+}
+
+static int rp_mem(bfq_ctx *c, const uint8_t *const *text, const uint64_t *text_len, const bfq_repair_opts *opts, uint8_t *const *out, const uint64_t *cap,
+                  bool device, bool measure, uint64_t *out_len, uint64_t *n_reads, bfq_repair_stats *stats)
+{
+    pr_zero3(out_len); pr_zero3(n_reads);
+    if (stats) *stats = bfq_repair_stats{};
+    return guarded(c, [&] {
+        if (!text || !text_len || !out_len || (!measure && (!out || !cap))) throw BfqError{BFQ_E_ARG, "null argument"};
+        if (!measure)
+            for (int k = 0; k < 3; k++)
+                if (!out[k] && cap[k]) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_repair_opts O = rp_opts(opts);
+        PrSrc src[3];
+        for (int k = 0; k < 3; k++) {
+            if (!text[k]) continue;
+            if (device) src[k].d = text[k]; else src[k].ref = HostRef::mem(text[k]);
+            src[k].len = text_len[k];
+        }
+        PrSink sink;
+        sink.device = device;
+        sink.sized = [&](const u64 *lens) { if (!measure) pr_check_caps(c, cap, lens, 3, out_len, 2); };
+        if (!measure && device) for (int k = 0; k < 3; k++) sink.d_dst[k] = out[k];
+        sink.put = [&](int k, const u8 *d_text, u64 len) {
+            bfq_phase("d2h_write");
+            bfq_download(c, out[k], d_text, len);
+            bfq_phase("gpu");
+        };
+        u64 nr[3] = {0, 0, 0};
+        bfq_repair_stats S;
+        repair_core(c, src, O, measure, sink, nr, &S);
+        for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
+        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+        if (stats) *stats = S;
+    });
+}
+
+extern "C" int bfq_fastq_repair_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint64_t out_len[3],
+                                        uint64_t n_reads[3], bfq_repair_stats *stats)
+{
+    return rp_mem(c, h_text, text_len, opts, nullptr, nullptr, false, true, out_len, n_reads, stats);
+}
+extern "C" int bfq_fastq_repair(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint8_t *const h_out[3],
+                                const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_repair_stats *stats)
+{
+    return rp_mem(c, h_text, text_len, opts, h_out, cap, false, false, out_len, n_reads, stats);
+}
+extern "C" int bfq_fastq_repair_device(bfq_ctx *c, const uint8_t *const d_text[3], const uint64_t text_len[3], const bfq_repair_opts *opts,
+                                       uint8_t *const d_out[3], const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_repair_stats *stats)
+{
+    return rp_mem(c, d_text, text_len, opts, d_out, cap, true, false, out_len, n_reads, stats);
+}
+
+extern "C" int bfq_fastq_repair_fd(bfq_ctx *c, const int text_fd[3], const bfq_repair_opts *opts, const int out_fd[3], uint64_t out_len[3], uint64_t n_reads[3],
+                                   bfq_repair_stats *stats)
+{
+    pr_zero3(out_len); pr_zero3(n_reads);
+    if (stats) *stats = bfq_repair_stats{};
+    return guarded(c, [&] {
+        if (!out_len || !text_fd || !out_fd) throw BfqError{BFQ_E_ARG, "null argument"};
+        PrFiles F;
+        for (int k = 0; k < 3; k++) F.fd[k] = out_fd[k];
+        try {
+            const bfq_repair_opts O = rp_opts(opts);
+            PrSrc src[3];
+            for (int k = 0; k < 3; k++) {
+                if (text_fd[k] < 0) continue;
+                struct stat st;
+                if (fstat(text_fd[k], &st) != 0) throw BfqError{BFQ_E_IO, std::string("cannot stat a text file: ") + strerror(errno)};
+                src[k].ref = HostRef::file(text_fd[k]); src[k].len = (u64)st.st_size;
+            }
+            PrSink sink;
+            sink.sized = [&](const u64 *lens) {
+                F.start(lens, 3);
+                c->call.writeHint = (size_t)(lens[0] + lens[1] + lens[2]);
+            };
+            sink.put = [&](int k, const u8 *d_text, u64 n) { if (F.fd[k] >= 0) bfq_write_async(c, F.of[k].at(0), d_text, n); };
+            u64 nr[3] = {0, 0, 0};
+            bfq_repair_stats S;
+            repair_core(c, src, O, false, sink, nr, &S);
+            bfq_phase("d2h_write");
+            bfq_write_wait(c);
+            if (!F.finish(S.out_len, 3)) throw BfqError{BFQ_E_IO, "cannot size the output files"};
+            for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
+            if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+            if (stats) *stats = S;
+        } catch (...) {
+            F.fail(c, 3);
+            throw;
+        }
+    });
+}
+
+extern "C" int bfq_fastq_repair_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint8_t *const h_out[3],
+                                     const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_repair_stats *stats)
+{
+    pr_zero3(out_len); pr_zero3(n_reads);
+    if (stats) *stats = bfq_repair_stats{};
+    return pr_host_guarded([&] {
+        if (!text || !text_len || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
+        const bfq_repair_opts O = rp_opts(opts);
+        const bool measure = !h_out && !cap;
+        if (!measure && (!h_out || !cap)) throw BfqError{BFQ_E_ARG, "null argument"};
+        if (!measure)
+            for (int k = 0; k < 3; k++)
+                if (!h_out[k] && cap[k]) throw BfqError{BFQ_E_ARG, "null argument"};
+        bfq_repair_stats S;
+        bfq_pairs_err X;
+        u64 nr[3];
+        const int r = bfq_pairs_repair_host(text, text_len, O, h_out, cap, measure, &S, nr, &X);
+        if (r == 2) pr_refuse(X);
+        for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
+        if (r == 3) { X.kind = BFQ_PAIRS_E_CAP; X.merge = 2; pr_refuse(X); }
+        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+        if (stats) *stats = S;
     });
 }

@@ -281,6 +281,32 @@ def split_interleaved_input(eng, comm, inputs, out="", log=None):
     return q, q, None
 
 
+def repair_inputs(eng, comm, inputs, out="", log=None):
+    """--repair: the mates of the inputs -- two mate files that may each have lost reads, in any order, or one mixed file --
+    are matched by name on the GPU of rank 0 (eng.fastq_repair_files) into <name>_1.fastq and <name>_2.fastq beside the
+    outputs (bam_names), what finds no mate into <name>_singles.fastq, which the run does not touch; the run goes on as a
+    two-file paired run: returns (the new input list, the two files written, None) -- or, for a refusal, (the old list,
+    the files written, the library's message) on every rank, before any block runs."""
+    from . import api
+    q = bam_names(inputs[0], out, True)
+    singles = q[0][:-len("_1.fastq")] + "_singles.fastq"
+    why = None
+    if comm.rank == 0:
+        try:
+            texts = (None, inputs[0], inputs[1]) if len(inputs) == 2 else (inputs[0], None, None)
+            n, reads, st = eng.fastq_repair_files(texts, (singles, q[0], q[1]))
+            if log:
+                log(f"repair: {' '.join(inputs)} -> {q}, {reads[1]} pairs; {reads[0]} singletons -> {singles}, {st}")
+        except api.BfqError as e:
+            why = str(e)
+            if os.path.exists(singles):
+                os.remove(singles)
+    if comm.all_gather_i64([1 if why else 0])[0, 0]:
+        return list(inputs), q, why or "the inputs were refused on rank 0"
+    comm.barrier()
+    return q, q, None
+
+
 def merge_interleaved_output(eng, comm, outputs, path, check_names, log=None):
     """--interleaved-out: after the run rank 0 merges the two merged output texts into one file with the mates alternating
     (eng.fastq_interleave_files), the names compared when the run kept them.  Returns None, or the library's message on every
@@ -769,8 +795,22 @@ def main(argv=None):
                     help="with -p and a merged FASTQ output: after the run the two output texts are merged on the GPU of rank 0 into one "
                          "file with the mates alternating at PATH (the names compared with -H or --m3); not with --restore, "
                          "--streams-only or --compress")
+    ap.add_argument("--repair", action="store_true",
+                    help="the mates are matched by name on the GPU first, wherever they stand: with -p the two inputs are mate files that "
+                         "may each have lost reads; one input is a mixed file (/1 and /2 say which mate a record is).  The run goes on as "
+                         "-p on <name>_1.fastq / <name>_2.fastq beside the outputs (--keep-inflated keeps them); what finds no mate goes to "
+                         "<name>_singles.fastq, which the run does not touch; more than 1024 records of one name end the run")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.repair:
+        why = None
+        if a.restore or a.interleaved or a.bam:
+            why = "--repair reads FASTQ text in front of a run: not with --restore, --interleaved or --bam"
+        elif len(a.input) != (2 if a.paired else 1):
+            why = "--repair takes two mate files with -p, or one mixed file"
+        if why:
+            print("=== ERROR ===\n" + why, file=sys.stderr)
+            return 1
     if a.interleaved:
         why = None
         if len(a.input) != 1 or a.restore:
@@ -837,7 +877,9 @@ def main(argv=None):
     if a.restore and (len(a.input) not in (2, 3) or not a.out):
         print("=== ERROR ===\n--restore DNA.bsc QS.bsc [HDR.bsc] -o OUT.fq", file=sys.stderr)
         return 1
-    if a.paired and len(a.input) != 2 and not ((a.bam or a.interleaved) and len(a.input) == 1):
+    if a.repair:
+        a.paired = True
+    if a.paired and len(a.input) != 2 and not ((a.bam or a.interleaved or a.repair) and len(a.input) == 1):
         print("=== ERROR ===\npaired end mode", file=sys.stderr)
         return 1
     if a.m3:
@@ -889,6 +931,19 @@ def main(argv=None):
         if why:                                                      # (not properly paired: the library's message; every rank leaves with it)
             if comm.rank == 0:
                 print(f"=== ERROR ===\n--interleaved: {why}", file=sys.stderr)
+                for q in inflated:
+                    if os.path.exists(q) and not a.keep_inflated:
+                        os.remove(q)
+            eng.close()
+            if dist:
+                dist.destroy_process_group()
+            return 1
+    if a.repair:
+        a.input, mates, why = repair_inputs(eng, comm, a.input, a.out, log=log)
+        inflated += mates
+        if why:                                                      # (the library's message; every rank leaves with it)
+            if comm.rank == 0:
+                print(f"=== ERROR ===\n--repair: {why}", file=sys.stderr)
                 for q in inflated:
                     if os.path.exists(q) and not a.keep_inflated:
                         os.remove(q)

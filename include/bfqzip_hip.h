@@ -983,6 +983,53 @@ int bfq_fastq_interleave_fd(bfq_ctx *c, const int text_fd[3], const bfq_pairs_op
 int bfq_fastq_interleave_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_pairs_opts *opts, uint8_t *out, uint64_t cap,
                               uint64_t *out_len, bfq_pairs_stats *stats);
 const char *bfq_pairs_host_error(void);
+/* ---- repair paired FASTQ: the mates matched by name across files, wherever they stand (k_pairs.hip, the repair section;
+ * the definition: csrc/bfq_pairs.h).  For mate files that were filtered on their own, for the text of a coordinate-sorted BAM
+ * (bfq_bam_to_fastq without -1 -2, then this call with the text as text[0]) and for any mixed or shuffled interleaved file.
+ *   The texts: text[1], text[2] and text[0] as in bfq_fastq_interleave (a NULL text, or text_fd < 0, holds no reads); plain
+ *     FASTQ with the parsing, the messages and the 1f 8b refusal of the merge ("FASTQ repair: text <k> is compressed ...").
+ *     A record is its four lines byte for byte.  The global number g of a record counts the records of text 1, then those of
+ *     text 2, then those of text 0.
+ *   Key: as above, with mate_suffix.  Hint of a record: 1 from text 1, 2 from text 2; from text 0, with mate_suffix, 1 where
+ *     the key lost "/1" and 2 where it lost "/2"; else 0.
+ *   Group: all records of the call with equal keys (compared in full), split in global order by hint into L1, L2 and L0.
+ *     Pairs: (L1[k], L2[k]) for k < min(|L1|, |L2|), then (L0[2j], L0[2j+1]) for 2j + 1 < |L0|; the first record of a pair
+ *     goes to out[1], the second to out[2], every other record of the group to out[0].
+ *   Order: pairs in increasing global number of their out[1] record (a repaired R1 keeps R1's order), singletons in increasing
+ *     global number.  The outputs are a function of the texts and mate_suffix only: neither hash_bits nor seed shows in them.
+ *   opts (NULL: the defaults): mate_suffix 1, hash_bits 40 (1..40, else BFQ_E_ARG), seed 0; reserved != 0: BFQ_E_ARG.  The
+ *     records are sorted (stable radix passes, ceil(hash_bits / 8) of them) by the top hash_bits bits of a 64-bit hash of the
+ *     key (csrc/bfq_pairs.h states it) and each run of equal sort keys is cut into groups by the full hash and then the key's
+ *     bytes.  A run of more than 1024 records: BFQ_E_ARG, "FASTQ repair: more than 1024 records share a name or a name hash
+ *     (the first: record <i> of text <k>): names do not identify the mates" -- <i>: the smallest global number in such a
+ *     run, relative to its text.  The bound limits every loop of the grouping; a file of "@"-only headers is refused by it.
+ *     Small hash_bits force runs with several names in them: a knob for tests.
+ *   Every refusal writes nothing in any form and leaves the context usable; all sizes are exact before the first byte moves.
+ *       _measure : host texts in; out_len[3], n_reads[3] (reads per output) and *stats; nothing is written.
+ *       plain    : host buffers.  A cap[k] below its length: BFQ_E_ARG, nothing written, out_len[] = the lengths needed.
+ *       _device  : device buffers in and out, written straight after the last check.  A device text at an address that is no
+ *                  multiple of 16, or without its final LF, is copied first.
+ *       _fd      : open files; an out_fd[k] < 0 is not written; output files are sized to their text (0 on a failure).
+ *       _host    : one thread, no context, no GPU: the same bytes, stats and messages.  States the algorithm; NO entry point
+ *                  falls back to it.  Message: bfq_pairs_host_error().
+ *   Device memory: the texts as for the merge; in the workspace, reserved once from the counted lines: 8 bytes per line and
+ *   44 per record of index, 83 per record of hashes, sort records, roles, ranks, sizes and offsets, and -- host and file forms
+ *   -- the outputs.  Above ws_cap_mib: BFQ_E_NOMEM with the size in the message.
+ *   stats (may be NULL): records, pairs, singles, out_len[3], n_in[3] (records per input text), dup_groups (groups of more
+ *   than two records), mixed_runs (runs of equal sort key with more than one name), max_run (the longest run). */
+typedef struct bfq_repair_opts  { uint32_t mate_suffix, hash_bits; uint64_t seed; uint32_t reserved[2]; } bfq_repair_opts;
+typedef struct bfq_repair_stats { uint64_t records, pairs, singles, out_len[3], n_in[3], dup_groups, mixed_runs, max_run; } bfq_repair_stats;
+void bfq_repair_default_opts(bfq_repair_opts *o);
+int bfq_fastq_repair_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint64_t out_len[3],
+                             uint64_t n_reads[3], bfq_repair_stats *stats);
+int bfq_fastq_repair(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint8_t *const h_out[3],
+                     const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_repair_stats *stats);
+int bfq_fastq_repair_device(bfq_ctx *c, const uint8_t *const d_text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint8_t *const d_out[3],
+                            const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_repair_stats *stats);
+int bfq_fastq_repair_fd(bfq_ctx *c, const int text_fd[3], const bfq_repair_opts *opts, const int out_fd[3], uint64_t out_len[3], uint64_t n_reads[3],
+                        bfq_repair_stats *stats);
+int bfq_fastq_repair_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint8_t *const h_out[3],
+                          const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_repair_stats *stats);
 /* ---- bgzip-compressed output: BGZF members deflated on the device (k_deflate.hip; the format and every bound:
  * csrc/bfq_deflate.h).  A text of len bytes is cut at multiples of 65 280 bytes (htslib's member size; the cut depends on
  * nothing else); every piece becomes one BGZF member -- htslib's 18-byte header, a raw deflate payload, CRC32 and ISIZE --
