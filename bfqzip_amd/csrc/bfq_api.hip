@@ -977,7 +977,7 @@ static u8 *fastq_upload_and_reserve(bfq_ctx *c, const TextSrc *parts, int nparts
     u8 *d_fq = text_place(c, parts, M, pstart.data());
     const u64 len = pstart[nparts];
     bfq_phase("alloc");
-    c->reserve(16 * (len / 4096 + 16) + (64u << 20));
+    c->reserve(bfq_count_lines_bytes(len) + (64u << 20));
     bfq_phase("gpu");
     u64 nlines = bfq_fastq_count_lines(c, d_fq, len);
     u64 N = nlines / 4 + 1;
@@ -1072,12 +1072,12 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
         u8 *d_fq = text_place(c, &text, M, ps);
         const u64 tl = ps[1];
         bfq_phase("alloc");
-        c->reserve(16 * (tl / 4096 + 16) + (64u << 20));
+        c->reserve(bfq_count_lines_bytes(tl) + (64u << 20));
         bfq_phase("gpu");
         const u64 nlines = bfq_fastq_count_lines(c, d_fq, tl);
         const u64 Nb = nlines / 4 + 1;
         bfq_phase("alloc");
-        const size_t parseBytes = (tl + 8192) + 128 * (Nb + 64) + 8 * (nlines + 64) + 16 * (tl / 4096 + 16) + (64u << 20);
+        const size_t parseBytes = (tl + 8192) + 128 * (Nb + 64) + bfq_line_index_bytes(tl, nlines) + 4 * (size_t)(tl / BFQ_NL_CHUNK) + 4096 + (64u << 20);
         pws.alloc(c, parseBytes, "the parsed records");
         ScopedArena parse(c, pws.p, parseBytes);                // the small arena of the line count comes back below
         bfq_phase("gpu");

@@ -77,8 +77,7 @@ extern "C" int bfq_bam_to_fastq_host(const uint8_t *raw, uint64_t raw_len, const
 {
     if (out_len) out_len[0] = out_len[1] = out_len[2] = 0;
     if (n_reads) n_reads[0] = n_reads[1] = n_reads[2] = 0;
-    g_bamHostErr.clear();
-    try {
+    return host_guarded(g_bamHostErr, [&] {
         if (!out_len || !n_reads || (!raw && raw_len) || (h_out && !cap)) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_bam_opts O = bam_opts(opts);
         bfq_bam_tag_stats *tagStats = nullptr, TS{};
@@ -95,14 +94,7 @@ extern "C" int bfq_bam_to_fastq_host(const uint8_t *raw, uint64_t raw_len, const
         if (r == 1) bam_refuse(E);
         for (int o = 0; o < 3; o++) { out_len[o] = ol[o]; n_reads[o] = nr[o]; }
         if (r == 2) throw BfqError{BFQ_E_ARG, BAM_SMALL};
-        return BFQ_OK;
-    } catch (const BfqError &e) {
-        g_bamHostErr = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        g_bamHostErr = "host out of memory";
-        return BFQ_E_NOMEM;
-    }
+    });
 }
 
 // Steps 1-3, shared by both directions (bfq_bam.h states what it leaves).
@@ -212,7 +204,6 @@ static void bam_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *op
     for (int o = 0; o < 3; o++) where[o] = W.text[o];
 }
 
-static void zero3(uint64_t *a) { if (a) a[0] = a[1] = a[2] = 0; }
 // runs bam_core and leaves out_len / n_reads as the header states: the lengths on success and on a short capacity, else 0
 template <class After> static int bam_call(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *opts, BamMode mode, u8 *const d_out[3], const uint64_t capIn[3],
                                            uint64_t out_len[3], uint64_t n_reads[3], bfq_bam_stats *stats, After after)
@@ -265,15 +256,8 @@ extern "C" int bfq_bam_to_fastq_fd(bfq_ctx *c, int in_fd, uint64_t len, const bf
                                    uint64_t n_reads[3], bfq_bam_stats *stats)
 {
     // the BGZF directory is read from headers and trailers all over the file: the file is mapped, and uploaded from the mapping
-    struct Map {
-        void *p = MAP_FAILED; size_t n = 0;
-        ~Map() { if (p != MAP_FAILED) munmap(p, n); }
-    } map;
-    if (in_fd >= 0 && len) {
-        map.n = (size_t)len;
-        map.p = mmap(nullptr, map.n, PROT_READ, MAP_PRIVATE, in_fd, 0);
-    }
-    if (in_fd < 0 || (len && map.p == MAP_FAILED)) {
+    MappedInput map;
+    if (in_fd < 0 || !map.open(in_fd, (size_t)len)) {
         zero3(out_len); zero3(n_reads);
         return guarded(c, [&] {
             if (in_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
@@ -281,7 +265,7 @@ extern "C" int bfq_bam_to_fastq_fd(bfq_ctx *c, int in_fd, uint64_t len, const bf
         });
     }
     const uint64_t cap[3] = {~0ull, ~0ull, ~0ull};
-    return bam_call(c, len ? (const u8 *)map.p : nullptr, len, opts, BAM_ARENA, nullptr, cap, out_len, n_reads, stats,
+    return bam_call(c, map.data(), len, opts, BAM_ARENA, nullptr, cap, out_len, n_reads, stats,
                     [&](u8 *const *where, const u64 *ol) {
         bfq_phase("d2h_write");
         for (int o = 0; o < 3; o++) {

@@ -13,8 +13,6 @@
 // here falls back to it.
 #include <string.h>
 #include <stdio.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
 #include <algorithm>
 #include <functional>
 #include "bfq_internal.h"
@@ -27,8 +25,6 @@ void bfq_bam_launch_patch_check(bfq_ctx *c, const u8 *d_s, u64 len, const bfq_ba
                                 u64 only, u64 *d_firstBad, bfq_bamp_err *d_err);                                   // k_bam_patch.hip
 void bfq_bam_launch_patch(bfq_ctx *c, u8 *d_s, u64 len, const bfq_bam_job *d_jobs, u64 nj, u32 nref, const bfq_bam_opts &O, const bfq_bam_texts &T, bfq_bamp_cnt *d_cnt);
 
-#define BAMP_NL_CHUNK 4096u                                        // (k_fastq.hip's: bfq_line_index takes 12 bytes per chunk)
-
 static void patch_refuse(const bfq_bamp_err &X) { throw BfqError{BFQ_E_ARG, bfq_bamp_message(X)}; }
 static void patch_check_level(int level)
 {
@@ -39,8 +35,8 @@ extern "C" int bfq_bam_patch_host(const uint8_t *raw, uint64_t raw_len, const bf
                                   uint8_t *out_raw, uint64_t cap, bfq_bam_patch_stats *stats)
 {
     if (stats) *stats = bfq_bam_patch_stats{};
-    bfq_bam_host_error_set("");
-    try {
+    std::string err;
+    const int rc = host_guarded(err, [&] {
         if ((!raw && raw_len) || !text || !text_len || (!out_raw && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_bam_opts O = bfq_bam_opts_of(opts);
         static const u8 none = 0;
@@ -56,64 +52,30 @@ extern "C" int bfq_bam_patch_host(const uint8_t *raw, uint64_t raw_len, const bf
             throw BfqError{BFQ_E_ARG, "output buffer too small for the stream"};
         }
         if (stats) *stats = PS;
-        return BFQ_OK;
-    } catch (const BfqError &e) {
-        bfq_bam_host_error_set(e.msg);
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        bfq_bam_host_error_set("host out of memory");
-        return BFQ_E_NOMEM;
-    }
+    });
+    bfq_bam_host_error_set(err);                                    // (the BAM string: bfq_bam_host_error() reports both directions)
+    return rc;
 }
-
-// the texts of a call: on the host (h) or on the device (d); neither: absent
-struct PatchTexts { const u8 *h[3] = {nullptr, nullptr, nullptr}, *d[3] = {nullptr, nullptr, nullptr}; u64 len[3] = {0, 0, 0}; };
 
 // Steps 1-4.  extra(raw): arena bytes the caller needs behind them.  *C: the patched stream (d_s, raw).  sized(raw) runs
 // once the stream's length is known and before anything is checked against the texts: it throws for a short capacity.
-static void patch_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *opts, const PatchTexts &X, const std::function<size_t(u64)> &extra,
+static void patch_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *opts, const TextIn X[3], const std::function<size_t(u64)> &extra,
                        const std::function<void(u64)> &sized, bfq_bam_chain_dev *C, bfq_bam_patch_stats *stats)
 {
     const bfq_bam_opts O = bfq_bam_opts_of(opts);
     bfq_bamp_err R;
+    BfqTextSeen seen[3];
+    bfq_texts_look(c, X, 3, seen, false);
+    for (u32 k = 0; k < 3; k++)
+        if (seen[k].present && !bfq_bamp_gzip_ok(seen[k].first, seen[k].len, k, &R)) patch_refuse(R);
+    // Every text's lines, which size its index, are counted on the device before the arena is reserved.
+    TextPlaced t[3];
+    bfq_texts_place(c, X, bfq_texts_plan(seen, 3, false), 3, t);
     bool present[3];
-    u64 lines[3] = {0, 0, 0};
     size_t textNeed = 0;
     for (u32 k = 0; k < 3; k++) {
-        present[k] = X.h[k] || X.d[k];
-        if (!present[k]) continue;
-        u8 first[2] = {0, 0};
-        if (X.len[k] >= 2) {
-            if (X.h[k]) memcpy(first, X.h[k], 2);
-            else { HIP_CHECK(hipMemcpyAsync(first, X.d[k], 2, hipMemcpyDeviceToHost, c->stream)); c->sync(); }
-        }
-        if (!bfq_bamp_gzip_ok(first, X.len[k], k, &R)) patch_refuse(R);
-    }
-    // Host texts go up first, into the context's text buffer outside the arena -- as the FASTQ entry points place theirs --,
-    // so that every text's lines, which size its index, are counted on the device before the arena is reserved.  A device
-    // text stays where it lies unless its address is no multiple of 16 (the line kernels read 16 aligned bytes at a time).
-    const u8 *d_t[3] = {nullptr, nullptr, nullptr};
-    size_t bufNeed = 0, scratch = 0;
-    for (u32 k = 0; k < 3; k++)
-        if (present[k] && (X.h[k] || ((uintptr_t)X.d[k] & 15u) || !X.len[k])) bufNeed += ((size_t)X.len[k] + 16 + 255) & ~(size_t)255;
-    u8 *buf = bufNeed ? c->textBuf(bufNeed) : nullptr;
-    if (bufNeed) bfq_phase("read_h2d");
-    for (u32 k = 0; k < 3; k++) {
-        if (!present[k]) continue;
-        d_t[k] = X.d[k];
-        if (X.h[k] || ((uintptr_t)X.d[k] & 15u) || !X.len[k]) {
-            if (X.h[k]) bfq_upload(c, buf, X.h[k], X.len[k]);
-            else if (X.len[k]) HIP_CHECK(hipMemcpyAsync(buf, X.d[k], (size_t)X.len[k], hipMemcpyDeviceToDevice, c->stream));
-            d_t[k] = buf;
-            buf += ((size_t)X.len[k] + 16 + 255) & ~(size_t)255;
-        }
-        scratch = std::max(scratch, 12 * (size_t)(X.len[k] / BAMP_NL_CHUNK + 2) + 8192);
-    }
-    if (scratch) { bfq_phase("alloc"); c->reserve(scratch); bfq_phase("gpu"); }
-    for (u32 k = 0; k < 3; k++) {
-        if (!present[k]) continue;
-        lines[k] = bfq_fastq_count_lines(c, d_t[k], X.len[k]);
-        textNeed += 8 * (size_t)lines[k] + 12 * (size_t)(X.len[k] / BAMP_NL_CHUNK + 2) + 4096;
+        present[k] = seen[k].present;
+        if (present[k]) textNeed += bfq_line_index_bytes(t[k].len, t[k].lines) + 4096;
     }
     const std::function<size_t(u64)> more = [&](u64 raw) {
         const size_t np = (size_t)(raw / O.piece + 2);
@@ -125,8 +87,8 @@ static void patch_core(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *
     for (u32 k = 0; k < 3; k++) {
         if (!present[k]) continue;
         u64 nl = 0;
-        T.text[k] = d_t[k]; T.len[k] = X.len[k];
-        T.lineEnd[k] = bfq_line_index(c, d_t[k], X.len[k], &nl);
+        T.text[k] = t[k].d; T.len[k] = t[k].len;
+        T.lineEnd[k] = bfq_line_index(c, t[k].d, t[k].len, &nl);
         if (!bfq_bamp_lines_ok(nl, C->S.written[k], k, &R)) { c->profCollect(); patch_refuse(R); }
     }
     const u64 nj = C->jobs.size();
@@ -165,8 +127,8 @@ extern "C" int bfq_bam_patch_device(bfq_ctx *c, const uint8_t *h_in, uint64_t le
     if (stats) *stats = bfq_bam_patch_stats{};
     return guarded(c, [&] {
         if (!d_text || !text_len || !raw_len || (!d_out_raw && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
-        PatchTexts X;
-        for (int k = 0; k < 3; k++) { X.d[k] = d_text[k]; X.len[k] = d_text[k] ? text_len[k] : 0; }
+        TextIn X[3];
+        bfq_texts_of(d_text, text_len, true, X);
         bfq_bam_chain_dev C;
         bfq_bam_patch_stats PS{};
         patch_core(c, h_in, len, opts, X, [](u64) { return (size_t)0; }, [&](u64 raw) {
@@ -184,7 +146,7 @@ extern "C" int bfq_bam_patch_device(bfq_ctx *c, const uint8_t *h_in, uint64_t le
 }
 
 // host texts in, the compressed file out to dst (memory of cap bytes, or a file)
-static void patch_compressed(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *opts, const PatchTexts &X, int level, HostRef dst, u64 cap, uint64_t *out_len,
+static void patch_compressed(bfq_ctx *c, const u8 *h_in, u64 len, const bfq_bam_opts *opts, const TextIn X[3], int level, HostRef dst, u64 cap, uint64_t *out_len,
                              bfq_bam_patch_stats *stats)
 {
     patch_check_level(level);
@@ -207,8 +169,8 @@ extern "C" int bfq_bam_patch(bfq_ctx *c, const uint8_t *h_in, uint64_t len, cons
     if (stats) *stats = bfq_bam_patch_stats{};
     return guarded(c, [&] {
         if (!h_text || !text_len || !out_len || (!h_out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
-        PatchTexts X;
-        for (int k = 0; k < 3; k++) { X.h[k] = h_text[k]; X.len[k] = h_text[k] ? text_len[k] : 0; }
+        TextIn X[3];
+        bfq_texts_of(h_text, text_len, false, X);
         patch_compressed(c, h_in, len, opts, X, level, HostRef::mem(h_out), cap, out_len, stats);
     });
 }
@@ -219,26 +181,15 @@ extern "C" int bfq_bam_patch_fd(bfq_ctx *c, int bam_fd, uint64_t len, const bfq_
     if (out_len) *out_len = 0;
     if (stats) *stats = bfq_bam_patch_stats{};
     // the files are mapped, and uploaded from the mappings (the BGZF directory is read from headers and trailers all over the file)
-    struct Map {
-        void *p = MAP_FAILED; size_t n = 0;
-        bool open(int fd, size_t len) { n = len; p = len ? mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0) : MAP_FAILED; return !len || p != MAP_FAILED; }
-        ~Map() { if (p != MAP_FAILED) munmap(p, n); }
-    } bam, text[3];
+    MappedInput bam, text[3];
     return guarded(c, [&] {
         if (!out_len || !text_fd) throw BfqError{BFQ_E_ARG, "null argument"};
         if (bam_fd < 0 || out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
         if (!bam.open(bam_fd, (size_t)len)) throw BfqError{BFQ_E_IO, std::string("cannot map the input file: ") + strerror(errno)};
-        PatchTexts X;
-        static const u8 none = 0;
-        for (int k = 0; k < 3; k++) {
-            if (text_fd[k] < 0) continue;
-            struct stat st;
-            if (fstat(text_fd[k], &st) != 0 || !text[k].open(text_fd[k], (size_t)st.st_size)) throw BfqError{BFQ_E_IO, std::string("cannot map a text file: ") + strerror(errno)};
-            X.h[k] = st.st_size ? (const u8 *)text[k].p : &none;
-            X.len[k] = (u64)st.st_size;
-        }
+        TextIn X[3];
+        bfq_texts_map(text_fd, text, X);
         try {
-            patch_compressed(c, len ? (const u8 *)bam.p : nullptr, len, opts, X, level, HostRef::file(out_fd, 0), ~0ull, out_len, stats);
+            patch_compressed(c, bam.data(), len, opts, X, level, HostRef::file(out_fd, 0), ~0ull, out_len, stats);
             if (ftruncate(out_fd, (off_t)*out_len) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, std::string("cannot size the output file: ") + strerror(errno)};
         } catch (...) {
             if (ftruncate(out_fd, 0) != 0) {}

@@ -121,17 +121,10 @@ extern "C" int bfq_bgzf_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, int out_
         if (!out_len) throw BfqError{BFQ_E_ARG, "null argument"};
         if (in_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
         // the directory is read from the headers and trailers all over the file: the file is mapped, and uploaded from the mapping
-        struct Map {
-            void *p = MAP_FAILED; size_t n = 0;
-            ~Map() { if (p != MAP_FAILED) munmap(p, n); }
-        } map;
-        if (len) {
-            map.n = (size_t)len;
-            map.p = mmap(nullptr, map.n, PROT_READ, MAP_PRIVATE, in_fd, 0);
-            if (map.p == MAP_FAILED) throw BfqError{BFQ_E_IO, std::string("cannot map the input file: ") + strerror(errno)};
-        }
+        MappedInput map;
+        if (!map.open(in_fd, (size_t)len)) throw BfqError{BFQ_E_IO, std::string("cannot map the input file: ") + strerror(errno)};
         u8 *d_text = nullptr;
-        const u64 raw = bgzf_inflate_core(c, len ? (const u8 *)map.p : nullptr, len, nullptr, ~0ull, &d_text);
+        const u64 raw = bgzf_inflate_core(c, map.data(), len, nullptr, ~0ull, &d_text);
         if (out_fd >= 0) {
             bfq_phase("d2h_write");
             bfq_download(c, HostRef::file(out_fd, 0), d_text, raw);
@@ -144,29 +137,13 @@ extern "C" int bfq_bgzf_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, int out_
 
 // ---------------------------------------------------------------- text sources: plain or BGZF, measured and placed once
 // (fastq_upload_and_reserve and fastq_build_ebwt_oneshot of bfq_api.hip, both sides of bfq_compare.hip)
-static bool src_read(const TextSrc &t, u64 off, u8 *dst, size_t n)
-{
-    if (t.ref.ptr) { memcpy(dst, (const u8 *)t.ref.ptr + off, n); return true; }
-    size_t got = 0;
-    while (got < n) {
-        const ssize_t r = pread(t.ref.fd, dst + got, n - got, (off_t)(t.ref.off + off + got));
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) return false;
-        got += (size_t)r;
-    }
-    return true;
-}
+static TextIn src_in(const TextSrc &t) { TextIn in; in.ref = t.ref; in.len = t.len; return in; }
 bool bfq_text_is_gzip(const TextSrc &t)
 {
-    u8 b[2] = {0, 0};
-    return t.len >= 2 && !t.ref.null() && src_read(t, 0, b, 2) && b[0] == 0x1F && b[1] == 0x8B;
-}
-static bool src_ends_with_newline(const TextSrc &t)
-{
-    if (!t.len) return true;
-    u8 b = 0;
-    if (!src_read(t, t.len - 1, &b, 1)) throw BfqError{BFQ_E_IO, "cannot read the input file"};
-    return b == (u8)'\n';
+    const TextIn in = src_in(t);
+    BfqTextSeen s;
+    bfq_texts_look(nullptr, &in, 1, &s, false);
+    return bfq_seen_gzip(s);
 }
 // staging of one BGZF part behind the text: compressed bytes | directory | status word, newline flag
 static u64 stage_dir_off(u64 len) { return (len + 16 + 255) & ~255ull; }
@@ -180,9 +157,13 @@ void bfq_text_measure(const TextSrc *parts, int nparts, TextMeasure *M)
         TextMeasure::Part &P = M->part[p];
         P = TextMeasure::Part{};
         if (parts[p].len && parts[p].ref.null()) throw BfqError{BFQ_E_ARG, "null FASTQ text"};
-        if (!bfq_text_is_gzip(parts[p])) {
+        const TextIn in = src_in(parts[p]);
+        BfqTextSeen seen;                                          // one look: the first two bytes, then, of a plain part, the last
+        bfq_texts_look(nullptr, &in, 1, &seen, false);
+        if (!bfq_seen_gzip(seen)) {
+            bfq_texts_look(nullptr, &in, 1, &seen, true);
             P.raw = parts[p].len;
-            P.addNl = src_ends_with_newline(parts[p]) ? 0 : 1;
+            P.addNl = seen.last == 10 ? 0 : 1;
             M->bound += P.raw + P.addNl;
             continue;
         }

@@ -15,13 +15,7 @@
 using CmpSrc = TextSrc;
 struct CmpInput { const CmpSrc *parts; int nparts; u64 len; TextMeasure M; };   // len: a bound once measured, the length once placed
 
-static void cmp_nomem(bfq_ctx *c, size_t need)
-{
-    char b[240];
-    snprintf(b, sizeof b, "comparing needs %.2f GiB of device memory (both texts + index + diff records), above the cap of %.2f GiB "
-                          "(bfq_params.ws_cap_mib / BFQ_WS_CAP)", need / 1073741824.0, c->wsLimit() / 1073741824.0);
-    throw BfqError{BFQ_E_NOMEM, b};
-}
+static void cmp_nomem(bfq_ctx *c, size_t need) { bfq_nomem_cap(c, "comparing", "both texts + index + diff records", need); }
 
 // the length a text has on the device (the shared pair of bfq_bgzf.hip: a part that lacks its final newline gets one, a
 // BGZF part is inflated); what is refused is passed on with the input's name in front
@@ -64,14 +58,15 @@ static void compare_core(bfq_ctx *c, CmpInput A, CmpInput B, const u8 *h_permz, 
     cmp_upload(c, B, "B", d_b, d_a + sum);
     bfq_phase("alloc");
     const u64 maxLen = std::max(A.len, B.len);
-    c->reserve(16 * (maxLen / 4096 + 16) + (64u << 20));
+    c->reserve(bfq_count_lines_bytes(maxLen) + (64u << 20));
     bfq_phase("gpu");
     const u64 nlA = bfq_fastq_count_lines(c, d_a, A.len), nlB = bfq_fastq_count_lines(c, d_b, B.len);
     const u64 Nb = std::max(nlA, nlB) / 4 + 1;
     // per text: line ends, chunk counts of the line index, records + read offsets + lengths, the scans' partial sums; once: the
     // container's payload, the permutation and its inverse, the per-read counts and their scan, the report, the diff records
     const u64 diffCap = std::min(capDiffs, A.len / 2);            // a text of len bytes has at most len / 2 bases
-    const size_t perText = 8 * (size_t)(std::max(nlA, nlB) + 64) + 16 * (size_t)(maxLen / 4096 + 16) + (32 + 8 + 4 + 16) * (size_t)(Nb + 64);
+    // (slack, as reserved so far: 16 bytes per read, 16 per chunk of text where the line kernels take 12, and 4 KiB)
+    const size_t perText = bfq_fastq_index_bytes(maxLen, std::max(nlA, nlB)) + 16 * (size_t)(Nb + 64) + 4 * (size_t)(maxLen / BFQ_NL_CHUNK) + 4096;
     const size_t need = 2 * perText + (havePerm ? 24 : 0) * (size_t)(Nb + 64) + (4 + 8) * (size_t)(Nb + 64) + (size_t)(Nb >> 7) + sizeof(bfq_compare_report) +
                         16 * (size_t)diffCap + (8u << 20);
     if (c->wsLimit() && sum + need > c->wsLimit()) cmp_nomem(c, sum + need);

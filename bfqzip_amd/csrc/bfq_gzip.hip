@@ -48,8 +48,7 @@ extern "C" int bfq_gzip_inflate_host(const uint8_t *h_in, uint64_t len, uint64_t
                                      bfq_gzip_stats *stats)
 {
     if (out_len) *out_len = 0;
-    g_gzipHostErr.clear();
-    try {
+    return host_guarded(g_gzipHostErr, [&] {
         if (!out_len || (!h_in && len) || (cap && !h_out)) throw BfqError{BFQ_E_ARG, "null argument"};
         chunk = gzip_chunk(chunk);
         static const u8 none = 0;
@@ -63,11 +62,7 @@ extern "C" int bfq_gzip_inflate_host(const uint8_t *h_in, uint64_t len, uint64_t
         if (r == 2) { *out_len = raw; throw BfqError{BFQ_E_ARG, GZIP_SMALL}; }
         if (r == 1) throw BfqError{BFQ_E_ARG, gzip_message(E)};
         *out_len = raw;
-        return BFQ_OK;
-    } catch (const BfqError &e) {
-        g_gzipHostErr = e.msg;
-        return e.code;
-    }
+    });
 }
 
 // The text of h_in[0, len) at d_out (cap bytes; nullptr: in the arena), or steps 1-2 only (measure).  Returns the raw length
@@ -209,18 +204,11 @@ extern "C" int bfq_gzip_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, uint64_t
         if (!out_len) throw BfqError{BFQ_E_ARG, "null argument"};
         if (in_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
         // the decoders' records are walked between two uploads of the same bytes at most: the file is mapped
-        struct Map {
-            void *p = MAP_FAILED; size_t n = 0;
-            ~Map() { if (p != MAP_FAILED) munmap(p, n); }
-        } map;
-        if (len) {
-            map.n = (size_t)len;
-            map.p = mmap(nullptr, map.n, PROT_READ, MAP_PRIVATE, in_fd, 0);
-            if (map.p == MAP_FAILED) throw BfqError{BFQ_E_IO, std::string("cannot map the input file: ") + strerror(errno)};
-        }
+        MappedInput map;
+        if (!map.open(in_fd, (size_t)len)) throw BfqError{BFQ_E_IO, std::string("cannot map the input file: ") + strerror(errno)};
         u8 *d_text = nullptr;
         u64 needed = 0;
-        const u64 raw = gzip_core(c, len ? (const u8 *)map.p : nullptr, len, chunk, false, nullptr, ~0ull, &needed, stats, &d_text);
+        const u64 raw = gzip_core(c, map.data(), len, chunk, false, nullptr, ~0ull, &needed, stats, &d_text);
         if (out_fd >= 0) {
             bfq_phase("d2h_write");
             bfq_download(c, HostRef::file(out_fd, 0), d_text, raw);

@@ -16,6 +16,7 @@
 #include "bfq_common.h"
 #include "bfq_internal_host.h"
 #include "bfq_arena.h"
+#include "bfq_texts.h"
 
 #define HIP_CHECK(expr)                                                                        \
     do {                                                                                       \
@@ -239,6 +240,44 @@ struct TextMeasure {
 void bfq_text_measure(const TextSrc *parts, int nparts, TextMeasure *M);
 void bfq_text_put(bfq_ctx *c, const TextSrc *parts, TextMeasure *M, u8 *d_dst, u8 *d_stage, u64 *pstart);
 bool bfq_text_is_gzip(const TextSrc &t);        // begins with 1f 8b (the entry points that do not take BGZF refuse by it)
+// The plain texts of a call, up to three, staged one way (bfq_texts.hip; the plan and the sizes: bfq_texts.h).  A text is host
+// memory or an open file (ref), or device memory (d); neither: absent.
+//   bfq_text_peek   n bytes at `off` of a text of any of the three kinds (c may be null for the first two)
+//   bfq_texts_look  fills seen[0, n) and allocates nothing: last = false, everything but the last byte; last = true, the last
+//                   byte of what was filled before.  Between the two, and before bfq_texts_place, every caller refuses what it
+//                   refuses, in its own words and order.
+//   bfq_texts_place the text buffer for plan.bufNeed; what moves uploaded or copied there, with its LF where the plan adds one;
+//                   the arena reserved for counting; the lines of every present text counted.  out[k]: where text k stands,
+//                   its staged length, its lines (newlines + 1); an absent text: nullptr, 0, 0.
+struct TextIn {
+    HostRef ref; const u8 *d = nullptr; u64 len = 0;
+    bool present() const { return d || !ref.null(); }
+};
+struct TextPlaced { const u8 *d = nullptr; u64 len = 0, lines = 0; };
+#define BFQ_LOCAL __attribute__((visibility("hidden")))            // (the library's dynamic symbols stay as they were)
+BFQ_LOCAL void bfq_text_peek(bfq_ctx *c, const TextIn &in, u64 off, u8 *dst, size_t n);
+BFQ_LOCAL void bfq_texts_look(bfq_ctx *c, const TextIn *in, int n, BfqTextSeen *seen, bool last);
+BFQ_LOCAL void bfq_texts_place(bfq_ctx *c, const TextIn *in, const BfqTextPlan &plan, int n, TextPlaced *out);
+// the texts of an entry point's arguments: host or device pointers (nullptr: absent), or open files (< 0: absent) mapped into
+// map[] (an empty file: a text of no bytes)
+static inline void bfq_texts_of(const uint8_t *const *text, const uint64_t *len, bool device, TextIn X[3])
+{
+    for (int k = 0; k < 3; k++) {
+        X[k] = TextIn{};
+        if (device) X[k].d = text[k]; else X[k].ref = HostRef::mem(text[k]);
+        X[k].len = text[k] ? len[k] : 0;
+    }
+}
+BFQ_LOCAL void bfq_texts_map(const int fd[3], MappedInput map[3], TextIn X[3]);
+static inline bool bfq_seen_gzip(const BfqTextSeen &s) { return s.len >= 2 && s.first[0] == 0x1F && s.first[1] == 0x8B; }
+// the refusal of a call whose texts, outputs and index do not fit under the workspace cap
+[[noreturn]] static inline void bfq_nomem_cap(bfq_ctx *c, const char *whatNeeds, const char *whatItHolds, size_t need)
+{
+    char b[240];
+    snprintf(b, sizeof b, "%s needs %.2f GiB of device memory (%s), above the cap of %.2f GiB (bfq_params.ws_cap_mib / BFQ_WS_CAP)", whatNeeds,
+             need / 1073741824.0, whatItHolds, c->wsLimit() / 1073741824.0);
+    throw BfqError{BFQ_E_NOMEM, b};
+}
 void bfq_upload(bfq_ctx *c, void *d_dst, const void *h_src, size_t len);
 void bfq_download(bfq_ctx *c, void *h_dst, const void *d_src, size_t len);
 // background writes: the bytes [d_src, d_src + len) as they are once the work queued so far on the context's stream has

@@ -1,7 +1,9 @@
 // bfq_internal_host.h -- host-only helpers of libbfqhip.so (bfq_host.cpp): no HIP types here.
 #pragma once
 #include <stdint.h>
+#include <sys/mman.h>
 #include <atomic>
+#include <new>
 #include <string>
 #include "../../include/bfqzip_hip.h"
 
@@ -9,6 +11,34 @@
 struct BfqError {
     int code;
     std::string msg;
+};
+
+// the body of a *_host entry point (no context): err, the calling thread's error string, is cleared first and receives what
+// the body throws
+template <class F> static int host_guarded(std::string &err, F body)
+{
+    err.clear();
+    try {
+        body();
+        return BFQ_OK;
+    } catch (const BfqError &e) {
+        err = e.msg;
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        err = "host out of memory";
+        return BFQ_E_NOMEM;
+    }
+}
+static inline void zero3(uint64_t *a) { if (a) a[0] = a[1] = a[2] = 0; }
+
+// an input file as read-only memory, unmapped when it goes.  open(): false with errno set; an empty file maps nothing.
+struct MappedInput {
+    void *p = MAP_FAILED; size_t n = 0;
+    MappedInput() = default;
+    MappedInput(const MappedInput &) = delete; MappedInput &operator=(const MappedInput &) = delete;
+    bool open(int fd, size_t len) { n = len; p = len ? mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0) : MAP_FAILED; return !len || p != MAP_FAILED; }
+    const uint8_t *data() const { return p != MAP_FAILED ? (const uint8_t *)p : nullptr; }
+    ~MappedInput() { if (p != MAP_FAILED) munmap(p, n); }
 };
 
 // The BFQ_* environment variables.  bfq_env(): read once per process (first use) -- tracing, lease, thread counts.

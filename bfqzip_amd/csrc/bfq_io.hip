@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <unistd.h>
 #include <sys/mman.h>
+#include <sys/stat.h>
 #include <errno.h>
 #include <time.h>
 #include <stdio.h>
@@ -225,6 +226,79 @@ void bfq_download(bfq_ctx *c, HostRef dst, const void *d_src, size_t len)
     staged_copy(c, (char *)d_src, dst, len, false);
 }
 void bfq_download(bfq_ctx *c, void *h_dst, const void *d_src, size_t len) { bfq_download(c, HostRef::mem(h_dst), d_src, len); }
+
+// ---------------------------------------------------------------- the plain FASTQ texts of a call (bfq_internal.h: TextIn)
+// The one prologue of uBAM out, BAM patch, split / merge / repair of mates and reorder.  The plan and every size are
+// bfq_texts.h's.  What moves goes into the text buffer, slot by slot; the arena is reserved for the counting alone.
+void bfq_text_peek(bfq_ctx *c, const TextIn &in, u64 off, u8 *dst, size_t n)
+{
+    if (in.d) { HIP_CHECK(hipMemcpyAsync(dst, in.d + off, n, hipMemcpyDeviceToHost, c->stream)); c->sync(); return; }
+    if (in.ref.ptr) { memcpy(dst, (const u8 *)in.ref.ptr + off, n); return; }
+    size_t got = 0;
+    while (got < n) {
+        const ssize_t r = pread(in.ref.fd, dst + got, n - got, (off_t)(in.ref.off + off + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) throw BfqError{BFQ_E_IO, "cannot read the input file"};
+        got += (size_t)r;
+    }
+}
+
+void bfq_texts_map(const int fd[3], MappedInput map[3], TextIn X[3])
+{
+    static const u8 none = 0;
+    for (int k = 0; k < 3; k++) {
+        if (fd[k] < 0) continue;
+        struct stat st;
+        if (fstat(fd[k], &st) != 0 || !map[k].open(fd[k], (size_t)st.st_size)) throw BfqError{BFQ_E_IO, std::string("cannot map a text file: ") + strerror(errno)};
+        X[k].ref = HostRef::mem(st.st_size ? map[k].data() : &none);
+        X[k].len = (u64)st.st_size;
+    }
+}
+
+void bfq_texts_look(bfq_ctx *c, const TextIn *in, int n, BfqTextSeen *seen, bool last)
+{
+    for (int k = 0; k < n; k++) {
+        if (last) {
+            if (seen[k].present && seen[k].len) bfq_text_peek(c, in[k], in[k].len - 1, &seen[k].last, 1);
+            continue;
+        }
+        seen[k] = BfqTextSeen{};
+        if (!in[k].present()) continue;
+        seen[k].present = true;
+        seen[k].device = in[k].d != nullptr;
+        seen[k].addr = (uintptr_t)in[k].d;
+        seen[k].len = in[k].len;
+        if (in[k].len >= 2) bfq_text_peek(c, in[k], 0, seen[k].first, 2);
+    }
+}
+
+void bfq_texts_place(bfq_ctx *c, const TextIn *in, const BfqTextPlan &plan, int n, TextPlaced *out)
+{
+    u8 *buf = plan.bufNeed ? c->textBuf(plan.bufNeed) : nullptr;
+    if (plan.bufNeed) bfq_phase("read_h2d");
+    u64 maxLen = 0;
+    bool any = false;
+    for (int k = 0; k < n; k++) {
+        const BfqTextPlan::Slot &t = plan.t[k];
+        out[k] = TextPlaced{};
+        if (!t.present) continue;
+        any = true;
+        maxLen = std::max(maxLen, t.len);
+        out[k].d = in[k].d; out[k].len = t.len;
+        if (!t.moves) continue;
+        u8 *dst = buf + t.off;
+        if (!in[k].d) bfq_upload(c, dst, in[k].ref, in[k].len);
+        else if (in[k].len) HIP_CHECK(hipMemcpyAsync(dst, in[k].d, (size_t)in[k].len, hipMemcpyDeviceToDevice, c->stream));
+        if (t.len > in[k].len) HIP_CHECK(hipMemsetAsync(dst + in[k].len, '\n', 1, c->stream));
+        out[k].d = dst;
+    }
+    if (!any) return;
+    bfq_phase("alloc");
+    c->reserve(bfq_count_lines_bytes(maxLen) + (1u << 20));
+    bfq_phase("gpu");
+    for (int k = 0; k < n; k++)
+        if (plan.t[k].present) out[k].lines = bfq_fastq_count_lines(c, out[k].d, out[k].len);
+}
 
 // ---------------------------------------------------------------- background writes (one-shot tools)
 // The drop-in tools write 9 GB files (BFQzip.py:184,215-222 at 30 M x 150 bp).  Their outputs leave the device while the GPU

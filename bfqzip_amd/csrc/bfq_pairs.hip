@@ -24,8 +24,6 @@
 
 static_assert(sizeof(bfq_pairs_opts) == 16 && sizeof(bfq_pairs_stats) == 48 && sizeof(bfq_repair_opts) == 24 && sizeof(bfq_repair_stats) == 96, "the C-ABI's structures");
 
-#define PR_NL_CHUNK 4096u                                          // (k_fastq.hip's: bfq_line_index takes 12 bytes per chunk)
-
 static void pr_refuse(const bfq_pairs_err &X) { throw BfqError{bfq_pairs_code(X), bfq_pairs_message(X)}; }
 static bfq_pairs_opts pr_opts(const bfq_pairs_opts *in)
 {
@@ -40,28 +38,13 @@ extern "C" void bfq_pairs_default_opts(bfq_pairs_opts *o) { if (o) bfq_pairs_def
 static thread_local std::string g_pairsHostErr;
 extern "C" const char *bfq_pairs_host_error(void) { return g_pairsHostErr.c_str(); }
 
-template <class F> static int pr_host_guarded(F body)
-{
-    g_pairsHostErr.clear();
-    try {
-        body();
-        return BFQ_OK;
-    } catch (const BfqError &e) {
-        g_pairsHostErr = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        g_pairsHostErr = "host out of memory";
-        return BFQ_E_NOMEM;
-    }
-}
-
 extern "C" int bfq_fastq_deinterleave_host(const uint8_t *text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const h_out[3], const uint64_t cap[3],
                                            uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats)
 {
     if (out_len) out_len[0] = out_len[1] = out_len[2] = 0;
     if (n_reads) n_reads[0] = n_reads[1] = n_reads[2] = 0;
     if (stats) *stats = bfq_pairs_stats{};
-    return pr_host_guarded([&] {
+    return host_guarded(g_pairsHostErr, [&] {
         if (!out_len || (!text && len)) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_pairs_opts O = pr_opts(opts);
         const bool measure = !h_out && !cap;
@@ -86,7 +69,7 @@ extern "C" int bfq_fastq_interleave_host(const uint8_t *const text[3], const uin
 {
     if (out_len) *out_len = 0;
     if (stats) *stats = bfq_pairs_stats{};
-    return pr_host_guarded([&] {
+    return host_guarded(g_pairsHostErr, [&] {
         if (!text || !text_len || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_pairs_opts O = pr_opts(opts);
         const bool measure = !out && !cap;
@@ -102,91 +85,51 @@ extern "C" int bfq_fastq_interleave_host(const uint8_t *const text[3], const uin
 }
 
 // ---------------------------------------------------------------- the texts of a call
-// a text: host memory or an open file (ref), or device memory (d); neither: absent
-struct PrSrc {
-    HostRef ref; const u8 *d = nullptr; u64 len = 0;
-    bool present() const { return d || !ref.null(); }
-};
-
-static void pr_peek(bfq_ctx *c, const PrSrc &s, u64 off, u8 *dst, size_t n)
-{
-    if (s.d) { HIP_CHECK(hipMemcpyAsync(dst, s.d + off, n, hipMemcpyDeviceToHost, c->stream)); c->sync(); }
-    else if (s.ref.ptr) memcpy(dst, (const u8 *)s.ref.ptr + off, n);
-    else if (pread(s.ref.fd, dst, n, (off_t)(s.ref.off + off)) != (ssize_t)n) throw BfqError{BFQ_E_IO, "cannot read the input file"};
-}
-
-static void pr_nomem(bfq_ctx *c, size_t need)
-{
-    char b[240];
-    snprintf(b, sizeof b, "splitting or merging the mates needs %.2f GiB of device memory (text + outputs + index), above the cap of %.2f GiB "
-                          "(bfq_params.ws_cap_mib / BFQ_WS_CAP)", need / 1073741824.0, c->wsLimit() / 1073741824.0);
-    throw BfqError{BFQ_E_NOMEM, b};
-}
+static void pr_nomem(bfq_ctx *c, size_t need) { bfq_nomem_cap(c, "splitting or merging the mates", "text + outputs + index", need); }
 
 // Step 1 for the texts src[0, 3) (merge: the refusal names the text): t[k] = text k on the device with its index (an absent
 // or empty text: no records; merge = 2: the repair).  perRec / arenaOut: what steps 2 and 3 take from the arena beside the
 // index, in bytes per record, and whether the outputs lie there.
-static void pr_stage(bfq_ctx *c, const PrSrc src[3], u32 merge, size_t perRec, bool arenaOut, PrText t[3])
+static void pr_stage(bfq_ctx *c, const TextIn src[3], u32 merge, size_t perRec, bool arenaOut, PrText t[3])
 {
-    u64 tl[3] = {0, 0, 0};
-    bool moved[3] = {false, false, false};
-    size_t bufNeed = 0;
+    TextIn in[3];                                                   // (an empty text is handed on as absent: it gets no slot)
+    for (u32 k = 0; k < 3; k++)
+        if (src[k].present() && src[k].len) in[k] = src[k];
+    BfqTextSeen seen[3];
+    bfq_texts_look(c, in, 3, seen, false);
     for (u32 k = 0; k < 3; k++) {
-        t[k] = PrText{nullptr, nullptr, 0, 0};
-        if (!src[k].present() || !src[k].len) continue;
-        u8 first[2] = {0, 0};
-        if (src[k].len >= 2) pr_peek(c, src[k], 0, first, 2);
         bfq_pairs_err X;
-        if (!bfq_pairs_gzip_ok(first, src[k].len, merge, k, &X)) pr_refuse(X);
+        if (seen[k].present && !bfq_pairs_gzip_ok(seen[k].first, seen[k].len, merge, k, &X)) pr_refuse(X);
     }
-    for (u32 k = 0; k < 3; k++) {
-        if (!src[k].present() || !src[k].len) continue;
-        u8 last = 10;
-        pr_peek(c, src[k], src[k].len - 1, &last, 1);
-        tl[k] = src[k].len + (last == 10 ? 0 : 1);
-        // a device text stays where it lies unless its address is no multiple of 16 (the line kernels read 16 aligned bytes at
-        // a time) or it lacks its final LF (which it gets in the copy)
-        moved[k] = !src[k].d || ((uintptr_t)src[k].d & 15u) || tl[k] != src[k].len;
-        if (moved[k]) bufNeed += ((size_t)tl[k] + 64 + 255) & ~(size_t)255;
-    }
-    const u64 bytes = tl[0] + tl[1] + tl[2], maxLen = std::max(tl[0], std::max(tl[1], tl[2]));
+    bfq_texts_look(c, in, 3, seen, true);
+    const BfqTextPlan plan = bfq_texts_plan(seen, 3, true);
+    const u64 bytes = plan.t[0].len + plan.t[1].len + plan.t[2].len;
     const size_t outBytes = arenaOut ? (size_t)bytes + 3 * 4096 : 0;
-    if (c->wsLimit() && bufNeed + outBytes > c->wsLimit()) pr_nomem(c, bufNeed + outBytes);
+    if (c->wsLimit() && plan.bufNeed + outBytes > c->wsLimit()) pr_nomem(c, plan.bufNeed + outBytes);
     bfq_phase("alloc");
-    u8 *buf = bufNeed ? c->textBuf(bufNeed) : nullptr;
-    if (bufNeed) bfq_phase("read_h2d");
-    for (u32 k = 0; k < 3; k++) {
-        if (!tl[k]) continue;
-        t[k].buf = src[k].d; t[k].len = tl[k];
-        if (!moved[k]) continue;
-        if (src[k].d) HIP_CHECK(hipMemcpyAsync(buf, src[k].d, (size_t)src[k].len, hipMemcpyDeviceToDevice, c->stream));
-        else bfq_upload(c, buf, src[k].ref, src[k].len);
-        if (tl[k] > src[k].len) HIP_CHECK(hipMemsetAsync(buf + src[k].len, '\n', 1, c->stream));
-        t[k].buf = buf;
-        buf += ((size_t)tl[k] + 64 + 255) & ~(size_t)255;
-    }
-    bfq_phase("alloc");
-    c->reserve(12 * (size_t)(maxLen / PR_NL_CHUNK + 2) + 8192 + (1u << 20));
-    bfq_phase("gpu");
-    u64 lines[3] = {0, 0, 0}, nb = 0;
+    TextPlaced p[3];
+    bfq_texts_place(c, in, plan, 3, p);
+    // per text its index, and slack: 12 KiB for alignment gaps and the small buffers (flags, counters) between the arrays, and
+    // the scan over its records' lengths twice more; then what steps 2 and 3 take per record, with room for four scans at a time
+    u64 nb = 0;
     size_t need = outBytes + (4u << 20);
     for (u32 k = 0; k < 3; k++) {
-        if (!tl[k]) continue;
-        lines[k] = bfq_fastq_count_lines(c, t[k].buf, tl[k]);
-        const u64 n = lines[k] / 4 + 2;
+        t[k] = PrText{p[k].d, nullptr, p[k].len, 0};
+        if (!p[k].d) continue;
+        const u64 n = p[k].lines / 4 + 2;
         nb += n;
-        need += 8 * (size_t)(lines[k] + 64) + 12 * (size_t)(tl[k] / PR_NL_CHUNK + 2) + 8192 + 44 * (size_t)(n + 64) + 32 * (size_t)(n / 4096 + 2);
+        need += bfq_fastq_index_bytes(p[k].len, p[k].lines) + 12288 + 2 * bfq_scan_bytes(n);
     }
-    need += perRec * (size_t)(nb + 64) + 64 * (size_t)(nb / 4096 + 2);
-    if (c->wsLimit() && bufNeed + need > c->wsLimit()) pr_nomem(c, bufNeed + need);
+    need += perRec * (size_t)(nb + 64) + 4 * bfq_scan_bytes(nb) + 4096;
+    if (c->wsLimit() && plan.bufNeed + need > c->wsLimit()) pr_nomem(c, plan.bufNeed + need);
     bfq_phase("alloc");
     c->reserve(need);
     bfq_phase("gpu");
     c->zeroCounters();
     for (u32 k = 0; k < 3; k++) {
-        if (!tl[k]) continue;
+        if (!t[k].buf) continue;
         DevFastq fq;
-        bfq_fastq_index(c, t[k].buf, tl[k], &fq);
+        bfq_fastq_index(c, t[k].buf, t[k].len, &fq);
         t[k].rec = (const FqRec *)fq.rec; t[k].N = fq.N;
     }
 }
@@ -211,9 +154,9 @@ static u64 pr_first_bad(bfq_ctx *c, const PrText &a, const PrText *b, u64 P, u32
     return bad;
 }
 
-static void split_core(bfq_ctx *c, const PrSrc &in, const bfq_pairs_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_pairs_stats *S)
+static void split_core(bfq_ctx *c, const TextIn &in, const bfq_pairs_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_pairs_stats *S)
 {
-    const PrSrc src[3] = {in, PrSrc{}, PrSrc{}};
+    const TextIn src[3] = {in, TextIn{}, TextIn{}};
     PrText t3[3];
     pr_stage(c, src, 0, O.orphans ? 57 : 8, !measure && !sink.device, t3);
     const PrText &t = t3[0];
@@ -270,7 +213,7 @@ static void split_core(bfq_ctx *c, const PrSrc &in, const bfq_pairs_opts &O, boo
     c->profCollect();
 }
 
-static void merge_core(bfq_ctx *c, const PrSrc src[3], const bfq_pairs_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_pairs_stats *S)
+static void merge_core(bfq_ctx *c, const TextIn src[3], const bfq_pairs_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_pairs_stats *S)
 {
     PrText t[3];
     pr_stage(c, src, 1, 8, !measure && !sink.device, t);
@@ -297,7 +240,6 @@ static void merge_core(bfq_ctx *c, const PrSrc src[3], const bfq_pairs_opts &O, 
 }
 
 // ---------------------------------------------------------------- the split's entry points
-static void pr_zero3(uint64_t *a) { if (a) a[0] = a[1] = a[2] = 0; }
 // the capacities against the lengths: a short one leaves out_len[] = the lengths needed
 static void pr_check_caps(bfq_ctx *c, const uint64_t *cap, const u64 *lens, int n, uint64_t *out_len, u32 merge)
 {
@@ -311,10 +253,10 @@ static void pr_check_caps(bfq_ctx *c, const uint64_t *cap, const u64 *lens, int 
     pr_refuse(X);
 }
 
-static int pr_split_mem(bfq_ctx *c, PrSrc in, const bfq_pairs_opts *opts, uint8_t *const *out, const uint64_t *cap, bool device, bool measure,
+static int pr_split_mem(bfq_ctx *c, TextIn in, const bfq_pairs_opts *opts, uint8_t *const *out, const uint64_t *cap, bool device, bool measure,
                         uint64_t *out_len, uint64_t *n_reads, bfq_pairs_stats *stats)
 {
-    pr_zero3(out_len); pr_zero3(n_reads);
+    zero3(out_len); zero3(n_reads);
     if (stats) *stats = bfq_pairs_stats{};
     return guarded(c, [&] {
         if (!out_len || (!in.present() && in.len) || (!measure && (!out || !cap))) throw BfqError{BFQ_E_ARG, "null argument"};
@@ -343,21 +285,21 @@ static int pr_split_mem(bfq_ctx *c, PrSrc in, const bfq_pairs_opts *opts, uint8_
 extern "C" int bfq_fastq_deinterleave_measure(bfq_ctx *c, const uint8_t *h_text, uint64_t len, const bfq_pairs_opts *opts, uint64_t out_len[3],
                                               uint64_t n_reads[3], bfq_pairs_stats *stats)
 {
-    PrSrc in;
+    TextIn in;
     in.ref = HostRef::mem(h_text); in.len = len;
     return pr_split_mem(c, in, opts, nullptr, nullptr, false, true, out_len, n_reads, stats);
 }
 extern "C" int bfq_fastq_deinterleave(bfq_ctx *c, const uint8_t *h_text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const h_out[3],
                                       const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats)
 {
-    PrSrc in;
+    TextIn in;
     in.ref = HostRef::mem(h_text); in.len = len;
     return pr_split_mem(c, in, opts, h_out, cap, false, false, out_len, n_reads, stats);
 }
 extern "C" int bfq_fastq_deinterleave_device(bfq_ctx *c, const uint8_t *d_text, uint64_t len, const bfq_pairs_opts *opts, uint8_t *const d_out[3],
                                              const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_pairs_stats *stats)
 {
-    PrSrc in;
+    TextIn in;
     in.d = d_text; in.len = len;
     return pr_split_mem(c, in, opts, d_out, cap, true, false, out_len, n_reads, stats);
 }
@@ -396,7 +338,7 @@ struct PrFiles {
 extern "C" int bfq_fastq_deinterleave_fd(bfq_ctx *c, int in_fd, uint64_t len, const bfq_pairs_opts *opts, const int out_fd[3], uint64_t out_len[3],
                                          uint64_t n_reads[3], bfq_pairs_stats *stats)
 {
-    pr_zero3(out_len); pr_zero3(n_reads);
+    zero3(out_len); zero3(n_reads);
     if (stats) *stats = bfq_pairs_stats{};
     return guarded(c, [&] {
         if (!out_len || !out_fd) throw BfqError{BFQ_E_ARG, "null argument"};
@@ -405,7 +347,7 @@ extern "C" int bfq_fastq_deinterleave_fd(bfq_ctx *c, int in_fd, uint64_t len, co
         for (int k = 0; k < 3; k++) F.fd[k] = out_fd[k];
         try {
             const bfq_pairs_opts O = pr_opts(opts);
-            PrSrc in;
+            TextIn in;
             in.ref = HostRef::file(in_fd); in.len = len;
             PrSink sink;
             sink.sized = [&](const u64 *lens) {
@@ -434,17 +376,13 @@ static int pr_merge_mem(bfq_ctx *c, const uint8_t *const *text, const uint64_t *
                         bool measure, uint64_t *out_len, uint64_t *n_reads, bfq_pairs_stats *stats)
 {
     if (out_len) *out_len = 0;
-    pr_zero3(n_reads);
+    zero3(n_reads);
     if (stats) *stats = bfq_pairs_stats{};
     return guarded(c, [&] {
         if (!text || !text_len || !out_len || (!measure && !out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_pairs_opts O = pr_opts(opts);
-        PrSrc src[3];
-        for (int k = 0; k < 3; k++) {
-            if (!text[k]) continue;
-            if (device) src[k].d = text[k]; else src[k].ref = HostRef::mem(text[k]);
-            src[k].len = text_len[k];
-        }
+        TextIn src[3];
+        bfq_texts_of(text, text_len, device, src);
         PrSink sink;
         sink.device = device;
         sink.sized = [&](const u64 *total) { if (!measure) pr_check_caps(c, &cap, total, 1, out_len, 1); };
@@ -490,7 +428,7 @@ extern "C" int bfq_fastq_interleave_fd(bfq_ctx *c, const int text_fd[3], const b
         F.fd[0] = out_fd;
         try {
             const bfq_pairs_opts O = pr_opts(opts);
-            PrSrc src[3];
+            TextIn src[3];
             for (int k = 0; k < 3; k++) {
                 if (text_fd[k] < 0) continue;
                 struct stat st;
@@ -534,7 +472,7 @@ static bfq_repair_opts rp_opts(const bfq_repair_opts *in)
     return O;
 }
 
-static void repair_core(bfq_ctx *c, const PrSrc src[3], const bfq_repair_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_repair_stats *S)
+static void repair_core(bfq_ctx *c, const TextIn src[3], const bfq_repair_opts &O, bool measure, const PrSink &sink, u64 nReads[3], bfq_repair_stats *S)
 {
     PrText t[3];
     pr_stage(c, src, 2, RP_PER_REC, !measure && !sink.device, t);
@@ -594,7 +532,7 @@ static void repair_core(bfq_ctx *c, const PrSrc src[3], const bfq_repair_opts &O
 static int rp_mem(bfq_ctx *c, const uint8_t *const *text, const uint64_t *text_len, const bfq_repair_opts *opts, uint8_t *const *out, const uint64_t *cap,
                   bool device, bool measure, uint64_t *out_len, uint64_t *n_reads, bfq_repair_stats *stats)
 {
-    pr_zero3(out_len); pr_zero3(n_reads);
+    zero3(out_len); zero3(n_reads);
     if (stats) *stats = bfq_repair_stats{};
     return guarded(c, [&] {
         if (!text || !text_len || !out_len || (!measure && (!out || !cap))) throw BfqError{BFQ_E_ARG, "null argument"};
@@ -602,12 +540,8 @@ static int rp_mem(bfq_ctx *c, const uint8_t *const *text, const uint64_t *text_l
             for (int k = 0; k < 3; k++)
                 if (!out[k] && cap[k]) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_repair_opts O = rp_opts(opts);
-        PrSrc src[3];
-        for (int k = 0; k < 3; k++) {
-            if (!text[k]) continue;
-            if (device) src[k].d = text[k]; else src[k].ref = HostRef::mem(text[k]);
-            src[k].len = text_len[k];
-        }
+        TextIn src[3];
+        bfq_texts_of(text, text_len, device, src);
         PrSink sink;
         sink.device = device;
         sink.sized = [&](const u64 *lens) { if (!measure) pr_check_caps(c, cap, lens, 3, out_len, 2); };
@@ -645,7 +579,7 @@ extern "C" int bfq_fastq_repair_device(bfq_ctx *c, const uint8_t *const d_text[3
 extern "C" int bfq_fastq_repair_fd(bfq_ctx *c, const int text_fd[3], const bfq_repair_opts *opts, const int out_fd[3], uint64_t out_len[3], uint64_t n_reads[3],
                                    bfq_repair_stats *stats)
 {
-    pr_zero3(out_len); pr_zero3(n_reads);
+    zero3(out_len); zero3(n_reads);
     if (stats) *stats = bfq_repair_stats{};
     return guarded(c, [&] {
         if (!out_len || !text_fd || !out_fd) throw BfqError{BFQ_E_ARG, "null argument"};
@@ -653,7 +587,7 @@ extern "C" int bfq_fastq_repair_fd(bfq_ctx *c, const int text_fd[3], const bfq_r
         for (int k = 0; k < 3; k++) F.fd[k] = out_fd[k];
         try {
             const bfq_repair_opts O = rp_opts(opts);
-            PrSrc src[3];
+            TextIn src[3];
             for (int k = 0; k < 3; k++) {
                 if (text_fd[k] < 0) continue;
                 struct stat st;
@@ -685,9 +619,9 @@ extern "C" int bfq_fastq_repair_fd(bfq_ctx *c, const int text_fd[3], const bfq_r
 extern "C" int bfq_fastq_repair_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint8_t *const h_out[3],
                                      const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_repair_stats *stats)
 {
-    pr_zero3(out_len); pr_zero3(n_reads);
+    zero3(out_len); zero3(n_reads);
     if (stats) *stats = bfq_repair_stats{};
-    return pr_host_guarded([&] {
+    return host_guarded(g_pairsHostErr, [&] {
         if (!text || !text_len || !out_len) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_repair_opts O = rp_opts(opts);
         const bool measure = !h_out && !cap;

@@ -24,7 +24,6 @@
 
 #define RO_MAX_MATES 2
 
-struct RoSrc { HostRef ref; u64 len; };
 // where a mate's text goes once it is known to be good; put() is called at most once per mate
 struct RoSink {
     u64 cap[RO_MAX_MATES] = {~0ull, ~0ull};
@@ -41,22 +40,7 @@ struct RoOrder {
     std::function<void(const u64 *order, u64 N)> done;
 };
 
-static bool ro_ends_with_newline(const RoSrc &t)
-{
-    if (!t.len) return true;
-    if (t.ref.ptr) return ((const u8 *)t.ref.ptr)[t.len - 1] == (u8)'\n';
-    u8 b = 0;
-    if (pread(t.ref.fd, &b, 1, (off_t)(t.ref.off + t.len - 1)) != 1) throw BfqError{BFQ_E_IO, "cannot read the input file"};
-    return b == (u8)'\n';
-}
-
-static void ro_nomem(bfq_ctx *c, size_t need)
-{
-    char b[240];
-    snprintf(b, sizeof b, "reordering needs %.2f GiB of device memory (input + output text + index), above the cap of %.2f GiB "
-                          "(bfq_params.ws_cap_mib / BFQ_WS_CAP)", need / 1073741824.0, c->wsLimit() / 1073741824.0);
-    throw BfqError{BFQ_E_NOMEM, b};
-}
+static void ro_nomem(bfq_ctx *c, size_t need) { bfq_nomem_cap(c, "reordering", "input + output text + index", need); }
 
 static void ro_check_parts(int nparts, const char *what)
 {
@@ -71,49 +55,44 @@ static void ro_check_opts(const bfq_reorder_opts *o, int nparts, int *k)
     if (*k < BFQ_RO_KMIN || *k > BFQ_RO_KMAX) throw BfqError{BFQ_E_ARG, "bfq_reorder_opts.k: 8..32 (0: 21)"};
 }
 
-// lengths of the outputs: known from the inputs alone
-static void ro_lengths(const RoSrc *src, int np, u64 *tl)
+// The inputs looked at, part by part, and where they go on the device.  The plan's lengths are the outputs': known from the
+// inputs alone.  A part of no bytes is a text whatever its pointer.
+static BfqTextPlan ro_plan(bfq_ctx *c, TextIn *src, int np)
 {
+    static const u8 none = 0;
+    BfqTextSeen seen[RO_MAX_MATES];
     for (int p = 0; p < np; p++) {
-        if (src[p].len && src[p].ref.null()) throw BfqError{BFQ_E_ARG, "null FASTQ text"};
-        if (bfq_text_is_gzip(TextSrc{src[p].ref, src[p].len}))
+        if (src[p].len && !src[p].present()) throw BfqError{BFQ_E_ARG, "null FASTQ text"};
+        if (!src[p].present()) src[p].ref = HostRef::mem(&none);
+        bfq_texts_look(c, &src[p], 1, &seen[p], false);
+        if (bfq_seen_gzip(seen[p]))
             throw BfqError{BFQ_E_ARG, "a bgzip-compressed (BGZF) input is not reordered as it is: inflate first (bfq_bgzf_inflate, bfq_bgzf -d)"};
-        tl[p] = src[p].len + (ro_ends_with_newline(src[p]) ? 0 : 1);
+        bfq_texts_look(c, &src[p], 1, &seen[p], true);
     }
+    return bfq_texts_plan(seen, np, true);
 }
 
-static void reorder_core(bfq_ctx *c, const RoSrc *src, int np, const RoOrder &order, const RoSink &sink, const u64 *tl,
+static void reorder_core(bfq_ctx *c, const TextIn *src, int np, const RoOrder &order, const RoSink &sink, const BfqTextPlan &plan,
                          uint64_t *n_reads)
 {
     ro_check_parts(np, order.what);
-    u64 toff[RO_MAX_MATES + 1] = {0, 0, 0}, sum = 0;
-    for (int p = 0; p < np; p++) {
-        if (tl[p] > sink.cap[p]) throw BfqError{BFQ_E_ARG, "output buffer smaller than the FASTQ text (the input's length, + 1 without a final newline)"};
-        toff[p] = sum;
-        sum += (tl[p] + 64 + 255) & ~255ull;                    // every text 256-byte aligned and padded (16-byte loads)
-    }
-    toff[np] = sum;
+    for (int p = 0; p < np; p++)
+        if (plan.t[p].len > sink.cap[p]) throw BfqError{BFQ_E_ARG, "output buffer smaller than the FASTQ text (the input's length, + 1 without a final newline)"};
+    const size_t sum = plan.bufNeed;
     if (c->wsLimit() && 2 * sum > c->wsLimit()) ro_nomem(c, 2 * sum);
     bfq_phase("alloc");
-    u8 *d_in = c->textBuf(sum + 64);
-    bfq_phase("read_h2d");
-    for (int p = 0; p < np; p++) {
-        bfq_upload(c, d_in + toff[p], src[p].ref, src[p].len);
-        if (tl[p] > src[p].len) HIP_CHECK(hipMemsetAsync(d_in + toff[p] + src[p].len, '\n', 1, c->stream));
-    }
-    bfq_phase("alloc");
-    const u64 maxLen = *std::max_element(tl, tl + np);
-    c->reserve(16 * (maxLen / 4096 + 16) + (64u << 20));
-    bfq_phase("gpu");
-    u64 nlines = 0;
-    for (int p = 0; p < np; p++) nlines = std::max(nlines, bfq_fastq_count_lines(c, d_in + toff[p], tl[p]));
+    TextPlaced in[RO_MAX_MATES];
+    bfq_texts_place(c, src, plan, np, in);
+    u64 maxLen = 0, nlines = 0;
+    for (int p = 0; p < np; p++) { maxLen = std::max(maxLen, in[p].len); nlines = std::max(nlines, in[p].lines); }
     const u64 Nb = nlines / 4 + 1;
     // per mate: the output, line ends, chunk counts of the line index, records + read offsets + lengths, sizes + new offsets;
     // once: two sets of sort records, the permutation, the radix passes' digit tables, the scans' partial sums; the packed
     // permutation of the keeping calls (8 bytes per read at most).  The way back has the container, the unpacked permutation
     // and its inverse where the forward calls have their sort records.
     const u64 nbRadix = std::min(Nb / BFQ_RS_TILE, std::max(Nb / BFQ_RS_BLOCK_ELEMS, (u64)8192)) + 2;   // radix blocks of any n <= Nb (bfq_radix_block_elems)
-    const size_t perMate = (size_t)(maxLen + 4096) + 8 * (size_t)(nlines + 64) + 16 * (size_t)(maxLen / 4096 + 16) + (32 + 8 + 4 + 16) * (size_t)(Nb + 64);
+    // (slack, as reserved so far: 16 bytes per chunk of text where the line kernels take 12, and 4 KiB)
+    const size_t perMate = (size_t)(maxLen + 4096) + bfq_fastq_index_bytes(maxLen, nlines) + (8 + 8) * (size_t)(Nb + 64) + 4 * (size_t)(maxLen / BFQ_NL_CHUNK) + 4096;
     const size_t need = np * perMate + (24 + 8 + order.extraPerRead) * (size_t)(Nb + 64) + 12 * 256 * (size_t)nbRadix + (size_t)(Nb >> 7) + (8u << 20);
     if (c->wsLimit() && sum + need > c->wsLimit()) ro_nomem(c, sum + need);
     bfq_phase("alloc");
@@ -124,8 +103,8 @@ static void reorder_core(bfq_ctx *c, const RoSrc *src, int np, const RoOrder &or
     u64 N = 0;
     for (int p = 0; p < np; p++) {
         DevFastq fq;
-        bfq_fastq_index(c, d_in + toff[p], tl[p], &fq);
-        mate[p] = RoText{d_in + toff[p], (const FqRec *)fq.rec, tl[p]};
+        bfq_fastq_index(c, in[p].d, in[p].len, &fq);
+        mate[p] = RoText{in[p].d, (const FqRec *)fq.rec, in[p].len};
         if (p && fq.N != N) {
             char b[200];
             snprintf(b, sizeof b, "the mates differ in their number of records: %llu in the first file, %llu in the second",
@@ -140,9 +119,9 @@ static void reorder_core(bfq_ctx *c, const RoSrc *src, int np, const RoOrder &or
     const u64 *perm = order.make(mate, np, N, sizes);
     for (int p = 0; p < np; p++) {
         bfq_exscan_u64(c, sizes[p], newOff[p], N, newOff[p] + N);
-        u8 *d_out = c->alloc<u8>(tl[p] + 64);
+        u8 *d_out = c->alloc<u8>(in[p].len + 64);
         bfq_reorder_gather(c, mate[p], perm, newOff[p], N, d_out);
-        sink.put(p, d_out, tl[p]);
+        sink.put(p, d_out, in[p].len);
     }
     if (order.done) order.done(perm, N);
     c->sync();
@@ -223,25 +202,24 @@ static int ro_run_mem(bfq_ctx *c, const char *what, const bfq_text_part *parts, 
     if (n_reads) *n_reads = 0;
     return guarded(c, [&] {
         if (!parts || !h_out || !cap || nparts < 1 || nparts > RO_MAX_MATES) throw BfqError{BFQ_E_ARG, std::string(what) + ": 1 or 2 parts, their outputs and capacities"};
-        RoSrc src[RO_MAX_MATES];
+        TextIn src[RO_MAX_MATES];
         RoSink sink;
-        u64 tl[RO_MAX_MATES] = {0, 0};
         for (int p = 0; p < nparts; p++) {
             if (!h_out[p] && cap[p]) throw BfqError{BFQ_E_ARG, "null argument"};
-            src[p] = RoSrc{HostRef::mem(parts[p].data), parts[p].len};
+            src[p].ref = HostRef::mem(parts[p].data); src[p].len = parts[p].len;
             sink.cap[p] = cap[p];
         }
-        ro_lengths(src, nparts, tl);
+        const BfqTextPlan plan = ro_plan(c, src, nparts);
         sink.put = [&](int p, const u8 *d_text, u64 len) {
             bfq_phase("d2h_write");
             bfq_download(c, h_out[p], d_text, len);
             bfq_phase("gpu");
         };
         uint64_t N = 0;
-        reorder_core(c, src, nparts, order(), sink, tl, &N);
+        reorder_core(c, src, nparts, order(), sink, plan, &N);
         if (finish) finish(N);
         if (n_reads) *n_reads = N;
-        if (out_len) for (int p = 0; p < nparts; p++) out_len[p] = tl[p];
+        if (out_len) for (int p = 0; p < nparts; p++) out_len[p] = plan.t[p].len;
     });
 }
 
@@ -260,10 +238,10 @@ static int ro_run_fd(bfq_ctx *c, const char *what, const int *in_fd, const uint6
         OutFile of[RO_MAX_MATES];
         int opened = 0;
         try {
-            RoSrc src[RO_MAX_MATES];
-            u64 tl[RO_MAX_MATES] = {0, 0};
-            for (int p = 0; p < nparts; p++) src[p] = RoSrc{HostRef::file(in_fd[p]), in_len[p]};
-            ro_lengths(src, nparts, tl);
+            TextIn src[RO_MAX_MATES];
+            for (int p = 0; p < nparts; p++) { src[p].ref = HostRef::file(in_fd[p]); src[p].len = in_len[p]; }
+            const BfqTextPlan plan = ro_plan(c, src, nparts);
+            const u64 tl[RO_MAX_MATES] = {plan.t[0].len, plan.t[1].len};
             const RoOrder ord = order();
             // mapped to their final length and pre-faulted beside the upload
             for (int p = 0; p < nparts; p++) { of[p].open(out_fd[p], tl[p] + 4096, tl[p]); opened = p + 1; }
@@ -271,7 +249,7 @@ static int ro_run_fd(bfq_ctx *c, const char *what, const int *in_fd, const uint6
             RoSink sink;
             sink.put = [&](int p, const u8 *d_text, u64 len) { bfq_write_async(c, of[p].at(0), d_text, len); };
             uint64_t N = 0;
-            reorder_core(c, src, nparts, ord, sink, tl, &N);
+            reorder_core(c, src, nparts, ord, sink, plan, &N);
             if (queue) queue(N);
             bfq_phase("d2h_write");
             bfq_write_wait(c);

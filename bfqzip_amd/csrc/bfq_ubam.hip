@@ -15,8 +15,6 @@
 // here falls back to it.
 #include <string.h>
 #include <stdio.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
 #include <algorithm>
 #include <functional>
 #include "bfq_internal.h"
@@ -29,7 +27,6 @@ void bfq_ubam_launch_size(bfq_ctx *c, const bfq_ubam_job &J, u64 nrec, u32 *d_si
                           bfq_ubam_tcnt *d_tcnt);                                                                                           // k_ubam.hip
 void bfq_ubam_launch_write(bfq_ctx *c, const bfq_ubam_job &J, u64 nrec, const u64 *d_off, u8 *d_out, u64 rawLen, bfq_ubam_cnt *d_cnt, const bfq_ubam_tagsel &G);
 
-#define UBAM_NL_CHUNK 4096u                                        // (k_fastq.hip's: bfq_line_index takes 12 bytes per chunk)
 #define UBAM_NONE (~0ull)
 
 static void ubam_refuse(const bfq_ubam_err &X) { throw BfqError{bfq_ubam_code(X), bfq_ubam_message(X)}; }
@@ -61,8 +58,7 @@ extern "C" int bfq_fastq_to_bam_host(const uint8_t *const text[3], const uint64_
 {
     if (raw_len) *raw_len = 0;
     if (stats) *stats = bfq_ubam_stats{};
-    g_ubamHostErr.clear();
-    try {
+    return host_guarded(g_ubamHostErr, [&] {
         if (!text || !text_len || !raw_len || (!out_raw && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
         const bfq_ubam_opts O = ubam_opts(opts);
         bfq_ubam_tag_stats *tagStats = nullptr, TS{};
@@ -76,43 +72,38 @@ extern "C" int bfq_fastq_to_bam_host(const uint8_t *const text[3], const uint64_
         *raw_len = S.raw_len;
         if (r == 3) throw BfqError{BFQ_E_ARG, "output buffer too small for the stream"};
         if (stats) *stats = S;
-        return BFQ_OK;
-    } catch (const BfqError &e) {
-        g_ubamHostErr = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        g_ubamHostErr = "host out of memory";
-        return BFQ_E_NOMEM;
-    }
+    });
 }
 
-// the texts of a call: on the host (h) or on the device (d); neither: absent
-struct UbamTexts { const u8 *h[3] = {nullptr, nullptr, nullptr}, *d[3] = {nullptr, nullptr, nullptr}; u64 len[3] = {0, 0, 0}; };
 // what steps 1-3 leave: the stream in the arena and the counts
 struct UbamStream { u8 *d_s = nullptr; u64 raw = 0; bfq_ubam_stats S{}; bfq_ubam_tag_stats T{}; };
 
+// arena bytes of a text's line index here, generously: `bytes` is the length of all texts of the call, not of this one (the
+// restore path knows only a bound), and 8 KiB of slack go with each text for the small buffers between the indexes
+static size_t ubam_index_bytes(u64 bytes, u64 lines) { return bfq_line_index_bytes(bytes, lines) + 8192; }
 // arena bytes of steps 1-3 (behind the counting of the lines) for texts of `bytes` bytes and at most `lines` lines in all,
-// of which `texts` are present; + extra(bound of the stream)
-static size_t ubam_need(u64 bytes, u64 lines, u32 texts, size_t hdrLen, size_t tagLen, bool stream, u64 *rawBound)
+// whose line indexes take `index` bytes; + extra(bound of the stream).  (The scan over the sizes: twice over, and 4 KiB.)
+static size_t ubam_need(u64 bytes, u64 lines, size_t index, size_t hdrLen, size_t tagLen, bool stream, u64 *rawBound)
 {
     const u64 nrec = lines / 4 + 3;
     *rawBound = hdrLen + bytes + nrec * (53 + tagLen) + 64;
-    return 8 * (size_t)(lines + 2 * texts) + texts * (12 * (size_t)(bytes / UBAM_NL_CHUNK + 2) + 8192) + 12 * (size_t)(nrec + 2) + 32 * (size_t)(nrec / 4096 + 2) +
-           (stream ? (size_t)*rawBound : 0) + tagLen + (64u << 10);
+    return index + 12 * (size_t)(nrec + 2) + 2 * bfq_scan_bytes(nrec) + 4096 + (stream ? (size_t)*rawBound : 0) + tagLen + (64u << 10);
 }
 
-// Steps 2-3 on texts that stand on the device at 16-byte aligned addresses, in an arena that holds ubam_need() bytes above
-// its top.  sized(raw) runs once the stream's length is known and before anything is written: it throws for a short capacity.
-static void ubam_records(bfq_ctx *c, const u8 *const d_t[3], const u64 len[3], const bool present[3], const bfq_ubam_opts &O, const bfq_ubam_tagsel &G, bool measure,
-                         const std::function<void(u64)> &sized, UbamStream *out)
+// Steps 2-3 on texts that stand on the device at 16-byte aligned addresses (T[k].d; nullptr: absent), in an arena that holds
+// ubam_need() bytes above its top.  sized(raw) runs once the stream's length is known and before anything is written: it
+// throws for a short capacity.
+static void ubam_records(bfq_ctx *c, const TextPlaced T[3], const bfq_ubam_opts &O, const bfq_ubam_tagsel &G, bool measure, const std::function<void(u64)> &sized,
+                         UbamStream *out)
 {
     bfq_ubam_err R;
     bfq_ubam_job J{};
     u64 lines[3] = {0, 0, 0}, reads[3] = {0, 0, 0};
+    const bool present[3] = {T[0].d != nullptr, T[1].d != nullptr, T[2].d != nullptr};
     for (u32 k = 0; k < 3; k++) {
         if (!present[k]) continue;
-        J.T.text[k] = d_t[k]; J.T.len[k] = len[k];
-        J.T.lineEnd[k] = bfq_line_index(c, d_t[k], len[k], &lines[k]);
+        J.T.text[k] = T[k].d; J.T.len[k] = T[k].len;
+        J.T.lineEnd[k] = bfq_line_index(c, T[k].d, T[k].len, &lines[k]);
     }
     if (!bfq_ubam_counts_ok(lines, present, reads, &R)) { c->profCollect(); ubam_refuse(R); }
     const std::vector<u8> hdr = bfq_ubam_header(O), tag = bfq_ubam_tag(O);
@@ -161,56 +152,29 @@ static void ubam_records(bfq_ctx *c, const u8 *const d_t[3], const u64 len[3], c
 }
 
 // Steps 1-3.  extra(bound): arena bytes the caller needs behind them for a stream of at most that length.
-static void ubam_core(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts &O, const bfq_ubam_tagsel &G, bool measure, const std::function<size_t(u64)> &extra,
+static void ubam_core(bfq_ctx *c, const TextIn X[3], const bfq_ubam_opts &O, const bfq_ubam_tagsel &G, bool measure, const std::function<size_t(u64)> &extra,
                       const std::function<void(u64)> &sized, UbamStream *out)
 {
     bfq_ubam_err R;
-    bool present[3];
-    u32 texts = 0;
-    for (u32 k = 0; k < 3; k++) {
-        present[k] = X.h[k] || X.d[k];
-        if (!present[k]) continue;
-        texts++;
-        u8 first[2] = {0, 0};
-        if (X.len[k] >= 2) {
-            if (X.h[k]) memcpy(first, X.h[k], 2);
-            else { HIP_CHECK(hipMemcpyAsync(first, X.d[k], 2, hipMemcpyDeviceToHost, c->stream)); c->sync(); }
-        }
-        if (!bfq_ubam_gzip_ok(first, X.len[k], k, &R)) ubam_refuse(R);
-    }
-    // Host texts go up first, into the context's text buffer outside the arena, so that every text's lines, which size its
-    // index and the records' arrays, are counted on the device before the arena is reserved.  A device text stays where it
-    // lies unless its address is no multiple of 16 (the line kernels read 16 aligned bytes at a time).
-    const u8 *d_t[3] = {nullptr, nullptr, nullptr};
-    size_t bufNeed = 0, scratch = 0;
-    auto moved = [&](u32 k) { return X.h[k] || ((uintptr_t)X.d[k] & 15u) || !X.len[k]; };
+    BfqTextSeen seen[3];
+    bfq_texts_look(c, X, 3, seen, false);
     for (u32 k = 0; k < 3; k++)
-        if (present[k] && moved(k)) bufNeed += ((size_t)X.len[k] + 16 + 255) & ~(size_t)255;
-    u8 *buf = bufNeed ? c->textBuf(bufNeed) : nullptr;
-    if (bufNeed) bfq_phase("read_h2d");
+        if (seen[k].present && !bfq_ubam_gzip_ok(seen[k].first, seen[k].len, k, &R)) ubam_refuse(R);
+    // Every text's lines, which size its index and the records' arrays, are counted on the device before the arena is reserved.
+    TextPlaced T[3];
+    bfq_texts_place(c, X, bfq_texts_plan(seen, 3, false), 3, T);
     u64 bytes = 0, lines = 0;
-    for (u32 k = 0; k < 3; k++) {
-        if (!present[k]) continue;
-        d_t[k] = X.d[k];
-        if (moved(k)) {
-            if (X.h[k]) bfq_upload(c, buf, X.h[k], X.len[k]);
-            else if (X.len[k]) HIP_CHECK(hipMemcpyAsync(buf, X.d[k], (size_t)X.len[k], hipMemcpyDeviceToDevice, c->stream));
-            d_t[k] = buf;
-            buf += ((size_t)X.len[k] + 16 + 255) & ~(size_t)255;
-        }
-        scratch = std::max(scratch, 12 * (size_t)(X.len[k] / UBAM_NL_CHUNK + 2) + 8192);
-        bytes += X.len[k];
-    }
-    if (scratch) { bfq_phase("alloc"); c->reserve(scratch); bfq_phase("gpu"); }
+    size_t index = 0;
+    for (u32 k = 0; k < 3; k++) { bytes += T[k].len; lines += T[k].lines; }
     for (u32 k = 0; k < 3; k++)
-        if (present[k]) lines += bfq_fastq_count_lines(c, d_t[k], X.len[k]);
+        if (T[k].d) index += ubam_index_bytes(bytes, T[k].lines);
     const std::vector<u8> hdr = bfq_ubam_header(O), tag = bfq_ubam_tag(O);
     u64 bound = 0;
-    const size_t need = ubam_need(bytes, lines, texts, hdr.size(), tag.size(), !measure, &bound);
+    const size_t need = ubam_need(bytes, lines, index, hdr.size(), tag.size(), !measure, &bound);
     bfq_phase("alloc");
     c->reserve(need + (measure ? 0 : extra(bound)) + (1u << 20));
     bfq_phase("gpu");
-    ubam_records(c, d_t, X.len, present, O, G, measure, sized, out);
+    ubam_records(c, T, O, G, measure, sized, out);
 }
 
 extern "C" int bfq_fastq_to_bam_measure(bfq_ctx *c, const uint8_t *const h_text[3], const uint64_t text_len[3], const bfq_ubam_opts *opts, uint64_t *raw_len,
@@ -224,8 +188,8 @@ extern "C" int bfq_fastq_to_bam_measure(bfq_ctx *c, const uint8_t *const h_text[
         const bfq_ubam_opts O = ubam_opts(opts);
         bfq_ubam_tag_stats *tagStats = nullptr;
         const bfq_ubam_tagsel G = ubam_tags(opts, &tagStats);
-        UbamTexts X;
-        for (int k = 0; k < 3; k++) { X.h[k] = h_text[k]; X.len[k] = h_text[k] ? text_len[k] : 0; }
+        TextIn X[3];
+        bfq_texts_of(h_text, text_len, false, X);
         UbamStream U;
         ubam_core(c, X, O, G, true, [](u64) { return (size_t)0; }, [](u64) {}, &U);
         if (tagStats) *tagStats = U.T;
@@ -245,8 +209,8 @@ extern "C" int bfq_fastq_to_bam_device(bfq_ctx *c, const uint8_t *const d_text[3
         const bfq_ubam_opts O = ubam_opts(opts);
         bfq_ubam_tag_stats *tagStats = nullptr;
         const bfq_ubam_tagsel G = ubam_tags(opts, &tagStats);
-        UbamTexts X;
-        for (int k = 0; k < 3; k++) { X.d[k] = d_text[k]; X.len[k] = d_text[k] ? text_len[k] : 0; }
+        TextIn X[3];
+        bfq_texts_of(d_text, text_len, true, X);
         UbamStream U;
         ubam_core(c, X, O, G, false, [](u64) { return (size_t)0; }, [&](u64 raw) {
             if (cap >= raw) return;
@@ -264,7 +228,7 @@ extern "C" int bfq_fastq_to_bam_device(bfq_ctx *c, const uint8_t *const d_text[3
 }
 
 // host texts in, the compressed file out to dst (memory of cap bytes, or a file)
-static void ubam_compressed(bfq_ctx *c, const UbamTexts &X, const bfq_ubam_opts *opts, HostRef dst, u64 cap, uint64_t *out_len, bfq_ubam_stats *stats)
+static void ubam_compressed(bfq_ctx *c, const TextIn X[3], const bfq_ubam_opts *opts, HostRef dst, u64 cap, uint64_t *out_len, bfq_ubam_stats *stats)
 {
     const bfq_ubam_opts O = ubam_opts(opts);
     bfq_ubam_tag_stats *tagStats = nullptr;
@@ -288,8 +252,8 @@ extern "C" int bfq_fastq_to_bam(bfq_ctx *c, const uint8_t *const h_text[3], cons
     if (stats) *stats = bfq_ubam_stats{};
     return guarded(c, [&] {
         if (!h_text || !text_len || !out_len || (!h_out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
-        UbamTexts X;
-        for (int k = 0; k < 3; k++) { X.h[k] = h_text[k]; X.len[k] = h_text[k] ? text_len[k] : 0; }
+        TextIn X[3];
+        bfq_texts_of(h_text, text_len, false, X);
         ubam_compressed(c, X, opts, HostRef::mem(h_out), cap, out_len, stats);
     });
 }
@@ -299,23 +263,12 @@ extern "C" int bfq_fastq_to_bam_fd(bfq_ctx *c, const int text_fd[3], const bfq_u
     if (out_len) *out_len = 0;
     if (stats) *stats = bfq_ubam_stats{};
     // the files are mapped, and uploaded from the mappings
-    struct Map {
-        void *p = MAP_FAILED; size_t n = 0;
-        bool open(int fd, size_t len) { n = len; p = len ? mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0) : MAP_FAILED; return !len || p != MAP_FAILED; }
-        ~Map() { if (p != MAP_FAILED) munmap(p, n); }
-    } text[3];
+    MappedInput text[3];
     return guarded(c, [&] {
         if (!out_len || !text_fd) throw BfqError{BFQ_E_ARG, "null argument"};
         if (out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
-        UbamTexts X;
-        static const u8 none = 0;
-        for (int k = 0; k < 3; k++) {
-            if (text_fd[k] < 0) continue;
-            struct stat st;
-            if (fstat(text_fd[k], &st) != 0 || !text[k].open(text_fd[k], (size_t)st.st_size)) throw BfqError{BFQ_E_IO, std::string("cannot map a text file: ") + strerror(errno)};
-            X.h[k] = st.st_size ? (const u8 *)text[k].p : &none;
-            X.len[k] = (u64)st.st_size;
-        }
+        TextIn X[3];
+        bfq_texts_map(text_fd, text, X);
         try {
             ubam_compressed(c, X, opts, HostRef::file(out_fd, 0), ~0ull, out_len, stats);
             if (ftruncate(out_fd, (off_t)*out_len) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, std::string("cannot size the output file: ") + strerror(errno)};
@@ -337,19 +290,19 @@ size_t bfq_ubam_held_need(bfq_ctx *c, u64 bound, const bfq_ubam_opts *opts)
     bfq_ubam_tag_stats *tagStats = nullptr;
     ubam_tags(opts, &tagStats);                                     // (a tag list that is refused: here, before the restore begins)
     u64 rawBound = 0;
-    const size_t need = ubam_need(bound, 4 * (bound / 6 + 1), 1, bfq_ubam_header(O).size(), bfq_ubam_tag(O).size(), true, &rawBound);
+    const u64 lines = 4 * (bound / 6 + 1);
+    const size_t need = ubam_need(bound, lines, ubam_index_bytes(bound, lines), bfq_ubam_header(O).size(), bfq_ubam_tag(O).size(), true, &rawBound);
     return need + bfq_deflate_need(c, rawBound, false, 0) + 4096;
 }
 u64 bfq_ubam_held(bfq_ctx *c, const u8 *d_text, u64 len, const bfq_ubam_opts *opts, HostRef dst, bfq_ubam_stats *stats)
 {
     const bfq_ubam_opts O = ubam_opts(opts);
-    const u8 *d_t[3] = {d_text, nullptr, nullptr};
-    const u64 lens[3] = {len, 0, 0};
-    const bool present[3] = {true, false, false};
+    TextPlaced T[3];
+    T[0].d = d_text; T[0].len = len;
     bfq_ubam_tag_stats *tagStats = nullptr;
     const bfq_ubam_tagsel G = ubam_tags(opts, &tagStats);
     UbamStream U;
-    ubam_records(c, d_t, lens, present, O, G, false, [](u64) {}, &U);
+    ubam_records(c, T, O, G, false, [](u64) {}, &U);
     const u64 zl = bfq_deflate_core(c, U.d_s, HostRef{}, U.raw, (int)O.level, dst, true, 0);
     if (stats) *stats = U.S;
     if (tagStats) *tagStats = U.T;

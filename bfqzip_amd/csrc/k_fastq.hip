@@ -14,7 +14,7 @@
 #include "bfq_internal.h"
 #include "bfq_device.h"
 
-#define NL_CHUNK 4096                                  // bytes per workgroup iteration (16 per thread)
+static_assert(sizeof(FqRec) == BFQ_FQREC_BYTES, "bfq_fastq_index_bytes() counts a record by it");
 
 __device__ __forceinline__ u32 nl_mask16(const u8 *__restrict__ buf, u64 pos, u64 len)
 {
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void k_nl_count(const u8 *__restrict__ buf, u6
 {
     __shared__ u32 sh[4];
     for (u64 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
-        u32 c = __popc(nl_mask16(buf, ch * NL_CHUNK + (u64)threadIdx.x * 16, len));
+        u32 c = __popc(nl_mask16(buf, ch * BFQ_NL_CHUNK + (u64)threadIdx.x * 16, len));
         u32 tot;
         bfq_block_exscan32(c, sh, &tot);
         if (threadIdx.x == 0) counts[ch] = tot;
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void k_nl_write(const u8 *__restrict__ buf, u6
 {
     __shared__ u32 sh[4];
     for (u64 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
-        u64 pos = ch * NL_CHUNK + (u64)threadIdx.x * 16;
+        u64 pos = ch * BFQ_NL_CHUNK + (u64)threadIdx.x * 16;
         u32 m = nl_mask16(buf, pos, len);
         u32 tot;
         u32 ex = bfq_block_exscan32(__popc(m), sh, &tot);
@@ -203,10 +203,7 @@ __global__ __launch_bounds__(256) void k_fq_hdr_gather(const u8 *__restrict__ bu
 // virtual end at `len`.  *nlines = number of lines.
 u64 *bfq_line_index(bfq_ctx *c, const u8 *d_buf, u64 len, u64 *nlines)
 {
-    u64 nchunks = ceil_div(len ? len : 1, NL_CHUNK);
-    u32 *counts = c->alloc<u32>(nchunks);
-    u64 *bases = c->alloc<u64>(nchunks);
-    u64 *d_total = c->alloc<u64>(1);
+    const auto [counts, bases, d_total, nchunks] = bfq_nl_alloc(c->ws, len);   // (what bfq_line_index_bytes() counts: bfq_texts.h)
     KLAUNCH(c, K_FASTQ, (double)len, k_nl_count, bfq_grid(nchunks, 1), 256, d_buf, len, counts, nchunks);
     bfq_exscan_u32(c, counts, bases, nchunks, d_total);
     u64 nl = 0;
@@ -214,7 +211,7 @@ u64 *bfq_line_index(bfq_ctx *c, const u8 *d_buf, u64 len, u64 *nlines)
     u8 last = 10;
     if (len) HIP_CHECK(hipMemcpyAsync(&last, d_buf + len - 1, 1, hipMemcpyDeviceToHost, c->stream));
     c->sync();
-    u64 *lineEnd = c->alloc<u64>(nl + 2);
+    u64 *lineEnd = bfq_nl_alloc_ends(c->ws, nl);
     if (nl) KLAUNCH(c, K_FASTQ, (double)len + 8.0 * (double)nl, k_nl_write, bfq_grid(nchunks, 1), 256, d_buf, len,
                     (const u64 *)bases, lineEnd, nchunks);
     if (len && last != 10) {
@@ -229,10 +226,7 @@ u64 *bfq_line_index(bfq_ctx *c, const u8 *d_buf, u64 len, u64 *nlines)
 u64 bfq_fastq_count_lines(bfq_ctx *c, const u8 *d_buf, u64 len)
 {
     size_t m = c->mark();
-    u64 nchunks = ceil_div(len ? len : 1, NL_CHUNK);
-    u32 *counts = c->alloc<u32>(nchunks);
-    u64 *bases = c->alloc<u64>(nchunks);
-    u64 *d_total = c->alloc<u64>(1);
+    const auto [counts, bases, d_total, nchunks] = bfq_nl_alloc(c->ws, len);   // (bfq_count_lines_bytes())
     KLAUNCH(c, K_FASTQ, (double)len, k_nl_count, bfq_grid(nchunks, 1), 256, d_buf, len, counts, nchunks);
     bfq_exscan_u32(c, counts, bases, nchunks, d_total);
     u64 nl = 0;
