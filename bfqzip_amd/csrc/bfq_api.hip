@@ -1030,7 +1030,7 @@ static void fastq_build_ebwt_core(bfq_ctx *c, TextSrc text, int term_out, HostRe
 }
 
 // ---- the one-shot tools (gsufsort / eGap / bfq_int / bfq_ext processes): files in, files out.
-// (an output file: OutFile, bfq_internal.h)
+// (the output files: OutFiles, bfq_outfiles.h)
 static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int term_out, int bwt_fd, int qs_fd, int lcp_fd, int lcp_bytes,
                                      uint64_t *n_rows, uint64_t *n_reads)
 {
@@ -1040,14 +1040,6 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
     // The outputs are sized to their bound (rows <= bytes / 2) and pre-faulted in the background -- from the moment the tool
     // opened them (bfq_output_prefault) or from here: by the time the first pile is sorted the page-cache pages exist and the
     // copy out of the staging buffers runs at memcpy speed.
-    OutFile ob, oq, ol;
-    u64 n = 0;
-    auto openOutputs = [&](u64 textBound, u64 est) {
-        const u64 capRows = textBound / 2 + 64;
-        ob.open(bwt_fd, capRows, est);
-        oq.open(qs_fd, capRows, est);
-        if (wantLcp) ol.open(lcp_fd, capRows * (u64)lcp_bytes, est * (u64)lcp_bytes);
-    };
     // HBM of this process, and why it is cut into pieces: the driver scrubs freed HBM at ~30 GB/s and the NEXT process's
     // allocations wait for it (profiles/microbench/alloc_after_exit.hip; profiles/r3/dropin_phases.md: bfq_int waited 1.3-4.3 s
     // behind a gsufsort that had held 102 GiB).  So every piece is as small as its contents and goes back the moment it is dead:
@@ -1056,115 +1048,115 @@ static void fastq_build_ebwt_oneshot(bfq_ctx *c, int fastq_fd, uint64_t len, int
     //   arena         sort records + histograms of ONE pile, sized from the actual pile sizes, in the parse arena's memory
     //                 (what the next process waits for is everything this one ever gave back, not what it held last)
     //   text arrays   T8 / Q8 / packed text: until the last pile is sorted
-    DevBuf pws, tws;                                             // parse arena, text arrays: freed after the writers have been waited for
-    auto finish = [&](bool ok) {
-        if (!ok) { try { bfq_write_wait(c); } catch (...) {} }
-        const bool a = ob.close(ok ? n : 0), b = oq.close(ok ? n : 0), l = ol.close(ok ? n * (u64)lcp_bytes : 0);
-        if (ok && !(a && b && l)) throw BfqError{BFQ_E_IO, "cannot size the output files"};
+    DevBuf pws, tws;                                             // parse arena, text arrays: declared before the outputs: freed after the writers have been waited for
+    const int fds[3] = {bwt_fd, qs_fd, lcp_fd};
+    OutFiles F(fds, 3, [c] { bfq_write_wait(c); });
+    enum { OB, OQ, OL };
+    u64 n = 0;
+    auto openOutputs = [&](u64 textBound, u64 est) {
+        const u64 capRows = textBound / 2 + 64;
+        F.open(OB, capRows, est);
+        F.open(OQ, capRows, est);
+        F.open(OL, capRows * (u64)lcp_bytes, est * (u64)lcp_bytes);
     };
-    try {
-        // a BGZF file: every size follows from its raw length, which the measure gives (host only: headers and trailers)
-        TextMeasure M;
-        try { bfq_text_measure(&text, 1, &M); }
-        catch (...) { openOutputs(len, 0); throw; }             // (the outputs of a refused input are cut to nothing below)
-        openOutputs(M.bound, bfq_fastq_rows_estimate(fastq_fd, len));
-        u64 ps[2];
-        u8 *d_fq = text_place(c, &text, M, ps);
-        const u64 tl = ps[1];
-        bfq_phase("alloc");
-        c->reserve(bfq_count_lines_bytes(tl) + (64u << 20));
-        bfq_phase("gpu");
-        const u64 nlines = bfq_fastq_count_lines(c, d_fq, tl);
-        const u64 Nb = nlines / 4 + 1;
-        bfq_phase("alloc");
-        const size_t parseBytes = (tl + 8192) + 128 * (Nb + 64) + bfq_line_index_bytes(tl, nlines) + 4 * (size_t)(tl / BFQ_NL_CHUNK) + 4096 + (64u << 20);
-        pws.alloc(c, parseBytes, "the parsed records");
-        ScopedArena parse(c, pws.p, parseBytes);                // the small arena of the line count comes back below
-        bfq_phase("gpu");
-        c->zeroCounters();
-        DevFastq fq;
-        bfq_fastq_parse(c, d_fq, tl, &fq);
-        n = fq.total + fq.N;
-        const u64 N = fq.N;
-        if (n_rows) *n_rows = n;
-        if (n_reads) *n_reads = N;
-        c->call.writeHint = (size_t)n * (2 + (wantLcp ? (size_t)lcp_bytes : 0));
-        const u64 npad = (n + 64 + 255) & ~255ull;
-        const bool ext = 2 * npad <= c->textCap;                // always (rows <= bytes / 2); the FASTQ text is dead from here on
-        u8 *raw = nullptr;
-        auto hook = [&](u64 start, u64 m) {                     // rows [start, start + m) are final: out they go while the next pile is sorted
-            if (!m) return;
-            if (ob.fd >= 0) bfq_write_async(c, ob.at(start), c->d_bwt + start, m);
-            if (oq.fd >= 0) bfq_write_async(c, oq.at(start), c->d_qual + start, m);
-            if (wantLcp) {
-                if (lcp_bytes == 2) bfq_write_async(c, ol.at(2 * start), c->d_lcp + start, 2 * m);
-                else {
-                    u8 *r = raw + (size_t)lcp_bytes * start;
-                    KLAUNCH(c, K_MISC, (double)(lcp_bytes + 2) * (double)m, k_lcp_narrow, bfq_grid(m, 256), 256, (const u16 *)(c->d_lcp + start), lcp_bytes, m, r);
-                    bfq_write_async(c, ol.at((u64)lcp_bytes * start), r, (size_t)lcp_bytes * m);
-                }
+    // a BGZF file: every size follows from its raw length, which the measure gives (host only: headers and trailers)
+    TextMeasure M;
+    try { bfq_text_measure(&text, 1, &M); }
+    catch (...) { openOutputs(len, 0); throw; }                 // (the outputs of a refused input are opened, and left empty)
+    openOutputs(M.bound, bfq_fastq_rows_estimate(fastq_fd, len));
+    u64 ps[2];
+    u8 *d_fq = text_place(c, &text, M, ps);
+    const u64 tl = ps[1];
+    bfq_phase("alloc");
+    c->reserve(bfq_count_lines_bytes(tl) + (64u << 20));
+    bfq_phase("gpu");
+    const u64 nlines = bfq_fastq_count_lines(c, d_fq, tl);
+    const u64 Nb = nlines / 4 + 1;
+    bfq_phase("alloc");
+    const size_t parseBytes = (tl + 8192) + 128 * (Nb + 64) + bfq_line_index_bytes(tl, nlines) + 4 * (size_t)(tl / BFQ_NL_CHUNK) + 4096 + (64u << 20);
+    pws.alloc(c, parseBytes, "the parsed records");
+    ScopedArena parse(c, pws.p, parseBytes);                // the small arena of the line count comes back below
+    bfq_phase("gpu");
+    c->zeroCounters();
+    DevFastq fq;
+    bfq_fastq_parse(c, d_fq, tl, &fq);
+    n = fq.total + fq.N;
+    const u64 N = fq.N;
+    if (n_rows) *n_rows = n;
+    if (n_reads) *n_reads = N;
+    c->call.writeHint = (size_t)n * (2 + (wantLcp ? (size_t)lcp_bytes : 0));
+    const u64 npad = (n + 64 + 255) & ~255ull;
+    const bool ext = 2 * npad <= c->textCap;                // always (rows <= bytes / 2); the FASTQ text is dead from here on
+    u8 *raw = nullptr;
+    auto hook = [&](u64 start, u64 m) {                     // rows [start, start + m) are final: out they go while the next pile is sorted
+        if (!m) return;
+        if (F.present(OB)) bfq_write_async(c, F.at(OB, start), c->d_bwt + start, m);
+        if (F.present(OQ)) bfq_write_async(c, F.at(OQ, start), c->d_qual + start, m);
+        if (wantLcp) {
+            if (lcp_bytes == 2) bfq_write_async(c, F.at(OL, 2 * start), c->d_lcp + start, 2 * m);
+            else {
+                u8 *r = raw + (size_t)lcp_bytes * start;
+                KLAUNCH(c, K_MISC, (double)(lcp_bytes + 2) * (double)m, k_lcp_narrow, bfq_grid(m, 256), 256, (const u16 *)(c->d_lcp + start), lcp_bytes, m, r);
+                bfq_write_async(c, F.at(OL, (u64)lcp_bytes * start), r, (size_t)lcp_bytes * m);
             }
-        };
-        const size_t lcpExtra = wantLcp ? (size_t)(lcp_bytes == 2 ? 0 : lcp_bytes) * (n + 256) + 4096 : 0;
-        if (n < (32u << 20)) {
-            // a small collection: one piece in one arena (0.9 GB at most); the parsed reads stay where they are meanwhile
-            parse.restore();
-            bfq_phase("alloc");
-            c->reserve(ws_need(n, N, lcpExtra));
-            bfq_phase("gpu");
-            if (ext) { c->call.extBwt = c->d_text; c->call.extQual = c->d_text + npad; }
-            if (wantLcp && lcp_bytes != 2) raw = c->alloc<u8>((size_t)lcp_bytes * n + 64);
-            c->call.onRows = hook;
-            bfq_step1_device(c, fq.bases, fq.quals, fq.roff, N, fq.total, term_out, nullptr);
-        } else {
-            const u64 nwords = n / BFQ_SYMS_PER_WORD + 3;
-            const size_t w3 = (8 * bfq_t3_alloc(nwords) + 255) & ~(size_t)255;
-            bfq_phase("alloc");
-            tws.alloc(c, 2 * npad + w3 + 8 * (N + 2) + 4096, "the text arrays");
-            bfq_phase("gpu");
-            PileText pt{(u8 *)tws.p, (u8 *)tws.p + npad, (u64 *)(tws.p + 2 * npad)};
-            u64 *roff2 = (u64 *)(tws.p + 2 * npad + w3);
-            bfq_build_text(c, fq.bases, fq.quals, fq.roff, N, n, pt.T8, pt.Q8, pt.text3, nwords);
-            HIP_CHECK(hipMemcpyAsync(roff2, fq.roff, 8 * (N + 1), hipMemcpyDeviceToDevice, c->stream));
-            u64 cnt[36];
-            bfq_pile_pair_counts(c, pt.T8, n, cnt);             // synchronises
-            c->fetchCounters();
-            check_counters(c);                                  // forbidden symbols, reads beyond BFQ_MAX_READ_LEN
-            parse.restore();                                    // the parsed reads are dead
-            // piles above an eighth of the rows are split by their second symbol; the arena holds the largest piece
-            const u64 capTarget = n / 8 + (1u << 20);
-            u64 cap = 1u << 20;
-            for (int s1 = 1; s1 <= 5; s1++) {
-                u64 tot = 0, big = 0;
-                for (int s2 = 0; s2 <= 5; s2++) { tot += cnt[6 * s1 + s2]; big = std::max(big, cnt[6 * s1 + s2]); }
-                cap = std::max(cap, tot <= capTarget ? tot : big);
-            }
-            bfq_phase("alloc");
-            const size_t needPiles = bfq_ws_need_piles(n, N, cap, lcpExtra + (wantLcp ? 2 * (n + 256) : 0), true);
-            if (parseBytes >= needPiles + (1u << 20) && !(c->wsLimit() && parseBytes > c->wsLimit()))
-                c->adoptWorkspace(pws.release(), parseBytes);   // the pile arena lives where the parsed reads were
-            else pws.free();
-            c->reserve(needPiles);
-            bfq_phase("gpu");
-            c->call.piles = true;
-            c->call.lcpScratch = !wantLcp;
-            if (ext) { c->call.extBwt = c->d_text; c->call.extQual = c->d_text + npad; }
-            if (wantLcp && lcp_bytes != 2) raw = c->alloc<u8>((size_t)lcp_bytes * n + 64);
-            c->call.onRows = hook;
-            bfq_step1_piles(c, nullptr, nullptr, roff2, N, fq.total, term_out, nullptr, &pt, capTarget);
         }
-        finish_call(c);                                         // waits for the stream
-        bfq_phase("d2h_write");
-        if (ext && !wantLcp) {                                  // what is still being written lives in the text buffer: the rest goes back now
-            c->dropWorkspace();
-            tws.free(); pws.free();
+    };
+    const size_t lcpExtra = wantLcp ? (size_t)(lcp_bytes == 2 ? 0 : lcp_bytes) * (n + 256) + 4096 : 0;
+    if (n < (32u << 20)) {
+        // a small collection: one piece in one arena (0.9 GB at most); the parsed reads stay where they are meanwhile
+        parse.restore();
+        bfq_phase("alloc");
+        c->reserve(ws_need(n, N, lcpExtra));
+        bfq_phase("gpu");
+        if (ext) { c->call.extBwt = c->d_text; c->call.extQual = c->d_text + npad; }
+        if (wantLcp && lcp_bytes != 2) raw = c->alloc<u8>((size_t)lcp_bytes * n + 64);
+        c->call.onRows = hook;
+        bfq_step1_device(c, fq.bases, fq.quals, fq.roff, N, fq.total, term_out, nullptr);
+    } else {
+        const u64 nwords = n / BFQ_SYMS_PER_WORD + 3;
+        const size_t w3 = (8 * bfq_t3_alloc(nwords) + 255) & ~(size_t)255;
+        bfq_phase("alloc");
+        tws.alloc(c, 2 * npad + w3 + 8 * (N + 2) + 4096, "the text arrays");
+        bfq_phase("gpu");
+        PileText pt{(u8 *)tws.p, (u8 *)tws.p + npad, (u64 *)(tws.p + 2 * npad)};
+        u64 *roff2 = (u64 *)(tws.p + 2 * npad + w3);
+        bfq_build_text(c, fq.bases, fq.quals, fq.roff, N, n, pt.T8, pt.Q8, pt.text3, nwords);
+        HIP_CHECK(hipMemcpyAsync(roff2, fq.roff, 8 * (N + 1), hipMemcpyDeviceToDevice, c->stream));
+        u64 cnt[36];
+        bfq_pile_pair_counts(c, pt.T8, n, cnt);             // synchronises
+        c->fetchCounters();
+        check_counters(c);                                  // forbidden symbols, reads beyond BFQ_MAX_READ_LEN
+        parse.restore();                                    // the parsed reads are dead
+        // piles above an eighth of the rows are split by their second symbol; the arena holds the largest piece
+        const u64 capTarget = n / 8 + (1u << 20);
+        u64 cap = 1u << 20;
+        for (int s1 = 1; s1 <= 5; s1++) {
+            u64 tot = 0, big = 0;
+            for (int s2 = 0; s2 <= 5; s2++) { tot += cnt[6 * s1 + s2]; big = std::max(big, cnt[6 * s1 + s2]); }
+            cap = std::max(cap, tot <= capTarget ? tot : big);
         }
-        bfq_write_wait(c);
-    } catch (...) {
-        finish(false);
-        throw;
+        bfq_phase("alloc");
+        const size_t needPiles = bfq_ws_need_piles(n, N, cap, lcpExtra + (wantLcp ? 2 * (n + 256) : 0), true);
+        if (parseBytes >= needPiles + (1u << 20) && !(c->wsLimit() && parseBytes > c->wsLimit()))
+            c->adoptWorkspace(pws.release(), parseBytes);   // the pile arena lives where the parsed reads were
+        else pws.free();
+        c->reserve(needPiles);
+        bfq_phase("gpu");
+        c->call.piles = true;
+        c->call.lcpScratch = !wantLcp;
+        if (ext) { c->call.extBwt = c->d_text; c->call.extQual = c->d_text + npad; }
+        if (wantLcp && lcp_bytes != 2) raw = c->alloc<u8>((size_t)lcp_bytes * n + 64);
+        c->call.onRows = hook;
+        bfq_step1_piles(c, nullptr, nullptr, roff2, N, fq.total, term_out, nullptr, &pt, capTarget);
     }
-    finish(true);
+    finish_call(c);                                         // waits for the stream
+    bfq_phase("d2h_write");
+    if (ext && !wantLcp) {                                  // what is still being written lives in the text buffer: the rest goes back now
+        c->dropWorkspace();
+        tws.free(); pws.free();
+    }
+    const u64 fin[3] = {n, n, n * (u64)lcp_bytes};
+    F.commit(fin);
 }
 
 extern "C" int bfq_fastq_build_ebwt(bfq_ctx *c, const uint8_t *h_fastq, uint64_t len, int term_out, uint8_t *h_bwt,
@@ -1354,11 +1346,11 @@ extern "C" int bfq_fastq_run_streams(bfq_ctx *c, const uint8_t *h_fastq, uint64_
 
 static void smooth_invert_fastq_core(bfq_ctx *c, HostRef bwt, HostRef qs, HostRef lcp, int lcp_bytes, uint64_t n, HostRef headers,
                                      bool haveHeaders, uint64_t headers_len, HostRef out, uint64_t cap, uint64_t *out_len, bfq_stats *st,
-                                     const OutFile *outFile = nullptr)
+                                     OutFiles *outFile = nullptr)
 {
     SmoothOut r;
     smooth_invert_core(c, bwt, qs, lcp, lcp_bytes, n, 3 * (n + 4096) + 2 * headers_len + (32u << 20), st, &r);
-    if (outFile && outFile->m) bfq_outmap_extend(outFile->m, haveHeaders ? headers_len + 2 * r.total + 4 * r.N : 2 * r.total + 6 * r.N);
+    if (outFile) outFile->extend(0, haveHeaders ? headers_len + 2 * r.total + 4 * r.N : 2 * r.total + 6 * r.N);   // (within the bound it is mapped to)
     u8 *d_hdr = nullptr;
     if (haveHeaders) {
         d_hdr = c->alloc<u8>(headers_len + 64);
@@ -1369,8 +1361,8 @@ static void smooth_invert_fastq_core(bfq_ctx *c, HostRef bwt, HostRef qs, HostRe
     if (out_len) *out_len = ol;
     if (ol > cap) throw BfqError{BFQ_E_ARG, "output buffer smaller than the FASTQ text (see bfq_fastq_out_bound)"};
     if (outFile) {
-        if (outFile->m && ol > bfq_outmap_len(outFile->m)) throw BfqError{BFQ_E_IO, "output mapping smaller than the FASTQ text"};
-        bfq_write_async(c, outFile->at(0), d_out, ol);
+        outFile->extend(0, ol);
+        bfq_write_async(c, outFile->at(0, 0), d_out, ol);
     } else bfq_download(c, out, d_out, ol);
     finish_call(c, st);
     if (outFile) { bfq_phase("d2h_write"); bfq_write_wait(c); }
@@ -1393,20 +1385,14 @@ extern "C" int bfq_smooth_invert_fastq_fd(bfq_ctx *c, int bwt_fd, int qs_fd, int
         if (bwt_fd < 0 || qs_fd < 0 || out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
         // the FASTQ text is at least 2 n bytes (bases + qualities + their newlines) and at most 6 n + the header file
         // (a collection of empty reads): mapped to the bound, pre-faulted to what is certain while the eBWT is uploaded
-        OutFile of;
-        of.open(out_fd, 6 * n + headers_len + 4096, 2 * n);
+        OutFiles F(out_fd, [c] { bfq_write_wait(c); });
+        F.open(0, 6 * n + headers_len + 4096, 2 * n);
         uint64_t ol = 0;
-        try {
-            smooth_invert_fastq_core(c, HostRef::file(bwt_fd), HostRef::file(qs_fd), lcp_fd >= 0 ? HostRef::file(lcp_fd) : HostRef(), lcp_bytes, n,
-                                     headers_fd >= 0 ? HostRef::file(headers_fd) : HostRef(), headers_fd >= 0, headers_len, HostRef::file(out_fd),
-                                     ~0ull, &ol, st, &of);
-        } catch (...) {
-            try { bfq_write_wait(c); } catch (...) {}
-            of.close(0);
-            throw;
-        }
+        smooth_invert_fastq_core(c, HostRef::file(bwt_fd), HostRef::file(qs_fd), lcp_fd >= 0 ? HostRef::file(lcp_fd) : HostRef(), lcp_bytes, n,
+                                 headers_fd >= 0 ? HostRef::file(headers_fd) : HostRef(), headers_fd >= 0, headers_len, HostRef::file(out_fd),
+                                 ~0ull, &ol, st, &F);
         if (out_len) *out_len = ol;
-        if (!of.close(ol)) throw BfqError{BFQ_E_IO, "cannot size the output file"};
+        F.commit(&ol);
     });
 }
 

@@ -272,7 +272,7 @@ extern "C" int bfq_bam_to_fastq_fd(bfq_ctx *c, int in_fd, uint64_t len, const bf
             if (!out_fd || out_fd[o] < 0) continue;
             bfq_download(c, HostRef::file(out_fd[o], 0), where[o], ol[o]);
             c->sync();
-            if (ftruncate(out_fd[o], (off_t)ol[o]) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, std::string("cannot size the output file: ") + strerror(errno)};
+            bfq_fd_size(out_fd[o], ol[o], "cannot size the output file: ", true);
         }
     });
 }

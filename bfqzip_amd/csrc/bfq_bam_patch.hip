@@ -190,7 +190,7 @@ extern "C" int bfq_bam_patch_fd(bfq_ctx *c, int bam_fd, uint64_t len, const bfq_
         bfq_texts_map(text_fd, text, X);
         try {
             patch_compressed(c, bam.data(), len, opts, X, level, HostRef::file(out_fd, 0), ~0ull, out_len, stats);
-            if (ftruncate(out_fd, (off_t)*out_len) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, std::string("cannot size the output file: ") + strerror(errno)};
+            bfq_fd_size(out_fd, *out_len, "cannot size the output file: ", true);
         } catch (...) {
             if (ftruncate(out_fd, 0) != 0) {}
             *out_len = 0;

@@ -129,7 +129,7 @@ extern "C" int bfq_bgzf_inflate_fd(bfq_ctx *c, int in_fd, uint64_t len, int out_
             bfq_phase("d2h_write");
             bfq_download(c, HostRef::file(out_fd, 0), d_text, raw);
             c->sync();
-            if (ftruncate(out_fd, (off_t)raw) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, std::string("cannot size the output file: ") + strerror(errno)};
+            bfq_fd_size(out_fd, raw, "cannot size the output file: ", true);
         }
         *out_len = raw;
     });

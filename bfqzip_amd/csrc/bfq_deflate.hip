@@ -165,7 +165,7 @@ extern "C" int bfq_bgzf_deflate_fd(bfq_ctx *c, int in_fd, uint64_t len, int leve
         if (len >= 2 && pread(in_fd, first, 2, 0) != 2) throw BfqError{BFQ_E_IO, std::string("cannot read the input file: ") + strerror(errno)};
         defl_refuse_gzip(first, len);
         const u64 ol = bfq_deflate_core(c, nullptr, HostRef::file(in_fd, 0), len, level, HostRef::file(out_fd, 0), false, 0);
-        if (ftruncate(out_fd, (off_t)ol) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, std::string("cannot size the output file: ") + strerror(errno)};
+        bfq_fd_size(out_fd, ol, "cannot size the output file: ", true);
         *out_len = ol;
     });
 }

@@ -17,6 +17,7 @@
 #include "bfq_internal_host.h"
 #include "bfq_arena.h"
 #include "bfq_texts.h"
+#include "bfq_outfiles.h"
 
 #define HIP_CHECK(expr)                                                                        \
     do {                                                                                       \
@@ -212,14 +213,6 @@ struct ScopedEvent {
     operator hipEvent_t() const { return e; }
 };
 
-// a host-side operand of a transfer: memory, or an open file at an offset (the front-ends' files)
-struct HostRef {
-    void *ptr = nullptr; int fd = -1; u64 off = 0;
-    bfq_outmap *om = nullptr;       // ptr lies `off` bytes into this output mapping: pages are populated before they are written
-    static HostRef mem(const void *p) { HostRef h; h.ptr = const_cast<void *>(p); return h; }
-    static HostRef file(int fd, u64 off = 0) { HostRef h; h.fd = fd; h.off = off; return h; }
-    bool null() const { return !ptr && fd < 0; }
-};
 void bfq_upload(bfq_ctx *c, void *d_dst, HostRef src, size_t len);
 void bfq_download(bfq_ctx *c, HostRef dst, const void *d_src, size_t len);
 // A text source of a call -- memory or an open file -- measured and placed (bfq_bgzf.hip).  A FASTQ text cannot begin with
@@ -280,6 +273,13 @@ static inline bool bfq_seen_gzip(const BfqTextSeen &s) { return s.len >= 2 && s.
 }
 void bfq_upload(bfq_ctx *c, void *d_dst, const void *h_src, size_t len);
 void bfq_download(bfq_ctx *c, void *h_dst, const void *d_src, size_t len);
+// a sink's download to host memory: in the d2h_write phase, and back to gpu
+static inline void bfq_download_phase(bfq_ctx *c, void *h_dst, const void *d_src, size_t len)
+{
+    bfq_phase("d2h_write");
+    bfq_download(c, h_dst, d_src, len);
+    bfq_phase("gpu");
+}
 // background writes: the bytes [d_src, d_src + len) as they are once the work queued so far on the context's stream has
 // finished go to dst (memory -- e.g. an output mapping -- or a file offset) through the writer's own staging workers; the
 // call returns at once.  bfq_write_wait(): all of them have arrived (throws what went wrong).  d_src must stay valid till then.
@@ -289,36 +289,6 @@ void bfq_write_wait(bfq_ctx *c);
 struct BfqAsyncUpload;
 BfqAsyncUpload *bfq_upload_begin(bfq_ctx *c, void *d_dst, HostRef src, size_t len);
 void bfq_upload_join(BfqAsyncUpload *u);
-
-// An output file of the *_fd entry points: mapped and pre-faulted in the background when it is a regular file, written with
-// pwrite otherwise.
-struct OutFile {
-    int fd = -1;
-    bfq_outmap *m = nullptr;
-    HostRef at(u64 off) const
-    {
-        if (!m) return HostRef::file(fd, off);
-        HostRef h = HostRef::mem(bfq_outmap_ptr(m) + off);
-        h.om = m; h.off = off;
-        return h;
-    }
-    void open(int f, u64 mapLen, u64 prefault)
-    {
-        fd = f;
-        if (f < 0) return;
-        m = bfq_outmap_take(f, mapLen);
-        if (m) bfq_outmap_extend(m, prefault);
-        else m = bfq_outmap_open(f, mapLen, prefault);
-    }
-    bool close(u64 finalLen)
-    {
-        bool ok = true;
-        if (m) ok = bfq_outmap_close(m, finalLen);
-        else if (fd >= 0) ok = ftruncate(fd, (off_t)finalLen) == 0 || errno == EINVAL;   // EINVAL: not a regular file
-        m = nullptr;
-        return ok;
-    }
-};
 
 #define KLAUNCH(ctx, kid, bytes, kernel, grid, block, ...)                                     \
     do {                                                                                       \

@@ -6,6 +6,7 @@
 #include <new>
 #include <string>
 #include "../../include/bfqzip_hip.h"
+#include "bfq_common.h"
 
 // what a failing stage throws: a BFQ_E_* code and the text bfq_last_error() returns
 struct BfqError {
@@ -89,3 +90,12 @@ void bfq_outmap_extend(bfq_outmap *m, uint64_t prefault_len);
 bool bfq_outmap_close(bfq_outmap *m, uint64_t final_len);
 bool bfq_outmap_ensure(bfq_outmap *m, uint64_t off, uint64_t len);   // before copying into [off, off + len); false: use pwrite on bfq_outmap_fd()
 int bfq_outmap_fd(bfq_outmap *m);
+
+// a host-side operand of a transfer: memory, or an open file at an offset (the front-ends' files)
+struct HostRef {
+    void *ptr = nullptr; int fd = -1; u64 off = 0;
+    bfq_outmap *om = nullptr;       // ptr lies `off` bytes into this output mapping: pages are populated before they are written
+    static HostRef mem(const void *p) { HostRef h; h.ptr = const_cast<void *>(p); return h; }
+    static HostRef file(int fd, u64 off = 0) { HostRef h; h.fd = fd; h.off = off; return h; }
+    bool null() const { return !ptr && fd < 0; }
+};

@@ -7,7 +7,7 @@
 //   2  the checks -- the record counts, the keys of the pairs -- and the sizes: exact output lengths, and the capacities
 //      checked against them.  Up to here nothing of the caller's has been touched
 //   3  the move, one copy of every record: into the caller's device buffers, or into the arena and from there through
-//      bfq_download (host buffers) or the background writers (files)
+//      bfq_download (host buffers) or the background writers (files: committed or left empty, OutFiles, bfq_outfiles.h)
 //   arena   per text 8 bytes per line (and 12 per 4 KiB while they are indexed) and 44 per record; 16 bytes per pair (orphan
 //           mode: 57 per record; repair: 83 per record) of sizes and offsets; the outputs unless they are the caller's device
 //           buffers
@@ -239,7 +239,7 @@ static void merge_core(bfq_ctx *c, const TextIn src[3], const bfq_pairs_opts &O,
     c->profCollect();
 }
 
-// ---------------------------------------------------------------- the split's entry points
+// ---------------------------------------------------------------- what the entry points share
 // the capacities against the lengths: a short one leaves out_len[] = the lengths needed
 static void pr_check_caps(bfq_ctx *c, const uint64_t *cap, const u64 *lens, int n, uint64_t *out_len, u32 merge)
 {
@@ -253,6 +253,64 @@ static void pr_check_caps(bfq_ctx *c, const uint64_t *cap, const u64 *lens, int 
     pr_refuse(X);
 }
 
+// host or device buffers out: the body of the memory forms of the split, the merge (n = 1) and the repair.  run(sink, nr, &S)
+// resolves the options and calls the core.
+template <class Stats, class Run>
+static void pr_run_mem(bfq_ctx *c, uint8_t *const *out, const uint64_t *cap, int n, bool device, bool measure, u32 merge, uint64_t *out_len, uint64_t *n_reads,
+                       Stats *stats, Run run)
+{
+    if (!measure)
+        for (int k = 0; k < n; k++)
+            if (!out[k] && cap[k]) throw BfqError{BFQ_E_ARG, "null argument"};
+    PrSink sink;
+    sink.device = device;
+    sink.sized = [&](const u64 *lens) { if (!measure) pr_check_caps(c, cap, lens, n, out_len, merge); };
+    if (!measure && device) for (int k = 0; k < n; k++) sink.d_dst[k] = out[k];
+    sink.put = [&](int k, const u8 *d_text, u64 len) { bfq_download_phase(c, out[k], d_text, len); };
+    u64 nr[3] = {0, 0, 0};
+    Stats S;
+    run(sink, nr, &S);
+    for (int k = 0; k < n; k++) out_len[k] = S.out_len[k];
+    if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+    if (stats) *stats = S;
+}
+
+// open files out: the body of the *_fd forms.  The files are opened once the lengths are known, committed at them, and left
+// empty when the call fails (OutFiles, bfq_outfiles.h).
+template <class Stats, class Run>
+static void pr_run_fd(bfq_ctx *c, const int *out_fd, int n, uint64_t *out_len, uint64_t *n_reads, Stats *stats, Run run)
+{
+    OutFiles F(out_fd, n, [c] { bfq_write_wait(c); });
+    PrSink sink;
+    sink.sized = [&](const u64 *lens) {
+        F.openAt(lens);
+        u64 sum = 0;
+        for (int k = 0; k < n; k++) sum += lens[k];
+        c->call.writeHint = (size_t)sum;
+    };
+    sink.put = [&](int k, const u8 *d_text, u64 len) { if (F.present(k)) bfq_write_async(c, F.at(k, 0), d_text, len); };
+    u64 nr[3] = {0, 0, 0};
+    Stats S;
+    run(sink, nr, &S);
+    bfq_phase("d2h_write");
+    F.commit(S.out_len);
+    for (int k = 0; k < n; k++) out_len[k] = S.out_len[k];
+    if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
+    if (stats) *stats = S;
+}
+
+// the texts of a call's descriptors (< 0: absent): a text is as long as its file
+static void pr_texts_fd(const int text_fd[3], TextIn src[3])
+{
+    for (int k = 0; k < 3; k++) {
+        if (text_fd[k] < 0) continue;
+        struct stat st;
+        if (fstat(text_fd[k], &st) != 0) throw BfqError{BFQ_E_IO, std::string("cannot stat a text file: ") + strerror(errno)};
+        src[k].ref = HostRef::file(text_fd[k]); src[k].len = (u64)st.st_size;
+    }
+}
+
+// ---------------------------------------------------------------- the split's entry points
 static int pr_split_mem(bfq_ctx *c, TextIn in, const bfq_pairs_opts *opts, uint8_t *const *out, const uint64_t *cap, bool device, bool measure,
                         uint64_t *out_len, uint64_t *n_reads, bfq_pairs_stats *stats)
 {
@@ -260,25 +318,8 @@ static int pr_split_mem(bfq_ctx *c, TextIn in, const bfq_pairs_opts *opts, uint8
     if (stats) *stats = bfq_pairs_stats{};
     return guarded(c, [&] {
         if (!out_len || (!in.present() && in.len) || (!measure && (!out || !cap))) throw BfqError{BFQ_E_ARG, "null argument"};
-        if (!measure)
-            for (int k = 0; k < 3; k++)
-                if (!out[k] && cap[k]) throw BfqError{BFQ_E_ARG, "null argument"};
-        const bfq_pairs_opts O = pr_opts(opts);
-        PrSink sink;
-        sink.device = device;
-        sink.sized = [&](const u64 *lens) { if (!measure) pr_check_caps(c, cap, lens, 3, out_len, 0); };
-        if (!measure && device) for (int k = 0; k < 3; k++) sink.d_dst[k] = out[k];
-        sink.put = [&](int k, const u8 *d_text, u64 len) {
-            bfq_phase("d2h_write");
-            bfq_download(c, out[k], d_text, len);
-            bfq_phase("gpu");
-        };
-        u64 nr[3] = {0, 0, 0};
-        bfq_pairs_stats S;
-        split_core(c, in, O, measure, sink, nr, &S);
-        for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
-        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
-        if (stats) *stats = S;
+        pr_run_mem(c, out, cap, 3, device, measure, 0, out_len, n_reads, stats,
+                   [&](const PrSink &sink, u64 *nr, bfq_pairs_stats *S) { split_core(c, in, pr_opts(opts), measure, sink, nr, S); });
     });
 }
 
@@ -304,37 +345,6 @@ extern "C" int bfq_fastq_deinterleave_device(bfq_ctx *c, const uint8_t *d_text, 
     return pr_split_mem(c, in, opts, d_out, cap, true, false, out_len, n_reads, stats);
 }
 
-// the output files of a call: opened once the lengths are known, left empty when the call fails
-struct PrFiles {
-    OutFile of[3];
-    int fd[3] = {-1, -1, -1};
-    bool open = false;
-    void start(const u64 *lens, int n)
-    {
-        for (int k = 0; k < n; k++)
-            if (fd[k] >= 0) of[k].open(fd[k], lens[k] + 4096, lens[k]);
-        open = true;
-    }
-    bool finish(const uint64_t *lens, int n)
-    {
-        bool ok = true;
-        for (int k = 0; k < n; k++)
-            if (fd[k] >= 0) ok = of[k].close(lens[k]) && ok;
-        open = false;
-        return ok;
-    }
-    void fail(bfq_ctx *c, int n)
-    {
-        if (open) { try { bfq_write_wait(c); } catch (...) {} }
-        for (int k = 0; k < n; k++) {
-            if (fd[k] < 0) continue;
-            if (open) of[k].close(0);
-            else if (ftruncate(fd[k], 0) != 0) {}
-        }
-        open = false;
-    }
-};
-
 extern "C" int bfq_fastq_deinterleave_fd(bfq_ctx *c, int in_fd, uint64_t len, const bfq_pairs_opts *opts, const int out_fd[3], uint64_t out_len[3],
                                          uint64_t n_reads[3], bfq_pairs_stats *stats)
 {
@@ -343,31 +353,12 @@ extern "C" int bfq_fastq_deinterleave_fd(bfq_ctx *c, int in_fd, uint64_t len, co
     return guarded(c, [&] {
         if (!out_len || !out_fd) throw BfqError{BFQ_E_ARG, "null argument"};
         if (in_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
-        PrFiles F;
-        for (int k = 0; k < 3; k++) F.fd[k] = out_fd[k];
-        try {
+        pr_run_fd(c, out_fd, 3, out_len, n_reads, stats, [&](const PrSink &sink, u64 *nr, bfq_pairs_stats *S) {
             const bfq_pairs_opts O = pr_opts(opts);
             TextIn in;
             in.ref = HostRef::file(in_fd); in.len = len;
-            PrSink sink;
-            sink.sized = [&](const u64 *lens) {
-                F.start(lens, 3);
-                c->call.writeHint = (size_t)(lens[0] + lens[1] + lens[2]);
-            };
-            sink.put = [&](int k, const u8 *d_text, u64 n) { if (F.fd[k] >= 0) bfq_write_async(c, F.of[k].at(0), d_text, n); };
-            u64 nr[3] = {0, 0, 0};
-            bfq_pairs_stats S;
-            split_core(c, in, O, false, sink, nr, &S);
-            bfq_phase("d2h_write");
-            bfq_write_wait(c);
-            if (!F.finish(S.out_len, 3)) throw BfqError{BFQ_E_IO, "cannot size the output files"};
-            for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
-            if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
-            if (stats) *stats = S;
-        } catch (...) {
-            F.fail(c, 3);
-            throw;
-        }
+            split_core(c, in, O, false, sink, nr, S);
+        });
     });
 }
 
@@ -380,24 +371,12 @@ static int pr_merge_mem(bfq_ctx *c, const uint8_t *const *text, const uint64_t *
     if (stats) *stats = bfq_pairs_stats{};
     return guarded(c, [&] {
         if (!text || !text_len || !out_len || (!measure && !out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
-        const bfq_pairs_opts O = pr_opts(opts);
-        TextIn src[3];
-        bfq_texts_of(text, text_len, device, src);
-        PrSink sink;
-        sink.device = device;
-        sink.sized = [&](const u64 *total) { if (!measure) pr_check_caps(c, &cap, total, 1, out_len, 1); };
-        sink.d_dst[0] = device ? out : nullptr;
-        sink.put = [&](int, const u8 *d_text, u64 len) {
-            bfq_phase("d2h_write");
-            bfq_download(c, out, d_text, len);
-            bfq_phase("gpu");
-        };
-        u64 nr[3] = {0, 0, 0};
-        bfq_pairs_stats S;
-        merge_core(c, src, O, measure, sink, nr, &S);
-        *out_len = S.out_len[0];
-        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
-        if (stats) *stats = S;
+        pr_run_mem(c, &out, &cap, 1, device, measure, 1, out_len, n_reads, stats, [&](const PrSink &sink, u64 *nr, bfq_pairs_stats *S) {
+            const bfq_pairs_opts O = pr_opts(opts);
+            TextIn src[3];
+            bfq_texts_of(text, text_len, device, src);
+            merge_core(c, src, O, measure, sink, nr, S);
+        });
     });
 }
 
@@ -424,35 +403,12 @@ extern "C" int bfq_fastq_interleave_fd(bfq_ctx *c, const int text_fd[3], const b
     return guarded(c, [&] {
         if (!out_len || !text_fd) throw BfqError{BFQ_E_ARG, "null argument"};
         if (out_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
-        PrFiles F;
-        F.fd[0] = out_fd;
-        try {
+        pr_run_fd(c, &out_fd, 1, out_len, nullptr, stats, [&](const PrSink &sink, u64 *nr, bfq_pairs_stats *S) {
             const bfq_pairs_opts O = pr_opts(opts);
             TextIn src[3];
-            for (int k = 0; k < 3; k++) {
-                if (text_fd[k] < 0) continue;
-                struct stat st;
-                if (fstat(text_fd[k], &st) != 0) throw BfqError{BFQ_E_IO, std::string("cannot stat a text file: ") + strerror(errno)};
-                src[k].ref = HostRef::file(text_fd[k]); src[k].len = (u64)st.st_size;
-            }
-            PrSink sink;
-            sink.sized = [&](const u64 *total) {
-                F.start(total, 1);
-                c->call.writeHint = (size_t)*total;
-            };
-            sink.put = [&](int, const u8 *d_text, u64 n) { bfq_write_async(c, F.of[0].at(0), d_text, n); };
-            u64 nr[3] = {0, 0, 0};
-            bfq_pairs_stats S;
-            merge_core(c, src, O, false, sink, nr, &S);
-            bfq_phase("d2h_write");
-            bfq_write_wait(c);
-            if (!F.finish(S.out_len, 1)) throw BfqError{BFQ_E_IO, "cannot size the output file"};
-            *out_len = S.out_len[0];
-            if (stats) *stats = S;
-        } catch (...) {
-            F.fail(c, 1);
-            throw;
-        }
+            pr_texts_fd(text_fd, src);
+            merge_core(c, src, O, false, sink, nr, S);
+        });
     });
 }
 
@@ -536,27 +492,12 @@ static int rp_mem(bfq_ctx *c, const uint8_t *const *text, const uint64_t *text_l
     if (stats) *stats = bfq_repair_stats{};
     return guarded(c, [&] {
         if (!text || !text_len || !out_len || (!measure && (!out || !cap))) throw BfqError{BFQ_E_ARG, "null argument"};
-        if (!measure)
-            for (int k = 0; k < 3; k++)
-                if (!out[k] && cap[k]) throw BfqError{BFQ_E_ARG, "null argument"};
-        const bfq_repair_opts O = rp_opts(opts);
-        TextIn src[3];
-        bfq_texts_of(text, text_len, device, src);
-        PrSink sink;
-        sink.device = device;
-        sink.sized = [&](const u64 *lens) { if (!measure) pr_check_caps(c, cap, lens, 3, out_len, 2); };
-        if (!measure && device) for (int k = 0; k < 3; k++) sink.d_dst[k] = out[k];
-        sink.put = [&](int k, const u8 *d_text, u64 len) {
-            bfq_phase("d2h_write");
-            bfq_download(c, out[k], d_text, len);
-            bfq_phase("gpu");
-        };
-        u64 nr[3] = {0, 0, 0};
-        bfq_repair_stats S;
-        repair_core(c, src, O, measure, sink, nr, &S);
-        for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
-        if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
-        if (stats) *stats = S;
+        pr_run_mem(c, out, cap, 3, device, measure, 2, out_len, n_reads, stats, [&](const PrSink &sink, u64 *nr, bfq_repair_stats *S) {
+            const bfq_repair_opts O = rp_opts(opts);
+            TextIn src[3];
+            bfq_texts_of(text, text_len, device, src);
+            repair_core(c, src, O, measure, sink, nr, S);
+        });
     });
 }
 
@@ -583,36 +524,12 @@ extern "C" int bfq_fastq_repair_fd(bfq_ctx *c, const int text_fd[3], const bfq_r
     if (stats) *stats = bfq_repair_stats{};
     return guarded(c, [&] {
         if (!out_len || !text_fd || !out_fd) throw BfqError{BFQ_E_ARG, "null argument"};
-        PrFiles F;
-        for (int k = 0; k < 3; k++) F.fd[k] = out_fd[k];
-        try {
+        pr_run_fd(c, out_fd, 3, out_len, n_reads, stats, [&](const PrSink &sink, u64 *nr, bfq_repair_stats *S) {
             const bfq_repair_opts O = rp_opts(opts);
             TextIn src[3];
-            for (int k = 0; k < 3; k++) {
-                if (text_fd[k] < 0) continue;
-                struct stat st;
-                if (fstat(text_fd[k], &st) != 0) throw BfqError{BFQ_E_IO, std::string("cannot stat a text file: ") + strerror(errno)};
-                src[k].ref = HostRef::file(text_fd[k]); src[k].len = (u64)st.st_size;
-            }
-            PrSink sink;
-            sink.sized = [&](const u64 *lens) {
-                F.start(lens, 3);
-                c->call.writeHint = (size_t)(lens[0] + lens[1] + lens[2]);
-            };
-            sink.put = [&](int k, const u8 *d_text, u64 n) { if (F.fd[k] >= 0) bfq_write_async(c, F.of[k].at(0), d_text, n); };
-            u64 nr[3] = {0, 0, 0};
-            bfq_repair_stats S;
-            repair_core(c, src, O, false, sink, nr, &S);
-            bfq_phase("d2h_write");
-            bfq_write_wait(c);
-            if (!F.finish(S.out_len, 3)) throw BfqError{BFQ_E_IO, "cannot size the output files"};
-            for (int k = 0; k < 3; k++) out_len[k] = S.out_len[k];
-            if (n_reads) for (int k = 0; k < 3; k++) n_reads[k] = nr[k];
-            if (stats) *stats = S;
-        } catch (...) {
-            F.fail(c, 3);
-            throw;
-        }
+            pr_texts_fd(text_fd, src);
+            repair_core(c, src, O, false, sink, nr, S);
+        });
     });
 }
 

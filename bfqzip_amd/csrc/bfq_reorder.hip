@@ -210,11 +210,7 @@ static int ro_run_mem(bfq_ctx *c, const char *what, const bfq_text_part *parts, 
             sink.cap[p] = cap[p];
         }
         const BfqTextPlan plan = ro_plan(c, src, nparts);
-        sink.put = [&](int p, const u8 *d_text, u64 len) {
-            bfq_phase("d2h_write");
-            bfq_download(c, h_out[p], d_text, len);
-            bfq_phase("gpu");
-        };
+        sink.put = [&](int p, const u8 *d_text, u64 len) { bfq_download_phase(c, h_out[p], d_text, len); };
         uint64_t N = 0;
         reorder_core(c, src, nparts, order(), sink, plan, &N);
         if (finish) finish(N);
@@ -224,10 +220,10 @@ static int ro_run_mem(bfq_ctx *c, const char *what, const bfq_text_part *parts, 
 }
 
 // open files in, open files out: the body of bfq_fastq_reorder_fd / _keep_fd / bfq_fastq_unreorder_fd.  queue(N) may add
-// background writes of its own after the texts'; failed() cleans up what it wrote.
+// background writes of its own after the texts', to extra_fd (< 0: none), and returns that file's length: it is a third
+// member of the outputs, never mapped, and left empty with them.
 static int ro_run_fd(bfq_ctx *c, const char *what, const int *in_fd, const uint64_t *in_len, int nparts, const int *out_fd, uint64_t *out_len,
-                     uint64_t *n_reads, const std::function<RoOrder()> &order, const std::function<void(u64)> &queue,
-                     const std::function<void()> &failed)
+                     uint64_t *n_reads, const std::function<RoOrder()> &order, int extra_fd = -1, const std::function<u64(u64)> &queue = nullptr)
 {
     if (out_len) for (int p = 0; p < nparts && p < RO_MAX_MATES; p++) out_len[p] = 0;
     if (n_reads) *n_reads = 0;
@@ -235,39 +231,25 @@ static int ro_run_fd(bfq_ctx *c, const char *what, const int *in_fd, const uint6
         if (!in_fd || !in_len || !out_fd || nparts < 1 || nparts > RO_MAX_MATES) throw BfqError{BFQ_E_ARG, std::string(what) + ": 1 or 2 input and output files"};
         for (int p = 0; p < nparts; p++)
             if (in_fd[p] < 0 || out_fd[p] < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
-        OutFile of[RO_MAX_MATES];
-        int opened = 0;
-        try {
-            TextIn src[RO_MAX_MATES];
-            for (int p = 0; p < nparts; p++) { src[p].ref = HostRef::file(in_fd[p]); src[p].len = in_len[p]; }
-            const BfqTextPlan plan = ro_plan(c, src, nparts);
-            const u64 tl[RO_MAX_MATES] = {plan.t[0].len, plan.t[1].len};
-            const RoOrder ord = order();
-            // mapped to their final length and pre-faulted beside the upload
-            for (int p = 0; p < nparts; p++) { of[p].open(out_fd[p], tl[p] + 4096, tl[p]); opened = p + 1; }
-            c->call.writeHint = (size_t)(tl[0] + tl[1]);
-            RoSink sink;
-            sink.put = [&](int p, const u8 *d_text, u64 len) { bfq_write_async(c, of[p].at(0), d_text, len); };
-            uint64_t N = 0;
-            reorder_core(c, src, nparts, ord, sink, plan, &N);
-            if (queue) queue(N);
-            bfq_phase("d2h_write");
-            bfq_write_wait(c);
-            opened = 0;
-            bool ok = true;
-            for (int p = 0; p < nparts; p++) ok = of[p].close(tl[p]) && ok;
-            if (!ok) throw BfqError{BFQ_E_IO, "cannot size the output files"};
-            if (n_reads) *n_reads = N;
-            if (out_len) for (int p = 0; p < nparts; p++) out_len[p] = tl[p];
-        } catch (...) {
-            if (opened) { try { bfq_write_wait(c); } catch (...) {} }
-            for (int p = 0; p < nparts; p++) {
-                if (p >= opened && !of[p].m && of[p].fd < 0) { of[p].fd = out_fd[p]; of[p].m = bfq_outmap_take(out_fd[p], 0); }   // (a mapping the caller registered goes with the file's contents)
-                of[p].close(0);
-            }
-            if (failed) failed();
-            throw;
-        }
+        const int fds[RO_MAX_MATES + 1] = {out_fd[0], nparts > 1 ? out_fd[1] : -1, extra_fd};
+        OutFiles F(fds, RO_MAX_MATES + 1, [c] { bfq_write_wait(c); });
+        TextIn src[RO_MAX_MATES];
+        for (int p = 0; p < nparts; p++) { src[p].ref = HostRef::file(in_fd[p]); src[p].len = in_len[p]; }
+        const BfqTextPlan plan = ro_plan(c, src, nparts);
+        u64 fin[RO_MAX_MATES + 1] = {plan.t[0].len, plan.t[1].len, 0};
+        const RoOrder ord = order();
+        // mapped to their final length and pre-faulted beside the upload
+        for (int p = 0; p < nparts; p++) F.open(p, fin[p] + 4096, fin[p]);
+        c->call.writeHint = (size_t)(fin[0] + fin[1]);
+        RoSink sink;
+        sink.put = [&](int p, const u8 *d_text, u64 len) { bfq_write_async(c, F.at(p, 0), d_text, len); };
+        uint64_t N = 0;
+        reorder_core(c, src, nparts, ord, sink, plan, &N);
+        if (queue) fin[RO_MAX_MATES] = queue(N);
+        bfq_phase("d2h_write");
+        F.commit(fin);
+        if (n_reads) *n_reads = N;
+        if (out_len) for (int p = 0; p < nparts; p++) out_len[p] = fin[p];
     });
 }
 
@@ -282,7 +264,7 @@ extern "C" int bfq_fastq_reorder_fd(bfq_ctx *c, const int *in_fd, const uint64_t
                                     const int *out_fd, uint64_t *out_len, uint64_t *n_reads)
 {
     return ro_run_fd(c, "bfq_fastq_reorder_fd", in_fd, in_len, nparts, out_fd, out_len, n_reads,
-                     [&] { return ro_sorted_order(c, opts, nparts, nullptr); }, nullptr, nullptr);
+                     [&] { return ro_sorted_order(c, opts, nparts, nullptr); });
 }
 
 // ---- the permutation kept: the same calls, and the BFQPERM1 container of what they did --------------------------------------
@@ -323,16 +305,16 @@ extern "C" int bfq_fastq_reorder_keep_fd(bfq_ctx *c, const int *in_fd, const uin
                                  if (perm_fd < 0) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
                                  return ro_sorted_order(c, opts, nparts, nullptr, &packed, ~0ull);
                              },
-                             [&](u64 N) {
+                             perm_fd, [&](u64 N) {
                                  const u64 nw = bfq_perm_words(N, bfq_perm_width(N));
                                  u8 hdr[BFQ_PERM_HDR];
                                  ro_put_header(hdr, N, opts);
                                  total = BFQ_PERM_HDR + 8 * nw;
-                                 if (ftruncate(perm_fd, (off_t)total) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, "cannot size the permutation file"};
+                                 bfq_fd_size(perm_fd, total, "cannot size the permutation file");
                                  if (pwrite(perm_fd, hdr, BFQ_PERM_HDR, 0) != BFQ_PERM_HDR) throw BfqError{BFQ_E_IO, "cannot write the permutation file"};
                                  if (nw) bfq_write_async(c, HostRef::file(perm_fd, BFQ_PERM_HDR), packed, 8 * nw);
-                             },
-                             [&] { if (perm_fd >= 0) (void)!ftruncate(perm_fd, 0); });
+                                 return total;
+                             });
     if (rc == BFQ_OK && permz_len) *permz_len = total;
     return rc;
 }
@@ -367,5 +349,5 @@ extern "C" int bfq_fastq_unreorder_fd(bfq_ctx *c, const int *in_fd, const uint64
 {
     RoMap pm;
     return ro_run_fd(c, "bfq_fastq_unreorder_fd", in_fd, in_len, nparts, out_fd, out_len, n_reads,
-                     [&] { return ro_inverse_order(c, pm.open(perm_fd, permz_len), permz_len); }, nullptr, nullptr);
+                     [&] { return ro_inverse_order(c, pm.open(perm_fd, permz_len), permz_len); });
 }

@@ -543,38 +543,24 @@ static int rs_run_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64
         const RsSrc permz{ordered ? mP.open(perm_fd, permz_len) : nullptr, ordered ? permz_len : 0};
         const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
         const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
-        OutFile of;
-        bool opened = false;
-        try {
-            RsPlan P;
-            rs_plan(dna, qs, hdr, haveHdr, P);
-            // mapped to the bound; what is certain of it (the bases, the qualities and their newlines) is pre-faulted beside
-            // the upload and the decoding
-            of.open(out_fd, P.textBound + 4096, P.rawD + P.rawQ);
-            opened = true;
-            RsSink sink;
-            sink.sized = [&](u64 len) {
-                if (of.m && len > bfq_outmap_len(of.m)) throw BfqError{BFQ_E_IO, "output mapping smaller than the FASTQ text"};
-                if (of.m) bfq_outmap_extend(of.m, len);
-            };
-            sink.put = [&](const u8 *d_text, u64 len) {
-                bfq_write_async(c, of.at(0), d_text, len);
-                c->sync();
-                bfq_phase("d2h_write");
-                bfq_write_wait(c);
-            };
-            uint64_t ol = 0;
-            restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads, ordered ? &permz : nullptr);
-            if (out_len) *out_len = ol;
-            opened = false;
-            if (!of.close(ol)) throw BfqError{BFQ_E_IO, "cannot size the output file"};
-        } catch (...) {
-            if (opened) { try { bfq_write_wait(c); } catch (...) {} }
-            else { of.fd = out_fd; of.m = bfq_outmap_take(out_fd, 0); }   // (a mapping the caller registered goes with the file's contents)
-            of.close(0);
-            if (out_len) *out_len = 0;
-            throw;
-        }
+        OutFiles F(out_fd, [c] { bfq_write_wait(c); });
+        RsPlan P;
+        rs_plan(dna, qs, hdr, haveHdr, P);
+        // mapped to the bound; what is certain of it (the bases, the qualities and their newlines) is pre-faulted beside
+        // the upload and the decoding
+        F.open(0, P.textBound + 4096, P.rawD + P.rawQ);
+        RsSink sink;
+        sink.sized = [&](u64 len) { F.extend(0, len); };
+        sink.put = [&](const u8 *d_text, u64 len) {
+            bfq_write_async(c, F.at(0, 0), d_text, len);
+            c->sync();
+            bfq_phase("d2h_write");
+            bfq_write_wait(c);
+        };
+        uint64_t ol = 0;
+        restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads, ordered ? &permz : nullptr);
+        F.commit(&ol);
+        if (out_len) *out_len = ol;
     });
 }
 
@@ -611,23 +597,17 @@ extern "C" int bfq_fastq_restore_bgzf_fd(bfq_ctx *c, int dna_fd, uint64_t dna_le
         const RsSrc permz{ordered ? mP.open(perm_fd, permz_len) : nullptr, ordered ? permz_len : 0};
         const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
         const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
-        try {
-            u64 zl = 0;
-            RsSink sink;
-            sink.extraWs = [&](u64 bound) { return bfq_deflate_need(c, bound, false, 0); };
-            sink.put = [&](const u8 *d_text, u64 len) { zl = bfq_deflate_core(c, d_text, HostRef{}, len, level, HostRef::file(out_fd, 0), true, 0); };
-            uint64_t ol = 0;
-            restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads, ordered ? &permz : nullptr);
-            if (ftruncate(out_fd, (off_t)zl) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, "cannot size the output file"};
-            if (out_len) *out_len = zl;
-            if (raw_len) *raw_len = ol;
-        } catch (...) {
-            if (ftruncate(out_fd, 0) != 0) {}
-            if (out_len) *out_len = 0;
-            if (raw_len) *raw_len = 0;
-            if (n_reads) *n_reads = 0;
-            throw;
-        }
+        OutFiles F(out_fd, [c] { bfq_write_wait(c); });         // never mapped: the deflated members go through the descriptor
+        u64 zl = 0;
+        RsSink sink;
+        sink.extraWs = [&](u64 bound) { return bfq_deflate_need(c, bound, false, 0); };
+        sink.put = [&](const u8 *d_text, u64 len) { zl = bfq_deflate_core(c, d_text, HostRef{}, len, level, F.at(0, 0), true, 0); };
+        uint64_t ol = 0, nr = 0;
+        restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, &nr, ordered ? &permz : nullptr);
+        F.commit(&zl);
+        if (out_len) *out_len = zl;
+        if (raw_len) *raw_len = ol;
+        if (n_reads) *n_reads = nr;
     });
 }
 
@@ -649,22 +629,16 @@ extern "C" int bfq_fastq_restore_bam_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len
         const RsSrc permz{ordered ? mP.open(perm_fd, permz_len) : nullptr, ordered ? permz_len : 0};
         const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
         const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
-        try {
-            u64 zl = 0;
-            bfq_ubam_stats S{};
-            RsSink sink;
-            sink.extraWs = [&](u64 bound) { return bfq_ubam_held_need(c, bound, opts); };
-            sink.put = [&](const u8 *d_text, u64 len) { zl = bfq_ubam_held(c, d_text, len, opts, HostRef::file(out_fd, 0), &S); };
-            restore_core(c, dna, qs, hdr, haveHdr, sink, nullptr, nullptr, ordered ? &permz : nullptr);
-            if (ftruncate(out_fd, (off_t)zl) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, "cannot size the output file"};
-            if (out_len) *out_len = zl;
-            if (stats) *stats = S;
-        } catch (...) {
-            if (ftruncate(out_fd, 0) != 0) {}
-            if (out_len) *out_len = 0;
-            if (stats) *stats = bfq_ubam_stats{};
-            throw;
-        }
+        OutFiles F(out_fd, [c] { bfq_write_wait(c); });         // never mapped, as above
+        u64 zl = 0;
+        bfq_ubam_stats S{};
+        RsSink sink;
+        sink.extraWs = [&](u64 bound) { return bfq_ubam_held_need(c, bound, opts); };
+        sink.put = [&](const u8 *d_text, u64 len) { zl = bfq_ubam_held(c, d_text, len, opts, F.at(0, 0), &S); };
+        restore_core(c, dna, qs, hdr, haveHdr, sink, nullptr, nullptr, ordered ? &permz : nullptr);
+        F.commit(&zl);
+        if (out_len) *out_len = zl;
+        if (stats) *stats = S;
     });
 }
 
@@ -880,43 +854,28 @@ extern "C" int bfq_fastq_restore_grouped_fd(bfq_ctx *c, int dna_fd, uint64_t dna
         RsMap mD, mQ, mH;
         const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
         const RsSrc hdr{haveHdr ? mH.open(hdr_fd, hdr_len) : nullptr, haveHdr ? hdr_len : 0};
-        OutFile of;
-        bool opened = false;
-        try {
-            const std::vector<RsGroup> G = rs_groups(dna, qs, hdr, haveHdr);
-            rs_range(G.size(), first, &count);
-            u64 bound = 0, certain = 0;
-            for (u64 k = first; k < first + count; k++) { bound += G[k].g.text_bound; certain += 2 * G[k].g.raw_stream; }
-            of.open(out_fd, bound + 4096, certain);
-            opened = true;
-            c->call.writeHint = (size_t)bound;
-            RsGroupSink sink;
-            sink.sized = [&](u64 len) {
-                if (of.m && len > bfq_outmap_len(of.m)) throw BfqError{BFQ_E_IO, "output mapping smaller than the FASTQ text"};
-                if (of.m) bfq_outmap_extend(of.m, len);
-            };
-            // the background writers know one wait, for everything queued: it is made before a text is queued, so that the
-            // text before it travels beside the decoding, the index and the formatting of this one
-            sink.put = [&](const u8 *d_text, u64 off, u64 len, int) {
-                bfq_phase("d2h_write");
-                bfq_write_wait(c);
-                bfq_write_async(c, of.at(off), d_text, len);
-            };
-            sink.wait = [&](int) {};
-            uint64_t ol = 0;
-            restore_grouped_core(c, dna, qs, hdr, haveHdr, G, first, count, sink, &ol, n_reads);
+        OutFiles F(out_fd, [c] { bfq_write_wait(c); });
+        const std::vector<RsGroup> G = rs_groups(dna, qs, hdr, haveHdr);
+        rs_range(G.size(), first, &count);
+        u64 bound = 0, certain = 0;
+        for (u64 k = first; k < first + count; k++) { bound += G[k].g.text_bound; certain += 2 * G[k].g.raw_stream; }
+        F.open(0, bound + 4096, certain);
+        c->call.writeHint = (size_t)bound;
+        RsGroupSink sink;
+        sink.sized = [&](u64 len) { F.extend(0, len); };
+        // the background writers know one wait, for everything queued: it is made before a text is queued, so that the
+        // text before it travels beside the decoding, the index and the formatting of this one
+        sink.put = [&](const u8 *d_text, u64 off, u64 len, int) {
             bfq_phase("d2h_write");
             bfq_write_wait(c);
-            if (out_len) *out_len = ol;
-            opened = false;
-            if (!of.close(ol)) throw BfqError{BFQ_E_IO, "cannot size the output file"};
-        } catch (...) {
-            if (opened) { try { bfq_write_wait(c); } catch (...) {} }
-            else { of.fd = out_fd; of.m = bfq_outmap_take(out_fd, 0); }   // (a mapping the caller registered goes with the file's contents)
-            of.close(0);
-            if (out_len) *out_len = 0;
-            if (n_reads) *n_reads = 0;
-            throw;
-        }
+            bfq_write_async(c, F.at(0, off), d_text, len);
+        };
+        sink.wait = [&](int) {};
+        uint64_t ol = 0, nr = 0;
+        restore_grouped_core(c, dna, qs, hdr, haveHdr, G, first, count, sink, &ol, &nr);
+        bfq_phase("d2h_write");
+        F.commit(&ol);
+        if (out_len) *out_len = ol;
+        if (n_reads) *n_reads = nr;
     });
 }

@@ -271,7 +271,7 @@ extern "C" int bfq_fastq_to_bam_fd(bfq_ctx *c, const int text_fd[3], const bfq_u
         bfq_texts_map(text_fd, text, X);
         try {
             ubam_compressed(c, X, opts, HostRef::file(out_fd, 0), ~0ull, out_len, stats);
-            if (ftruncate(out_fd, (off_t)*out_len) != 0 && errno != EINVAL) throw BfqError{BFQ_E_IO, std::string("cannot size the output file: ") + strerror(errno)};
+            bfq_fd_size(out_fd, *out_len, "cannot size the output file: ", true);
         } catch (...) {
             if (ftruncate(out_fd, 0) != 0) {}
             *out_len = 0;

@@ -178,6 +178,38 @@ def test_refusals(engine, tmp_path):
         assert got == mwant and st.as_dict() == mst, name
 
 
+def test_registered_outputs_of_a_refused_split_end_empty(engine, tmp_path):
+    """outputs a tool registered (bfq_output_prefault) before a call that is refused before their lengths are known: the
+    mappings go with the call, the files end empty and not at the registered 8192 bytes; registered again, a good call
+    picks the mappings up and cuts the files to their lengths"""
+    import ctypes as C
+    from bfqzip_amd import _lib
+    L = _lib.lib()
+    recs = [P.rec(b"@r%d/%d" % (k // 2, k % 2 + 1), b"ACGT"[:k % 3 + 2]) for k in range(4)]
+    fds = [os.open(str(tmp_path / ("g%d.fq" % k)), os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) for k in range(3)]
+    try:
+        def call(text):
+            for fd in fds:
+                assert L.bfq_output_prefault(fd, 8192, 4096) == 0 and os.fstat(fd).st_size == 8192
+            src = os.open(put(tmp_path, "gin.fq", text), os.O_RDONLY)
+            try:
+                O, st, ol, nr = api.pairs_opts(), _lib.PairsStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+                rc = L.bfq_fastq_deinterleave_fd(engine.h, src, len(text), C.byref(O), (C.c_int * 3)(*fds), ol, nr, C.byref(st))
+            finally:
+                os.close(src)
+            return rc, [os.pread(fd, 8192, 0) for fd in fds]
+        with pytest.raises(P.Refused) as want:
+            P.split(b"".join(recs[:3]))
+        rc, got = call(b"".join(recs[:3]))
+        assert rc == want.value.code and L.bfq_last_error(engine.h).decode().endswith(want.value.msg) and "odd" in want.value.msg
+        assert got == [b"", b"", b""]
+        rc, got = call(b"".join(recs))
+        assert rc == 0 and got == P.split(b"".join(recs))[0] == [b"", recs[0] + recs[2], recs[1] + recs[3]]
+    finally:
+        for fd in fds:
+            os.close(fd)
+
+
 @pytest.mark.parametrize("name", ("lanes", "orphans-singles-first"))
 def test_capacity_one_byte_short(engine, name):
     text, opts = P.split_cases()[name]
