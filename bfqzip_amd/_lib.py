@@ -33,6 +33,7 @@ SYMBOLS = [
     "bfq_fastq_restore_ordered", "bfq_fastq_restore_ordered_fd",
     "bfq_fastq_restore_groups", "bfq_stream_members", "bfq_fastq_restore_grouped", "bfq_fastq_restore_grouped_fd",
     "bfq_fastq_compare", "bfq_fastq_compare_fd",
+    "bfq_fastq_kmers", "bfq_fastq_kmers_fd", "bfq_fastq_kmers_host", "bfq_kmers_host_error", "bfq_kmers_geometry",
     "bfq_bgzf_probe", "bfq_bgzf_index", "bfq_bgzf_inflate", "bfq_bgzf_inflate_device", "bfq_bgzf_inflate_fd",
     "bfq_bgzf_deflate_bound", "bfq_bgzf_deflate_host", "bfq_bgzf_deflate", "bfq_bgzf_deflate_device", "bfq_bgzf_deflate_fd",
     "bfq_fastq_restore_bgzf_fd",
@@ -246,6 +247,25 @@ class CompareReport(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in COMPARE_SCALARS] + [(k, C.c_uint64 * n) for k, n in COMPARE_ARRAYS] + [("reserved", C.c_uint64 * 8)]
 
 
+class KmerOpts(C.Structure):
+    """bfq_kmer_opts: k (8..31), solid (2..15), canonical, reserved (must be 0), part_records (0: what the memory allows)"""
+    _fields_ = [(k, C.c_uint32) for k in ("k", "solid", "canonical", "reserved")] + [("part_records", C.c_uint64)]
+
+
+class KmerEntry(C.Structure):
+    _fields_ = [("kmer", C.c_uint64), ("count_a", C.c_uint32), ("count_b", C.c_uint32)]
+
+
+KMER_SCALARS = ("k", "solid", "canonical", "n_partitions", "n_reads_a", "n_reads_b", "reads_short_a", "reads_short_b", "windows_a", "windows_b",
+                "windows_skipped_a", "windows_skipped_b", "distinct_a", "distinct_b", "distinct_both", "only_a", "only_b", "occ_only_a",
+                "occ_only_b", "distinct_changed", "n_listed")
+KMER_ARRAYS = (("hist_a", 256), ("hist_b", 256), ("joint", 16 * 16), ("trans", 3 * 3))
+
+
+class KmerReport(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in KMER_SCALARS] + [(k, C.c_uint64 * n) for k, n in KMER_ARRAYS] + [("reserved", C.c_uint64 * 8)]
+
+
 class FastqJob(C.Structure):
     _fields_ = [("parts", C.POINTER(TextPart)), ("nparts", C.c_int32), ("keep_headers", C.c_int32),
                 ("out_fastq", C.c_void_p), ("cap_fastq", C.c_uint64),
@@ -386,6 +406,13 @@ def lib():
         L.bfq_stream_compress_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_fastq_compare.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(TextPart), C.c_int, vp, u64, C.POINTER(CompareReport), vp, u64]
         L.bfq_fastq_compare_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.POINTER(CompareReport), vp, u64]
+        pko, pkr = C.POINTER(KmerOpts), C.POINTER(KmerReport)
+        L.bfq_fastq_kmers.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(TextPart), C.c_int, pko, pkr, vp, u64]
+        L.bfq_fastq_kmers_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, pko, pkr, vp, u64]
+        L.bfq_fastq_kmers_host.argtypes = [vp, u64, vp, u64, pko, pkr, vp, u64]
+        L.bfq_kmers_host_error.restype = C.c_char_p
+        L.bfq_kmers_host_error.argtypes = []
+        L.bfq_kmers_geometry.argtypes = [pu64, pu64, pu64]
         L.bfq_bgzf_probe.argtypes = [vp, u64]
         L.bfq_bgzf_index.argtypes = [vp, u64, C.POINTER(BgzfMember), u64, pu64, pu64, pu64]
         L.bfq_bgzf_inflate.argtypes = [vp, vp, u64, vp, u64, pu64]

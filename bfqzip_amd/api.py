@@ -154,6 +154,70 @@ class CompareReport:
         return d
 
 
+KMER_DTYPE = np.dtype([("kmer", "<u8"), ("count_a", "<u4"), ("count_b", "<u4")])
+
+
+class KmerReport:
+    """What Engine.fastq_kmers found (bfq_kmer_report): the scalar fields as ints, hist_a / hist_b (256 bins), joint (16 x 16,
+    [min(cA, 15)][min(cB, 15)]) and trans (3 x 3, [class in A][class in B], classes absent / weak / solid) as uint64 arrays,
+    .listed the listed k-mers as a structured array (KMER_DTYPE, ascending), .solid_lost = trans[2][0], .unchanged = no k-mer's
+    count differs."""
+
+    def __init__(self, raw, listed):
+        for k in _lib.KMER_SCALARS:
+            setattr(self, k, int(getattr(raw, k)))
+        for k, n in _lib.KMER_ARRAYS:
+            setattr(self, k, np.array(getattr(raw, k), np.uint64))
+        self.joint = self.joint.reshape(16, 16)
+        self.trans = self.trans.reshape(3, 3)
+        self.listed = listed
+
+    @property
+    def solid_lost(self):
+        return int(self.trans[2, 0])
+
+    @property
+    def unchanged(self):
+        return self.distinct_changed == 0
+
+    def kmer_strings(self):
+        """The listed k-mers as ACGT strings."""
+        return ["".join("ACGT"[(int(v) >> (2 * (self.k - 1 - i))) & 3] for i in range(self.k)) for v in self.listed["kmer"]]
+
+    def as_dict(self):
+        """Plain ints and lists (JSON): every field of the report, and the list as [k-mer string, count_a, count_b]."""
+        d = {k: getattr(self, k) for k in _lib.KMER_SCALARS}
+        for k, _ in _lib.KMER_ARRAYS:
+            d[k] = [int(v) for v in getattr(self, k).reshape(-1)]
+        d["list"] = [[s, int(e["count_a"]), int(e["count_b"])] for s, e in zip(self.kmer_strings(), self.listed)]
+        return d
+
+
+def _kmer_call(call, k, solid, canonical, max_list, list_out, part_records):
+    O = _lib.KmerOpts(k=k, solid=solid, canonical=1 if canonical else 0, reserved=0, part_records=int(part_records))
+    buf = list_out if list_out is not None else np.zeros(max(int(max_list), 1), KMER_DTYPE)
+    assert buf.dtype == KMER_DTYPE and len(buf) >= max_list
+    raw = _lib.KmerReport()
+    call(C.byref(O), C.byref(raw), _ptr(buf) if max_list else None, int(max_list))
+    return KmerReport(raw, buf[:min(int(raw.n_listed), int(max_list))])
+
+
+def fastq_kmers_host(a, b=None, k=21, solid=3, canonical=True, max_list=0, list_out=None, part_records=0):
+    """bfq_fastq_kmers_host: the k-mer report of plain text a (against b) on one thread of the host, no GPU: a KmerReport.
+    It states the algorithm; nothing falls back to it."""
+    L = _lib.lib()
+    a = _u8(a)
+    b = _u8(b) if b is not None else None
+    pad = np.zeros(1, np.uint8)
+
+    def call(po, pr, pl, cap):
+        rc = L.bfq_fastq_kmers_host(_ptr(a if len(a) else pad), len(a), _ptr(b if len(b) else pad) if b is not None else None,
+                                    len(b) if b is not None else 0, po, pr, pl, cap)
+        if rc:
+            raise BfqError(rc, L.bfq_kmers_host_error().decode())
+    return _kmer_call(call, k, solid, canonical, max_list, list_out, part_records)
+
+
 def restore_groups(dna, qs, hdr=None):
     """The group plan of an archive (bfq_fastq_restore_groups: container headers only, no GPU): a list of dicts, one per
     group that decodes on its own -- a block of a sharded run -- with the keys of bfq_restore_group (dna_off, dna_len, qs_off,
@@ -1569,6 +1633,43 @@ class Engine:
             for fd in fds:
                 if fd >= 0:
                     os.close(fd)
+
+    # ---- which k-mers a run removed, kept and created (bfq_fastq_kmers)
+    def fastq_kmers(self, a_parts, b_parts=None, k=21, solid=3, canonical=True, max_list=0, list_out=None, part_records=0):
+        """The k-mer spectrum of A, or of A ("before") against B ("after"), each a list of 1..4 texts taken as one: a
+        KmerReport.  Nothing is paired: the order of the reads does not matter.  max_list: list that many k-mers at most
+        that went solid -> absent or absent -> solid (.listed).  list_out: a KMER_DTYPE array of at least max_list entries to
+        fill.  part_records: the records of a value range at most (0: what the memory allows).  Malformed text or options
+        out of range raise BfqError and leave list_out untouched."""
+        pa, pb = [_u8(p) for p in a_parts], [_u8(p) for p in (b_parts or [])]
+
+        def parts(arrs):
+            tp = (_lib.TextPart * max(len(arrs), 1))()
+            for i, x in enumerate(arrs):
+                tp[i].data = x.ctypes.data if len(x) else None
+                tp[i].len = len(x)
+            return tp
+        return _kmer_call(lambda po, pr, pl, cap: self._ck(self.L.bfq_fastq_kmers(self.h, parts(pa), len(pa), parts(pb) if pb else None, len(pb),
+                                                                                   po, pr, pl, cap)), k, solid, canonical, max_list, list_out, part_records)
+
+    def fastq_kmers_files(self, a_path, b_path=None, k=21, solid=3, canonical=True, max_list=0, list_out=None, part_records=0):
+        """fastq_kmers on named files (bfq_fastq_kmers_fd)."""
+        import os
+        fds = []
+        try:
+            for p in (a_path, b_path):
+                fds.append(os.open(p, os.O_RDONLY) if p is not None else -1)
+            size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
+            return _kmer_call(lambda po, pr, pl, cap: self._ck(self.L.bfq_fastq_kmers_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), po, pr, pl, cap)),
+                              k, solid, canonical, max_list, list_out, part_records)
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+    @staticmethod
+    def fastq_kmers_host(a, b=None, k=21, solid=3, canonical=True, max_list=0, list_out=None, part_records=0):
+        return fastq_kmers_host(a, b, k=k, solid=solid, canonical=canonical, max_list=max_list, list_out=list_out, part_records=part_records)
 
     # ---- the permutation as a container (host only)
     @staticmethod

@@ -26,7 +26,8 @@ const char *const BFQ_KERNEL_NAMES[K_NUM] = {
     "k_cluster", "k_invert_count", "k_invert", "k_synth", "k_fastq", "k_bfs", "k_codec", "misc",
     "k_restore_index", "k_fq_format_lines", "k_reorder_keys", "k_reorder_gather",
     "k_fq_format_ordered", "k_perm_pack", "k_perm_invert", "k_posbin_l1", "k_posbin_l2", "k_posbin_apply", "k_posbin_check",
-    "k_cmp_check", "k_cmp_compare", "k_cmp_emit", "k_bgzf_inflate", "k_bgzf_deflate", "k_ubam_size", "k_ubam_write", "k_pairs_cmp", "k_pairs_move"};
+    "k_cmp_check", "k_cmp_compare", "k_cmp_emit", "k_bgzf_inflate", "k_bgzf_deflate", "k_ubam_size", "k_ubam_write", "k_pairs_cmp", "k_pairs_move",
+    "k_km_hist", "k_km_count", "k_km_emit", "k_km_rekey", "k_km_seg", "k_km_stats"};
 
 static thread_local std::string g_createErr;
 

@@ -32,7 +32,8 @@ enum BfqKernel {
     K_REFINE_WAVE, K_REFINE_BIG, K_EMIT, K_RANK_BUILD, K_RANK_FINAL, K_LCP_FLAGS, K_CLUSTER,
     K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER,
     K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_POSBIN_L1, K_POSBIN_L2, K_POSBIN_APPLY, K_POSBIN_CHECK,
-    K_CMP_CHECK, K_CMP_COMPARE, K_CMP_EMIT, K_BGZF, K_DEFLATE, K_UBAM_SIZE, K_UBAM_WRITE, K_PAIRS_CMP, K_PAIRS_MOVE, K_NUM
+    K_CMP_CHECK, K_CMP_COMPARE, K_CMP_EMIT, K_BGZF, K_DEFLATE, K_UBAM_SIZE, K_UBAM_WRITE, K_PAIRS_CMP, K_PAIRS_MOVE,
+    K_KM_HIST, K_KM_COUNT, K_KM_EMIT, K_KM_REKEY, K_KM_SEG, K_KM_STATS, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -527,3 +528,13 @@ void bfq_compare_check(bfq_ctx *c, CmpText A, CmpText B, const u64 *inv, u64 N, 
 void bfq_compare_pass(bfq_ctx *c, CmpText A, CmpText B, const u64 *inv, u64 N, u64 total, bfq_compare_report *d_rep, u32 *readDiffs);
 void bfq_compare_emit(bfq_ctx *c, CmpText A, CmpText B, const u64 *inv, u64 N, u64 total, const u32 *readDiffs, const u64 *diffOff, u64 cap,
                       bfq_compare_diff *d_out);
+
+// the k-mer spectrum of one or two FASTQ texts (k_kmers.hip; bfq_kmers.hip drives them; the constants: bfq_kmers.h).  A text of
+// the call: its bytes, its record index, its records.  bases: the text's sequence bytes (for the profile's byte counts).
+struct KmText { const u8 *buf; const FqRec *rec; u64 N; };
+void bfq_kmers_hist(bfq_ctx *c, const KmText &T, u32 k, u32 canonical, u64 bases, u64 *d_hist, u64 *d_scal);   // d_hist[4096] and d_scal[3] (short reads, valid, skipped) are added to
+void bfq_kmers_count(bfq_ctx *c, const KmText &T, u32 k, u32 canonical, u32 binLo, u32 binHi, u64 bases, u32 *cnt);
+void bfq_kmers_emit(bfq_ctx *c, const KmText &T, u32 k, u32 canonical, u32 binLo, u32 binHi, u32 src, u64 bases, u64 records, const u64 *off, SortRec out);
+SortRec bfq_kmers_sort(bfq_ctx *c, SortRec a, SortRec b, u64 n, u32 k);   // the records start in a; returns the buffer that holds the result
+size_t bfq_kmers_seg_bytes(u64 n);                                        // arena bytes of bfq_kmers_runs
+void bfq_kmers_runs(bfq_ctx *c, SortRec S, u64 n, u32 k, u32 solid, u64 *heads, struct bfq_kmer_report *d_rep, struct bfq_kmer_entry *d_list, u64 capList);

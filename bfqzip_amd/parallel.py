@@ -399,6 +399,27 @@ def write_reports(eng, comm, before, outputs, log=None):
     return paths
 
 
+def write_kmer_reports(eng, comm, before, outputs, k, log=None):
+    """--report-kmers K after the run: rank 0 counts the k-mers of every merged FASTQ output against the input it came from
+    (eng.fastq_kmers_files: nothing is paired, so any order of the reads will do and no permutation file is read) and writes
+    `<output fastq>.kmers.json` (the keys of KmerReport.as_dict()), one per mate, beside what --report writes.  Returns the
+    report names."""
+    import json
+    comm.barrier()
+    paths = [o + ".kmers.json" for o in outputs]
+    if comm.rank == 0:
+        for src, o, p in zip(before, outputs, paths):
+            rep = eng.fastq_kmers_files(src, o, k=k)
+            with open(p, "w") as f:
+                json.dump(rep.as_dict(), f)
+                f.write("\n")
+            if log:
+                log(f"k-mers: {o} against {src}: k {k}: {rep.only_a} of {rep.distinct_a} distinct k-mers removed, {rep.only_b} created, "
+                    f"{rep.solid_lost} solid ones lost -> {p}")
+    comm.barrier()
+    return paths
+
+
 KINDS = ("fastq", "dna", "qs", "hdr")
 
 
@@ -764,6 +785,9 @@ def main(argv=None):
     ap.add_argument("--report", action="store_true",
                     help="after the run, compare every merged FASTQ output with the input in the same order on the GPU and write "
                          "<output fastq>.report.json (needs the uncompressed merged FASTQ text: not with --streams-only or --compress)")
+    ap.add_argument("--report-kmers", type=int, default=0, metavar="K",
+                    help="after the run, count the K-mers (8..31) of every merged FASTQ output against the input on the GPU and write "
+                         "<output fastq>.kmers.json: which k-mers the run removed, kept and created (any read order; same limits as --report)")
     ap.add_argument("--restore", action="store_true",
                     help="the way back: the inputs are DNA.bsc QS.bsc [HDR.bsc] of a --compress run, -o OUT.fq the FASTQ file to write; "
                          "group k of the archive (one per block) is restored by rank k mod world")
@@ -884,6 +908,9 @@ def main(argv=None):
         return 1
     if a.m3:
         a.headers = True
+    if a.report_kmers and (not 8 <= a.report_kmers <= 31 or a.restore or ((a.m2 or a.m3) and a.streams_only) or (a.compress and not a.m0 and not a.glob)):
+        print("=== ERROR ===\n--report-kmers K: K is 8..31, and it reads the merged FASTQ text: not with --restore, --streams-only or --compress", file=sys.stderr)
+        return 1
     if a.report and (a.restore or ((a.m2 or a.m3) and a.streams_only) or (a.compress and not a.m0 and not a.glob)):
         print("=== ERROR ===\n--report compares the merged FASTQ text: not with --restore, --streams-only or --compress", file=sys.stderr)
         return 1
@@ -973,6 +1000,8 @@ def main(argv=None):
             log(f"keep-order: the {'containers' if compress else 'raw streams'} stay in run order; pass {perm_path} to bfq_restore -P")
     if a.report:                                                     # against what is in the outputs' order: the originals unless the run reordered for good
         write_reports(eng, comm, original if (perm_path or not a.reorder) else a.input, [n["fastq"] for n in names], log=log)
+    if a.report_kmers:                                               # (the original input always: the order does not matter)
+        write_kmer_reports(eng, comm, original, [n["fastq"] for n in names], a.report_kmers, log=log)
     if a.bam_out:
         comm.barrier()
         failed = None

@@ -611,6 +611,73 @@ int bfq_fastq_compare   (bfq_ctx *c, const bfq_text_part *a, int na, const bfq_t
                          bfq_compare_report *rep, bfq_compare_diff *h_diffs, uint64_t cap_diffs);
 int bfq_fastq_compare_fd(bfq_ctx *c, int a_fd, uint64_t a_len, int b_fd, uint64_t b_len, int perm_fd, uint64_t permz_len,
                          bfq_compare_report *rep, bfq_compare_diff *h_diffs, uint64_t cap_diffs);
+/* ---- which k-mers a run removed, kept and created: the k-mer spectrum of one FASTQ text, or of two side by side (k_kmers.hip,
+ * bfq_kmers.hip; tests/kmers_model.py states it in Python).  bfq_fastq_compare says how much a run touched; this says whether
+ * what it touched was noise: a sequencing error makes up to k k-mers that occur once, a real allele makes k-mers that occur
+ * about as often as the coverage, so a run that does its job removes weak k-mers and loses no solid ones.  Nothing is paired:
+ * the report does not depend on the order of the reads, and the texts may hold different numbers of records.
+ * Inputs: A and B exactly as bfq_fastq_compare* takes them (1..BFQ_MAX_PARTS parts read as one text, a part without its final
+ *   newline gets one, a BGZF part is inflated, four lines per record, a CR before the LF dropped; malformed text: the parser's
+ *   code and message, prefixed "A: " or "B: ").  B may be absent (nb = 0, b_fd < 0, b NULL): every B field is then 0 and the
+ *   call is the spectrum of one file.
+ * Windows: k consecutive bytes of a sequence line; valid when all k are one of A C G T (upper case).  Any other byte breaks
+ *   the windows that hold it: those count in windows_skipped_*.  A read shorter than k has no window and counts in reads_short_*
+ *   (so windows + windows_skipped = the sum of len - k + 1 over the reads of at least k bases).
+ * Coding: A 0, C 1, G 2, T 3, the first base most significant: a window is a 2k-bit integer.  Its k-mer is min(that value, the
+ *   value of its reverse complement); with opts.canonical = 0 the forward value.  Even k is allowed (a palindrome is its own
+ *   reverse complement and counts once per window).  k: 8..31.
+ * Report: with cA / cB the number of windows of A / B whose k-mer is x, over the distinct x of both texts:
+ *   distinct_a (cA > 0), distinct_b, distinct_both, only_a (cB = 0), only_b, occ_only_a (the sum of cA where cB = 0), occ_only_b,
+ *   distinct_changed (cA != cB); hist_a[min(cA, 255)] for cA > 0 and hist_b likewise (bin 0 stays 0); joint[16 * min(cA, 15) +
+ *   min(cB, 15)]; trans[3 * class(cA) + class(cB)] with the classes absent (0), weak (1 .. solid - 1), solid (>= solid), solid =
+ *   opts.solid, 2..15: trans[6], "solid lost", is the number to look at first.  k, solid and canonical are the options as
+ *   taken; n_partitions says in how many value ranges the k-mers were sorted (below).  Every field is a 64-bit integer sum:
+ *   the report is exact and depends neither on the launch geometry nor on the partitioning.
+ * List: the k-mers whose class pair is solid -> absent or absent -> solid, in ascending value, with their counts (saturating
+ *   at 2^32 - 1): n_listed of them exist, the first min(n_listed, cap_list) go to h_list, nothing is written beyond them.
+ *   cap_list = 0 with h_list = NULL is the plain report.
+ * opts (NULL: k 21, solid 3, canonical 1, part_records 0); reserved != 0: BFQ_E_ARG.
+ * How: one pass over the sequence lines where they lie in the staged texts counts the valid windows and their histogram over
+ *   the top 12 bits of the k-mer (4096 bins, A and B together).  The host cuts the bins into ascending ranges -- a bin joins the
+ *   range before it while the range's records stay within part_records (0: what the memory below allows; a range is never
+ *   smaller than one non-empty bin, empty bins belong to nobody) -- and per range: the windows in range are counted per read,
+ *   scanned and emitted as 12-byte sort records, sorted on the whole 2k-bit key by the suffix sort's radix passes (2k <= 40:
+ *   ceil(2k / 8) passes; above: the bits below the top 40 first, one re-keying kernel, then five passes), and the runs of equal
+ *   k-mers are counted.  The ranges ascend, so the sums and the list simply continue from one to the next.
+ * Device memory: the two texts as staged + about 172 bytes of index per read of both (bfq_fastq_index, and 12 bytes for the
+ *   per-read counts and their scan) + 16 bytes per list entry asked for (min(cap_list, the valid windows)) + per record of
+ *   the largest range 2 x 12 bytes for the sort's two buffers, 12 x 256 bytes per radix block and 36 bytes per 2048 records for
+ *   the run counts.  Above ws_cap_mib: the ranges get smaller; when the texts and their index alone, or one bin, do not fit:
+ *   BFQ_E_NOMEM with the size in the message (a bin's records are named).  A range holds less than 2^32 records.
+ * Refusals: k or solid out of range, cap_list without a buffer: BFQ_E_ARG.  On every refusal *rep is zeroed and h_list untouched.
+ *   bfq_fastq_kmers      : host buffers (pinned: direct DMA)
+ *   bfq_fastq_kmers_fd   : open files; b_fd < 0: no B
+ *   bfq_fastq_kmers_host : one thread of the host, plain text only, no context and no GPU: the same report and list.  It
+ *                          states the algorithm and is what the tests compare with; NO entry point falls back to it.  Message:
+ *                          bfq_kmers_host_error() (of the calling thread).
+ *   bfq_kmers_geometry   : introspection: the rows of a workgroup's chunk when the runs of the sorted records are found, the
+ *                          runs of a workgroup's chunk when they are counted and listed, the start positions one lane owns. */
+typedef struct bfq_kmer_opts { uint32_t k, solid, canonical, reserved; uint64_t part_records; } bfq_kmer_opts;   /* 24 bytes */
+typedef struct bfq_kmer_entry { uint64_t kmer; uint32_t count_a, count_b; } bfq_kmer_entry;                      /* 16 bytes */
+typedef struct bfq_kmer_report {
+    uint64_t k, solid, canonical, n_partitions;
+    uint64_t n_reads_a, n_reads_b, reads_short_a, reads_short_b;
+    uint64_t windows_a, windows_b, windows_skipped_a, windows_skipped_b;
+    uint64_t distinct_a, distinct_b, distinct_both, only_a, only_b, occ_only_a, occ_only_b, distinct_changed;
+    uint64_t n_listed;
+    uint64_t hist_a[256], hist_b[256];                     /* distinct k-mers by multiplicity, bin 255: >= 255 */
+    uint64_t joint[16 * 16];                               /* [16 * min(cA, 15) + min(cB, 15)] */
+    uint64_t trans[3 * 3];                                 /* [3 * class in A + class in B] */
+    uint64_t reserved[8];
+} bfq_kmer_report;
+int bfq_fastq_kmers     (bfq_ctx *c, const bfq_text_part *a, int na, const bfq_text_part *b, int nb, const bfq_kmer_opts *opts,
+                         bfq_kmer_report *rep, bfq_kmer_entry *h_list, uint64_t cap_list);
+int bfq_fastq_kmers_fd  (bfq_ctx *c, int a_fd, uint64_t a_len, int b_fd, uint64_t b_len, const bfq_kmer_opts *opts,
+                         bfq_kmer_report *rep, bfq_kmer_entry *h_list, uint64_t cap_list);
+int bfq_fastq_kmers_host(const uint8_t *a, uint64_t a_len, const uint8_t *b, uint64_t b_len, const bfq_kmer_opts *opts,
+                         bfq_kmer_report *rep, bfq_kmer_entry *h_list, uint64_t cap_list);
+const char *bfq_kmers_host_error(void);
+int bfq_kmers_geometry(uint64_t *seg_chunk_rows, uint64_t *run_chunk_runs, uint64_t *lane_starts);
 /* ---- bgzip-compressed input: BGZF inflated on the device (k_bgzf.hip; the format and every bound: csrc/bfq_bgzf.h).
  * A BGZF file (bgzip, htslib, BCL Convert) is a chain of independent gzip members of at most 64 KiB in and out; each states
  * its size in its header ('B','C' subfield) and its CRC32 and raw size (ISIZE) in its trailer, so the place of every
