@@ -21,7 +21,7 @@ SYMBOLS = [
     "bfq_text_count_lines", "bfq_text_nth_newline", "bfq_file_put", "bfq_file_map", "bfq_file_unmap", "bfq_fastq_build_ebwt_fd", "bfq_smooth_invert_fastq_fd",
     "bfq_glob_begin", "bfq_glob_local_text", "bfq_glob_pile_counts", "bfq_glob_init_out", "bfq_glob_run_pile", "bfq_glob_finish",
     "bfq_synth_default", "bfq_synth_total", "bfq_synth_host", "bfq_synth_device", "bfq_synth_fastq",
-    "bfq_posbin_geometry", "bfq_radix_geometry", "bfq_refine_form", "bfq_prof_enable", "bfq_prof_reset", "bfq_prof_count", "bfq_prof_get", "bfq_prof_trace_select", "bfq_prof_trace",
+    "bfq_posbin_geometry", "bfq_posbin_sparse_last", "bfq_radix_geometry", "bfq_refine_form", "bfq_prof_enable", "bfq_prof_reset", "bfq_prof_count", "bfq_prof_get", "bfq_prof_trace_select", "bfq_prof_trace",
     "bfq_stream_bound", "bfq_stream_raw_len", "bfq_stream_compress", "bfq_stream_decompress",
     "bfq_stream_reserve", "bfq_stream_compress_device", "bfq_stream_ebwt_decode",
     "bfq_names_compress", "bfq_names_compress_device",
@@ -486,6 +486,7 @@ def lib():
         L.bfq_fastq_repair_host.argtypes = [C.POINTER(vp), a3, pro, C.POINTER(vp), a3, a3, a3, prs]
         L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
+        L.bfq_posbin_sparse_last.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(u64)]
         L.bfq_radix_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(u64)]
         L.bfq_refine_form.argtypes = [vp]
         L.bfq_prof_enable.argtypes = [vp, C.c_int]

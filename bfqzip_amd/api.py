@@ -1707,6 +1707,12 @@ class Engine:
         return int(self.L.bfq_stream_bound(n))
 
     # ---- profiling
+    def posbin_sparse_last(self):
+        """(polarity, rows_sent) of the last call's position bins: 0 = keep, 1 = const, -1 = every row travelled or none ran."""
+        pol, sent = C.c_int(-1), C.c_uint64(0)
+        self._ck(self.L.bfq_posbin_sparse_last(self.h, C.byref(pol), C.byref(sent)))
+        return int(pol.value), int(sent.value)
+
     def refine_form(self):
         """The refinement's chunk kernel in use: 1 = text words by two loads side by side, 0 = BFQ_REFINE_PIPE=0 (as set_params() read it)."""
         return int(self.L.bfq_refine_form(self.h))

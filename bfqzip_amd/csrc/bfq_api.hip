@@ -305,6 +305,13 @@ extern "C" int bfq_posbin_geometry(uint64_t n_rows, uint64_t *window, int *bin_s
     if (bin_shift) *bin_shift = s;
     return s >= 0 ? BFQ_OK : BFQ_E_ARG;
 }
+extern "C" int bfq_posbin_sparse_last(bfq_ctx *c, int *polarity, uint64_t *rows_sent)
+{
+    if (!c) return BFQ_E_ARG;
+    if (polarity) *polarity = c->pbLastPolarity;
+    if (rows_sent) *rows_sent = c->pbLastSent;
+    return BFQ_OK;
+}
 extern "C" int bfq_radix_geometry(uint64_t n_rows, uint64_t *tile_rows, uint64_t *block_rows)
 {
     if (tile_rows) *tile_rows = BFQ_RS_TILE;
@@ -336,6 +343,8 @@ static void finish_call(bfq_ctx *c, bfq_stats *st = nullptr)
 {
     c->fetchCounters();
     c->profCollect();
+    c->pbLastPolarity = c->h_cnt.pbPolarity ? (int)c->h_cnt.pbPolarity - 1 : -1;
+    c->pbLastSent = c->h_cnt.pbSent;
     check_counters(c);
     if (!st) return;
     const u64 *s = c->h_cnt.stats;
@@ -619,13 +628,15 @@ static void steps34_positions(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, 
 // one LDS placement per window (k_posbin.hip).  Streams 36 bytes per row in coalesced runs where k_lf_build + k_invert
 // fetched one random 64-byte sector per base.  Arena: text + (w1, w2) words kept (8.5 n), flags and edits 3 n, level-1
 // records 8 n -- below the 24 n of the sort buffers that step 1 has just given back (ws_need() is unchanged).
+// By default only the rows that differ from the input (or from the input base with M = 2's constant quality) travel: the
+// caller's input arrays are the last kernel's default (k_posbin.hip, "sparse form"); 36 bytes per row is the upper bound then.
 static size_t posbins_room_needed(u64 n)
 {
     const size_t pb = bfq_posbins_need(n);
     if (pb == ~(size_t)0) return pb;
     return pb + 3 * (n + 64 + 256) + 24 * (n / 256 + 8) + (1u << 20);   // + flags, the two edit arrays, k_cluster's tables
 }
-static void steps34_posbins(bfq_ctx *c, const u64 *d_roff, u8 *d_out_bases, u8 *d_out_quals)
+static void steps34_posbins(bfq_ctx *c, const u8 *d_bases, const u8 *d_quals, const u64 *d_roff, u8 *d_out_bases, u8 *d_out_quals)
 {
     const u64 n = c->n, N = c->N;
     if (!n) return;
@@ -641,7 +652,7 @@ static void steps34_posbins(bfq_ctx *c, const u64 *d_roff, u8 *d_out_bases, u8 *
         bfq_clusters(c, none, c->d_bwt, c->d_qual, in, n, &pm);
         c->release(mk);
     }
-    bfq_posbins(c, const_cast<u64 *>(c->call.d_w12), repl, editQual, n, d_roff, N, c->P.B, d_out_bases, d_out_quals);
+    bfq_posbins(c, const_cast<u64 *>(c->call.d_w12), repl, editQual, n, d_roff, N, c->P.B, d_bases, d_quals, d_out_bases, d_out_quals);
 }
 
 // ---- the whole path under a workspace cap (the counterpart of bfq_ext's pile files, bfq_ext.cpp:190-348, and
@@ -728,7 +739,7 @@ extern "C" int bfq_run_reads_device(bfq_ctx *c, const uint8_t *d_bases, const ui
                 c->release(c->call.keepMark);
                 c->call.keepRecs = false;
             }
-            if (c->call.keepRecs && posBins) steps34_posbins(c, roff, d_out_bases, d_out_quals);
+            if (c->call.keepRecs && posBins) steps34_posbins(c, d_bases, d_quals, roff, d_out_bases, d_out_quals);
             else if (c->call.keepRecs) steps34_positions(c, d_bases, d_quals, roff, d_out_bases, d_out_quals);
             else steps234_device(c, (u64 *)d_read_off, d_out_bases, d_out_quals);
         }

@@ -60,6 +60,8 @@ BfqEnv bfq_env_read()
         e.posMode = geti("BFQ_POSMODE", 0) != 0;
         e.posBins = geti("BFQ_POSBINS", 1) != 0;
         e.posBinWc = geti("BFQ_POSBIN_WC", 1) != 0;
+        e.posBinSparse = geti("BFQ_POSBIN_SPARSE", 1) != 0;
+        if (const char *v = getenv("BFQ_POSBIN_POLARITY")) e.posBinPolarity = !strcmp(v, "keep") ? 0 : !strcmp(v, "const") ? 1 : -1;
         e.fuseKeys = geti("BFQ_FUSEKEYS", 1) != 0;
         e.refinePipe = geti("BFQ_REFINE_PIPE", 1) != 0;
         e.ioThreads = geti("BFQ_IO_THREADS", 0);

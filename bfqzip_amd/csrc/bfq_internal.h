@@ -58,7 +58,9 @@ struct DevCounters {
     u64 hugeRows;        // their rows
     u64 bigClusters;     // clusters above CL_BIG rows, left to k_cluster_big
     u64 bigTotal;        // segments > 64 rows of the piles already refined (pile mode: bigCount restarts per pile)
-    u64 pad[5];
+    u64 pbPolarity;      // sparse position bins: the polarity level 1 chose + 1 (0: the call ran no sparse stage)
+    u64 pbSent;          // ... and the rows it sent
+    u64 pad[3];
 };
 
 // the tabulated rank queries: one u64 per eBWT row (layout: bfq_rank.h)
@@ -125,6 +127,8 @@ struct bfq_ctx {
 
     DevCounters *d_cnt = nullptr;   // device
     DevCounters h_cnt;              // host copy
+    int pbLastPolarity = -1;        // what the last finished call's sparse position bins did (bfq_posbin_sparse_last): -1 = none ran
+    u64 pbLastSent = 0;
     double *d_powtab = nullptr;     // 256 doubles: pow(10,-(q-33)/10) by host libm
     double *d_qthr = nullptr;       // thresholds for round(-10*log10(x))
     int qthrLo = 0, qthrN = 0;
@@ -458,7 +462,8 @@ bool bfq_is_pinned(const void *p);
 // the rows back in text order by position bins instead of LF walks (k_posbin.hip): w12 = the sorted records' (w1, w2) words
 // (overwritten), repl / editQual = k_cluster's row-local edits; the reads go out back to back (read i at roff[i])
 size_t bfq_posbins_need(u64 n);                   // arena bytes it takes; ~0: more rows than two partition levels hold
-void bfq_posbins(bfq_ctx *c, u64 *w12, const u8 *repl, const u8 *editQual, u64 n, const u64 *d_roff, u64 N, int B, u8 *outSym, u8 *outQual);
+void bfq_posbins(bfq_ctx *c, u64 *w12, const u8 *repl, const u8 *editQual, u64 n, const u64 *d_roff, u64 N, int B, const u8 *inSym, const u8 *inQual,
+                 u8 *outSym, u8 *outQual);
 
 void bfq_synth_launch(bfq_ctx *c, const bfq_synth *s, u8 *d_bases, u8 *d_quals, u64 *d_roff);
 u8 *bfq_synth_headers(bfq_ctx *c, const bfq_synth *s, u64 *len);   // k_synth.hip

@@ -53,6 +53,8 @@ struct BfqEnv {
     bool posMode = false;           // BFQ_POSMODE=1: steps 3-4 without LF table (position mode)
     bool posBins = true;            // BFQ_POSBINS=0: the device-resident fused path inverts by LF walks again (A/B runs)
     bool posBinWc = true;           // BFQ_POSBIN_WC=0: the position bins write per-tile runs at the bin's cursor again, not whole 64-byte chunks (A/B runs)
+    bool posBinSparse = true;       // BFQ_POSBIN_SPARSE=0: every row travels through the position bins again, not only those that differ from the default (A/B runs)
+    int posBinPolarity = -1;        // BFQ_POSBIN_POLARITY=keep|const: the sparse form's default is forced (const: M = 2 only); unset: chosen on the device
     bool fuseKeys = true;           // BFQ_FUSEKEYS=0: step 1 in one piece writes the sort records with k_build_keys and streams all five passes again (A/B runs)
     bool refinePipe = true;         // BFQ_REFINE_PIPE=0: the refinement's chunk kernel loads a round's third text word behind the first two again (k_refine_chunk_seq; A/B runs)
     int ioThreads = 0;              // BFQ_IO_THREADS: staging workers (0: by core count)

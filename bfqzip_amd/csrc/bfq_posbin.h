@@ -44,6 +44,41 @@ BFQ_HD u32 bfq_posbin_tail_kept(u32 carried, u32 fresh, u32 chunk) { return (car
 // slot inside a bin of cap records of the idx-th record the tail cursor handed out (idx < cap)
 BFQ_HD u64 bfq_posbin_tail_slot(u64 cap, u64 idx) { return cap - 1 - idx; }
 
+// Sparse form (the default): the outputs are the inputs with edits applied and the inputs are resident in the outputs' layout,
+// so a row travels only if its final (symbol, quality) differs from a default the last kernel works out by itself at that
+// position.  Two defaults ("polarities"), chosen per call on the device: KEEP = (input base, input quality), CONST = (input
+// base, the constant v every smoothed quality becomes when M = 2); both binned when B = 1.  Rows whose symbol is the
+// terminator are never sent.  The choice changes the number of rows sent, never the result.
+#define BFQ_PB_KEEP 0
+#define BFQ_PB_CONST 1
+// forced: -1 = choose (CONST iff M = 2 and more than half of the bases were smoothed), else the polarity itself
+BFQ_HD int bfq_posbin_polarity(int M, int forced, u64 smoothed, u64 bases)
+{
+    if (forced >= 0) return forced;
+    return M == 2 && 2 * smoothed > bases ? BFQ_PB_CONST : BFQ_PB_KEEP;
+}
+BFQ_HD u32 bfq_posbin_default_qual(int polarity, int B, u32 inQual, u32 v)
+{
+    const u32 q = (polarity == BFQ_PB_CONST ? v : inQual) & 0xFFu;
+    return B ? bfq_bin8(q) : q;
+}
+// Bins fill partially then: the live records of a bin of cap slots are its head region [0, head) and its tail region
+// [cap - tail, cap); what lies between was never written and is not a record.
+BFQ_HD bool bfq_posbin_live(u64 cap, u64 head, u64 tail, u64 idx) { return idx < cap && (idx < head || idx + tail >= cap); }
+// slots [t0, t0 + len) of the bin hold no live record (wholly in the gap, or beyond the bin)
+BFQ_HD bool bfq_posbin_gap_tile(u64 cap, u64 head, u64 tail, u64 t0, u64 len)
+{
+    const u64 end = t0 + len < cap ? t0 + len : cap;
+    return t0 >= cap || (t0 >= head && end + tail <= cap);
+}
+// Terminators of a window as a bitmap (word w: window positions [64 w, 64 w + 64)) with pre[w] = terminators in the words
+// below w: terminators strictly before window position idx.  A symbol's packed slot in the window's output is idx - that.
+BFQ_HD bool bfq_posbin_is_term(const u64 *bm, u32 idx) { return (bm[idx >> 6] >> (idx & 63u)) & 1ull; }
+BFQ_HD u32 bfq_posbin_term_rank(const u64 *bm, const u32 *pre, u32 idx)
+{
+    return pre[idx >> 6] + (u32)bfq_popc64(bm[idx >> 6] & ((1ull << (idx & 63u)) - 1ull));
+}
+
 // Terminated-text coordinates: read i stands at roff[i] + i, its terminator at roff[i + 1] + i.  Number of terminators
 // strictly before position q = index of the read q lies in (a terminator belongs to the read it ends); q - that = where
 // q's symbol goes when the reads are written back to back.

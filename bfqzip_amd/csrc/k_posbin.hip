@@ -15,6 +15,14 @@
 // inside a bin is free.  Every store is checked against the bin's capacity: rows that do not form a permutation of the
 // positions are counted in errInvert instead of being written anywhere.  Level 1, whose bins lie far apart, writes whole
 // 64-byte chunks instead of the tile's runs (k_posbin_l1_wc below; BFQ_POSBIN_WC=0: the runs, for A/B runs).
+//
+// Sparse form (the default; BFQ_POSBIN_SPARSE=0: every row travels as described above).  The result is the input with edits
+// applied and the input lies in device memory in the outputs' layout, so level 1 sends a row only if its final (symbol,
+// quality) differs from a default k_posbin_apply works out by itself: the input, or -- M = 2, most qualities smoothed -- the
+// input base with the constant quality (bfq_posbin.h; chosen on the device, no host synchronisation).  Bins and windows
+// then fill partially: level 2 reads a bin's head and tail regions only and skips the tiles in the gap, k_posbin_apply starts
+// from the default, lays the window's records over it and takes the terminators from the read offsets.  What is lost: bins
+// are not exactly filled any more, so the check after level 1 is "sent = landed, no bin above its capacity", not "a permutation".
 #include <type_traits>
 #include "bfq_internal.h"
 #include "bfq_device.h"
@@ -41,10 +49,11 @@ __device__ __forceinline__ u64 pb_l1_value(u64 x, u32 rp, u32 q, int B, u64 n)
 // LEVEL 1: in = the sorted records' (w1, w2) words, out = u64 records; LEVEL 2: in = level 1's records, out = u32 records.
 // A tile's records into registers: v = the record, lb = its bin relative to binBase (0xFFFF: not to be written, counted in
 // errInvert where it is a live row), rk = its rank among the tile's records of that bin (lcnt: zeroed, a barrier ago)
-template <int LEVEL>
+// SPARSE (level 2): the tile is slots [t0, t0 + PB_TILE) of a level-1 bin filled to head / tail: what lies in its gap is no row
+template <int LEVEL, bool SPARSE>
 __device__ __forceinline__ void pb_load_rank(const u64 *__restrict__ in, const u8 *__restrict__ repl, const u8 *__restrict__ editQual, int B, u64 n,
                                              u64 tbase, u64 binBase, int shiftOut, u32 *lcnt, DevCounters *cnt, u64 (&v)[PB_ITEMS],
-                                             u32 (&lb)[PB_ITEMS], u32 (&rk)[PB_ITEMS])
+                                             u32 (&lb)[PB_ITEMS], u32 (&rk)[PB_ITEMS], u64 cap1 = 0, u64 head = 0, u64 tail = 0, u64 t0 = 0)
 {
     const u32 tid = threadIdx.x;
     // the arrays are padded by 16 entries and more: a vector load that starts inside them stays inside them
@@ -63,7 +72,7 @@ __device__ __forceinline__ void pb_load_rank(const u64 *__restrict__ in, const u
             const u64 val = LEVEL == 1 ? pb_l1_value(x[k], (rp4 >> (8 * k)) & 0xFFu, (eq4 >> (8 * k)) & 0xFFu, B, n) : x[k];
             const u64 pos = bfq_val_pos(val);
             const u64 l = (pos >> shiftOut) - binBase;            // (a bin below binBase wraps to a huge value)
-            const bool live = j + k < n;
+            const bool live = j + k < n && (!SPARSE || bfq_posbin_live(cap1, head, tail, t0 + (j + k - tbase)));
             const bool ok = live && pos < n && l < (u64)BFQ_PB_MAX_BINS;
             if (live && !ok) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
             v[r * 4 + k] = val;
@@ -73,12 +82,15 @@ __device__ __forceinline__ void pb_load_rank(const u64 *__restrict__ in, const u
     }
 }
 
-// per-tile runs at the bin's cursor (BFQ_POSBIN_WC=0)
-template <int LEVEL>
+// per-tile runs at the bin's cursor (level 1: BFQ_POSBIN_WC=0).  SPARSE (level 2 behind the sparse level 1): cur1 = level 1's
+// cursors; a tile that lies wholly in its bin's gap is skipped without a load, and the windows fill partially -- their
+// cursors hold the counts afterwards.
+template <int LEVEL, bool SPARSE>
 __global__ __launch_bounds__(PB_THREADS) void k_posbin_part(const u64 *__restrict__ in, const u8 *__restrict__ repl, const u8 *__restrict__ editQual,
                                                              int B, u64 n, int shiftIn, int shiftOut, u32 *__restrict__ cursor, u32 curStride,
-                                                             void *__restrict__ outv, u64 ntiles, DevCounters *cnt)
+                                                             void *__restrict__ outv, u64 ntiles, DevCounters *cnt, const u32 *__restrict__ cur1)
 {
+    static_assert(!SPARSE || LEVEL == 2, "level 1's sparse form is k_posbin_l1_wc");
     typedef typename std::conditional<LEVEL == 1, u64, u32>::type OutT;
     __shared__ OutT stage[PB_TILE];
     __shared__ u16 sbin[PB_TILE];
@@ -90,12 +102,18 @@ __global__ __launch_bounds__(PB_THREADS) void k_posbin_part(const u64 *__restric
     for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const u64 tbase = tile * PB_TILE;
         const u64 binBase = LEVEL == 1 ? 0ull : (tbase >> shiftIn) << (shiftIn - shiftOut);
+        u64 cap1 = 0, head = 0, tail = 0, t0 = 0;
+        if (SPARSE) {
+            const u64 g1 = tbase >> shiftIn;
+            cap1 = bfq_posbin_cap(n, shiftIn, g1); head = cur1[g1 * PB_CUR_STRIDE]; tail = cur1[g1 * PB_CUR_STRIDE + 1]; t0 = tbase - (g1 << shiftIn);
+            if (bfq_posbin_gap_tile(cap1, head, tail, t0, PB_TILE)) continue;          // (the same for the whole workgroup)
+        }
         lcnt[tid] = 0; lcnt[tid + PB_THREADS] = 0;
         __syncthreads();
 
         u64 v[PB_ITEMS];
         u32 lb[PB_ITEMS], rk[PB_ITEMS];
-        pb_load_rank<LEVEL>(in, repl, editQual, B, n, tbase, binBase, shiftOut, lcnt, cnt, v, lb, rk);
+        pb_load_rank<LEVEL, SPARSE>(in, repl, editQual, B, n, tbase, binBase, shiftOut, lcnt, cnt, v, lb, rk, cap1, head, tail, t0);
         __syncthreads();
 
         // thread t: bins 2 t and 2 t + 1 -- where they start in the staged tile, and their runs' places in the global bins
@@ -178,11 +196,35 @@ __device__ __forceinline__ void pw_tail_out(const u64 *left, u32 b, u32 nl, u64 
     }
 }
 
+// SPARSE: the row is sent iff its final (code, quality) differs from the default at its position (bfq_posbin.h), which the row
+// knows from its own payload: the eBWT symbol and its quality as the input had them
+__device__ __forceinline__ bool pb_l1_send(u64 x, u64 val, int pol, int B, u32 dqConst)
+{
+    const u64 pay = bfq_rec_pay((u32)x, (u32)(x >> 32));
+    const u32 oc = bfq_val_code(pay);
+    const u32 dq = pol == BFQ_PB_CONST ? dqConst : bfq_posbin_default_qual(BFQ_PB_KEEP, B, bfq_val_qual(pay), 0u);
+    return oc != 0u && (bfq_val_code(val) != oc || bfq_val_qual(val) != dq);
+}
+
 // (two workgroups per CU -- 72 KiB of LDS each -- are four waves per SIMD: 128 VGPRs)
+// SPARSE: rows that match the default take no rank, no staging slot and no cursor claim, so the bins fill partially (heads
+// still go up in whole chunks, tails down from the end).  Every workgroup works the polarity out for itself from the
+// smoothing counter, which is final when k_cluster and k_big_* are done; workgroup 0 leaves it (+ 1) in cnt->pbPolarity for
+// k_posbin_apply and the host.  The rows sent are counted, one atomic per workgroup.
+template <bool SPARSE>
 __global__ __launch_bounds__(PW_THREADS, 4) void k_posbin_l1_wc(const u64 *__restrict__ in, const u8 *__restrict__ repl, const u8 *__restrict__ editQual, int B, u64 n,
-                                                                int shiftOut, u32 *__restrict__ cursor, u64 *__restrict__ out, u64 ntiles, DevCounters *cnt)
+                                                                int shiftOut, u32 *__restrict__ cursor, u64 *__restrict__ out, u64 ntiles, DevCounters *cnt,
+                                                                int M, int polForce, u32 vq, u64 bases)
 {
     constexpr u32 C = PW_C;
+    int pol = BFQ_PB_KEEP;
+    u32 dqConst = 0;
+    u64 sentWg = 0;                                 // (thread 0's copy counts)
+    if (SPARSE) {
+        pol = bfq_posbin_polarity(M, polForce, cnt->stats[6], bases);
+        dqConst = bfq_posbin_default_qual(BFQ_PB_CONST, B, 0u, vq);
+        if (blockIdx.x == 0 && threadIdx.x == 0) cnt->pbPolarity = (u64)pol + 1;
+    }
     __shared__ u64 stage[PB_TILE];
     __shared__ u64 left[(C - 1) * PB_LS];
     // per bin and tile: lcnt = records; pk0 = start in the staged tile | first chunk << 16; pk1 = tail carried in | whole chunks << 16;
@@ -216,9 +258,10 @@ __global__ __launch_bounds__(PW_THREADS, 4) void k_posbin_l1_wc(const u64 *__res
                 const bool live = j + k < n;
                 const bool ok = live && pos < n && l < (u64)BFQ_PB_MAX_BINS;
                 if (live && !ok) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
+                const bool send = ok && (!SPARSE || pb_l1_send(x[k], val, pol, B, dqConst));
                 v[r * 4 + k] = val;
-                lb[r * 4 + k] = ok ? (u32)l : 0xFFFFu;
-                rk[r * 4 + k] = ok ? atomicAdd(&lcnt[l], 1u) : 0u;
+                lb[r * 4 + k] = send ? (u32)l : 0xFFFFu;
+                rk[r * 4 + k] = send ? atomicAdd(&lcnt[l], 1u) : 0u;
             }
         }
         if (tile + gridDim.x < ntiles) pw_load(in, repl, editQual, n, (tile + gridDim.x) * PB_TILE, raw);
@@ -230,6 +273,7 @@ __global__ __launch_bounds__(PW_THREADS, 4) void k_posbin_l1_wc(const u64 *__res
         u32 totals;                                 // (records: at most 4096, chunks: fewer -- one scan for both)
         const u32 ex = pw_block_exscan32(c | (f << 16), sh, &totals);
         const u32 nchunks = totals >> 16;
+        sentWg += totals & 0xFFFFu;
         pk0[tid] = ex; pk1[tid] = nl | (f << 16);
         if (f) gb[tid] = atomicAdd(head, h);
         __syncthreads();
@@ -265,14 +309,32 @@ __global__ __launch_bounds__(PW_THREADS, 4) void k_posbin_l1_wc(const u64 *__res
         }
     }
     pw_tail_out(left, tid, nl, n, shiftOut, tail, out, cnt);
+    if (SPARSE && tid == 0 && sentWg) atomicAdd((unsigned long long *)&cnt->pbSent, (unsigned long long)sentWg);
 }
 
 // after level 1: head and tail regions tile every bin exactly (stores beyond a bin's capacity were dropped and counted
 // where they were tried; two regions that overlap inside it show here)
-__global__ void k_posbin_check(const u32 *__restrict__ cursor, u64 nbins, u64 n, int shift, DevCounters *cnt)
+// sparse (one workgroup): the bins are not exactly filled any more, so what can be told is "sent = landed, no overlap": no
+// bin holds more than its capacity, and heads and tails add up to the rows level 1 counted as sent
+__global__ void k_posbin_check(const u32 *__restrict__ cursor, u64 nbins, u64 n, int shift, int sparse, DevCounters *cnt)
 {
-    const u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < nbins && (u64)cursor[b * PB_CUR_STRIDE] + cursor[b * PB_CUR_STRIDE + 1] != bfq_posbin_cap(n, shift, b)) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
+    if (!sparse) {
+        const u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+        if (b < nbins && (u64)cursor[b * PB_CUR_STRIDE] + cursor[b * PB_CUR_STRIDE + 1] != bfq_posbin_cap(n, shift, b)) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
+        return;
+    }
+    __shared__ unsigned long long landed;
+    if (threadIdx.x == 0) landed = 0;
+    __syncthreads();
+    u64 mine = 0;
+    for (u64 b = threadIdx.x; b < nbins; b += blockDim.x) {
+        const u64 ht = (u64)cursor[b * PB_CUR_STRIDE] + cursor[b * PB_CUR_STRIDE + 1];
+        if (ht > bfq_posbin_cap(n, shift, b)) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
+        mine += ht;
+    }
+    if (mine) atomicAdd(&landed, (unsigned long long)mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && landed != cnt->pbSent) atomicAdd((unsigned long long *)&cnt->errInvert, 1ull);
 }
 
 #define PA_THREADS 512
@@ -357,6 +419,107 @@ __global__ __launch_bounds__(PA_THREADS, 4) void k_posbin_apply(const u32 *__res
     }
 }
 
+// bytes [a, a + len) of an LDS array come from g[a, a + len), every byte through f (f4: four bytes of a word at once).  vec: g is
+// 16-byte aligned -- whole pieces as one load; the ragged ends, and everything when the input is aligned otherwise than the
+// output, byte by byte: no load leaves the range (the caller's arrays are exact-size)
+template <class F, class F4>
+__device__ __forceinline__ void pb_fill(u8 *lds, u32 a, u32 len, const u8 *g, bool vec, F f, F4 f4)
+{
+    const u32 end = a + len;
+    if (!vec) {
+        for (u32 i = a + threadIdx.x; i < end; i += PA_THREADS) lds[i] = f(g[i]);
+        return;
+    }
+    const u32 pieces = (end + 15) >> 4;
+    for (u32 k = threadIdx.x; k < pieces; k += PA_THREADS) {
+        const u32 lo = k << 4;
+        if (lo >= a && lo + 16 <= end) {
+            uint4 x = *(const uint4 *)(g + lo);
+            x.x = f4(x.x); x.y = f4(x.y); x.z = f4(x.z); x.w = f4(x.w);
+            *(uint4 *)(lds + lo) = x;
+        } else for (u32 i = (lo > a ? lo : a); i < lo + 16 && i < end; i++) lds[i] = f(g[i]);
+    }
+}
+__device__ __forceinline__ u32 pb_bin8x4(u32 w) { return bfq_bin8(w & 0xFFu) | (bfq_bin8((w >> 8) & 0xFFu) << 8) | (bfq_bin8((w >> 16) & 0xFFu) << 16) | (bfq_bin8(w >> 24) << 24); }
+
+// The sparse form of the last stage: the window's packed output range [o0, o0 + len) starts as the default -- the input's
+// bases, and its qualities (KEEP) or the constant (CONST: no quality is read), binned when B = 1 -- and the window's records,
+// as many as its level-2 cursor counted, are laid over it.  No record stands for a terminator any more: the window's
+// terminators come from the read offsets, as a bitmap with per-word prefix counts (bfq_posbin.h; one 64-bit word per thread),
+// and a record's packed slot is its window position minus the terminators before it.  A record that names a position
+// outside the window, a terminator's position or no base is counted in errInvert, not followed.
+// (two workgroups per CU -- 70 KiB of LDS each)
+__global__ __launch_bounds__(PA_THREADS, 4) void k_posbin_apply_sparse(const u32 *__restrict__ rec, const u32 *__restrict__ wcur, u64 n, const u64 *__restrict__ roff,
+                                                                    u64 N, const u8 *inSym, const u8 *inQual, int B, u32 vq, u8 *outSym, u8 *outQual, u64 nwin,
+                                                                    DevCounters *cnt)
+{
+    __shared__ __attribute__((aligned(16))) u8 ls[BFQ_PB_W + 32];
+    __shared__ __attribute__((aligned(16))) u8 lq[BFQ_PB_W + 32];
+    __shared__ u64 bm[PA_THREADS];
+    __shared__ u32 pre[PA_THREADS];
+    __shared__ u32 sh[PA_THREADS / 64];
+    __shared__ u64 shBefore;
+    static_assert(PA_THREADS * 64 == BFQ_PB_W, "one bitmap word per thread");
+    const u32 tid = threadIdx.x, lane = bfq_lane(), w = tid >> 6;
+    const int pol = cnt->pbPolarity == (u64)BFQ_PB_CONST + 1 ? BFQ_PB_CONST : BFQ_PB_KEEP;
+    const u32 dqConst = bfq_posbin_default_qual(BFQ_PB_CONST, B, 0u, vq);
+
+    for (u64 win = blockIdx.x; win < nwin; win += gridDim.x) {
+        const u64 q0 = win << BFQ_PB_WSHIFT;
+        const u32 cap = (u32)bfq_posbin_cap(n, BFQ_PB_WSHIFT, win);
+        if (tid == 0) shBefore = bfq_posbin_reads_before(roff, N, q0);
+        bm[tid] = 0;
+        __syncthreads();
+        const u64 rb = shBefore;                                    // the reads from rb on end at q0 or behind it
+        for (u64 i = rb + tid; i < N; i += PA_THREADS) {
+            const u64 t = roff[i + 1] + i;
+            if (t >= q0 + cap) break;
+            const u32 d = (u32)(t - q0);
+            atomicOr((unsigned long long *)&bm[d >> 6], 1ull << (d & 63u));
+        }
+        __syncthreads();
+        const u32 mine = (u32)bfq_popc64(bm[tid]);
+        const u32 inc = bfq_wave_incscan32(mine);
+        if (lane == 63) sh[w] = inc;
+        __syncthreads();
+        u32 before = inc - mine, terms = 0;
+#pragma unroll
+        for (int k = 0; k < PA_THREADS / 64; k++) { const u32 t = sh[k]; before += k < (int)w ? t : 0u; terms += t; }
+        pre[tid] = before;
+        const u64 o0 = q0 - rb;                                     // where the window's first symbol goes
+        const u32 len = cap - terms;
+        const u32 bS = (u32)(((uintptr_t)outSym + o0) & 15u), bQ = (u32)(((uintptr_t)outQual + o0) & 15u);
+        pb_fill(ls, bS, len, inSym + o0 - bS, (((uintptr_t)inSym + o0) & 15u) == bS, [](u8 x) { return x; }, [](u32 x) { return x; });
+        if (pol == BFQ_PB_CONST) {
+            const u32 c4 = dqConst * 0x01010101u;                   // (whole pieces: the slack around the range is the array's own)
+            for (u32 k = tid; k < (bQ + len + 15) >> 4; k += PA_THREADS) *(uint4 *)(lq + (k << 4)) = uint4{c4, c4, c4, c4};
+        } else if (B) pb_fill(lq, bQ, len, inQual + o0 - bQ, (((uintptr_t)inQual + o0) & 15u) == bQ, [](u8 x) { return (u8)bfq_bin8(x); }, [](u32 x) { return pb_bin8x4(x); });
+        else pb_fill(lq, bQ, len, inQual + o0 - bQ, (((uintptr_t)inQual + o0) & 15u) == bQ, [](u8 x) { return x; }, [](u32 x) { return x; });
+        __syncthreads();
+
+        // the records over the default (the record array is padded: a vector load that starts inside it stays inside it)
+        u32 nrec = wcur[win], bad = 0;
+        if (nrec > cap) nrec = cap;                                 // (what went beyond was dropped and counted by level 2)
+        for (u32 k = tid * 4; k < nrec; k += PA_THREADS * 4) {
+            const uint4 r4 = *(const uint4 *)(rec + q0 + k);
+            const u32 r[4] = {r4.x, r4.y, r4.z, r4.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if (k + i >= nrec) break;
+                const u32 idx = r[i] & (BFQ_PB_W - 1u), code = (r[i] >> BFQ_PB_WSHIFT) & 7u, q = (r[i] >> (BFQ_PB_WSHIFT + 3)) & 0xFFu;
+                if (idx >= cap || code == 0u || code > 5u || bfq_posbin_is_term(bm, idx)) { bad++; continue; }
+                const u32 slot = idx - bfq_posbin_term_rank(bm, pre, idx);
+                ls[bS + slot] = bfq_code_sym(code); lq[bQ + slot] = (u8)q;
+            }
+        }
+        if (bad) atomicAdd((unsigned long long *)&cnt->errInvert, (unsigned long long)bad);
+        __syncthreads();
+        pb_flush(ls, bS, len, outSym + o0 - bS);
+        pb_flush(lq, bQ, len, outQual + o0 - bQ);
+        __syncthreads();
+    }
+}
+
 // workgroups of `kernel` that run at once (at most one per tile)
 static unsigned pb_resident(bfq_ctx *c, const void *kernel, int threads, u64 ntiles)
 {
@@ -376,12 +539,18 @@ size_t bfq_posbins_need(u64 n)
 }
 
 // w12: the sorted records' (w1, w2) words in row order (n + 16 entries) -- dead after level 1, level 2's records go there;
-// repl / editQual: one byte per row (0 / the row's quality where k_cluster changed nothing)
-void bfq_posbins(bfq_ctx *c, u64 *w12, const u8 *repl, const u8 *editQual, u64 n, const u64 *d_roff, u64 N, int B, u8 *outSym, u8 *outQual)
+// repl / editQual: one byte per row (0 / the row's quality where k_cluster changed nothing); inSym / inQual: the call's inputs,
+// laid out like the outputs (the sparse form's defaults; may be the outputs themselves)
+void bfq_posbins(bfq_ctx *c, u64 *w12, const u8 *repl, const u8 *editQual, u64 n, const u64 *d_roff, u64 N, int B, const u8 *inSym, const u8 *inQual,
+                 u8 *outSym, u8 *outQual)
 {
     if (!n) return;
     const int s1 = bfq_posbin_shift(n);
     if (s1 < 0) throw BfqError{BFQ_E_ARG, "too many rows for the position bins"};
+    // BFQ_POSBIN_SPARSE=0: every row travels, as before; BFQ_POSBIN_WC=0 is the dense per-tile-run path as a whole
+    const bool sparse = c->env.posBinWc && c->env.posBinSparse;
+    const int force = c->env.posBinPolarity;
+    if (sparse && force == BFQ_PB_CONST && c->P.M != 2) throw BfqError{BFQ_E_ARG, "BFQ_POSBIN_POLARITY=const needs M = 2"};
     const size_t mk = c->mark();
     const u64 nb1 = bfq_posbin_bins(n, s1), nwin = bfq_posbin_bins(n, BFQ_PB_WSHIFT), ntiles = ceil_div(n, PB_TILE);
     u64 *rec8 = c->alloc<u64>(n + 16);
@@ -390,20 +559,29 @@ void bfq_posbins(bfq_ctx *c, u64 *w12, const u8 *repl, const u8 *editQual, u64 n
     u32 *rec4 = (u32 *)w12;
     HIP_CHECK(hipMemsetAsync(cur, 0, 4 * (nb1 * PB_CUR_STRIDE + nwin), c->stream));
     const unsigned grid = (unsigned)(ntiles > BFQ_MAX_GRID ? BFQ_MAX_GRID : ntiles);
+    const unsigned agrid = (unsigned)(nwin > BFQ_MAX_GRID ? BFQ_MAX_GRID : nwin);
+    const u32 vq = (u32)c->P.v & 0xFFu;
+    // The algorithmic bytes handed to the profiler stay the dense bound (36 bytes per row) in the sparse form too: how many rows
+    // were sent is known on the device only, and reading it back here would cost a synchronisation.
     if (c->env.posBinWc) {
         // whole chunks are aligned when the array is: bin bases and head claims are multiples of the chunk
         if ((uintptr_t)rec8 & (BFQ_PB_CHUNK_BYTES - 1)) throw BfqError{BFQ_E_ARG, "position bins: record array not 64-byte aligned"};
         // as many workgroups as run at once: a workgroup's tails are written once, at its end
-        KLAUNCH(c, K_POSBIN_L1, 18.0 * (double)n, k_posbin_l1_wc, pb_resident(c, (const void *)k_posbin_l1_wc, PW_THREADS, ntiles), PW_THREADS, (const u64 *)w12, repl,
-                editQual, B, n, s1, cur, rec8, ntiles, c->d_cnt);
-        KLAUNCH(c, K_POSBIN_CHECK, 8.0 * (double)nb1, k_posbin_check, bfq_grid(nb1, 256), 256, (const u32 *)cur, nb1, n, s1, c->d_cnt);
+        const auto l1 = sparse ? k_posbin_l1_wc<true> : k_posbin_l1_wc<false>;
+        KLAUNCH(c, K_POSBIN_L1, 18.0 * (double)n, l1, pb_resident(c, (const void *)l1, PW_THREADS, ntiles), PW_THREADS, (const u64 *)w12, repl,
+                editQual, B, n, s1, cur, rec8, ntiles, c->d_cnt, c->P.M, force, vq, n - N);
+        if (sparse) KLAUNCH(c, K_POSBIN_CHECK, 8.0 * (double)nb1, k_posbin_check, 1, BFQ_PB_MAX_BINS, (const u32 *)cur, nb1, n, s1, 1, c->d_cnt);
+        else KLAUNCH(c, K_POSBIN_CHECK, 8.0 * (double)nb1, k_posbin_check, bfq_grid(nb1, 256), 256, (const u32 *)cur, nb1, n, s1, 0, c->d_cnt);
     } else {
-        KLAUNCH(c, K_POSBIN_L1, 18.0 * (double)n, k_posbin_part<1>, grid, PB_THREADS, (const u64 *)w12, repl, editQual, B, n, 0, s1, cur,
-                (u32)PB_CUR_STRIDE, (void *)rec8, ntiles, c->d_cnt);
+        const auto l1 = k_posbin_part<1, false>;
+        KLAUNCH(c, K_POSBIN_L1, 18.0 * (double)n, l1, grid, PB_THREADS, (const u64 *)w12, repl, editQual, B, n, 0, s1, cur,
+                (u32)PB_CUR_STRIDE, (void *)rec8, ntiles, c->d_cnt, (const u32 *)nullptr);
     }
-    KLAUNCH(c, K_POSBIN_L2, 12.0 * (double)n, k_posbin_part<2>, grid, PB_THREADS, (const u64 *)rec8, (const u8 *)nullptr, (const u8 *)nullptr, 0, n, s1,
-            (int)BFQ_PB_WSHIFT, cur2, 1u, (void *)rec4, ntiles, c->d_cnt);
-    const unsigned agrid = (unsigned)(nwin > BFQ_MAX_GRID ? BFQ_MAX_GRID : nwin);
-    KLAUNCH(c, K_POSBIN_APPLY, 4.0 * (double)n + 2.0 * (double)(n - N), k_posbin_apply, agrid, PA_THREADS, (const u32 *)rec4, n, d_roff, N, outSym, outQual, nwin);
+    const auto l2 = sparse ? k_posbin_part<2, true> : k_posbin_part<2, false>;
+    KLAUNCH(c, K_POSBIN_L2, 12.0 * (double)n, l2, grid, PB_THREADS, (const u64 *)rec8, (const u8 *)nullptr, (const u8 *)nullptr, 0, n, s1,
+            (int)BFQ_PB_WSHIFT, cur2, 1u, (void *)rec4, ntiles, c->d_cnt, (const u32 *)cur);
+    if (sparse) KLAUNCH(c, K_POSBIN_APPLY, 4.0 * (double)n + 2.0 * (double)(n - N), k_posbin_apply_sparse, agrid, PA_THREADS, (const u32 *)rec4, (const u32 *)cur2, n,
+                        d_roff, N, inSym, inQual, B, vq, outSym, outQual, nwin, c->d_cnt);
+    else KLAUNCH(c, K_POSBIN_APPLY, 4.0 * (double)n + 2.0 * (double)(n - N), k_posbin_apply, agrid, PA_THREADS, (const u32 *)rec4, n, d_roff, N, outSym, outQual, nwin);
     c->release(mk);
 }

@@ -1146,6 +1146,12 @@ int  bfq_prof_count(bfq_ctx *c);
  * the window (text positions per workgroup of the last stage) and the shift of a first-level bin (2^shift positions).
  * BFQ_E_ARG (bin_shift -1): more rows than two partition levels hold; such a call inverts by LF walks. */
 int  bfq_posbin_geometry(uint64_t n_rows, uint64_t *window, int *bin_shift);
+/* introspection: what the position bins of the context's last finished call did.  By default only the rows whose final
+ * (base, quality) differs from a default at their position travel: polarity 0 = the default is the input ("keep"), 1 = the
+ * input base with the constant quality of M = 2 ("const"; chosen on the device when more than half of the bases were
+ * smoothed, or forced by BFQ_POSBIN_POLARITY=keep|const), -1 = the call sent every row (BFQ_POSBIN_SPARSE=0, BFQ_POSBIN_WC=0)
+ * or ran no position bins.  rows_sent: the rows that travelled = the output positions that differ from the default. */
+int  bfq_posbin_sparse_last(bfq_ctx *c, int *polarity, uint64_t *rows_sent);
 /* introspection: how the suffix sort cuts n_rows rows -- the rows of a scatter tile and of a radix block (a whole number of
  * tiles, which one workgroup runs through one after the other; fewer tiles for smaller collections). */
 int  bfq_radix_geometry(uint64_t n_rows, uint64_t *tile_rows, uint64_t *block_rows);
