@@ -17,7 +17,7 @@ SYMBOLS = [
     "bfq_phase_enable", "bfq_phase", "bfq_phase_report", "bfq_output_prefault", "bfq_fastq_rows_estimate", "bfq_build_ebwt", "bfq_count_reads",
     "bfq_smooth_invert", "bfq_run_reads", "bfq_run_reads_device", "bfq_fetch_ebwt",
     "bfq_fastq_out_bound", "bfq_fastq_build_ebwt", "bfq_fastq_run", "bfq_fastq_run_streams",
-    "bfq_smooth_invert_fastq", "bfq_fastq_run_job", "bfq_host_alloc", "bfq_host_free",
+    "bfq_smooth_invert_fastq", "bfq_fastq_run_job", "bfq_fastq_run_job_edits", "bfq_host_alloc", "bfq_host_free",
     "bfq_text_count_lines", "bfq_text_nth_newline", "bfq_file_put", "bfq_file_map", "bfq_file_unmap", "bfq_fastq_build_ebwt_fd", "bfq_smooth_invert_fastq_fd",
     "bfq_glob_begin", "bfq_glob_local_text", "bfq_glob_pile_counts", "bfq_glob_init_out", "bfq_glob_run_pile", "bfq_glob_finish",
     "bfq_synth_default", "bfq_synth_total", "bfq_synth_host", "bfq_synth_device", "bfq_synth_fastq",
@@ -33,6 +33,10 @@ SYMBOLS = [
     "bfq_fastq_restore_ordered", "bfq_fastq_restore_ordered_fd",
     "bfq_fastq_restore_groups", "bfq_stream_members", "bfq_fastq_restore_grouped", "bfq_fastq_restore_grouped_fd",
     "bfq_fastq_compare", "bfq_fastq_compare_fd",
+    "bfq_edits_bound", "bfq_edits_member_len", "bfq_edits_info", "bfq_edits_encode", "bfq_edits_decode", "bfq_edits_host_error",
+    "bfq_fastq_edits_host", "bfq_fastq_unedit_host", "bfq_edits_make_device", "bfq_edits_apply_device",
+    "bfq_fastq_edits", "bfq_fastq_edits_device", "bfq_fastq_edits_fd", "bfq_fastq_unedit", "bfq_fastq_unedit_fd",
+    "bfq_fastq_restore_edited", "bfq_fastq_restore_edited_fd",
     "bfq_fastq_kmers", "bfq_fastq_kmers_fd", "bfq_fastq_kmers_host", "bfq_kmers_host_error", "bfq_kmers_geometry",
     "bfq_bgzf_probe", "bfq_bgzf_index", "bfq_bgzf_inflate", "bfq_bgzf_inflate_device", "bfq_bgzf_inflate_fd",
     "bfq_bgzf_deflate_bound", "bfq_bgzf_deflate_host", "bfq_bgzf_deflate", "bfq_bgzf_deflate_device", "bfq_bgzf_deflate_fd",
@@ -247,6 +251,17 @@ class CompareReport(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in COMPARE_SCALARS] + [(k, C.c_uint64 * n) for k, n in COMPARE_ARRAYS] + [("reserved", C.c_uint64 * 8)]
 
 
+class EditStats(C.Structure):
+    """bfq_edit_stats: reads, bases, edits, reads_touched, bytes (of the container)"""
+    _fields_ = [(k, C.c_uint64) for k in ("reads", "bases", "edits", "reads_touched", "bytes")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "EditStats(%s)" % ", ".join("%s=%d" % kv for kv in self.as_dict().items())
+
+
 class KmerOpts(C.Structure):
     """bfq_kmer_opts: k (8..31), solid (2..15), canonical, reserved (must be 0), part_records (0: what the memory allows)"""
     _fields_ = [(k, C.c_uint32) for k in ("k", "solid", "canonical", "reserved")] + [("part_records", C.c_uint64)]
@@ -278,6 +293,11 @@ class FastqJob(C.Structure):
                 ("compress_streams", C.c_int32), ("name_codec", C.c_int32),
                 ("dna_bytes", C.c_uint64), ("qs_bytes", C.c_uint64), ("hdr_bytes", C.c_uint64),
                 ("qual_codec", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class JobEdits(C.Structure):
+    """bfq_job_edits: out_edits, cap_edits, edits_bytes (what bfq_fastq_run_job_edits takes beside the job)"""
+    _fields_ = [("out_edits", C.c_void_p), ("cap_edits", C.c_uint64), ("edits_bytes", C.c_uint64)]
 
 
 def build(clean=False):
@@ -341,6 +361,7 @@ def lib():
         L.bfq_smooth_invert_fastq.argtypes = [vp, vp, vp, vp, C.c_int, u64, vp, u64, vp, u64, C.POINTER(u64),
                                               C.POINTER(Stats)]
         L.bfq_fastq_run_job.argtypes = [vp, C.POINTER(FastqJob), C.POINTER(Stats)]
+        L.bfq_fastq_run_job_edits.argtypes = [vp, C.POINTER(FastqJob), C.POINTER(JobEdits), C.POINTER(Stats)]
         L.bfq_glob_begin.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(u64), C.POINTER(u64)]
         L.bfq_glob_local_text.argtypes = [vp, vp, vp]
         L.bfq_glob_pile_counts.argtypes = [vp, vp, u64, vp]
@@ -406,6 +427,27 @@ def lib():
         L.bfq_stream_compress_device.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
         L.bfq_fastq_compare.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(TextPart), C.c_int, vp, u64, C.POINTER(CompareReport), vp, u64]
         L.bfq_fastq_compare_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.POINTER(CompareReport), vp, u64]
+        pes = C.POINTER(EditStats)
+        L.bfq_edits_bound.restype = u64
+        L.bfq_edits_bound.argtypes = [u64, u64]
+        L.bfq_edits_member_len.restype = C.c_int64
+        L.bfq_edits_member_len.argtypes = [vp, u64]
+        L.bfq_edits_info.argtypes = [vp, u64, pu64, pu64, pu64, pu64]
+        L.bfq_edits_encode.argtypes = [vp, vp, u64, u64, u64, u64, u64, vp, u64, pu64]
+        L.bfq_edits_decode.argtypes = [vp, u64, vp, vp, u64, pu64, pu64, pu64, pu64, pu64, pu64]
+        L.bfq_edits_host_error.restype = C.c_char_p
+        L.bfq_edits_host_error.argtypes = []
+        L.bfq_fastq_edits_host.argtypes = [vp, u64, vp, u64, vp, u64, pu64, pes]
+        L.bfq_fastq_unedit_host.argtypes = [vp, u64, vp, u64, vp, u64, pu64, pes]
+        L.bfq_edits_make_device.argtypes = [vp, vp, vp, vp, u64, u64, vp, u64, pu64, pes]
+        L.bfq_edits_apply_device.argtypes = [vp, vp, u64, vp, vp, u64, u64, C.c_int, pes]
+        L.bfq_fastq_edits.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(TextPart), C.c_int, vp, u64, pu64, pes]
+        L.bfq_fastq_edits_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, pu64, pes]
+        L.bfq_fastq_edits_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, pu64, pes]
+        L.bfq_fastq_unedit.argtypes = [vp, vp, u64, vp, u64, vp, u64, pu64, pes]
+        L.bfq_fastq_unedit_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, pu64, pes]
+        L.bfq_fastq_restore_edited.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64, pu64, pu64]
+        L.bfq_fastq_restore_edited_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, pu64, pu64]
         pko, pkr = C.POINTER(KmerOpts), C.POINTER(KmerReport)
         L.bfq_fastq_kmers.argtypes = [vp, C.POINTER(TextPart), C.c_int, C.POINTER(TextPart), C.c_int, pko, pkr, vp, u64]
         L.bfq_fastq_kmers_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, pko, pkr, vp, u64]

@@ -64,7 +64,7 @@ class PinnedBuffer:
 
 class JobResult:
     """Outputs of Engine.fastq_job: arrays trimmed to their lengths + where every input part's share starts."""
-    __slots__ = ("fastq", "dna", "qs", "hdr", "n_reads", "total_bases", "part_reads", "part_fastq_off",
+    __slots__ = ("fastq", "dna", "qs", "hdr", "edits", "n_reads", "total_bases", "part_reads", "part_fastq_off",
                  "part_stream_off", "part_hdr_off", "stats")
 
 
@@ -617,6 +617,9 @@ class HostText:
     text_nth_newline = staticmethod(text_nth_newline)
     file_put = staticmethod(file_put)
     restore_groups = staticmethod(restore_groups)
+    edits_info = staticmethod(lambda z: edits_info(z))
+    fastq_edits_host = staticmethod(lambda a, b, out=None: fastq_edits_host(a, b, out))
+    fastq_unedit_host = staticmethod(lambda t, z, out=None: fastq_unedit_host(t, z, out))
 
 
 class Engine:
@@ -738,14 +741,18 @@ class Engine:
         return (dna[:sl.value].tobytes(), qs[:sl.value].tobytes(),
                 hdr[:hl.value].tobytes() if want_headers else None, st.as_dict())
 
-    def fastq_job(self, parts, keep_headers=False, fastq=True, streams=False, hdr=False, out=None, compress=False, names=False, quals=False):
+    def fastq_job(self, parts, keep_headers=False, fastq=True, streams=False, hdr=False, out=None, compress=False, names=False, quals=False,
+                  edits=False):
         """One block of BFQzip_parallel.py in one call (bfq_fastq_run_job): `parts` = 1..4 byte ranges (bytes,
         uint8 arrays, memmap slices) processed as one collection; outputs as asked: the FASTQ text, the --m2
         streams (dna, qs), the --m3 header stream.  `out` may give reusable output arrays (e.g. PinnedBuffer.array)
         under the keys 'fastq', 'dna', 'qs', 'hdr'.  compress=True: the streams come back as BFQRANS2 containers
         (steps 1-5 of the reference in one call; stream_decompress gives the raw stream).  names=True (with compress): the
         header stream leaves as names_compress writes it (the tokenised BFQNAME1 container where that is shorter).  quals=True
-        (with compress 1 or 3): the quality stream leaves as quals_compress writes it (BFQQUAL1 where that is shorter)."""
+        (with compress 1 or 3): the quality stream leaves as quals_compress writes it (BFQQUAL1 where that is shorter).
+        edits=True (not with compress 2 or 3): .edits is the BFQEDIT1 member of the run's base edits -- the input's byte at
+        every base the run changed (fastq_unedit / fastq_restore(edits=) write them back); out['edits'] may give its buffer
+        (default: input length / 8 + 4096 bytes; too small: BfqError whose .needed is the size that suffices)."""
         arrs = [_u8(p) for p in parts]
         np_ = len(arrs)
         tp = (_lib.TextPart * np_)()
@@ -769,6 +776,10 @@ class Engine:
         zcap = (2 * int(self.L.bfq_stream_bound(inlen)) + 64) if compress else 0      # a tiny stream's container is larger than the stream
         bd, bq = buf("dna", streams, max(inlen + 16, zcap)), buf("qs", streams, max(inlen + 16, zcap))
         bh = buf("hdr", hdr, max(inlen + 16, zcap))
+        be = buf("edits", edits, inlen // 8 + 4096)
+        JE = _lib.JobEdits()
+        if be is not None:
+            JE.out_edits = be.ctypes.data; JE.cap_edits = len(be)
         if bf is not None:
             J.out_fastq = bf.ctypes.data; J.cap_fastq = len(bf)
         if bd is not None:
@@ -776,8 +787,14 @@ class Engine:
         if bh is not None:
             J.out_hdr = bh.ctypes.data; J.cap_hdr = len(bh)
         st = _lib.Stats()
-        self._ck(self.L.bfq_fastq_run_job(self.h, C.byref(J), C.byref(st)))
+        rc = (self.L.bfq_fastq_run_job_edits(self.h, C.byref(J), C.byref(JE), C.byref(st)) if be is not None else
+              self.L.bfq_fastq_run_job(self.h, C.byref(J), C.byref(st)))
+        if rc:
+            e = BfqError(rc, self.L.bfq_last_error(self.h).decode())
+            e.needed = int(JE.edits_bytes)                         # (cap_edits too small: the size that suffices)
+            raise e
         r = JobResult()
+        r.edits = be[:JE.edits_bytes] if be is not None else None
         r.fastq = bf[:J.fastq_len] if bf is not None else None
         r.dna = bd[:J.dna_bytes] if bd is not None else None
         r.qs = bq[:J.qs_bytes] if bq is not None else None
@@ -845,6 +862,7 @@ class Engine:
             J.out_hdr = bh.ctypes.data; J.cap_hdr = len(bh)
         self._ck(self.L.bfq_glob_finish(self.h, dna.data_ptr() if sl else None, qs.data_ptr() if sl else None, C.byref(J)))
         r = JobResult()
+        r.edits = None
         r.fastq = bf[:J.fastq_len] if bf is not None else None
         r.dna = bd[:J.dna_bytes] if bd is not None else None
         r.qs = bq[:J.qs_bytes] if bq is not None else None
@@ -1411,7 +1429,7 @@ class Engine:
         return dna[:int(sl.value)], qs[:int(sl.value)], int(nr.value)
 
     # ---- the way back: containers -> FASTQ text (bfq_fastq_restore)
-    def fastq_restore(self, dna, qs, hdr=None, out=None, perm=None, groups=None):
+    def fastq_restore(self, dna, qs, hdr=None, out=None, perm=None, groups=None, edits=None):
         """The FASTQ text of a collection from the containers of its streams (fastq_job(compress=1 / 2 / 3), stream_compress,
         the .bsc files of parallel.py --compress): (text as a uint8 array, n_reads).  hdr=None: every header line is "@".
         `out`: a uint8 array to fill (e.g. PinnedBuffer.array); the result is a view of it.  Streams that do not belong
@@ -1421,9 +1439,13 @@ class Engine:
         `groups`: True, or (first, count) with count None = to the end: block by block (bfq_fastq_restore_grouped) -- the
         groups of HostText.restore_groups one after another in a device workspace sized by the largest of them, the same
         bytes as without; several BFQEBWT1 members are taken.  A failure after the first group may leave the texts of the
-        groups before it in `out`.  Not with `perm`."""
+        groups before it in `out`.  Not with `perm`.
+        `edits`: the BFQEDIT1 members of the run's base edits (fastq_job(edits=True), one per block, back to back): the text
+        comes back with the input's bases (bfq_fastq_restore_edited); with `perm` too, the edits first.  Not with `groups`."""
         if groups is not None and groups is not False and perm is not None:
             raise ValueError("fastq_restore: groups and perm do not go together (records in the original order draw on all groups at once)")
+        if groups is not None and groups is not False and edits is not None:
+            raise ValueError("fastq_restore: groups and edits do not go together (a grouped text goes through fastq_unedit)")
         dna, qs = _u8(dna), _u8(qs)
         hdr = _u8(hdr) if hdr is not None else None
         perm = _u8(perm) if perm is not None else None
@@ -1444,7 +1466,16 @@ class Engine:
             if bound < 0:
                 raise BfqError(-1, "not a container (BFQDNAC1 / BFQRANS2 / BFQLINE1 / BFQNAME1 / BFQQUAL1 / BFQEBWT1)")
             out = np.empty(max(bound, 1), np.uint8)
-        if perm is not None:
+        if edits is not None:
+            ez = _u8(edits)
+            if not len(ez):
+                raise BfqError(-1, "edits: not a BFQEDIT1 container (empty)")
+            if perm is not None and not len(perm):
+                raise BfqError(-1, "perm: not a BFQPERM1 container (empty)")
+            self._ck(self.L.bfq_fastq_restore_edited(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), hl,
+                                                     _ptr(perm), len(perm) if perm is not None else 0, _ptr(ez), len(ez),
+                                                     _ptr(out), len(out), C.byref(ol), C.byref(nr)))
+        elif perm is not None:
             self._ck(self.L.bfq_fastq_restore_ordered(self.h, _ptr(dna), len(dna), _ptr(qs), len(qs), _ptr(hdr), hl,
                                                       _ptr(perm) if len(perm) else None, len(perm), _ptr(out), len(out), C.byref(ol), C.byref(nr)))
         else:
@@ -1452,15 +1483,20 @@ class Engine:
                                               _ptr(out), len(out), C.byref(ol), C.byref(nr)))
         return out[:int(ol.value)], int(nr.value)
 
-    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None, grouped=False, bgzf=False, level=1, ubam=False, **ubam_kw):
+    def fastq_restore_files(self, dna_path, qs_path, hdr_path, out_path, perm_path=None, grouped=False, bgzf=False, level=1, ubam=False,
+                            edits_path=None, **ubam_kw):
         """bfq_fastq_restore_fd on named files (hdr_path may be None); returns (bytes written, n_reads).  perm_path: the
         BFQPERM1 file of the reordering (bfq_fastq_restore_ordered_fd): the text in the order before it.  grouped: True or
         (first, count) as fastq_restore's `groups` (bfq_fastq_restore_grouped_fd); not with perm_path.  bgzf: out_path is
         written as BGZF (bfq_fastq_restore_bgzf_fd: the text is deflated on the device at `level` and never crosses to the
         host); the bytes written are the compressed ones; not with grouped.  ubam: out_path is written as an unaligned BAM
         (bfq_fastq_restore_bam_fd: the restored text becomes records on the device, unpaired, deflated at `level`; further
-        keywords: ubam_opts()); returns (bytes written, stats.records); not with grouped or bgzf."""
+        keywords: ubam_opts()); returns (bytes written, stats.records); not with grouped or bgzf.  edits_path: the BFQEDIT1
+        file of the run's base edits (bfq_fastq_restore_edited_fd): the text with the input's bases; with perm_path too, the
+        edits first; not with grouped, bgzf or ubam."""
         import os
+        if edits_path is not None and (grouped or bgzf or ubam):
+            raise ValueError("fastq_restore_files: edits_path does not go together with grouped, bgzf or ubam")
         if grouped and perm_path is not None:
             raise ValueError("fastq_restore_files: grouped and perm_path do not go together")
         if ubam and (grouped or bgzf):
@@ -1474,9 +1510,13 @@ class Engine:
             for p in (dna_path, qs_path, hdr_path, perm_path):
                 fds.append(os.open(p, os.O_RDONLY) if p is not None else -1)
             fds.append(os.open(out_path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            fds.append(os.open(edits_path, os.O_RDONLY) if edits_path is not None else -1)
             ol, nr = C.c_uint64(0), C.c_uint64(0)
             size = lambda fd: os.fstat(fd).st_size if fd >= 0 else 0
-            if ubam:
+            if edits_path is not None:
+                self._ck(self.L.bfq_fastq_restore_edited_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
+                                                            fds[3], size(fds[3]), fds[5], size(fds[5]), fds[4], C.byref(ol), C.byref(nr)))
+            elif ubam:
                 (O, held), st = ubam_opts(level=level, **ubam_kw), _lib.UbamStats()
                 st.tags = getattr(O, "tag_stats", None)
                 self._ck(self.L.bfq_fastq_restore_bam_fd(self.h, fds[0], size(fds[0]), fds[1], size(fds[1]), fds[2], size(fds[2]),
@@ -1634,6 +1674,89 @@ class Engine:
                 if fd >= 0:
                     os.close(fd)
 
+    # ---- bases back exactly: a run's base edits as a BFQEDIT1 container (bfq_fastq_edits / bfq_fastq_unedit)
+    @staticmethod
+    def _parts(arrs):
+        tp = (_lib.TextPart * max(len(arrs), 1))()
+        for i, x in enumerate(arrs):
+            tp[i].data = x.ctypes.data if len(x) else None
+            tp[i].len = len(x)
+        return tp
+
+    def fastq_edits(self, a_parts, b_parts, out=None):
+        """The BFQEDIT1 member of the run that made B (its output) from A (its input), each a list of 1..4 texts taken as one,
+        in the same read order: (member as a uint8 array, EditStats).  `out`: a uint8 array to fill (default: input length / 8
+        + 4096 bytes); too small, texts that do not pair or malformed text raise BfqError and leave it untouched."""
+        pa, pb = [_u8(p) for p in a_parts], [_u8(p) for p in b_parts]
+        out = out if out is not None else np.empty(sum(text_len(a) for a in pa) // 8 + 4096, np.uint8)
+        ol, st = C.c_uint64(0), _lib.EditStats()
+        self._ck(self.L.bfq_fastq_edits(self.h, self._parts(pa), len(pa), self._parts(pb), len(pb), _ptr(out), len(out), C.byref(ol), C.byref(st)))
+        return out[:int(ol.value)], st
+
+    def fastq_edits_device(self, d_a, a_len, d_b, b_len, d_out, cap):
+        """fastq_edits with both plain texts and the member in device memory (pointers, e.g. torch data_ptr()): (length, EditStats)."""
+        ol, st = C.c_uint64(0), _lib.EditStats()
+        self._ck(self.L.bfq_fastq_edits_device(self.h, d_a, a_len, d_b, b_len, d_out, cap, C.byref(ol), C.byref(st)))
+        return int(ol.value), st
+
+    def edits_make_device(self, d_in_bases, d_out_bases, d_roff, N, total, d_out, cap):
+        """bfq_edits_make_device: the member of two base arrays that share their read offsets (the layout of run_reads_device),
+        everything in device memory: (length, EditStats).  cap too small: BfqError; .needed holds the size that suffices."""
+        ol, st = C.c_uint64(0), _lib.EditStats()
+        rc = self.L.bfq_edits_make_device(self.h, d_in_bases, d_out_bases, d_roff, N, total, d_out, cap, C.byref(ol), C.byref(st))
+        if rc:
+            e = BfqError(rc, self.L.bfq_last_error(self.h).decode())
+            e.needed = int(st.bytes)
+            raise e
+        return int(ol.value), st
+
+    def edits_apply_device(self, edits, d_bases, d_roff, N, total, lines=False):
+        """bfq_edits_apply_device: the members of `edits` (host memory) validated against and written into a base array (or,
+        lines=True, a line stream) in device memory: EditStats.  Any refusal leaves the target untouched."""
+        z, st = _u8(edits), _lib.EditStats()
+        self._ck(self.L.bfq_edits_apply_device(self.h, _ptr(z) if len(z) else None, len(z), d_bases, d_roff, N, total, 1 if lines else 0, C.byref(st)))
+        return st
+
+    def _two_files(self, paths, out_path, call):
+        import os
+        fds = []
+        try:
+            for p in paths:
+                fds.append(os.open(p, os.O_RDONLY))
+            fds.append(os.open(out_path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644))
+            ol, st = C.c_uint64(0), _lib.EditStats()
+            self._ck(call(fds, [os.fstat(fd).st_size for fd in fds], C.byref(ol), C.byref(st)))
+            return int(ol.value), st
+        finally:
+            for fd in fds:
+                os.close(fd)
+
+    def fastq_edits_files(self, a_path, b_path, out_path):
+        """bfq_fastq_edits_fd on named files; returns (bytes written, EditStats).  On failure out_path is left empty."""
+        return self._two_files((a_path, b_path), out_path,
+                               lambda fd, sz, ol, st: self.L.bfq_fastq_edits_fd(self.h, fd[0], sz[0], fd[1], sz[1], fd[2], ol, st))
+
+    def fastq_unedit(self, text, edits, out=None):
+        """`text` (a run's output, plain or BGZF) with the input's bases written back from the BFQEDIT1 members of `edits`
+        (one per block, back to back); every other byte stays: (text as a uint8 array, EditStats).  Members that are damaged,
+        of another collection (reads, bases, read lengths) or of another output (target_sum) raise BfqError and leave `out`
+        untouched."""
+        t, z = _u8(text), _u8(edits)
+        out = out if out is not None else np.empty(text_len(t) + 1, np.uint8)
+        ol, st = C.c_uint64(0), _lib.EditStats()
+        self._ck(self.L.bfq_fastq_unedit(self.h, _ptr(t) if len(t) else None, len(t), _ptr(z) if len(z) else None, len(z), _ptr(out), len(out),
+                                         C.byref(ol), C.byref(st)))
+        return out[:int(ol.value)], st
+
+    def fastq_unedit_files(self, text_path, edits_path, out_path):
+        """bfq_fastq_unedit_fd on named files; returns (bytes written, EditStats).  On failure out_path is left empty."""
+        return self._two_files((text_path, edits_path), out_path,
+                               lambda fd, sz, ol, st: self.L.bfq_fastq_unedit_fd(self.h, fd[0], sz[0], fd[1], sz[1], fd[2], ol, st))
+
+    edits_info = staticmethod(lambda z: edits_info(z))
+    fastq_edits_host = staticmethod(lambda a, b, out=None: fastq_edits_host(a, b, out))
+    fastq_unedit_host = staticmethod(lambda t, z, out=None: fastq_unedit_host(t, z, out))
+
     # ---- which k-mers a run removed, kept and created (bfq_fastq_kmers)
     def fastq_kmers(self, a_parts, b_parts=None, k=21, solid=3, canonical=True, max_list=0, list_out=None, part_records=0):
         """The k-mer spectrum of A, or of A ("before") against B ("after"), each a list of 1..4 texts taken as one: a
@@ -1774,6 +1897,101 @@ class PermError(BfqError):
     def __init__(self, code, msg, first_bad=None):
         super().__init__(code, msg)
         self.first_bad = first_bad
+
+
+class EditsError(BfqError):
+    """A BFQEDIT1 container was refused; first_bad: its first offending edit, None for a fault in the header or the table."""
+
+    def __init__(self, code, msg, first_bad=None):
+        super().__init__(code, msg)
+        self.first_bad = first_bad
+
+
+def _edits_err():
+    return _lib.lib().bfq_edits_host_error().decode()
+
+
+def edits_bound(n_edits, total_bases):
+    """A capacity that always suffices for the BFQEDIT1 container of n_edits edits in total_bases bases (host only)."""
+    return int(_lib.lib().bfq_edits_bound(n_edits, total_bases))
+
+
+def edits_info(edits):
+    """dict(n_reads, total_bases, n_edits, members) of the BFQEDIT1 members of a buffer, from their headers and tables
+    (bfq_edits_info: host only, no GPU)."""
+    z = _u8(edits)
+    v = [C.c_uint64(0) for _ in range(4)]
+    rc = _lib.lib().bfq_edits_info(_ptr(z) if len(z) else None, len(z), *[C.byref(x) for x in v])
+    if rc:
+        raise EditsError(rc, _edits_err())
+    return dict(zip(("n_reads", "total_bases", "n_edits", "members"), (int(x.value) for x in v)))
+
+
+def edits_members(edits):
+    """The members of a buffer as views of it, one per block of a sharded run."""
+    z, L, out, at = _u8(edits), _lib.lib(), [], 0
+    while at < len(z):
+        n = int(L.bfq_edits_member_len(_ptr(z[at:]), len(z) - at))
+        if n < 0:
+            raise EditsError(-1, "member %d: not a well-formed BFQEDIT1 member" % len(out))
+        out.append(z[at:at + n])
+        at += n
+    return out
+
+
+def edits_encode(pos, byte, n_reads, total_bases, shape, target_sum):
+    """The edit list (pos: ascending uint64 positions, byte: the input's bytes there) -> one BFQEDIT1 member (bfq_edits_encode:
+    host only)."""
+    p, b = np.ascontiguousarray(pos, np.uint64), np.ascontiguousarray(byte, np.uint8)
+    assert len(p) == len(b)
+    out = np.empty(max(edits_bound(len(p), total_bases), 64), np.uint8)
+    ol = C.c_uint64(0)
+    rc = _lib.lib().bfq_edits_encode(_ptr(p) if len(p) else None, _ptr(b) if len(b) else None, len(p), n_reads, total_bases, shape, target_sum,
+                                     _ptr(out), len(out), C.byref(ol))
+    if rc:
+        raise EditsError(rc, "bfq_edits_encode: positions not ascending or not below the bases, or a byte outside 33..126")
+    return out[:int(ol.value)]
+
+
+def edits_decode(member):
+    """ONE BFQEDIT1 member -> dict(pos, byte, n_reads, total_bases, n_edits, shape, target_sum) (bfq_edits_decode: host only).
+    A member that is not well formed: EditsError with first_bad."""
+    z = _u8(member)
+    cap = max(len(z), 1)                                           # a member holds a byte per edit
+    p, b = np.empty(cap, np.uint64), np.empty(cap, np.uint8)
+    v = [C.c_uint64(0) for _ in range(6)]
+    rc = _lib.lib().bfq_edits_decode(_ptr(z) if len(z) else None, len(z), _ptr(p), _ptr(b), cap, *[C.byref(x) for x in v])
+    if rc:
+        fb = None if v[5].value == (1 << 64) - 1 else int(v[5].value)
+        raise EditsError(rc, "bfq_edits_decode: " + _edits_err() + ("" if fb is None else f": edit {fb}"), fb)
+    n = int(v[2].value)
+    return dict(pos=p[:n], byte=b[:n], n_reads=int(v[0].value), total_bases=int(v[1].value), n_edits=n, shape=int(v[3].value),
+                target_sum=int(v[4].value))
+
+
+def fastq_edits_host(a, b, out=None):
+    """bfq_fastq_edits_host: the BFQEDIT1 member of the run that made text b from text a, on one thread of the host (the
+    statement the device path is tested against).  Returns (member, EditStats)."""
+    a, b = _u8(a), _u8(b)
+    out = out if out is not None else np.empty(max(edits_bound(len(a) // 2, len(a) // 2), 64), np.uint8)
+    ol, st = C.c_uint64(0), _lib.EditStats()
+    rc = _lib.lib().bfq_fastq_edits_host(_ptr(a) if len(a) else None, len(a), _ptr(b) if len(b) else None, len(b), _ptr(out), len(out),
+                                         C.byref(ol), C.byref(st))
+    if rc:
+        raise EditsError(rc, _edits_err())
+    return out[:int(ol.value)], st
+
+
+def fastq_unedit_host(text, edits, out=None):
+    """bfq_fastq_unedit_host: text with the input's bases written back from the members of `edits`.  Returns (text, EditStats)."""
+    t, z = _u8(text), _u8(edits)
+    out = out if out is not None else np.empty(max(len(t), 1), np.uint8)
+    ol, st = C.c_uint64(0), _lib.EditStats()
+    rc = _lib.lib().bfq_fastq_unedit_host(_ptr(t) if len(t) else None, len(t), _ptr(z) if len(z) else None, len(z), _ptr(out), len(out),
+                                          C.byref(ol), C.byref(st))
+    if rc:
+        raise EditsError(rc, _edits_err())
+    return out[:int(ol.value)], st
 
 
 def perm_bound(n_reads):

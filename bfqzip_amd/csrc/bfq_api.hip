@@ -27,7 +27,8 @@ const char *const BFQ_KERNEL_NAMES[K_NUM] = {
     "k_restore_index", "k_fq_format_lines", "k_reorder_keys", "k_reorder_gather",
     "k_fq_format_ordered", "k_perm_pack", "k_perm_invert", "k_posbin_l1", "k_posbin_l2", "k_posbin_apply", "k_posbin_check",
     "k_cmp_check", "k_cmp_compare", "k_cmp_emit", "k_bgzf_inflate", "k_bgzf_deflate", "k_ubam_size", "k_ubam_write", "k_pairs_cmp", "k_pairs_move",
-    "k_km_hist", "k_km_count", "k_km_emit", "k_km_rekey", "k_km_seg", "k_km_stats"};
+    "k_km_hist", "k_km_count", "k_km_emit", "k_km_rekey", "k_km_seg", "k_km_stats",
+    "k_edit_check", "k_edit_count", "k_edit_write", "k_edit_segw", "k_edit_pack", "k_edit_unpack", "k_edit_locate", "k_edit_apply"};
 
 static thread_local std::string g_createErr;
 
@@ -1190,15 +1191,20 @@ extern "C" int bfq_fastq_build_ebwt_fd(bfq_ctx *c, int fastq_fd, uint64_t len, i
     });
 }
 
-extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
+// E: the run's base edits are wanted too (bfq_fastq_run_job_edits), nullptr: not
+static int fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_job_edits *E, bfq_stats *st)
 {
+    if (E && !E->out_edits) E = nullptr;
     return guarded(c, [&] {
         if (st) memset(st, 0, sizeof *st);
         if (!J || J->nparts < 1 || J->nparts > BFQ_MAX_PARTS || !J->parts) throw BfqError{BFQ_E_ARG, "bfq_fastq_job: 1..BFQ_MAX_PARTS parts"};
         const int np = J->nparts;
         J->fastq_len = J->stream_len = J->hdr_len = J->n_reads = J->total_bases = 0;
         J->dna_bytes = J->qs_bytes = J->hdr_bytes = 0;
+        if (E) E->edits_bytes = 0;
         const bool cz = J->compress_streams != 0;
+        if (E && (J->compress_streams == 2 || J->compress_streams == 3))
+            throw BfqError{BFQ_E_ARG, "bfq_fastq_run_job_edits: out_edits needs the bases in read order (compress_streams 0 or 1)"};
         if (J->name_codec != 0 && J->name_codec != 1) throw BfqError{BFQ_E_ARG, "bfq_fastq_job: name_codec is 0 or 1"};
         if (J->qual_codec != 0 && J->qual_codec != 1) throw BfqError{BFQ_E_ARG, "bfq_fastq_job: qual_codec is 0 or 1"};
         if (J->qual_codec == 1 && J->compress_streams == 2) throw BfqError{BFQ_E_ARG, "bfq_fastq_job: qual_codec needs qualities in read order (compress_streams 1 or 3)"};
@@ -1276,6 +1282,19 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
         if (J->out_dna || J->out_qs) { J->stream_len = sl; if (!cz) { J->dna_bytes = J->out_dna ? sl : 0; J->qs_bytes = J->out_qs ? sl : 0; } }
         c->release(m);                                         // the formatted text may reuse the pipeline's space:
         c->d_bwt = c->d_qual = nullptr; c->d_lcp = nullptr; c->d_gcnt = nullptr;   // the eBWT is gone (bfq_fetch_ebwt refuses)
+        if (E) {                                               // the run's base edits (BFQEDIT1): the parsed input bases against the output's
+            const size_t me = c->mark();
+            u8 *d_z = nullptr;
+            const u64 el = bfq_edits_make(c, EdSide{fq.bases, nullptr, 0}, EdSide{ob, nullptr, lines ? 1u : 0u}, fq.roff, fq.N, fq.total, E->cap_edits, &d_z, nullptr);
+            E->edits_bytes = el;
+            if (!d_z) {
+                char b[160];
+                snprintf(b, sizeof b, "the edits container needs %llu bytes, the buffer has %llu (cap_edits)", (unsigned long long)el, (unsigned long long)E->cap_edits);
+                throw BfqError{BFQ_E_ARG, b};
+            }
+            bfq_download(c, E->out_edits, d_z, el);
+            c->release(me);
+        }
         if (wantLines && cz) {                                 // step 5 on the device, in the space the pipeline has left
             const size_t mz = c->mark();
             const u64 bound = bfq_codec_bound(sl) < J->cap_stream ? bfq_codec_bound(sl) : J->cap_stream;
@@ -1324,6 +1343,9 @@ extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st)
         }
     });
 }
+
+extern "C" int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *J, bfq_stats *st) { return fastq_run_job(c, J, nullptr, st); }
+extern "C" int bfq_fastq_run_job_edits(bfq_ctx *c, bfq_fastq_job *J, bfq_job_edits *E, bfq_stats *st) { return fastq_run_job(c, J, E, st); }
 
 extern "C" int bfq_fastq_run(bfq_ctx *c, const uint8_t *h_fastq, uint64_t len, int keep_headers, uint8_t *h_out,
                              uint64_t cap, uint64_t *out_len, bfq_stats *st)

@@ -33,7 +33,8 @@ enum BfqKernel {
     K_INVERT_COUNT, K_INVERT, K_SYNTH, K_FASTQ, K_BFS, K_CODEC, K_MISC, K_RESTORE, K_FQ_FORMAT, K_RO_KEYS, K_RO_GATHER,
     K_FQ_FORMAT_ORD, K_PERM_PACK, K_PERM_INVERT, K_POSBIN_L1, K_POSBIN_L2, K_POSBIN_APPLY, K_POSBIN_CHECK,
     K_CMP_CHECK, K_CMP_COMPARE, K_CMP_EMIT, K_BGZF, K_DEFLATE, K_UBAM_SIZE, K_UBAM_WRITE, K_PAIRS_CMP, K_PAIRS_MOVE,
-    K_KM_HIST, K_KM_COUNT, K_KM_EMIT, K_KM_REKEY, K_KM_SEG, K_KM_STATS, K_NUM
+    K_KM_HIST, K_KM_COUNT, K_KM_EMIT, K_KM_REKEY, K_KM_SEG, K_KM_STATS,
+    K_EDIT_CHECK, K_EDIT_COUNT, K_EDIT_WRITE, K_EDIT_SEGW, K_EDIT_PACK, K_EDIT_UNPACK, K_EDIT_LOCATE, K_EDIT_APPLY, K_NUM
 };
 extern const char *const BFQ_KERNEL_NAMES[K_NUM];
 
@@ -543,3 +544,28 @@ void bfq_kmers_emit(bfq_ctx *c, const KmText &T, u32 k, u32 canonical, u32 binLo
 SortRec bfq_kmers_sort(bfq_ctx *c, SortRec a, SortRec b, u64 n, u32 k);   // the records start in a; returns the buffer that holds the result
 size_t bfq_kmers_seg_bytes(u64 n);                                        // arena bytes of bfq_kmers_runs
 void bfq_kmers_runs(bfq_ctx *c, SortRec S, u64 n, u32 k, u32 solid, u64 *heads, struct bfq_kmer_report *d_rep, struct bfq_kmer_entry *d_list, u64 capList);
+
+// a run's base edits as the container BFQEDIT1 (k_edits.hip; bfq_edits.hip drives them; layout: bfq_edits.h).  One side of a
+// make, or the target of an apply: where read r's bases lie -- rec != nullptr: at buf + rec[r].seqStart (a FASTQ text and its
+// record index), else at buf + roff[r] (+ r when `lines`: a line stream).  roff: N + 1 entries, the g of every read's first base.
+struct EdSide { const u8 *buf; const FqRec *rec; u32 lines; };
+void bfq_edit_check(bfq_ctx *c, EdSide A, EdSide B, const u64 *roff, u64 rBase, u64 n, u64 *d_badRead, u64 *d_shape);   // *d_badRead preset to all-ones, *d_shape to 0
+void bfq_edit_count(bfq_ctx *c, EdSide A, EdSide B, const u64 *roff, u64 N, u64 total, u32 *cnt, u64 *d_sums);           // d_sums[0] += reads touched
+void bfq_edit_write(bfq_ctx *c, EdSide A, EdSide B, const u64 *roff, u64 N, u64 E, u32 *cnt, const u64 *off, u64 *pos, u8 *byte, u64 *d_sums);   // d_sums[1] += target_sum
+void bfq_edit_segw(bfq_ctx *c, const u64 *pos, const u8 *byte, u64 E, u64 *first, u8 *wt, u64 *words, u64 *d_badEdit);
+void bfq_edit_pack(bfq_ctx *c, const u64 *pos, u64 E, const u8 *wt, const u64 *wordOff, u64 *gaps);
+void bfq_edit_unpack(bfq_ctx *c, const u64 *first, const u8 *wt, const u64 *gaps, const u64 *wordOff, u64 E, u64 *pos, u64 *d_badEdit);
+void bfq_edit_locate(bfq_ctx *c, const u64 *pos, const u8 *byte, u64 E, u64 T, u64 gBase, EdSide X, const u64 *roff, u64 N, u64 *addr, u64 *d_badEdit,
+                     u64 *d_sums);
+void bfq_edit_apply(bfq_ctx *c, const u64 *addr, const u8 *byte, u64 E, u8 *buf);
+// bfq_edits.hip.  The arena is the caller's: what they allocate stays above the current top.
+//   bfq_edits_make : the member of the edits between A ("before") and B ("after") at *d_member, its length returned.  cap: the
+//                    room the caller has for it; a member that does not fit is not made: *d_member = nullptr and the return
+//                    is a size that suffices (exact when at least its bytes fit).  Sides that are texts are held against each
+//                    other read by read first (BFQ_E_ARG naming the first read whose length differs).
+//   bfq_edits_apply: every member of [h_edits, h_edits + len) unpacked and held against the target (N reads, roff, `total`
+//                    bases); only then are the bytes written to d_buf.  Any refusal: BFQ_E_ARG, nothing written.
+size_t bfq_edits_make_need(u64 N, u64 total, u64 cap);
+u64 bfq_edits_make(bfq_ctx *c, EdSide A, EdSide B, const u64 *roff, u64 N, u64 total, u64 cap, u8 **d_member, bfq_edit_stats *st);
+size_t bfq_edits_apply_need(const u8 *h_edits, u64 len);           // throws BFQ_E_ARG when the bytes are no members
+void bfq_edits_apply(bfq_ctx *c, const u8 *h_edits, u64 len, u8 *d_buf, EdSide X, const u64 *roff, u64 N, u64 total, bfq_edit_stats *st);

@@ -386,14 +386,20 @@ struct RsSink {
 };
 
 // permz != nullptr: the records leave in the order before the reordering whose BFQPERM1 container this is
+// edits != nullptr: the BFQEDIT1 members of the run's base edits: the decoded DNA lines get the input's bytes back, in the
+// order of the run, before the text is formatted (no second pass over it)
 static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const RsSrc &hdr, bool haveHdr, const RsSink &sink,
-                         uint64_t *out_len, uint64_t *n_reads, const RsSrc *permz = nullptr)
+                         uint64_t *out_len, uint64_t *n_reads, const RsSrc *permz = nullptr, const RsSrc *edits = nullptr)
 {
     if (out_len) *out_len = 0;
     if (n_reads) *n_reads = 0;
     RsPlan P;
     rs_plan(dna, qs, hdr, haveHdr, P);
-    const size_t afterDecode = rs_index_bytes(P, permz != nullptr) + P.textBound + 4096 + (sink.extraWs ? sink.extraWs(P.textBound) : 0);
+    size_t editsWs = 0;                                           // bytes that are no members take no room: they are refused where the
+    if (edits) {                                                  // edits are applied, after the streams have had their say
+        try { editsWs = bfq_edits_apply_need(edits->h, edits->len); } catch (const BfqError &) {}
+    }
+    const size_t afterDecode = rs_index_bytes(P, permz != nullptr) + P.textBound + 4096 + (sink.extraWs ? sink.extraWs(P.textBound) : 0) + editsWs;
     u8 *dD = nullptr, *dQ = nullptr, *dH = nullptr;
     u64 lenD = P.rawD, lenQ = P.rawQ;
     if (P.ebwt) {
@@ -467,6 +473,12 @@ static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const Rs
         }
         inv = iv;
     }
+    if (edits) {                                                  // every member is held against the streams before a base is written
+        u64 total = 0;
+        HIP_CHECK(hipMemcpyAsync(&total, roff + N, 8, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        bfq_edits_apply(c, edits->h, edits->len, dD, EdSide{dD, nullptr, 1u}, roff, N, total, nullptr);
+    }
     if (ol > sink.cap) throw BfqError{BFQ_E_ARG, "output buffer smaller than the FASTQ text (see bfq_fastq_restore_bound)"};
     if (sink.sized) sink.sized(ol);
     if (inv) {                                                    // the same sizes in output order: the same total
@@ -484,7 +496,8 @@ static void restore_core(bfq_ctx *c, const RsSrc &dna, const RsSrc &qs, const Rs
 }
 
 static int rs_run_mem(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len, const uint8_t *h_hdr,
-                      uint64_t hdr_len, const RsSrc *permz, uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads)
+                      uint64_t hdr_len, const RsSrc *permz, uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads,
+                      const RsSrc *edits = nullptr)
 {
     return guarded(c, [&] {
         if (!h_dna || !h_qs || (!h_out && cap)) throw BfqError{BFQ_E_ARG, "null argument"};
@@ -495,7 +508,7 @@ static int rs_run_mem(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const 
             bfq_download(c, h_out, d_text, len);
             c->sync();                                            // pinned destinations are written by asynchronous DMA
         };
-        restore_core(c, RsSrc{h_dna, dna_len}, RsSrc{h_qs, qs_len}, RsSrc{h_hdr, hdr_len}, h_hdr != nullptr, sink, out_len, n_reads, permz);
+        restore_core(c, RsSrc{h_dna, dna_len}, RsSrc{h_qs, qs_len}, RsSrc{h_hdr, hdr_len}, h_hdr != nullptr, sink, out_len, n_reads, permz, edits);
     });
 }
 
@@ -530,15 +543,18 @@ struct RsMap {
 };
 
 static int rs_run_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len, bool ordered,
-                     int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads)
+                     int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads, int edits_fd = -1, uint64_t edits_len = 0)
 {
     if (out_len) *out_len = 0;
     if (n_reads) *n_reads = 0;
     return guarded(c, [&] {
         if (dna_fd < 0 || qs_fd < 0 || out_fd < 0 || (ordered && perm_fd < 0)) throw BfqError{BFQ_E_ARG, "bad file descriptor"};
         const bool haveHdr = hdr_fd >= 0;
-        RsMap mD, mQ, mH, mP;
+        RsMap mD, mQ, mH, mP, mE;
+        const bool edited = edits_fd >= 0;
         struct stat st;
+        if (edited && fstat(edits_fd, &st) == 0 && S_ISREG(st.st_mode) && (u64)st.st_size < edits_len) edits_len = (u64)st.st_size;   // (refused as members below)
+        const RsSrc editz{edited ? mE.open(edits_fd, edits_len) : nullptr, edited ? edits_len : 0};
         if (ordered && fstat(perm_fd, &st) == 0 && S_ISREG(st.st_mode) && (u64)st.st_size < permz_len) permz_len = (u64)st.st_size;   // (refused as a container below)
         const RsSrc permz{ordered ? mP.open(perm_fd, permz_len) : nullptr, ordered ? permz_len : 0};
         const RsSrc dna{mD.open(dna_fd, dna_len), dna_len}, qs{mQ.open(qs_fd, qs_len), qs_len};
@@ -558,7 +574,7 @@ static int rs_run_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64
             bfq_write_wait(c);
         };
         uint64_t ol = 0;
-        restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads, ordered ? &permz : nullptr);
+        restore_core(c, dna, qs, hdr, haveHdr, sink, &ol, n_reads, ordered ? &permz : nullptr, edited ? &editz : nullptr);
         F.commit(&ol);
         if (out_len) *out_len = ol;
     });
@@ -574,6 +590,24 @@ extern "C" int bfq_fastq_restore_ordered_fd(bfq_ctx *c, int dna_fd, uint64_t dna
                                             int perm_fd, uint64_t permz_len, int out_fd, uint64_t *out_len, uint64_t *n_reads)
 {
     return rs_run_fd(c, dna_fd, dna_len, qs_fd, qs_len, hdr_fd, hdr_len, true, perm_fd, permz_len, out_fd, out_len, n_reads);
+}
+
+// bfq_fastq_restore_ordered with an optional permutation and optional edits
+extern "C" int bfq_fastq_restore_edited(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                                        const uint8_t *h_hdr, uint64_t hdr_len, const uint8_t *h_permz, uint64_t permz_len,
+                                        const uint8_t *h_edits, uint64_t edits_len, uint8_t *h_out, uint64_t cap, uint64_t *out_len,
+                                        uint64_t *n_reads)
+{
+    const bool ordered = h_permz != nullptr || permz_len != 0, edited = h_edits != nullptr || edits_len != 0;
+    const RsSrc permz{h_permz, permz_len}, editz{h_edits, edits_len};
+    return rs_run_mem(c, h_dna, dna_len, h_qs, qs_len, h_hdr, hdr_len, ordered ? &permz : nullptr, h_out, cap, out_len, n_reads, edited ? &editz : nullptr);
+}
+
+extern "C" int bfq_fastq_restore_edited_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                           int perm_fd, uint64_t permz_len, int edits_fd, uint64_t edits_len, int out_fd, uint64_t *out_len,
+                                           uint64_t *n_reads)
+{
+    return rs_run_fd(c, dna_fd, dna_len, qs_fd, qs_len, hdr_fd, hdr_len, perm_fd >= 0, perm_fd, permz_len, out_fd, out_len, n_reads, edits_fd, edits_len);
 }
 
 // The text deflated where it lies (bfq_deflate.hip): the FASTQ text never crosses to the host.

@@ -1,6 +1,6 @@
 // restore_main.cpp -- the way back from the compressed streams to a FASTQ file (not a tool of the reference, which leaves
 // this to `7z x` / `bsc d` + `paste`):
-//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z | -b [-a LIST|'*']] -o OUT.fq [-V]
+//     bfq_restore -d OUT.fq.dna.bsc -q OUT.fq.qs.bsc [-H OUT.h.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-E RUN.edits] [-z | -b [-a LIST|'*']] -o OUT.fq [-V]
 // The inputs are what `bsc e`, bfq_fastq_job.compress_streams = 1 / 2 / 3 and parallel.py --compress write
 // (include/bfqzip_hip.h, bfq_fastq_restore_fd).  -P PERM: the BFQPERM1 file `bfq_reorder -P` / `parallel.py --keep-order`
 // wrote for the run: the records come back in the order of the original file (bfq_fastq_restore_ordered_fd).
@@ -12,7 +12,9 @@
 // deflated on the device and never crosses to the host), with and without -P; not with -g / -G.  -b: the output is written as an
 // unaligned BAM instead (OUT.bam: bfq_fastq_restore_bam_fd, the restored text becomes unpaired records on the device and those
 // are deflated there), with and without -P; not with -z, -g / -G; with -a LIST|'*' the fields XX:T:value of the restored header
-// lines become aux tags of the records (bfq_ubam_tag_opts, as bfq_bam -w -a).  Exit status 0 on success; 1 with the library's message
+// lines become aux tags of the records (bfq_ubam_tag_opts, as bfq_bam -w -a).  -E RUN.edits: the BFQEDIT1 file of the run's base
+// edits (`bfq_edits`, `parallel.py --keep-bases`): the text comes back with the input's bases (bfq_fastq_restore_edited_fd),
+// with and without -P; not with -g / -G / -l (a grouped text goes through `bfq_edits -u`), -z or -b.  Exit status 0 on success; 1 with the library's message
 // otherwise, and then OUT.fq is left empty.
 #include <unistd.h>
 #include <sys/mman.h>
@@ -21,11 +23,12 @@
 
 static int usage(const char *argv0)
 {
-    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-z | -b [-a LIST|'*']] -o OUT.fq [-V]\n"
+    fprintf(stderr, "usage: %s -d DNA.bsc -q QS.bsc [-H HEADERS.bsc] [-P PERM | -g | -G FIRST[:COUNT] | -l] [-E RUN.edits] [-z | -b [-a LIST|'*']] -o OUT.fq [-V]\n"
                     "  -d <arg>  container(s) of the DNA stream (OUT.fq.dna; BFQDNAC1 / BFQRANS2 members, or one BFQEBWT1) (REQUIRED)\n"
                     "  -q <arg>  container(s) of the quality stream (OUT.fq.qs) (REQUIRED)\n"
                     "  -H <arg>  container(s) of the header stream (OUT.h); without it every header line is \"@\"\n"
                     "  -P <arg>  BFQPERM1 file of the reordering the collection went through: the text in the order before it\n"
+                    "  -E <arg>  BFQEDIT1 file of the run's base edits: the text with the input's bases; not with -g / -G / -l, -z, -b\n"
                     "  -g        block by block: one group of members (a block of a sharded run) on the device at a time\n"
                     "  -G <arg>  FIRST[:COUNT]: only these groups of the plan (COUNT omitted: to the end)\n"
                     "  -l        print the plan of the groups and exit (no GPU, no output file; -o not needed)\n"
@@ -71,18 +74,19 @@ static int list_groups(const InFile &fd, const InFile &fq, const InFile *fh)
 int main(int argc, char **argv)
 {
     bfq_phase("start");
-    std::string dna, qs, hdr, perm, output;
+    std::string dna, qs, hdr, perm, edits, output;
     bool grouped = false, list = false, bgzf = false, ubam = false, tags = false, verbose = false;
     bfq_ubam_tag_opts X = {};
     bfq_ubam_tag_stats TS = {};
     uint64_t first = 0, count = ~0ull;
     int opt;
-    while ((opt = getopt(argc, argv, "d:q:H:P:o:gG:lzba:Vh")) != -1) {
+    while ((opt = getopt(argc, argv, "d:q:H:P:E:o:gG:lzba:Vh")) != -1) {
         switch (opt) {
         case 'd': dna = optarg; break;
         case 'q': qs = optarg; break;
         case 'H': hdr = optarg; break;
         case 'P': perm = optarg; break;
+        case 'E': edits = optarg; break;
         case 'o': output = optarg; break;
         case 'g': grouped = true; break;
         case 'G': {
@@ -109,6 +113,11 @@ int main(int argc, char **argv)
                         "restore the archive in one piece (without -g)\n", perm.c_str());
         return usage(argv[0]);
     }
+    if (!edits.empty() && (grouped || list || bgzf || ubam)) {
+        fprintf(stderr, "bfq_restore: -E does not go with -g / -G / -l (the edits count from the first read of the archive: restore in one piece, or "
+                        "put the bases back into the grouped text with bfq_edits -u), nor with -z or -b\n");
+        return usage(argv[0]);
+    }
     if (bgzf && grouped) {
         fprintf(stderr, "bfq_restore: -z does not go with -g / -G: the grouped restore writes plain text; restore the archive in one piece (without -g), "
                         "or compress the text afterwards (bfq_bgzf -c)\n");
@@ -120,8 +129,8 @@ int main(int argc, char **argv)
     }
     if (tags && !ubam) { fprintf(stderr, "bfq_restore: -a needs -b: tags are written into a BAM\n"); return usage(argv[0]); }
     if (tags) { bfq_ubam_default_opts(&X.o); X.o.reserved = BFQ_UBAM_OPTS_TAGS; X.stats = &TS; }
-    InFile fd, fq, fh, fp;
-    if (!fd.open(dna) || !fq.open(qs) || (!hdr.empty() && !fh.open(hdr)) || (!perm.empty() && !fp.open(perm))) { fprintf(stderr, "bfq_restore: cannot read the inputs\n"); return 1; }
+    InFile fd, fq, fh, fp, fe;
+    if (!fd.open(dna) || !fq.open(qs) || (!hdr.empty() && !fh.open(hdr)) || (!perm.empty() && !fp.open(perm)) || (!edits.empty() && !fe.open(edits))) { fprintf(stderr, "bfq_restore: cannot read the inputs\n"); return 1; }
     if (list) return list_groups(fd, fq, hdr.empty() ? nullptr : &fh);
     OutFile outText;
     if (!outText.open(output)) { perror("bfq_restore"); return 1; }
@@ -158,6 +167,8 @@ int main(int argc, char **argv)
                                                    tags ? &X.o : nullptr, outText.fd, &outLen, &US)
                    : bgzf ? bfq_fastq_restore_bgzf_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd, fp.size, 1,
                                                     outText.fd, &outLen, &rawLen, &reads)
+                   : !edits.empty() ? bfq_fastq_restore_edited_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, perm.empty() ? -1 : fp.fd,
+                                                                  fp.size, fe.fd, fe.size, outText.fd, &outLen, &reads)
                    : grouped ? bfq_fastq_restore_grouped_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, first, count, outText.fd, &outLen, &reads)
                    : perm.empty() ? bfq_fastq_restore_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, outText.fd, &outLen, &reads)
                                 : bfq_fastq_restore_ordered_fd(c, fd.fd, fd.size, fq.fd, fq.size, hdr.empty() ? -1 : fh.fd, fh.size, fp.fd, fp.size,

@@ -431,14 +431,16 @@ def _pinned_outputs(kinds, cap):
 
 
 def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fastq=True, want_streams=False,
-              want_hdr=False, out_bufs=None, log=None, compress=False, pinned=False, name_codec=False, qual_codec=False):
+              want_hdr=False, out_bufs=None, log=None, compress=False, pinned=False, name_codec=False, qual_codec=False, edits_path=None):
     """The whole multi-GPU job.  eng: Engine-like (fastq_job, text_line_counts/text_nth_newline via `eng.host`).
     Returns per-rank totals {"blocks", "reads", "bases", "stats"} (stats summed over this rank's blocks).
     compress: step 5 too (BFQzip.py:253-275) -- every block's share of every output goes through the stream codec
     (eng.stream_compress) and the files `<name>.bsc` hold one BFQRANS2 container per block, in block order
     (`bsc d` / stream_decompress read them back as one stream).  name_codec: the header shares go through
     eng.names_compress instead (the tokenised BFQNAME1 container where it is shorter; restore takes either), qual_codec:
-    the quality shares through eng.quals_compress (BFQQUAL1 where it is shorter)."""
+    the quality shares through eng.quals_compress (BFQQUAL1 where it is shorter).  edits_path (--keep-bases; one input
+    file): every block's job also makes the BFQEDIT1 member of its base edits (fastq_job(edits=True)) and the file holds
+    the members in block order, like every other output."""
     host = eng.host
     bufs = [map_file(p) for p in inputs]
     idx = [TextIndex(b, comm, host.text_line_counts, host.text_nth_newline) for b in bufs]
@@ -453,8 +455,14 @@ def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fas
             for k in kinds:
                 open(names[o][k], "wb").close()
     comm.barrier()
+    if edits_path and comm.rank == 0:
+        open(edits_path, "wb").close()
+        comm.barrier()
+    elif edits_path:
+        comm.barrier()
     fds = {(o, k): os.open(names[o][k], os.O_RDWR) for o in range(nout) for k in kinds}       # (read too: the writer maps the file)
-    cursor = np.zeros((nout, 4), np.int64)                           # next free byte of every output file
+    fd_edits = os.open(edits_path, os.O_RDWR) if edits_path else -1
+    cursor = np.zeros((nout, 5), np.int64)                           # next free byte of every output file (column 4: the edits)
     tot = {"blocks": 0, "reads": 0, "bases": 0, "stats": {}}
     out_bufs = out_bufs if out_bufs is not None else {}
     pins = None
@@ -466,7 +474,7 @@ def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fas
     rounds = (nblocks + comm.world - 1) // comm.world
     for rd in range(rounds):
         k = rd * comm.world + comm.rank
-        sizes = np.zeros((2, 4), np.int64)
+        sizes = np.zeros((2, 5), np.int64)
         res = None
         if k < nblocks:
             b0, b1, _ = blocks[0][k]
@@ -475,7 +483,9 @@ def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fas
                 c0, c1, _ = blocks[1][k]
                 parts.append(bufs[1][c0:c1])
             res = eng.fastq_job(parts, keep_headers=headers, fastq=want_fastq, streams=want_streams, hdr=want_hdr,
-                                out=out_bufs)
+                                out=out_bufs, **(dict(edits=True) if edits_path else {}))
+            if edits_path:
+                sizes[0, 4] = len(res.edits)
             cut = {"fastq": res.part_fastq_off, "dna": res.part_stream_off, "qs": res.part_stream_off,
                    "hdr": res.part_hdr_off}
             raw = {"fastq": res.fastq, "dna": res.dna, "qs": res.qs, "hdr": res.hdr}
@@ -498,7 +508,7 @@ def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fas
                 tot["stats"][key] = tot["stats"].get(key, 0) + v
             if log:
                 log(f"block {k + 1}/{nblocks}: {res.n_reads} reads, {res.total_bases} bases")
-        allsz = comm.all_gather_i64(sizes.reshape(-1)).reshape(comm.world, 2, 4)
+        allsz = comm.all_gather_i64(sizes.reshape(-1)).reshape(comm.world, 2, 5)
         before = allsz[:comm.rank].sum(axis=0)                       # blocks of this round that come first
         if res is not None:
             data = {"fastq": res.fastq, "dna": res.dna, "qs": res.qs, "hdr": res.hdr}
@@ -508,9 +518,13 @@ def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fas
                         lo = cut[kind][o]
                         piece = blobs[(o, kind)] if compress else data[kind][lo:lo + int(sizes[o, ki])]
                         pwrite_all(fds[(o, kind)], piece, int(cursor[o, ki] + before[o, ki]), host)
+            if edits_path:
+                pwrite_all(fd_edits, res.edits, int(cursor[0, 4] + before[0, 4]), host)
         cursor += allsz.sum(axis=0)[:nout]
     for fd in fds.values():
         os.close(fd)
+    if fd_edits >= 0:
+        os.close(fd_edits)
     if pins:
         for pb in pins.values():
             pb.free()
@@ -518,17 +532,23 @@ def run_files(eng, comm, inputs, t, names, paired=False, headers=False, want_fas
     return tot
 
 
-def restore_files(eng, comm, dna_path, qs_path, hdr_path, out_path, log=None):
+def restore_files(eng, comm, dna_path, qs_path, hdr_path, out_path, log=None, edits_path=None):
     """The way back of run_files(.., compress=True) on as many GPUs as it was written with: the three .bsc files are mapped,
     every rank computes the group plan from the container headers (eng.host.restore_groups: one group per block), group k
     goes to rank k mod world (eng.fastq_restore(.., groups=(k, 1))), after every round the text lengths are all-gathered
     (one integer per rank) and every rank writes its text at its final offset.  No payload collective, nothing per read on
     the host.  hdr_path may be None ("@" lines).  The two mates of a paired run are two invocations.  Returns this rank's
-    totals {"groups", "reads", "bytes"} with "bytes_all" = the length of the whole text."""
+    totals {"groups", "reads", "bytes"} with "bytes_all" = the length of the whole text.  edits_path (--keep-bases): the
+    BFQEDIT1 file the run wrote, one member per block = per group: the text of group k gets the input's bases back from
+    member k (eng.fastq_unedit) before it is written."""
+    from . import api
     host = eng.host
     dna, qs = map_file(dna_path), map_file(qs_path)
     hdr = map_file(hdr_path) if hdr_path is not None else None
     plan = host.restore_groups(dna, qs, hdr)
+    members = api.edits_members(map_file(edits_path)) if edits_path is not None else None
+    if members is not None and len(members) != len(plan):
+        raise ValueError(f"{edits_path}: {len(members)} members for an archive of {len(plan)} blocks")
     if comm.rank == 0:
         open(out_path, "wb").close()
     comm.barrier()
@@ -542,6 +562,8 @@ def restore_files(eng, comm, dna_path, qs_path, hdr_path, out_path, log=None):
             text, n = None, 0
             if k < len(plan):
                 text, n = eng.fastq_restore(dna, qs, hdr, groups=(k, 1))
+                if members is not None:
+                    text, _ = eng.fastq_unedit(text, members[k])
                 tot["groups"] += 1; tot["reads"] += n; tot["bytes"] += len(text)
                 if log:
                     log(f"group {k + 1}/{len(plan)}: {n} reads, {len(text)} bytes")
@@ -780,6 +802,11 @@ def main(argv=None):
     ap.add_argument("--keep-order", action="store_true",
                     help="with --reorder 1|2: keep the permutation as <first reordered intermediate>.perm and give the merged "
                          "FASTQ text back in input order (streams and --compress containers stay in run order: bfq_restore -P)")
+    ap.add_argument("--keep-bases", action="store_true",
+                    help="bases back exactly: every block's job also keeps the input's byte at every base the run changed; the "
+                         "BFQEDIT1 members go to OUT.edits in block order (one input file; not with --global).  With --restore: "
+                         "OUT.edits is read and the text comes back with the input's bases")
+    ap.add_argument("--edits", default="", metavar="PATH", help="with --keep-bases: the BFQEDIT1 file, instead of <output>.edits")
     ap.add_argument("--reorder-k", type=int, default=21, help="k-mer length of --reorder 2 (8..32)")
     ap.add_argument("--seed", type=int, default=0, help="seed of --reorder 1")
     ap.add_argument("--report", action="store_true",
@@ -898,6 +925,23 @@ def main(argv=None):
         if why:
             print("=== ERROR ===\n" + why, file=sys.stderr)
             return 1
+    if a.keep_bases:
+        why = None
+        if a.glob:
+            why = ("--keep-bases does not go with --global: the edits of a collection are made where one job holds its bases before and "
+                   "after the run, and the global mode spreads them over the ranks; run the blocks without --global, or make the file "
+                   "afterwards with bfq_edits -a IN.fq -b OUT.fq")
+        elif not a.restore and (a.paired or len(a.input) != 1):
+            why = "--keep-bases takes one input file: the member of a block covers both mates, the outputs of a paired run are cut by mate"
+        elif not a.restore and a.keep_order and a.reorder and not ((a.m2 or a.m3) and a.streams_only) and not (a.compress and not a.m0):
+            why = ("--keep-bases with --keep-order: the edits are in run order, the merged FASTQ text goes back to input order; use "
+                   "--compress (bfq_restore -P PERM -E OUT.edits undoes both) or --streams-only")
+        if why:
+            print("=== ERROR ===\n" + why, file=sys.stderr)
+            return 1
+    elif a.edits:
+        print("=== ERROR ===\n--edits names the file of --keep-bases", file=sys.stderr)
+        return 1
     if a.restore and (len(a.input) not in (2, 3) or not a.out):
         print("=== ERROR ===\n--restore DNA.bsc QS.bsc [HDR.bsc] -o OUT.fq", file=sys.stderr)
         return 1
@@ -937,7 +981,8 @@ def main(argv=None):
     eng = api.Engine(local, **par)
     log = (lambda m: print(f"[rank {comm.rank}] {m}", flush=True)) if a.v else None
     if a.restore:
-        tot = restore_files(eng, comm, a.input[0], a.input[1], a.input[2] if len(a.input) == 3 else None, a.out, log=log)
+        tot = restore_files(eng, comm, a.input[0], a.input[1], a.input[2] if len(a.input) == 3 else None, a.out, log=log,
+                            edits_path=(a.edits or os.path.splitext(a.out)[0] + ".edits") if a.keep_bases else None)
         if a.v:
             print(f"[rank {comm.rank}] {tot}", flush=True)
         eng.close()
@@ -990,7 +1035,8 @@ def main(argv=None):
     else:
         tot = run_files(eng, comm, a.input, a.threads, names, paired=a.paired, headers=a.headers,
                         want_fastq=not (streams and a.streams_only), want_streams=streams, want_hdr=a.m3, log=log,
-                        compress=a.compress and not a.m0, pinned=a.pinned, name_codec=a.names, qual_codec=a.quals)
+                        compress=a.compress and not a.m0, pinned=a.pinned, name_codec=a.names, qual_codec=a.quals,
+                        edits_path=(a.edits or os.path.splitext(names[0]["hdr"])[0] + ".edits") if a.keep_bases else None)
     if perm_path:
         want_fastq = not (streams and a.streams_only)
         compress = a.compress and not a.m0 and not a.glob

@@ -220,6 +220,14 @@ typedef struct bfq_fastq_job {
     int32_t  reserved1;
 } bfq_fastq_job;
 int bfq_fastq_run_job(bfq_ctx *c, bfq_fastq_job *job, bfq_stats *st);
+/* ... and the run's base edits in the same call (BFQEDIT1, below).  bfq_fastq_job keeps its size and every offset: what the
+ * edits need travels in a structure of its own beside it.  edits NULL or out_edits NULL: exactly bfq_fastq_run_job, nothing
+ * of it runs.  Else the member of this job's collection -- the input's byte at every base the run changed -- goes to
+ * out_edits and edits_bytes receives its length; with compress_streams 2 or 3 (no read-order bases): BFQ_E_ARG.  cap_edits
+ * too small: BFQ_E_ARG, the message holds the size that suffices and edits_bytes keeps it; out_edits and the job's FASTQ text
+ * are untouched then. */
+typedef struct bfq_job_edits { uint8_t *out_edits; uint64_t cap_edits, edits_bytes; } bfq_job_edits;
+int bfq_fastq_run_job_edits(bfq_ctx *c, bfq_fastq_job *job, bfq_job_edits *edits, bfq_stats *st);
 
 /* ---- one collection over several GPUs with the UNSHARDED result (opt-in; not in the reference, whose parallel driver
  * gives up the clusters that span blocks, README.md:107).  The per-GPU pieces; bfqzip_amd/parallel.py --global holds the
@@ -611,6 +619,121 @@ int bfq_fastq_compare   (bfq_ctx *c, const bfq_text_part *a, int na, const bfq_t
                          bfq_compare_report *rep, bfq_compare_diff *h_diffs, uint64_t cap_diffs);
 int bfq_fastq_compare_fd(bfq_ctx *c, int a_fd, uint64_t a_len, int b_fd, uint64_t b_len, int perm_fd, uint64_t permz_len,
                          bfq_compare_report *rep, bfq_compare_diff *h_diffs, uint64_t cap_diffs);
+/* ---- bases back exactly: a run's base edits as a side file, the opt-in container "BFQEDIT1" (k_edits.hip, bfq_edits.hip;
+ * tests/edits_model.py states it in Python).  A run changes few bases (0.26 % at 30 M x 150); keeping the input's byte at those
+ * positions beside the smoothed output makes the bases lossless while the DNA stream keeps its ratio.
+ * An edit is (g, byte): g = the index of a base in the collection's read order -- base j of read r has g = read_off[r] + j, no
+ * newline or terminator counted --, byte = the INPUT's byte there.  Edits are strictly ascending in g.  All fields little endian.
+ *   header, 64 bytes: "BFQEDIT1" | u64 N (reads) | u64 T (bases) | u64 E (edits) | u32 S = 1024 | u32 flags = 0 | u64 shape |
+ *                     u64 target_sum | u64 payload (bytes after the header).  shape = sum over the reads of fmix64(r 65536 + len_r),
+ *                     target_sum = sum over the edits of fmix64(g 256 + b), b = the byte the RUN'S OUTPUT holds at g; both mod
+ *                     2^64, fmix64 = MurmurHash3's 64-bit finaliser (the reorder key's).  T <= 2^56, E <= T.
+ *   segment table   : a segment is S consecutive edits (the last may be shorter), nseg = ceil(E / S).  u64 first[nseg], the g of
+ *                     each segment's first edit, then u8 w[nseg], zero-padded to a multiple of 8 bytes.
+ *   gaps            : the gap of edit k is g_k - g_(k-1) - 1 >= 0.  A segment of c edits packs its c - 1 gaps (its first edit
+ *                     has none: `first` states it) w bits each, gap j in bits [j w, (j + 1) w) of the segment's bit stream, bit b
+ *                     being bit b % 64 of word b / 64 (BFQPERM1's order).  Every segment starts on a fresh u64 word and
+ *                     zero-pads its last one: ceil((c - 1) w / 64) words.
+ *   bytes           : the E input bytes in order, zero-padded to a multiple of 8.
+ *   w is canonical  : the bit length of the segment's largest gap, 0 when it has none or all are 0.  The container is a function
+ *                     of the edit list: the host form, the device form and the Python model give identical bytes.  E = 0 is a
+ *                     valid container of 64 bytes.
+ * Well formed: the magic, S = 1024, flags = 0, T <= 2^56, E <= T, every w <= 56, the stated length exact, all padding of the
+ * table and of the bytes zero -- faults of the header and the table, found before any edit is looked at; first_bad is then
+ * UINT64_MAX, except for a w above 56, whose first_bad is the first edit of that segment.  Then, per edit: every w canonical and
+ * the padding bits of a segment's last word zero (both charged to the segment's first edit), `first` above the position of the
+ * edit before it (that is: the positions strictly ascending), every g < T, every byte in 33..126.  The first offending edit
+ * is the smallest such k.
+ * Several members may follow one another, one per block of a sharded run, like every other stream of an archive: member m's
+ * positions (and its read indexes in `shape`) count from the first base (read) after the members before it.  N is bounded by
+ * nothing in the file (reads may be empty): whoever applies members holds every member's N and T against the reads and bases
+ * the target has left behind the members before it, before either sizes a copy or a launch; sums of N or T over members
+ * saturate at UINT64_MAX instead of wrapping.
+ * Host only (no GPU; the statement the kernels are tested against; messages: bfq_edits_host_error(), per thread):
+ *   bfq_edits_bound      : a capacity that always suffices for E edits in T bases (0 when T > 2^56 or E > T)
+ *   bfq_edits_member_len : bytes of the first member of the buffer, -1 when its header or table is not well formed
+ *   bfq_edits_info       : the sums of N, T and E over all members and their number; BFQ_E_ARG naming the member whose header or
+ *                          table is wrong (the edits are not looked at)
+ *   bfq_edits_encode     : the edit list -> one member; BFQ_E_ARG and nothing written when cap is too small, a position is
+ *                          >= T or not above the one before it, or a byte is outside 33..126
+ *   bfq_edits_decode     : ONE member of exactly len bytes -> h_pos[E], h_byte[E] and the header's fields (any may be NULL);
+ *                          BFQ_E_ARG and nothing written when it is not well formed (*first_bad as above) or cap_entries < E
+ *   bfq_fastq_edits_host : two plain FASTQ texts in the same read order, A the run's input, B its output -> the member.  One
+ *                          thread; refusals as bfq_fastq_edits
+ *   bfq_fastq_unedit_host: a plain FASTQ text and the members of its edits -> the text with the input's bases, every other
+ *                          byte as it was.  Refusals as bfq_fastq_unedit
+ * On the device:
+ *   bfq_edits_make_device : both base arrays in device memory, reads back to back, read r at d_read_off[r] of both (the layout
+ *                           of bfq_run_reads_device); the member goes to d_out (device memory too).  d_read_off[0] != 0,
+ *                           d_read_off[N] != total, a read longer than BFQ_MAX_READ_LEN or offsets that are not ascending
+ *                           (the first such read named): BFQ_E_ARG before a base is read; bfq_edits_apply_device likewise.  cap too small: BFQ_E_ARG, the
+ *                           message holds the size that suffices, stats->bytes too, nothing is written.
+ *   bfq_edits_apply_device: the members (host memory) unpacked and validated on the device, then written into d_bases: a base
+ *                           array as above, or, lines != 0, a line stream (read r at d_read_off[r] + r).
+ *   bfq_fastq_edits / _device / _fd: two FASTQ texts in the same read order (each 1..BFQ_MAX_PARTS parts taken as one, a BGZF
+ *                           part is inflated, a part without its final newline gets one, CR before LF dropped: as
+ *                           bfq_fastq_compare takes them; _device: one plain text each, in device memory) -> the member.
+ *                           Refusals, BFQ_E_ARG with *out_len = 0 and nothing written (a file left empty): the record counts
+ *                           differ (both named); a read's sequence length differs (the smallest such read and both lengths
+ *                           named); a differing byte of A outside 33..126 (the edit named); cap too small (the size named).
+ *                           The _fd form has no capacity: it makes the member in input length / 8 + 4096 bytes and, should
+ *                           that not do (more than about a tenth of the bases differ), once more in the size that suffices.
+ *   bfq_fastq_unedit / _fd: one FASTQ text (plain or BGZF) and one or more members -> the text with the input's bases,
+ *                           otherwise byte for byte the (inflated) text; the members' reads and bases must add up to the
+ *                           text's.  Refusals, BFQ_E_ARG and nothing written (the file left empty): bytes that are no members;
+ *                           a damaged member (the member and its first offending edit named); N, T or shape that are not the
+ *                           text's (the message names both numbers); a target_sum that is not that of the text's bytes at the
+ *                           edit positions: "the text is not the output these edits were made from".
+ *   A pass proves the pairs fit and sums `shape`; a pass counts the differing bytes per read, 8 bytes per lane, 16 lanes per
+ *   read; an exclusive scan; a pass writes (g, byte) in order; one wave per segment finds the largest gap and packs.  The way
+ *   back: positions by a wave scan per segment, one atomic min for the first offending edit, one lane per edit finds its read
+ *   by binary search in the read offsets; nothing is written before every check of every member has passed.  Device memory:
+ *   the texts + their indexes + 12 bytes per read + about 18 bytes per edit (make) / 25 (apply).
+ * bfq_fastq_run_job_edits (bfq_job_edits: out_edits / cap_edits / edits_bytes) makes the member of a job's run in the same call, from the parsed
+ * input bases and the output bases while both are still on the device -- in the fused, pile and capped modes alike; without
+ * out_edits no kernel of these is launched.
+ * bfq_fastq_restore_edited / _fd: bfq_fastq_restore_ordered / _fd with an optional permutation (h_permz NULL and permz_len 0 /
+ * perm_fd < 0: none) and optional edits (h_edits NULL and edits_len 0 / edits_fd < 0: none): read-order containers as
+ * bfq_fastq_restore takes them, with the members that the jobs of the same blocks wrote to out_edits, back to back in block
+ * order.  After the streams have been checked (their messages come first) and the permutation validated, the members are held
+ * against the decoded DNA lines -- reads, bases, shape, target_sum, with the refusals of bfq_fastq_unedit -- and the input's
+ * bytes written into them; then the text is formatted once.  The edits are in the order of the run, the permutation is
+ * applied after them.  Nothing is written to h_out / out_fd on any refusal.  The grouped restore takes no edits: a text
+ * restored group by group goes through bfq_fastq_unedit. */
+typedef struct bfq_edit_stats { uint64_t reads, bases, edits, reads_touched, bytes; } bfq_edit_stats;
+uint64_t bfq_edits_bound(uint64_t n_edits, uint64_t total_bases);
+int64_t  bfq_edits_member_len(const uint8_t *h_edits, uint64_t len);
+int bfq_edits_info(const uint8_t *h_edits, uint64_t len, uint64_t *n_reads, uint64_t *total_bases, uint64_t *n_edits, uint64_t *members);
+int bfq_edits_encode(const uint64_t *h_pos, const uint8_t *h_byte, uint64_t n_edits, uint64_t n_reads, uint64_t total_bases,
+                     uint64_t shape, uint64_t target_sum, uint8_t *h_out, uint64_t cap, uint64_t *out_len);
+int bfq_edits_decode(const uint8_t *h_edits, uint64_t len, uint64_t *h_pos, uint8_t *h_byte, uint64_t cap_entries,
+                     uint64_t *n_reads, uint64_t *total_bases, uint64_t *n_edits, uint64_t *shape, uint64_t *target_sum,
+                     uint64_t *first_bad);
+const char *bfq_edits_host_error(void);
+int bfq_fastq_edits_host(const uint8_t *a, uint64_t a_len, const uint8_t *b, uint64_t b_len, uint8_t *h_out, uint64_t cap,
+                         uint64_t *out_len, bfq_edit_stats *stats);
+int bfq_fastq_unedit_host(const uint8_t *text, uint64_t len, const uint8_t *h_edits, uint64_t edits_len, uint8_t *h_out,
+                          uint64_t cap, uint64_t *out_len, bfq_edit_stats *stats);
+int bfq_edits_make_device(bfq_ctx *c, const uint8_t *d_in_bases, const uint8_t *d_out_bases, const uint64_t *d_read_off, uint64_t N,
+                          uint64_t total, uint8_t *d_out, uint64_t cap, uint64_t *out_len, bfq_edit_stats *stats);
+int bfq_edits_apply_device(bfq_ctx *c, const uint8_t *h_edits, uint64_t edits_len, uint8_t *d_bases, const uint64_t *d_read_off,
+                           uint64_t N, uint64_t total, int lines, bfq_edit_stats *stats);
+int bfq_fastq_edits(bfq_ctx *c, const bfq_text_part *a, int na, const bfq_text_part *b, int nb, uint8_t *h_out, uint64_t cap,
+                    uint64_t *out_len, bfq_edit_stats *stats);
+int bfq_fastq_edits_device(bfq_ctx *c, const uint8_t *d_a, uint64_t a_len, const uint8_t *d_b, uint64_t b_len, uint8_t *d_out,
+                           uint64_t cap, uint64_t *out_len, bfq_edit_stats *stats);
+int bfq_fastq_edits_fd(bfq_ctx *c, int a_fd, uint64_t a_len, int b_fd, uint64_t b_len, int out_fd, uint64_t *out_len,
+                       bfq_edit_stats *stats);
+int bfq_fastq_unedit(bfq_ctx *c, const uint8_t *h_text, uint64_t len, const uint8_t *h_edits, uint64_t edits_len, uint8_t *h_out,
+                     uint64_t cap, uint64_t *out_len, bfq_edit_stats *stats);
+int bfq_fastq_unedit_fd(bfq_ctx *c, int text_fd, uint64_t len, int edits_fd, uint64_t edits_len, int out_fd, uint64_t *out_len,
+                        bfq_edit_stats *stats);
+int bfq_fastq_restore_edited(bfq_ctx *c, const uint8_t *h_dna, uint64_t dna_len, const uint8_t *h_qs, uint64_t qs_len,
+                             const uint8_t *h_hdr, uint64_t hdr_len, const uint8_t *h_permz, uint64_t permz_len,
+                             const uint8_t *h_edits, uint64_t edits_len, uint8_t *h_out, uint64_t cap, uint64_t *out_len, uint64_t *n_reads);
+int bfq_fastq_restore_edited_fd(bfq_ctx *c, int dna_fd, uint64_t dna_len, int qs_fd, uint64_t qs_len, int hdr_fd, uint64_t hdr_len,
+                                int perm_fd, uint64_t permz_len, int edits_fd, uint64_t edits_len, int out_fd, uint64_t *out_len,
+                                uint64_t *n_reads);
 /* ---- which k-mers a run removed, kept and created: the k-mer spectrum of one FASTQ text, or of two side by side (k_kmers.hip,
  * bfq_kmers.hip; tests/kmers_model.py states it in Python).  bfq_fastq_compare says how much a run touched; this says whether
  * what it touched was noise: a sequencing error makes up to k k-mers that occur once, a real allele makes k-mers that occur
