@@ -310,7 +310,7 @@ void bfq_lcp_from_bwt(bfq_ctx *c, const u8 *bwt, u64 n, u64 N, int term, u16 *lc
         c->sync();
         void *dp = nullptr;
         HIP_CHECK(hipHostGetDevicePointer(&dp, hp, 0));
-        if (bfq_env().trace)
+        if (c->env.trace)
             fprintf(stderr, "[bfq] interval refinement: level %u holds %llu intervals, the ring %llu: queue moved to %.2f GB of pinned host memory\n",
                     level, (unsigned long long)live, (unsigned long long)a.qsize, room * 8 / 1e9);
         a.queue = (u64 *)((uintptr_t)dp - (uintptr_t)from * 8);    // indexed by absolute position from here on
@@ -355,7 +355,7 @@ void bfq_lcp_from_bwt(bfq_ctx *c, const u8 *bwt, u64 n, u64 N, int term, u16 *lc
         nside = t[1 + (cur ^ 1)];
         cur ^= 1;
     }
-    if (bfq_env().trace && ringEntries)
+    if (c->env.trace && ringEntries)
         fprintf(stderr, "[bfq] interval refinement: ring of %llu entries for %llu rows, at most %u launches per level%s\n",
                 (unsigned long long)ringEntries, (unsigned long long)n, chunksMax, hostQ.p ? ", finished in host memory" : "");
     // every LCP entry 1..n is written exactly once

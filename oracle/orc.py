@@ -81,6 +81,18 @@ def smooth_invert(bwt, qs, lcp, p):
     return ob[:tot].copy(), oq[:tot].copy(), oroff, st.as_dict()
 
 
+def lcp_from_bwt(bwt, term=ord("#")):
+    """LCP array (uint32[n]) of a given eBWT, identical suffixes in any order: every row's suffix located by LF walks,
+    neighbours compared directly, terminators never matching (what smooth_invert uses when lcp is None)."""
+    bwt = np.ascontiguousarray(bwt, np.uint8)
+    n = len(bwt)
+    lcp = np.empty(n, np.uint32)
+    rc = lib().orc_lcp_from_bwt(_p(bwt), C.c_uint64(n), int(term), _p(lcp, C.c_uint32))
+    if rc:
+        raise RuntimeError(f"orc_lcp_from_bwt rc={rc}")
+    return lcp
+
+
 def run_reads(bases, quals, roff, p):
     N = len(roff) - 1
     bases = np.ascontiguousarray(bases, np.uint8); quals = np.ascontiguousarray(quals, np.uint8)
