@@ -52,6 +52,7 @@ SYMBOLS = [
     "bfq_fastq_deinterleave_measure", "bfq_fastq_deinterleave", "bfq_fastq_deinterleave_device", "bfq_fastq_deinterleave_fd", "bfq_fastq_deinterleave_host",
     "bfq_fastq_interleave_measure", "bfq_fastq_interleave", "bfq_fastq_interleave_device", "bfq_fastq_interleave_fd", "bfq_fastq_interleave_host",
     "bfq_repair_default_opts", "bfq_fastq_repair_measure", "bfq_fastq_repair", "bfq_fastq_repair_device", "bfq_fastq_repair_fd", "bfq_fastq_repair_host",
+    "bfq_dedup_default_opts", "bfq_dedup_host_error", "bfq_fastq_dedup_measure", "bfq_fastq_dedup", "bfq_fastq_dedup_device", "bfq_fastq_dedup_fd", "bfq_fastq_dedup_host",
     "bfq_workspace_bytes", "bfq_workspace_read", "bfq_version",
 ]
 
@@ -230,6 +231,25 @@ class RepairStats(C.Structure):
 
     def __repr__(self):
         return "RepairStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
+
+
+class DedupOpts(C.Structure):
+    """bfq_dedup_opts: keep (0: the first unit of a group, 1: the best qualities), hash_bits (1..40), seed, reserved[2] (must be 0)"""
+    _fields_ = [("keep", C.c_uint32), ("hash_bits", C.c_uint32), ("seed", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+class DedupStats(C.Structure):
+    """bfq_dedup_stats: units, kept, removed, dup_groups, max_group, max_group_first, level_groups[32], level_units[32], out_len[2],
+    dup_len[2], mixed_runs, max_run, rounds"""
+    _fields_ = ([(k, C.c_uint64) for k in ("units", "kept", "removed", "dup_groups", "max_group", "max_group_first")] +
+                [("level_groups", C.c_uint64 * 32), ("level_units", C.c_uint64 * 32), ("out_len", C.c_uint64 * 2), ("dup_len", C.c_uint64 * 2)] +
+                [(k, C.c_uint64) for k in ("mixed_runs", "max_run", "rounds")])
+
+    def as_dict(self):
+        return {k: [int(v) for v in getattr(self, k)] if hasattr(getattr(self, k), "__len__") else int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "DedupStats(%s)" % ", ".join("%s=%s" % kv for kv in self.as_dict().items())
 
 
 CMP_SYMS = 6
@@ -526,6 +546,16 @@ def lib():
         L.bfq_fastq_repair_device.argtypes = [vp, C.POINTER(vp), a3, pro, C.POINTER(vp), a3, a3, a3, prs]
         L.bfq_fastq_repair_fd.argtypes = [vp, i3, pro, i3, a3, a3, prs]
         L.bfq_fastq_repair_host.argtypes = [C.POINTER(vp), a3, pro, C.POINTER(vp), a3, a3, a3, prs]
+        pdo, pds, a2, i2 = C.POINTER(DedupOpts), C.POINTER(DedupStats), C.POINTER(u64), C.POINTER(C.c_int)
+        L.bfq_dedup_default_opts.restype = None
+        L.bfq_dedup_default_opts.argtypes = [pdo]
+        L.bfq_dedup_host_error.restype = C.c_char_p
+        L.bfq_dedup_host_error.argtypes = []
+        L.bfq_fastq_dedup_measure.argtypes = [vp, C.POINTER(vp), a2, pdo, a2, a2, pds]
+        L.bfq_fastq_dedup.argtypes = [vp, C.POINTER(vp), a2, pdo, C.POINTER(vp), a2, C.POINTER(vp), a2, a2, a2, pds]
+        L.bfq_fastq_dedup_device.argtypes = [vp, C.POINTER(vp), a2, pdo, C.POINTER(vp), a2, C.POINTER(vp), a2, a2, a2, pds]
+        L.bfq_fastq_dedup_fd.argtypes = [vp, i2, pdo, i2, i2, a2, a2, pds]
+        L.bfq_fastq_dedup_host.argtypes = [C.POINTER(vp), a2, pdo, C.POINTER(vp), a2, C.POINTER(vp), a2, a2, a2, pds]
         L.bfq_fastq_restore_bgzf_fd.argtypes = [vp, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, u64, C.c_int, C.c_int, pu64, pu64, pu64]
         L.bfq_posbin_geometry.argtypes = [u64, C.POINTER(u64), C.POINTER(C.c_int)]
         L.bfq_posbin_sparse_last.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(u64)]

@@ -587,6 +587,64 @@ def fastq_repair_host(texts, outs=None, **opts):
     return [o[:int(n)] for o, n in zip(outs, ol)], st
 
 
+def dedup_opts(keep=0, hash_bits=40, seed=0, reserved=(0, 0)):
+    """bfq_dedup_opts (include/bfqzip_hip.h); the defaults are bfq_dedup_default_opts'.  keep: 0 keeps the first unit of every
+    group of equal sequences, 1 the one with the best qualities (ties: the first); hash_bits (1..40): the bits of the sequence
+    hash the units are sorted by -- small values are a test knob, the outputs do not depend on it, nor on seed; reserved must
+    be 0."""
+    o = _lib.DedupOpts()
+    o.keep, o.hash_bits, o.seed = int(keep), int(hash_bits), int(seed)
+    o.reserved[0], o.reserved[1] = (int(reserved), 0) if not hasattr(reserved, "__len__") else (int(reserved[0]), int(reserved[1]))
+    return o
+
+
+def _dedup_texts(texts):
+    """the one or two texts of a dedup call (None: absent) as pointer and length arrays"""
+    texts = [None if t is None else _u8(t) for t in list(texts) + [None] * (2 - len(texts))]
+    if len(texts) != 2:
+        raise ValueError("dedup: at most two texts")
+    ptrs = (C.c_void_p * 2)(*[None if t is None else (t if len(t) else _EMPTY_TEXT).ctypes.data for t in texts])
+    lens = (C.c_uint64 * 2)(*[0 if t is None else len(t) for t in texts])
+    return texts, ptrs, lens
+
+
+def _dedup_bufs(bufs):
+    return (C.c_void_p * 2)(*[b.ctypes.data if len(b) else None for b in bufs]), (C.c_uint64 * 2)(*[len(b) for b in bufs])
+
+
+def _dedup_call(fn, err, texts, outs, dups, opts):
+    """the memory forms' shared body: fn(ptrs, lens, opts, outs, caps, dups, caps, out_len, dup_len, stats) -> rc; err(): the
+    message.  dups: False (not written), True (sized by the call) or two uint8 arrays."""
+    keep, ptrs, lens = _dedup_texts(texts)
+    O, st, ol, dl = dedup_opts(**opts), _lib.DedupStats(), (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+    optrs, ocaps = _dedup_bufs(outs)
+    dptrs, dcaps = _dedup_bufs(dups) if dups is not False else (None, None)
+    rc = fn(ptrs, lens, C.byref(O), optrs, ocaps, dptrs, dcaps, ol, dl, C.byref(st))
+    if rc != 0:
+        _pairs_raise(rc, err(), list(ol) + list(dl))
+    return [o[:int(n)] for o, n in zip(outs, ol)], None if dups is False else [d[:int(n)] for d, n in zip(dups, dl)], st
+
+
+def fastq_dedup_host(texts, outs=None, dups=False, **opts):
+    """(kept[2], removed[2] or None, stats) of the FASTQ texts (texts[0]: the reads or the first mates; texts[1]: the second
+    mates, None: single-end) with exact duplicates removed by the host form (bfq_fastq_dedup_host: the steps of
+    csrc/bfq_dedup.h by one thread, no GPU): the statement of the algorithm -- Engine.fastq_dedup gives the same bytes, stats
+    and messages.  opts: dedup_opts().  `outs`: two uint8 arrays to fill; `dups`: False (the removed records are counted and
+    not written), True, or two uint8 arrays; a buffer that is too small raises BfqError with .needed = the four lengths,
+    nothing written."""
+    L = _lib.lib()
+    err = lambda: L.bfq_dedup_host_error().decode()
+    if outs is None or dups is True:
+        keep, ptrs, lens = _dedup_texts(texts)
+        O, st, ol, dl = dedup_opts(**opts), _lib.DedupStats(), (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+        rc = L.bfq_fastq_dedup_host(ptrs, lens, C.byref(O), None, None, None, None, ol, dl, C.byref(st))
+        if rc != 0:
+            _pairs_raise(rc, err(), list(ol) + list(dl))
+        outs = [np.empty(int(v), np.uint8) for v in ol] if outs is None else outs
+        dups = [np.empty(int(v), np.uint8) for v in dl] if dups is True else dups
+    return _dedup_call(L.bfq_fastq_dedup_host, err, texts, outs, dups, opts)
+
+
 def text_len(a):
     """The length a FASTQ source has as text: its own, or the raw length of a BGZF source (what output buffers are sized from)."""
     a = _u8(a)
@@ -612,6 +670,7 @@ class HostText:
     fastq_deinterleave_host = staticmethod(fastq_deinterleave_host)
     fastq_interleave_host = staticmethod(fastq_interleave_host)
     fastq_repair_host = staticmethod(fastq_repair_host)
+    fastq_dedup_host = staticmethod(fastq_dedup_host)
     FileRange = FileRange
     text_line_counts = staticmethod(text_line_counts)
     text_nth_newline = staticmethod(text_nth_newline)
@@ -1378,6 +1437,65 @@ class Engine:
             O, st, ol, nr = repair_opts(**opts), _lib.RepairStats(), (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
             self._pairs_ck(self.L.bfq_fastq_repair_fd(self.h, (C.c_int * 3)(*fds[0:3]), C.byref(O), (C.c_int * 3)(*fds[3:6]), ol, nr, C.byref(st)), ol)
             return [int(v) for v in ol], [int(v) for v in nr], st
+        finally:
+            for fd in fds:
+                if fd >= 0:
+                    os.close(fd)
+
+    # ---- exact duplicate removal: reads or pairs with equal sequences leave one unit (bfq_fastq_dedup*, csrc/bfq_dedup.h)
+    def fastq_dedup_measure(self, texts, **opts):
+        """bfq_fastq_dedup_measure: (the two kept lengths, the two removed lengths, stats) of the dedup of texts (see
+        fastq_dedup); nothing is written."""
+        keep, ptrs, lens = _dedup_texts(texts)
+        O, st, ol, dl = dedup_opts(**opts), _lib.DedupStats(), (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+        self._pairs_ck(self.L.bfq_fastq_dedup_measure(self.h, ptrs, lens, C.byref(O), ol, dl, C.byref(st)), list(ol) + list(dl))
+        return [int(v) for v in ol], [int(v) for v in dl], st
+
+    def fastq_dedup(self, texts, outs=None, dups=False, **opts):
+        """(kept[2], removed[2] or None, stats): exact duplicates removed on the GPU (bfq_fastq_dedup).  texts[0]: the reads
+        or the first mates; texts[1]: the second mates (None: single-end) -- the k-th records of both are one unit.  Units
+        with equal sequence lines (paired: both, in order) are a group; one unit of every group is kept -- the first, or with
+        keep=1 the one whose qualities sum highest --, in input order, byte for byte; the others are the removed records.
+        opts: dedup_opts() (hash_bits and seed never show in the outputs).  `outs`: two uint8 arrays to fill; `dups`: False
+        (counted, not written), True, or two uint8 arrays; without buffers the texts are measured first.  A buffer below its
+        text raises BfqError with .needed = the four lengths and nothing is written.  stats: units, kept, removed,
+        dup_groups, max_group, max_group_first and the duplication levels (level_groups / level_units)."""
+        if outs is None or dups is True:
+            ol, dl, _ = self.fastq_dedup_measure(texts, **opts)
+            outs = [np.empty(v, np.uint8) for v in ol] if outs is None else outs
+            dups = [np.empty(v, np.uint8) for v in dl] if dups is True else dups
+        fn = lambda *a: self.L.bfq_fastq_dedup(self.h, *a)
+        return _dedup_call(fn, lambda: self.L.bfq_last_error(self.h).decode(), texts, outs, dups, opts)
+
+    def fastq_dedup_device(self, d_texts, text_lens, d_outs, out_caps, d_dups=None, dup_caps=None, **opts):
+        """bfq_fastq_dedup_device: the texts at the device addresses d_texts (None / 0: absent), the kept texts at the device
+        addresses d_outs (out_caps bytes each), the removed ones at d_dups (None: not written); returns (kept lengths,
+        removed lengths, stats)."""
+        two = lambda v: (C.c_void_p * 2)(*[int(p) if p else None for p in list(v) + [None] * (2 - len(v))])
+        cap = lambda v: (C.c_uint64 * 2)(*[int(x) for x in list(v) + [0] * (2 - len(v))])
+        O, st, ol, dl = dedup_opts(**opts), _lib.DedupStats(), (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+        rc = self.L.bfq_fastq_dedup_device(self.h, two(d_texts), cap(text_lens), C.byref(O), two(d_outs), cap(out_caps),
+                                           None if d_dups is None else two(d_dups), None if d_dups is None else cap(dup_caps), ol, dl, C.byref(st))
+        self._pairs_ck(rc, list(ol) + list(dl))
+        return [int(v) for v in ol], [int(v) for v in dl], st
+
+    def fastq_dedup_files(self, texts, outs, dups=None, **opts):
+        """bfq_fastq_dedup_fd on named files: the FASTQ files texts[k] (texts[1] None: single-end), outs = the paths of the
+        kept records, dups = the paths of the removed ones (None: not written).  The outputs are left empty on a refusal.
+        Returns (kept lengths, removed lengths, stats)."""
+        import os
+        pad = lambda v: list(v or []) + [None] * (2 - len(v or []))
+        fds = []
+        try:
+            for t in pad(texts):
+                fds.append(os.open(t, os.O_RDONLY) if t is not None else -1)
+            for d in pad(outs) + pad(dups):
+                fds.append(os.open(d, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644) if d is not None else -1)
+            O, st, ol, dl = dedup_opts(**opts), _lib.DedupStats(), (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+            rc = self.L.bfq_fastq_dedup_fd(self.h, (C.c_int * 2)(*fds[0:2]), C.byref(O), (C.c_int * 2)(*fds[2:4]),
+                                           (C.c_int * 2)(*fds[4:6]) if dups else None, ol, dl, C.byref(st))
+            self._pairs_ck(rc, list(ol) + list(dl))
+            return [int(v) for v in ol], [int(v) for v in dl], st
         finally:
             for fd in fds:
                 if fd >= 0:

@@ -526,6 +526,22 @@ void bfq_repair_group(bfq_ctx *c, const PrText t[3], u64 N, u32 suffix, const u6
                       u64 *d_cnt);   // d_cnt[0, 2) zeroed: dup_groups, mixed_runs
 void bfq_repair_place(bfq_ctx *c, const PrText t[3], u64 N, const u8 *role, const u64 *anchor, const u64 *rank1, const u64 *rank0, u64 *slot, u64 *const sz[3]);
 void bfq_repair_move(bfq_ctx *c, const PrText t[3], u64 N, const u8 *role, const u64 *slot, const u64 *const off[3], u8 *const o[3]);
+void bfq_maxscan_u64(bfq_ctx *c, const u64 *in, u64 *out, u64 n);   // out[i] = max(in[0..i]); in == out is allowed
+// the texts of a call staged and indexed (bfq_pairs.hip)
+BFQ_LOCAL void bfq_pairs_stage(bfq_ctx *c, const TextIn src[3], const std::function<void(const u8 *, u64, u32)> &gzip, const char *what, size_t perRec,
+                               bool arenaOut, PrText t[3]);
+// exact duplicate removal (k_dedup.hip; bfq_dedup.hip drives them; the definition: bfq_dedup.h).  T: the one or two texts of
+// the call (nt), N: their units.
+struct DdTexts { PrText t[2]; u32 nt; };
+struct DdGroups { u64 *sg, *sh, *start, *head, *next, *rep; u8 *mixed; };   // per sorted position (head, next, mixed: read at run starts)
+void bfq_dedup_sort(bfq_ctx *c, const DdTexts &T, u64 N, const bfq_dedup_opts &O, u64 *h, u64 *score, SortRec a, SortRec b, const DdGroups &G, u64 *d_stat);
+// d_stat, in u64: the longest run, mixed runs, the round's unresolved, kept, the largest group, its first, levels
+enum { DD_S_MAXRUN = 0, DD_S_MIXED, DD_S_UNRES, DD_S_KEPT, DD_S_MAXGROUP, DD_S_FIRST, DD_S_LGROUPS, DD_S_LUNITS = DD_S_LGROUPS + 32, DD_S_NUM = DD_S_LUNITS + 32 };
+u64 bfq_dedup_round(bfq_ctx *c, const DdTexts &T, u64 N, const DdGroups &G, u64 *d_stat, bool first);   // one round; returns the unresolved positions; synchronises
+void bfq_dedup_first_bad(bfq_ctx *c, u64 N, const DdGroups &G, u64 *d_firstBad);           // *d_firstBad preset to all-ones
+void bfq_dedup_winners(bfq_ctx *c, u64 N, u32 keep, const DdGroups &G, const u64 *score, u64 *gsize, u64 *best, u64 *win, u8 *kept, u64 *d_stat);
+void bfq_dedup_sizes(bfq_ctx *c, const DdTexts &T, u64 N, const u8 *kept, u64 *const sz[2]);
+void bfq_dedup_move(bfq_ctx *c, const DdTexts &T, u64 N, const u8 *kept, const u64 *const off[2], u8 *const out[2], u8 *const dup[2]);
 
 // two FASTQ texts compared where they lie (k_compare.hip; bfq_compare.hip drives them).  inv == nullptr: read i of A pairs with
 // read i of B, else with read inv[i].  d_rep: a zeroed report on the device whose first_changed_read is all-ones.

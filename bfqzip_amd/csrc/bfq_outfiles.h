@@ -24,7 +24,7 @@ static inline void bfq_fd_size(int fd, u64 len, const char *what, bool errnoText
 
 class OutFiles {
 public:
-    static const int MAX = 3;
+    static const int MAX = 4;                                       // (the dedup: two kept texts, two removed)
     // drain(): every background write queued so far has arrived; it throws what went wrong
     OutFiles(const int *fd, int n, std::function<void()> drain) : n_(n < MAX ? n : MAX), drain_(std::move(drain))
     {

@@ -85,27 +85,26 @@ extern "C" int bfq_fastq_interleave_host(const uint8_t *const text[3], const uin
 }
 
 // ---------------------------------------------------------------- the texts of a call
-static void pr_nomem(bfq_ctx *c, size_t need) { bfq_nomem_cap(c, "splitting or merging the mates", "text + outputs + index", need); }
-
-// Step 1 for the texts src[0, 3) (merge: the refusal names the text): t[k] = text k on the device with its index (an absent
-// or empty text: no records; merge = 2: the repair).  perRec / arenaOut: what steps 2 and 3 take from the arena beside the
-// index, in bytes per record, and whether the outputs lie there.
-static void pr_stage(bfq_ctx *c, const TextIn src[3], u32 merge, size_t perRec, bool arenaOut, PrText t[3])
+// Step 1 for the texts src[0, 3): t[k] = text k on the device with its index (an absent or empty text: no records).  gzip(first,
+// len, k) refuses a text that begins with 1f 8b in the caller's words; what: the caller's work, for the refusal above the
+// workspace cap.  perRec / arenaOut: what steps 2 and 3 take from the arena beside the index, in bytes per record, and whether
+// the outputs lie there.  (bfq_dedup.hip stages its texts here too.)
+void bfq_pairs_stage(bfq_ctx *c, const TextIn src[3], const std::function<void(const u8 *, u64, u32)> &gzip, const char *what, size_t perRec, bool arenaOut,
+                     PrText t[3])
 {
+    auto nomem = [&](size_t need) { bfq_nomem_cap(c, what, "text + outputs + index", need); };
     TextIn in[3];                                                   // (an empty text is handed on as absent: it gets no slot)
     for (u32 k = 0; k < 3; k++)
         if (src[k].present() && src[k].len) in[k] = src[k];
     BfqTextSeen seen[3];
     bfq_texts_look(c, in, 3, seen, false);
-    for (u32 k = 0; k < 3; k++) {
-        bfq_pairs_err X;
-        if (seen[k].present && !bfq_pairs_gzip_ok(seen[k].first, seen[k].len, merge, k, &X)) pr_refuse(X);
-    }
+    for (u32 k = 0; k < 3; k++)
+        if (seen[k].present) gzip(seen[k].first, seen[k].len, k);
     bfq_texts_look(c, in, 3, seen, true);
     const BfqTextPlan plan = bfq_texts_plan(seen, 3, true);
     const u64 bytes = plan.t[0].len + plan.t[1].len + plan.t[2].len;
     const size_t outBytes = arenaOut ? (size_t)bytes + 3 * 4096 : 0;
-    if (c->wsLimit() && plan.bufNeed + outBytes > c->wsLimit()) pr_nomem(c, plan.bufNeed + outBytes);
+    if (c->wsLimit() && plan.bufNeed + outBytes > c->wsLimit()) nomem(plan.bufNeed + outBytes);
     bfq_phase("alloc");
     TextPlaced p[3];
     bfq_texts_place(c, in, plan, 3, p);
@@ -121,7 +120,7 @@ static void pr_stage(bfq_ctx *c, const TextIn src[3], u32 merge, size_t perRec, 
         need += bfq_fastq_index_bytes(p[k].len, p[k].lines) + 12288 + 2 * bfq_scan_bytes(n);
     }
     need += perRec * (size_t)(nb + 64) + 4 * bfq_scan_bytes(nb) + 4096;
-    if (c->wsLimit() && plan.bufNeed + need > c->wsLimit()) pr_nomem(c, plan.bufNeed + need);
+    if (c->wsLimit() && plan.bufNeed + need > c->wsLimit()) nomem(plan.bufNeed + need);
     bfq_phase("alloc");
     c->reserve(need);
     bfq_phase("gpu");
@@ -132,6 +131,15 @@ static void pr_stage(bfq_ctx *c, const TextIn src[3], u32 merge, size_t perRec, 
         bfq_fastq_index(c, t[k].buf, t[k].len, &fq);
         t[k].rec = (const FqRec *)fq.rec; t[k].N = fq.N;
     }
+}
+
+// ... for the split (merge = 0), the merge (1) and the repair (2): the refusal names the text
+static void pr_stage(bfq_ctx *c, const TextIn src[3], u32 merge, size_t perRec, bool arenaOut, PrText t[3])
+{
+    bfq_pairs_stage(c, src, [merge](const u8 *first, u64 len, u32 k) {
+        bfq_pairs_err X;
+        if (!bfq_pairs_gzip_ok(first, len, merge, k, &X)) pr_refuse(X);
+    }, "splitting or merging the mates", perRec, arenaOut, t);
 }
 
 // what becomes of the outputs: sized(len) runs once the lengths are exact and before anything is written (it throws for a

@@ -1,5 +1,6 @@
 // cli_common.h -- file helpers shared by the drop-in front-ends (host only).
 #pragma once
+#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -103,6 +104,34 @@ struct OutFile {
         return ok;
     }
     ~OutFile() { if (fd >= 0) ::close(fd); }
+};
+
+// An input file as plain text: itself, or -- when it begins with 1f 8b -- its inflated form in an unnamed temporary file
+// ($TMPDIR, /tmp): BGZF, or plain gzip with `gzip`.  tool: the name in front of the messages.
+struct TextFile {
+    InFile in;
+    int tmp = -1;
+    int fd = -1;
+    uint64_t size = 0;
+    bool open(bfq_ctx *c, const char *tool, const std::string &path, bool gzip)
+    {
+        if (!in.open(path)) { fprintf(stderr, "%s: cannot read %s\n", tool, path.c_str()); return false; }
+        fd = in.fd; size = in.size;
+        uint8_t first[2] = {0, 0};
+        if (size < 2 || pread(fd, first, 2, 0) != 2 || first[0] != 0x1F || first[1] != 0x8B) return true;
+        const char *dir = getenv("TMPDIR");
+        std::string name = std::string(dir && *dir ? dir : "/tmp") + "/" + tool + ".XXXXXX";
+        tmp = mkstemp(&name[0]);
+        if (tmp < 0) { fprintf(stderr, "%s: temporary file: %s\n", tool, strerror(errno)); return false; }
+        unlink(name.c_str());
+        uint64_t raw = 0;
+        bfq_gzip_stats gs = {};
+        const int rc = gzip ? bfq_gzip_inflate_fd(c, fd, size, 0, tmp, &raw, &gs) : bfq_bgzf_inflate_fd(c, fd, size, tmp, &raw);
+        if (rc) { fprintf(stderr, "%s: %s: %s\n", tool, path.c_str(), bfq_last_error(c)); return false; }
+        fd = tmp; size = raw;
+        return true;
+    }
+    ~TextFile() { if (tmp >= 0) ::close(tmp); }
 };
 
 // A tag selection of the command line ("*": every tag; "BC,RX": those) into the n_tags / tag[][] of bfq_bam_tag_opts and

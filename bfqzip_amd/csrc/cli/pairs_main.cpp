@@ -41,33 +41,6 @@ static int usage(const char *argv0)
     return 1;
 }
 
-// An input file as plain text: itself, or -- when it begins with 1f 8b -- its inflated form in an unnamed temporary file.
-struct TextFile {
-    InFile in;
-    int tmp = -1;
-    int fd = -1;
-    uint64_t size = 0;
-    bool open(bfq_ctx *c, const std::string &path, bool gzip)
-    {
-        if (!in.open(path)) { fprintf(stderr, "bfq_pairs: cannot read %s\n", path.c_str()); return false; }
-        fd = in.fd; size = in.size;
-        uint8_t first[2] = {0, 0};
-        if (size < 2 || pread(fd, first, 2, 0) != 2 || first[0] != 0x1F || first[1] != 0x8B) return true;
-        const char *dir = getenv("TMPDIR");
-        std::string name = std::string(dir && *dir ? dir : "/tmp") + "/bfq_pairs.XXXXXX";
-        tmp = mkstemp(&name[0]);
-        if (tmp < 0) { perror("bfq_pairs: temporary file"); return false; }
-        unlink(name.c_str());
-        uint64_t raw = 0;
-        bfq_gzip_stats gs = {};
-        const int rc = gzip ? bfq_gzip_inflate_fd(c, fd, size, 0, tmp, &raw, &gs) : bfq_bgzf_inflate_fd(c, fd, size, tmp, &raw);
-        if (rc) { fprintf(stderr, "bfq_pairs: %s: %s\n", path.c_str(), bfq_last_error(c)); return false; }
-        fd = tmp; size = raw;
-        return true;
-    }
-    ~TextFile() { if (tmp >= 0) ::close(tmp); }
-};
-
 // -r: the repair.  Returns the exit status.
 static int repair_main(int argc, char **argv)
 {
@@ -109,7 +82,7 @@ static int repair_main(int argc, char **argv)
     {
         TextFile text[3];
         for (int k = 0; k < 3; k++)
-            if (!in[k].empty() && !text[k].open(c, in[k], gzip)) return fail();
+            if (!in[k].empty() && !text[k].open(c, "bfq_pairs", in[k], gzip)) return fail();
         int rc = 0;
         if (count || outName[0].empty()) {                          // the counts first: singletons need a place before anything is written
             void *m[3] = {MAP_FAILED, MAP_FAILED, MAP_FAILED};
@@ -212,8 +185,8 @@ int main(int argc, char **argv)
         bool ok = true;
         if (mode == 'm') {
             for (int k = 0; k < 3 && ok; k++)
-                if (!mate[k].empty()) ok = text[k].open(c, mate[k], gzip);
-        } else ok = text[0].open(c, input, gzip);
+                if (!mate[k].empty()) ok = text[k].open(c, "bfq_pairs", mate[k], gzip);
+        } else ok = text[0].open(c, "bfq_pairs", input, gzip);
         if (!ok) { bfq_destroy(c); return fail(); }
         if (mode == 's') {
             const int fds[3] = {out[0].fd, out[1].fd, out[2].fd};

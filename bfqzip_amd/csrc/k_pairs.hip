@@ -18,16 +18,12 @@
 //                     split and merge find the source record from the output index: no role or permutation array.
 // Every loop ends at a length taken from the index, never at a byte found in the text.
 // The last section holds the repair (bfq_fastq_repair*): mates matched by name wherever they stand, with its own overview.
-#include "bfq_internal.h"
-#include "bfq_device.h"
-#include "bfq_pairs.h"
+#include "bfq_pairs_device.h"
 
 #define PR_SCAN_THREADS 256
 #define PR_SCAN_ITEMS 16
 #define PR_SCAN_CHUNK (PR_SCAN_THREADS * PR_SCAN_ITEMS)          // records per chunk of the max-scan (tests/pairs_model.py names it)
 
-// record i of a text: [hdrStart of i, hdrStart of i + 1) -- the last one ends with the text
-__device__ __forceinline__ u64 pr_rec_end(const PrText &t, u64 i) { return i + 1 < t.N ? t.rec[i + 1].hdrStart : t.len; }
 __device__ __forceinline__ bool pr_same(const PrText &a, u64 ia, const PrText &b, u64 ib, u32 suffix)
 {
     return bfq_pairs_same(a.buf, a.rec[ia].hdrStart, a.rec[ia].hdrLen, b.buf, b.rec[ib].hdrStart, b.rec[ib].hdrLen, suffix);
@@ -51,16 +47,6 @@ __global__ __launch_bounds__(256) void k_pairs_bounds(PrText a, u32 suffix, u64 
 }
 
 // ---- inclusive max-scan of u64 ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 pr_max(u64 x, u64 y) { return x > y ? x : y; }
-__device__ __forceinline__ u64 pr_wave_incmax(u64 m, u32 lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 t = __shfl_up(m, (unsigned)d);
-        if ((int)lane >= d) m = pr_max(m, t);
-    }
-    return m;
-}
 __global__ __launch_bounds__(PR_SCAN_THREADS) void k_pairs_maxred(const u64 *__restrict__ in, u64 n, u64 *__restrict__ maxs)
 {
     __shared__ u64 sh[4];
@@ -126,18 +112,6 @@ __global__ __launch_bounds__(256) void k_pairs_psizes(PrText a, u64 P, u64 *__re
 }
 
 // ---- the move --------------------------------------------------------------------------------------------------------------
-// n bytes by 16 lanes of which this is lane `sub`: bytes up to the first 16-byte boundary of the destination, 16-byte stores
-// (the loads are as aligned as the source happens to be), a byte tail.  Reads src[0, n) and writes dst[0, n), nothing else.
-__device__ __forceinline__ void pr_copy(u8 *__restrict__ dst, const u8 *__restrict__ src, u64 n, u32 sub)
-{
-    u64 head = (16 - ((u64)(uintptr_t)dst & 15)) & 15;
-    if (head > n) head = n;
-    if (sub < head) dst[sub] = src[sub];
-    const u64 body = (n - head) >> 4;
-    for (u64 q = sub; q < body; q += 16) *(uint4 *)(dst + head + 16 * q) = *(const uint4 *)(src + head + 16 * q);
-    const u64 done = head + 16 * body;
-    if (done + sub < n) dst[done + sub] = src[done + sub];
-}
 
 // strict split: record j of the text is mate 1 + (j & 1) of pair j / 2; off1[k]: where pair k's first mate starts in output 1
 __global__ __launch_bounds__(256) void k_pairs_split(PrText a, const u64 *__restrict__ off1, u8 *__restrict__ o1, u8 *__restrict__ o2)
@@ -182,7 +156,7 @@ void bfq_pairs_compare(bfq_ctx *c, const PrText &a, const PrText *b, u64 P, u32 
     KLAUNCH(c, K_PAIRS_CMP, 128.0 * (double)P, k_pairs_cmp, bfq_grid(P, 256), 256, a, b ? *b : a, b ? 1u : 0u, P, suffix, (unsigned long long *)d_firstBad);
 }
 
-static void pr_maxscan(bfq_ctx *c, const u64 *in, u64 *out, u64 n)
+void bfq_maxscan_u64(bfq_ctx *c, const u64 *in, u64 *out, u64 n)
 {
     const u64 nb = ceil_div(n, PR_SCAN_CHUNK);
     if (nb <= 1) {
@@ -192,7 +166,7 @@ static void pr_maxscan(bfq_ctx *c, const u64 *in, u64 *out, u64 n)
     const size_t m = c->mark();
     u64 *maxs = c->alloc<u64>(nb), *maxsInc = c->alloc<u64>(nb);
     KLAUNCH(c, K_SCAN, 8.0 * (double)n, k_pairs_maxred, nb, PR_SCAN_THREADS, in, n, maxs);
-    pr_maxscan(c, maxs, maxsInc, nb);
+    bfq_maxscan_u64(c, maxs, maxsInc, nb);
     KLAUNCH(c, K_SCAN, 16.0 * (double)n, k_pairs_maxdown, nb, PR_SCAN_THREADS, in, out, n, (const u64 *)maxsInc);
     c->release(m);   // stream-ordered, as in k_scan.hip
 }
@@ -202,7 +176,7 @@ void bfq_pairs_run_starts(bfq_ctx *c, const PrText &a, u32 suffix, u64 *start)
 {
     if (!a.N) return;
     KLAUNCH(c, K_PAIRS_CMP, 136.0 * (double)a.N, k_pairs_bounds, bfq_grid(a.N, 256), 256, a, suffix, start);
-    pr_maxscan(c, start, start, a.N);
+    bfq_maxscan_u64(c, start, start, a.N);
 }
 // ... the roles, the sizes per output (sz[k][i]: record i's size where it goes to output k, else 0) and d_cnt[0, 2): singles, pairs
 void bfq_pairs_roles(bfq_ctx *c, const PrText &a, const u64 *start, u8 *role, u64 *const sz[3], u64 *d_cnt)
@@ -268,16 +242,6 @@ __device__ __forceinline__ PrText rp_text(const RpTexts &T, u32 k)
     r.N = k == 1 ? T.t[1].N : k == 2 ? T.t[2].N : T.t[0].N;
     return r;
 }
-__device__ __forceinline__ u64 rp_index(u64 w12) { return ((w12 >> 32) << 24) | (w12 & 0xFFFFFFull); }
-__device__ __forceinline__ u64 rp_sort_key(const SortRec &r, u64 p) { return ((u64)r.w0[p] << 8) | (u64)((u32)r.w12[p] >> 24); }
-// n <= 8 bytes at p as a little-endian word, zero-padded: one 8-byte load where all 8 lie inside the header
-__device__ __forceinline__ u64 rp_word(const u8 *__restrict__ p, u64 n)
-{
-    if (n < 8) return bfq_repair_word(p, n);
-    u64 w;
-    __builtin_memcpy(&w, p, 8);
-    return w;
-}
 __device__ __forceinline__ u64 rp_group_min(u64 v)
 {
 #pragma unroll
@@ -326,8 +290,7 @@ __global__ __launch_bounds__(256) void k_repair_hash(RpTexts T, u64 N, u32 suffi
             const u64 hv = bfq_repair_finish(acc, l, seed), key = bfq_repair_sort_key(hv, hashBits);
             h[g] = hv;
             hint[g] = (u8)hi;
-            out.w0[g] = (u32)(key >> 8);
-            out.w12[g] = ((u64)(u32)(g >> 24) << 32) | (u64)((u32)((key & 255ull) << 24) | (u32)(g & 0xFFFFFFull));
+            rp_sort_rec(out, g, key);
         }
     }
 }
@@ -457,7 +420,7 @@ void bfq_repair_sort(bfq_ctx *c, const PrText t[3], u64 N, const bfq_repair_opts
     KLAUNCH(c, K_PAIRS_CMP, 90.0 * (double)N, k_repair_hash, bfq_grid(N, 256 / RP_LANES), 256, T, N, O.mate_suffix, O.hash_bits, (u64)O.seed, h, hint, a);
     const SortRec sorted = bfq_radix_sort(c, a, b, N, (int)(O.hash_bits + 7) / 8);
     KLAUNCH(c, K_MISC, 53.0 * (double)N, k_repair_sorted, bfq_grid(N, 256), 256, sorted, N, (const u64 *)h, (const u8 *)hint, sg, sh, start);
-    pr_maxscan(c, start, start, N);
+    bfq_maxscan_u64(c, start, start, N);
     KLAUNCH(c, K_MISC, 16.0 * (double)N, k_repair_runs, bfq_grid(N, 256), 256, (const u64 *)start, (const u64 *)sg, N, (unsigned long long *)d_stat);
 }
 // step 3's walk: role / anchor / the two role flags per global number; d_cnt[0, 2) zeroed: dup_groups, mixed_runs

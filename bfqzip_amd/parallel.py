@@ -307,6 +307,40 @@ def repair_inputs(eng, comm, inputs, out="", log=None):
     return q, q, None
 
 
+def dedup_names(inputs, out, paired):
+    """Where --dedup writes: beside the outputs (bam_names), (<name>.dedup.fastq, <name>.dups.fastq), or with -p
+    (<name>.dedup_1.fastq, <name>.dedup_2.fastq, <name>.dups_1.fastq, <name>.dups_2.fastq): (the kept files, the removed ones)"""
+    base = bam_names(inputs[0], out, False)[0][:-len(".fastq")]
+    tags = ("_1", "_2") if paired else ("",)
+    return [base + ".dedup" + t + ".fastq" for t in tags], [base + ".dups" + t + ".fastq" for t in tags]
+
+
+def dedup_inputs(eng, comm, inputs, out="", paired=False, best=False, log=None):
+    """--dedup: exact duplicates -- reads, or with -p pairs, with equal sequences -- are removed on the GPU of rank 0
+    (eng.fastq_dedup_files) before the run: the kept records go into the files of dedup_names() and the run goes on with them,
+    the removed ones into <name>.dups[_1|_2].fastq, which the run does not touch.  best: the unit with the best qualities of
+    every group is kept, else the first.  Returns (the new input list, the kept files, None) -- or, for a refusal, (the old
+    list, the kept files, the library's message) on every rank, before any block runs."""
+    from . import api
+    kept, dups = dedup_names(inputs, out, paired)
+    why = None
+    if comm.rank == 0:
+        try:
+            ol, dl, st = eng.fastq_dedup_files(inputs, kept, dups, keep=1 if best else 0)
+            if log:
+                log(f"dedup: {' '.join(inputs)} -> {kept}: {st.units} {'pairs' if paired else 'reads'}, {st.kept} kept, {st.removed} removed -> {dups} "
+                    f"({st.dup_groups} groups of duplicates, the largest of {st.max_group} at record {st.max_group_first})")
+        except api.BfqError as e:
+            why = str(e)
+            for q in dups:
+                if os.path.exists(q):
+                    os.remove(q)
+    if comm.all_gather_i64([1 if why else 0])[0, 0]:
+        return list(inputs), kept, why or "the inputs were refused on rank 0"
+    comm.barrier()
+    return kept, kept, None
+
+
 def merge_interleaved_output(eng, comm, outputs, path, check_names, log=None):
     """--interleaved-out: after the run rank 0 merges the two merged output texts into one file with the mates alternating
     (eng.fastq_interleave_files), the names compared when the run kept them.  Returns None, or the library's message on every
@@ -851,8 +885,21 @@ def main(argv=None):
                          "may each have lost reads; one input is a mixed file (/1 and /2 say which mate a record is).  The run goes on as "
                          "-p on <name>_1.fastq / <name>_2.fastq beside the outputs (--keep-inflated keeps them); what finds no mate goes to "
                          "<name>_singles.fastq, which the run does not touch; more than 1024 records of one name end the run")
+    ap.add_argument("--dedup", action="store_true",
+                    help="exact duplicates are removed on the GPU first: reads -- with -p pairs -- with equal sequences leave their first unit "
+                         "behind.  Behind the inflation and --repair, in front of --reorder; the run goes on with <name>.dedup.fastq (-p: "
+                         "<name>.dedup_1.fastq / <name>.dedup_2.fastq) beside the outputs (--keep-inflated keeps them); the removed records "
+                         "go to <name>.dups[_1|_2].fastq, which the run does not touch")
+    ap.add_argument("--dedup-best", action="store_true", help="--dedup, keeping the unit with the best qualities of every group of duplicates")
     ap.add_argument("--M", type=int, default=2); ap.add_argument("--B", type=int, default=0)
     a = ap.parse_args(argv)
+    a.dedup = a.dedup or a.dedup_best
+    if a.dedup and (a.restore or a.bam_out):
+        print("=== ERROR ===\n--dedup removes records in front of a run: not with --restore or --bam-out", file=sys.stderr)
+        return 1
+    if a.dedup and not (a.bam or a.interleaved or a.repair) and len(a.input) != (2 if a.paired else 1):
+        print("=== ERROR ===\n--dedup takes one input file, or two mate files with -p", file=sys.stderr)
+        return 1
     if a.repair:
         why = None
         if a.restore or a.interleaved or a.bam:
@@ -1016,6 +1063,19 @@ def main(argv=None):
         if why:                                                      # (the library's message; every rank leaves with it)
             if comm.rank == 0:
                 print(f"=== ERROR ===\n--repair: {why}", file=sys.stderr)
+                for q in inflated:
+                    if os.path.exists(q) and not a.keep_inflated:
+                        os.remove(q)
+            eng.close()
+            if dist:
+                dist.destroy_process_group()
+            return 1
+    if a.dedup:
+        a.input, kept, why = dedup_inputs(eng, comm, a.input, a.out, paired=a.paired, best=a.dedup_best, log=log)
+        inflated += kept
+        if why:                                                      # (the library's message; every rank leaves with it)
+            if comm.rank == 0:
+                print(f"=== ERROR ===\n--dedup: {why}", file=sys.stderr)
                 for q in inflated:
                     if os.path.exists(q) and not a.keep_inflated:
                         os.remove(q)

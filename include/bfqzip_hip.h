@@ -1220,6 +1220,64 @@ int bfq_fastq_repair_fd(bfq_ctx *c, const int text_fd[3], const bfq_repair_opts 
                         bfq_repair_stats *stats);
 int bfq_fastq_repair_host(const uint8_t *const text[3], const uint64_t text_len[3], const bfq_repair_opts *opts, uint8_t *const h_out[3],
                           const uint64_t cap[3], uint64_t out_len[3], uint64_t n_reads[3], bfq_repair_stats *stats);
+/* ---- exact duplicate removal: reads, or pairs, with equal sequences leave one unit behind (k_dedup.hip; the definition and
+ * the host form: csrc/bfq_dedup.h).  What clumpify's dedupe, fastuniq, seqkit rmdup -s and fastp --dedup do.
+ *   The texts: text[0] holds mate 1 or the single-end file, text[1] mate 2 (NULL, or text_fd < 0: single-end); plain FASTQ with
+ *     the parsing, the messages and the 1f 8b refusal of bfq_fastq_interleave ("FASTQ dedup: text <k> is compressed ...").  In
+ *     paired form the k-th records of the two texts are one unit; unequal record counts: BFQ_E_ARG, "FASTQ dedup: text 0 holds
+ *     <n> reads, text 1 holds <m>".  A record is its four lines byte for byte; the global number g of a unit is its record index.
+ *   Key of a unit: the bytes of the sequence line without its LF and without one trailing CR; paired: the ordered pair of the
+ *     mates' keys, lengths included -- ("AC","G") != ("A","CG"), (x,y) != (y,x).  Bytes compare as they are (case matters, N
+ *     equals N); header, '+' line and qualities are no part of the key.
+ *   Group: all units of the call with equal keys.  Kept unit of a group: keep = 0, the smallest g; keep = 1, the largest score
+ *     and among equals the smallest g; score = the sum of max(byte - 33, 0) over every quality byte of the unit (both mates;
+ *     the LF and one trailing CR are no quality bytes), a 64-bit sum.
+ *   out[0] / out[1]: the kept units' records in increasing g; dup[0] / dup[1]: every other unit's, in increasing g (optional:
+ *     absent, they are counted and not written).  The outputs are a function of the texts and keep only.
+ *   opts (NULL: the defaults): keep 0 (> 1: BFQ_E_ARG), hash_bits 40 (1..40, else BFQ_E_ARG), seed 0; reserved != 0: BFQ_E_ARG.
+ *     The units are sorted (stable radix passes) by the top hash_bits bits of a 64-bit hash of the key (csrc/bfq_dedup.h states
+ *     it); each run of equal sort keys is cut into groups in rounds: every unresolved unit is compared -- full hash, lengths,
+ *     bytes -- with its run's current head and joins it or proposes itself as the next head.  A run holds one sequence on real
+ *     data: one round.  The number of EQUAL units is not bounded; a run with more than 1024 DIFFERENT keys is refused after
+ *     round 1024: BFQ_E_ARG, "FASTQ dedup: more than 1024 different sequences share a hash (the first: record <g>)" -- <g>: the
+ *     smallest global number in such a run.  Small hash_bits force runs with several keys: a knob for tests.
+ *   Every refusal writes nothing in any form and leaves the context usable; all sizes are exact before the first byte moves.
+ *       _measure : host texts in; out_len[2], dup_len[2] and *stats; nothing is written.
+ *       plain    : host buffers.  A cap below its length: BFQ_E_ARG, nothing written, out_len[] / dup_len[] = the lengths needed.
+ *                  h_dup == NULL: the removed records are counted (dup_len[]) and not written, and dup_cap is not read.
+ *       _device  : device buffers in and out.  A device text at an address that is no multiple of 16, or without its final
+ *                  LF, is copied first.
+ *       _fd      : open files; out_fd[0] < 0, or in paired form out_fd[1] < 0: BFQ_E_ARG ("bad file descriptor"), the kept
+ *                  records need a place; dup_fd == NULL or dup_fd[k] < 0: not written; output files are sized to their text (0
+ *                  on a failure).
+ *       _host    : one thread, no context, no GPU: the same bytes, stats and messages.  States the algorithm; NO entry point
+ *                  falls back to it.  Message: bfq_dedup_host_error().
+ *   Device memory: the texts as for the merge; in the workspace, reserved once from the counted lines: 8 bytes per line and
+ *   44 per record of index, 114 per unit of hashes, scores, sort records, heads, groups and flags (then, in the same space, 32
+ *   of sizes and offsets), and -- host and file forms -- the outputs.  Above ws_cap_mib: BFQ_E_NOMEM with the size in the message.
+ *   stats (may be NULL): units, kept, removed, dup_groups (groups of >= 2), max_group, max_group_first (the smallest g in the
+ *   largest group, the smallest such g among equals; 0 without units), level_groups[k] / level_units[k]: the groups of
+ *   2^k <= size < 2^(k+1) and the units in them (FastQC's duplication levels, exact; k = 31 takes everything above),
+ *   out_len[2], dup_len[2]; and three that depend on hash_bits and seed: mixed_runs (runs with more than one key), max_run
+ *   (the longest run), rounds. */
+typedef struct bfq_dedup_opts  { uint32_t keep, hash_bits; uint64_t seed; uint32_t reserved[2]; } bfq_dedup_opts;
+typedef struct bfq_dedup_stats { uint64_t units, kept, removed, dup_groups, max_group, max_group_first, level_groups[32], level_units[32], out_len[2], dup_len[2],
+                                          mixed_runs, max_run, rounds; } bfq_dedup_stats;
+void bfq_dedup_default_opts(bfq_dedup_opts *o);
+int bfq_fastq_dedup_measure(bfq_ctx *c, const uint8_t *const h_text[2], const uint64_t text_len[2], const bfq_dedup_opts *opts, uint64_t out_len[2],
+                            uint64_t dup_len[2], bfq_dedup_stats *stats);
+int bfq_fastq_dedup(bfq_ctx *c, const uint8_t *const h_text[2], const uint64_t text_len[2], const bfq_dedup_opts *opts, uint8_t *const h_out[2],
+                    const uint64_t out_cap[2], uint8_t *const h_dup[2], const uint64_t dup_cap[2], uint64_t out_len[2], uint64_t dup_len[2],
+                    bfq_dedup_stats *stats);
+int bfq_fastq_dedup_device(bfq_ctx *c, const uint8_t *const d_text[2], const uint64_t text_len[2], const bfq_dedup_opts *opts, uint8_t *const d_out[2],
+                           const uint64_t out_cap[2], uint8_t *const d_dup[2], const uint64_t dup_cap[2], uint64_t out_len[2], uint64_t dup_len[2],
+                           bfq_dedup_stats *stats);
+int bfq_fastq_dedup_fd(bfq_ctx *c, const int text_fd[2], const bfq_dedup_opts *opts, const int out_fd[2], const int dup_fd[2], uint64_t out_len[2],
+                       uint64_t dup_len[2], bfq_dedup_stats *stats);
+int bfq_fastq_dedup_host(const uint8_t *const text[2], const uint64_t text_len[2], const bfq_dedup_opts *opts, uint8_t *const h_out[2],
+                         const uint64_t out_cap[2], uint8_t *const h_dup[2], const uint64_t dup_cap[2], uint64_t out_len[2], uint64_t dup_len[2],
+                         bfq_dedup_stats *stats);
+const char *bfq_dedup_host_error(void);
 /* ---- bgzip-compressed output: BGZF members deflated on the device (k_deflate.hip; the format and every bound:
  * csrc/bfq_deflate.h).  A text of len bytes is cut at multiples of 65 280 bytes (htslib's member size; the cut depends on
  * nothing else); every piece becomes one BGZF member -- htslib's 18-byte header, a raw deflate payload, CRC32 and ISIZE --
